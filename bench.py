@@ -24,12 +24,17 @@ Modes (--mode; default `auto` = `task` at --gpus 1, `grid` at --gpus N > 1):
   hybrid the same grid job with the runner's `hybrid` deal: full waves task-parallel, a last wave that would leave at least half of the
          ranks idle (44 temporal tasks on 8 GPUs: 5 waves + 4) frame-sharded over sub-groups of ranks (host/runner.py).
   frame-shard  every window split over all ranks with RCCL K/V all-gathers (latency mode, BASELINE config 4).
-Scaling curves compare like with like: the --gpus 1 line (task mode, `value` = resident steady state) ALSO runs one grid pass and
-reports it as `secondary.grid` ({latents_per_s, calls, timed_seconds, window_calls_per_task}); --gpus N > 1 lines (grid mode)
+Scaling curves compare like with like: the --gpus 1 --full line (task mode, `value` = resident steady state) ALSO runs one grid pass
+and reports it as `secondary.grid` ({latents_per_s, calls, timed_seconds, window_calls_per_task}); --gpus N > 1 lines (grid mode)
 carry the same object, so 1 -> N is `secondary.grid.latents_per_s` over `secondary.grid.latents_per_s`.
 
+A plain run does only what the headline figure needs: set-up, the W warm-up steps, the K timed steps, the outputs of the timed path
+if --dump-outputs DIR is given (DIR/<name>.npy, float32: the target-row latents of every task state the timed steps ran, a fixed-seed
+sample of each when they exceed 60 MB together) and the JSON line with the contract fields.  Everything else below -- the extra passes,
+the CPU baseline, the other precisions and sizes, the roofline and per-kernel figures -- runs with --full only.
+
 `python bench.py --gpus N` launches its own N ranks (torch.distributed.run on 127.0.0.1) when it is not already
-running under a launcher; rank 0 prints ONE JSON line: the contract fields, `roofline` (attention kernel: HIP-event
+running under a launcher; rank 0 prints ONE JSON line: the contract fields and, with --full, `roofline` (attention kernel: HIP-event
 timing in a one-task-at-a-time pass, PMC traffic from profiles/), `cpu_baseline` + `parity` (N = 1 only: the CPU
 oracle on one full spatial window with the SAME weights and input as the HIP UNet, timed and compared -- in both precisions of the
 product: `parity.modes.fast` is the judged arithmetic, `parity.modes.parity` the one that meets north_star's 1e-3), `secondary`
@@ -71,6 +76,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=4)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: the CPU baseline + parity, secondary.grid / prune_cond_rows / "
+                         "parity_precision / tolerance_mode / latent128 / vae, the roofline and kernel_breakdown_one_step passes (the --no-* "
+                         "options below switch single ones off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed to DIR/<name>.npy (float32; task mode): the target-row latents "
+                         "of every task state the timed steps ran, a fixed-seed sample of each when together they exceed 60 MB")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-vae", action="store_true", help="skip the (untimed, secondary) VAE encode / decode measurement")
     ap.add_argument("--mode", choices=["auto", "task", "grid", "hybrid", "frame-shard"], default="auto",
@@ -272,6 +284,36 @@ def run_unit(pipe, tasks, u, shard=None):
     run_call(pipe, tasks["spatial"], 2 * u, shard)
     run_call(pipe, tasks["spatial"], 2 * u + 1, shard)
     run_call(pipe, tasks["temporal"], u, shard)
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: at most this many bytes of array data (64 MB with the .npy headers to spare)
+
+
+def timed_outputs(ur, steps: int):
+    """What the `steps` timed units hand back to a caller: the latents of every task state they ran (stream si, stacks of z tasks),
+    target rows only (conditioning rows are inputs the window calls never write), as float32 arrays [rows, LAT_H * LAT_W, 4]."""
+    out = {}
+    for si, sizes in enumerate(deal_units(steps, ur.S, ur.batch)):
+        for z in sorted(set(sizes)):
+            for domain, t in ur.task_set(si, z).items():
+                target = t["cm"][:, 0, 0] != 0  # cond mask: 1 on target rows
+                out[f"latents_stream{si}_stack{z}_{domain}"] = t["lat"][target].float().cpu().numpy()
+    return out
+
+
+def write_outputs(arrays, outdir, budget: int = DUMP_BUDGET_BYTES):
+    """DIR/<name>.npy in float32.  When the arrays together exceed `budget` bytes, each one is replaced by the same fraction of its
+    elements: flat indices drawn without replacement by a generator seeded with 0 and sorted, so that runs with the same arguments
+    write the same elements and two builds compare output for output."""
+    outdir = Path(outdir)
+    outdir.mkdir(parents=True, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    frac = budget / total if total > budget else 1.0
+    for name, a in arrays.items():
+        if frac < 1.0:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, int(a.size * frac), replace=False))]
+        np.save(outdir / f"{name}.npy", a)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -762,6 +804,10 @@ def main():
     runner_mode = "task"
     if mode == "hybrid":  # the grid job under the runner's hybrid deal
         mode, runner_mode = "grid", "hybrid"
+    if args.steps < 1:
+        raise SystemExit("--steps: at least one timed step")
+    if args.dump_outputs and mode == "grid":
+        raise SystemExit("--dump-outputs: task and frame-shard modes only (the grid job's latents are the sampler's)")
     # DM4D_BENCH_SHARED_GPU=1 (testing only): all ranks share device 0 and rendezvous over gloo, so that the N > 1 code
     # paths can be exercised on a 1-GPU box; the numbers of such a run mean nothing
     shared = os.environ.get("DM4D_BENCH_SHARED_GPU") == "1"
@@ -798,9 +844,9 @@ def main():
     cfg = UNetConfig()
     state_dict = random_state_dict(unet_param_shapes(cfg), 0, dev)
     unet = UNetMultiviewConditionModel(cfg, state_dict, dev, args.precision)
-    want_cpu = (not args.no_cpu_baseline) and world == 1 and rank == 0
-    want_par = (not args.no_parity_precision) and world == 1 and rank == 0 and mode == "task" and not args.config5 and args.precision == "fast"
-    want_tol = (not args.no_tolerance_mode) and world == 1 and rank == 0 and mode == "task" and not args.config5 and args.precision == "fast"
+    want_cpu = args.full and (not args.no_cpu_baseline) and world == 1 and rank == 0
+    want_par = args.full and (not args.no_parity_precision) and world == 1 and rank == 0 and mode == "task" and not args.config5 and args.precision == "fast"
+    want_tol = args.full and (not args.no_tolerance_mode) and world == 1 and rank == 0 and mode == "task" and not args.config5 and args.precision == "fast"
     if not (want_cpu or want_par or want_tol):
         state_dict = None
     pipe = Diffuman4DPipeline(None, unet, DDIMScheduler(), dev)
@@ -856,13 +902,15 @@ def main():
     else:
         # set-up (untimed, not part of the W warm-up steps): the task states the passes below use, each run once
         k_pr = max(2, min(args.steps, 8))
-        ur.prepare(args.steps, args.warmup, 2, k_pr)
+        ur.prepare(args.steps, args.warmup, *((2, k_pr) if args.full else ()))
         run_units(0, args.warmup)  # W warm-up steps, dealt to the streams the way the timed steps are
         barrier()
         t0 = time.perf_counter()
         run_units(args.warmup, args.steps)
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            write_outputs(timed_outputs(ur, args.steps), args.dump_outputs)
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if shared else dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -870,7 +918,7 @@ def main():
     # Same-mode baseline for the N > 1 lines (which default to `grid`): ONE pass over the real 48 x 150 round structure on this
     # GPU, same depth rule, same runner code path (loader pool, task streams, per-round barrier) -> secondary.grid.  Not `value`.
     grid_secondary = None
-    if mode == "task" and world == 1 and not args.config5 and not args.no_grid_secondary:
+    if args.full and mode == "task" and world == 1 and not args.config5 and not args.no_grid_secondary:
         gdepth = grid_depth(args.steps)
         barrier()
         tg = time.perf_counter()
@@ -887,7 +935,7 @@ def main():
     # reference computes it for the conditioning frames too and drops it; latents bitwise equal, modelcheck
     # pipeline_prune_cond_rows*).
     prune_info = None
-    if mode == "task" and world == 1 and not args.prune_cond_rows and not args.no_vae:
+    if args.full and mode == "task" and world == 1 and not args.prune_cond_rows and not args.no_vae:
         pipe.prune_cond_rows = True
         run_units(args.warmup + args.steps, 2)
         barrier()
@@ -898,54 +946,73 @@ def main():
         pipe.prune_cond_rows = False
         prune_info = {"ms_per_step": round(tp / k_pr * 1e3, 3), "latents_per_s": round(LATENTS_PER_UNIT * k_pr / tp, 4), "steps": k_pr,
                       "note": "extension, not the judged value: noise predictions of conditioning frames are not computed (bitwise-equal latents)"}
-    # roofline pass: K units, one stack of tasks at a time (the stacks of the timed region, on one stream), an event pair around every
-    # attention launch on the launch stream.  With several task streams the launches of different stacks overlap on the device, so
-    # per-launch intervals taken inside the timed region above would measure the mix, not the kernel.
-    k_roof = min(args.steps, 4) if mode == "grid" else args.steps
-    ur.prepare_single(k_roof, min(ur.batch, max(1, args.steps)))
-    ops.KERNEL_TIMER = timer = []
-    t1 = time.perf_counter()
-    roof_sizes = ur.run_single_stream(args.warmup + args.steps, k_roof)
-    torch.cuda.synchronize()
-    dt_single = time.perf_counter() - t1
-    ops.KERNEL_TIMER = None
-
-    # per-family breakdown from one extra, UNTIMED stack with an event pair around every launch (the event records
-    # themselves would cost about 1 % inside the timed region); ms are per unit of the stack
-    breakdown = None
-    if rank == 0 or shard is not None:  # a frame-sharded unit contains collectives: every rank has to run it
-        ops.PROFILE = prof = []
-        prof_size = ur.run_single_stream(args.warmup + 2 * args.steps, min(ur.batch, max(1, args.steps)))[0]
+    # --full only: the figures below take passes of their own
+    breakdown = roofline = None
+    if args.full:
+        # roofline pass: K units, one stack of tasks at a time (the stacks of the timed region, on one stream), an event pair around every
+        # attention launch on the launch stream.  With several task streams the launches of different stacks overlap on the device, so
+        # per-launch intervals taken inside the timed region above would measure the mix, not the kernel.
+        k_roof = min(args.steps, 4) if mode == "grid" else args.steps
+        ur.prepare_single(k_roof, min(ur.batch, max(1, args.steps)))
+        ops.KERNEL_TIMER = timer = []
+        t1 = time.perf_counter()
+        roof_sizes = ur.run_single_stream(args.warmup + args.steps, k_roof)
         torch.cuda.synchronize()
-        ops.PROFILE = None
-    if rank == 0:
-        # `roofline` above is the largest single kernel, this is everything
-        breakdown = family_rows(prof, prof_size)
+        dt_single = time.perf_counter() - t1
+        ops.KERNEL_TIMER = None
+
+        # per-family breakdown from one extra, UNTIMED stack with an event pair around every launch (the event records
+        # themselves would cost about 1 % inside the timed region); ms are per unit of the stack
+        if rank == 0 or shard is not None:  # a frame-sharded unit contains collectives: every rank has to run it
+            ops.PROFILE = prof = []
+            prof_size = ur.run_single_stream(args.warmup + 2 * args.steps, min(ur.batch, max(1, args.steps)))[0]
+            torch.cuda.synchronize()
+            ops.PROFILE = None
+        if rank == 0:
+            # `roofline` above is the largest single kernel, this is everything
+            breakdown = family_rows(prof, prof_size)
+        # HBM traffic of the attention kernel from PMC counters (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of
+        # this same command, tools/profile_bench.sh -> profiles/*attn_traffic_pmc.json): bytes per launch = (2*FETCH_SIZE +
+        # WRITE_SIZE) KiB, the factor 2 being the gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md (HBM section).
+        traffic, traffic_file = None, None
+        for tf in sorted((ROOT / "profiles").glob("r*_attn_traffic_pmc.json"), reverse=True):
+            t = json.loads(tf.read_text())
+            if (LAT_H, LAT_W) == (72, 40) and int(t.get("task_batch", 1)) == kb:  # the newest record taken on the stacks this run launches
+                traffic = int((2 * t["FETCH_SIZE"]["avg_kb"] + t["WRITE_SIZE"]["avg_kb"]) * 1024)
+                traffic_file = tf.name
+                break
+        # MFMA-busy fraction of the same kernel from its own PMC pass (SQ_VALU_MFMA_BUSY_CYCLES against GRBM_GUI_ACTIVE, i.e. at
+        # the clock the chip actually ran under this load; tools/mfma_busy_summary.py -> profiles/*attn_mfma_busy_pmc.json)
+        mfma_busy = None
+        for mf in sorted((ROOT / "profiles").glob("r*_attn_mfma_busy_pmc.json"), reverse=True):
+            if (LAT_H, LAT_W) == (72, 40):
+                m = json.loads(mf.read_text())
+                mfma_busy = {"busy_frac_at_actual_clock": m.get("mfma_busy"), "clock_ghz": m.get("clock_ghz"),
+                             "frac_of_nominal_peak": m.get("frac_of_nominal_peak"), "source": f"profiles/{mf.name}"}
+            break
+        attn_ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in timer)
+        attn_fl = sum(f for _, f, _, _ in timer)
+        achieved = attn_fl / (attn_ms * 1e-3) / 1e12 if attn_ms > 0 else 0.0
+        if rank == 0:
+            roofline = {
+                "kernel": "attn64_kernel (the hand-placed 4 x 64-row form: 2-D + 3-D view/time attention, all 48 launches of a stack's 3 window "
+                          "calls; the launches whose key count is not a whole number of 64-key tiles -- the 9x5 level and the F = 24 call of the "
+                          "18x10 level, 2 % of the attention FLOPs -- run the 8-wave attn_kernel and are counted here too" +
+                          (f"; a stack = {kb} tasks sharing their calls, so a launch carries {kb} x the rows of one task)" if kb > 1 else ")"),
+                "bound": "mfma", "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
+                "traffic_note": f"avg HBM bytes per attn launch, PMC (2*FETCH_SIZE+WRITE_SIZE), profiles/{traffic_file} (collected on this "
+                                f"command with --task-streams 1, i.e. the same stacks of {kb}); algorithmic Q+K+V+O bytes average "
+                                f"{152 * kb}e6 per launch",
+                "avg_launch_ms": round(attn_ms / max(1, len(timer)), 4), "launches": len(timer),
+                "measured_in": f"a separate pass of {k_roof} units (2 spatial + 1 temporal window calls each) in stacks of {sorted(set(roof_sizes), reverse=True)} "
+                               f"with one stack in flight ({dt_single / max(1, k_roof) * 1e3:.1f} ms per unit), HIP events on the launch stream",
+                "share_of_step_time": round(attn_ms * 1e-3 / dt_single, 4),
+                "mfma_busy_pmc": mfma_busy,
+            }
     if world > 1:
         dist.barrier()
     finite = ur.finite()
-    # HBM traffic of the attention kernel from PMC counters (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of
-    # this same command, tools/profile_bench.sh -> profiles/*attn_traffic_pmc.json): bytes per launch = (2*FETCH_SIZE +
-    # WRITE_SIZE) KiB, the factor 2 being the gfx950 FETCH_SIZE correction of MI355X_MICROARCH.md (HBM section).
-    traffic, traffic_file = None, None
-    for tf in sorted((ROOT / "profiles").glob("r*_attn_traffic_pmc.json"), reverse=True):
-        t = json.loads(tf.read_text())
-        if (LAT_H, LAT_W) == (72, 40) and int(t.get("task_batch", 1)) == kb:  # the newest record taken on the stacks this run launches
-            traffic = int((2 * t["FETCH_SIZE"]["avg_kb"] + t["WRITE_SIZE"]["avg_kb"]) * 1024)
-            traffic_file = tf.name
-            break
-    # MFMA-busy fraction of the same kernel from its own PMC pass (SQ_VALU_MFMA_BUSY_CYCLES against GRBM_GUI_ACTIVE, i.e. at
-    # the clock the chip actually ran under this load; tools/mfma_busy_summary.py -> profiles/*attn_mfma_busy_pmc.json)
-    mfma_busy = None
-    for mf in sorted((ROOT / "profiles").glob("r*_attn_mfma_busy_pmc.json"), reverse=True):
-        if (LAT_H, LAT_W) == (72, 40):
-            m = json.loads(mf.read_text())
-            mfma_busy = {"busy_frac_at_actual_clock": m.get("mfma_busy"), "clock_ghz": m.get("clock_ghz"),
-                         "frac_of_nominal_peak": m.get("frac_of_nominal_peak"), "source": f"profiles/{mf.name}"}
-        break
-    attn_ms = sum(e0.elapsed_time(e1) for _, _, e0, e1 in timer)
-    attn_fl = sum(f for _, f, _, _ in timer)
-    achieved = attn_fl / (attn_ms * 1e-3) / 1e12 if attn_ms > 0 else 0.0
 
     if rank == 0:
         if mode == "grid":
@@ -991,29 +1058,15 @@ def main():
                 "finite_outputs": finite,
                 "extensions": (["prune_cond_rows"] if args.prune_cond_rows else []),
             },
-            "roofline": {
-                "kernel": "attn64_kernel (the hand-placed 4 x 64-row form: 2-D + 3-D view/time attention, all 48 launches of a stack's 3 window "
-                          "calls; the launches whose key count is not a whole number of 64-key tiles -- the 9x5 level and the F = 24 call of the "
-                          "18x10 level, 2 % of the attention FLOPs -- run the 8-wave attn_kernel and are counted here too" +
-                          (f"; a stack = {kb} tasks sharing their calls, so a launch carries {kb} x the rows of one task)" if kb > 1 else ")"),
-                "bound": "mfma", "achieved": round(achieved, 2), "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": round(achieved / MFMA_PEAK_TFLOPS, 4), "traffic": traffic,
-                "traffic_note": f"avg HBM bytes per attn launch, PMC (2*FETCH_SIZE+WRITE_SIZE), profiles/{traffic_file} (collected on this "
-                                f"command with --task-streams 1, i.e. the same stacks of {kb}); algorithmic Q+K+V+O bytes average "
-                                f"{152 * kb}e6 per launch",
-                "avg_launch_ms": round(attn_ms / max(1, len(timer)), 4), "launches": len(timer),
-                "measured_in": f"a separate pass of {k_roof} units (2 spatial + 1 temporal window calls each) in stacks of {sorted(set(roof_sizes), reverse=True)} "
-                               f"with one stack in flight ({dt_single / max(1, k_roof) * 1e3:.1f} ms per unit), HIP events on the launch stream",
-                "share_of_step_time": round(attn_ms * 1e-3 / dt_single, 4),
-                "mfma_busy_pmc": mfma_busy,
-            },
         }
         if grid_info is not None:
             out["config"]["grid"] = {"calls_per_rank": grid_info["calls_per_rank"], "window_calls_per_task": grid_info["depth"],
                                      "timed_seconds": round(dt, 3)}
         # secondary figures of SURVEY.md 8d (whole job): latent-steps/s, UNet window calls/s, sustained UNet TFLOP/s
         ut = UNIT_TFLOP.get((LAT_H, LAT_W))
-        out["kernel_breakdown_one_step"] = breakdown
+        if args.full:
+            out["roofline"] = roofline
+            out["kernel_breakdown_one_step"] = breakdown
         out["secondary"] = {
             "latent_steps_per_s": round(units_total * 3 * WINDOW / dt, 2),
             "unet_calls_per_s": round(units_total * 3 / dt, 3),
@@ -1031,9 +1084,9 @@ def main():
             out["secondary"]["parity_precision"] = precision_secondary(cfg, state_dict, dev, max(2, min(args.steps, 4)), "parity", 1, 1)
         if want_tol:
             out["secondary"]["tolerance_mode"] = precision_secondary(cfg, state_dict, dev, max(3, min(args.steps, 9)), "fp16", S, kb)
-        if world == 1 and mode == "task" and not args.no_latent128 and not args.config5 and (LAT_H, LAT_W) == (72, 40):
+        if args.full and world == 1 and mode == "task" and not args.no_latent128 and not args.config5 and (LAT_H, LAT_W) == (72, 40):
             out["secondary"]["latent128"] = latent128_secondary(pipe)
-        if world == 1 and not args.no_vae and LAT_H * LAT_W <= 128 * 128:
+        if args.full and world == 1 and not args.no_vae and LAT_H * LAT_W <= 128 * 128:
             out["secondary"]["vae"] = vae_secondary(dev)
         if want_cpu:  # rank 0 at N = 1 only (the CPU sample would skew multi-rank timing)
             # one unstacked task of each domain, its latents taken through PARITY_STATE_UNITS units first: the state rounds 3-4 compared

@@ -1,10 +1,11 @@
-"""GPU: bench.py honours its output contract -- exactly one JSON line on stdout with the required fields, the
-`roofline` and `cpu_baseline` objects, and sane values."""
+"""GPU: bench.py honours its output contract -- exactly one JSON line on stdout with the required fields (with --full: the
+`roofline` and `cpu_baseline` objects), sane values, and the outputs of the timed steps under --dump-outputs."""
 import json
 import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 ROOT = Path(__file__).resolve().parent.parent
@@ -14,7 +15,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 
 @pytest.mark.gpu
 def test_bench_prints_one_contract_line():
-    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1", "--cpu-frames", "2", "--grid-frames", "12"],
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--gpus", "1", "--steps", "1", "--warmup", "1", "--cpu-frames", "2", "--grid-frames", "12"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
@@ -70,7 +71,7 @@ def test_bench_with_the_default_task_streams():
     from diffuman4d_amd.host.runner import DEFAULT_GPU_STREAMS, DEFAULT_TASK_BATCH
     sys.path.insert(0, str(ROOT))
     import bench
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-grid-secondary",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-grid-secondary",
                         "--no-parity-precision", "--no-tolerance-mode", "--no-latent128"],
                        cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -91,12 +92,43 @@ def test_bench_with_the_default_task_streams():
 @pytest.mark.gpu
 def test_bench_main_line_in_the_fp16_precision():
     """`--precision fp16` (a profiling aid: the judged line stays bf16): the same units on the fp16 precision's kernels, `dtype` says so."""
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--precision", "fp16", "--no-grid-secondary", "--no-latent128",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "3", "--warmup", "1", "--precision", "fp16", "--no-grid-secondary", "--no-latent128",
                         "--no-vae"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][0])
     assert d["dtype"] == "fp16" and d["config"]["precision"] == "fp16" and d["config"]["finite_outputs"] is True and "cpu_baseline" not in d
     assert "tolerance_mode" not in d["secondary"] and "parity_precision" not in d["secondary"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_their_outputs(tmp_path):
+    """A plain run (no --full): set-up, warm-up, the K timed steps, the line -- no extra passes behind it -- and with --dump-outputs the
+    target-row latents of the task states the timed steps ran, float32, within 64 MB."""
+    from diffuman4d_amd.host.runner import DEFAULT_GPU_STREAMS, DEFAULT_TASK_BATCH
+    sys.path.insert(0, str(ROOT))
+    import bench
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)],
+                       cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"} <= set(d)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "latents/s" and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2.0 / (d["ms_per_step"] * 1e-3)) < 1e-2 * d["value"]
+    assert d["config"]["finite_outputs"] is True
+    assert not {"roofline", "cpu_baseline", "parity", "kernel_breakdown_one_step"} & set(d)
+    assert not {"grid", "prune_cond_rows", "parity_precision", "tolerance_mode", "latent128", "vae"} & set(d["secondary"])
+    S, kb = d["config"]["task_streams"], d["config"]["task_batch"]
+    assert (S, kb) == (min(3, DEFAULT_GPU_STREAMS), DEFAULT_TASK_BATCH)
+    want = {f"latents_stream{si}_stack{z}_{dom}.npy" for si, sizes in enumerate(bench.deal_units(3, S, kb)) for z in sizes
+            for dom in ("spatial", "temporal")}
+    files = {f.name: f for f in tmp_path.iterdir()}
+    assert set(files) == want and sum(f.stat().st_size for f in files.values()) <= 64 * 2 ** 20
+    for name, f in files.items():
+        a = np.load(f)
+        z = int(name.split("_stack")[1].split("_")[0])
+        assert a.dtype == np.float32 and a.shape == (z * (44 if "spatial" in name else 150), 72 * 40, 4) and np.isfinite(a).all()
 
 
 @pytest.mark.gpu

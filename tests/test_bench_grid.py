@@ -100,6 +100,47 @@ def test_unit_runner_runs_every_unit_once(small_latents, streams, batch):
     assert total() - base == pytest.approx((5 + 20 + 7) * 3 * 12 * 16)
 
 
+def test_dump_outputs_are_the_target_latents_of_the_timed_task_states(small_latents, tmp_path):
+    """--dump-outputs: the latents of every task state the timed units ran (target rows only), float32, one .npy per state and domain;
+    above the byte budget a seeded sample of each that two runs with the same arguments draw alike."""
+    fake = FakeDevicePipeline()
+    fake.dtype = torch.float32
+    ur = bench.UnitRunner(fake, torch.device("cpu"), 2, 2)
+    ur.prepare(3, 1)
+    ur.run(0, 1)
+    ur.run(1, 3)
+    arrays = bench.timed_outputs(ur, 3)  # 3 units on 2 streams in stacks of 2: stream 0 one stack of 2, stream 1 one single task
+    assert set(arrays) == {f"latents_stream{si}_stack{z}_{d}" for si, z in ((0, 2), (1, 1)) for d in ("spatial", "temporal")}
+    for (si, z), targets in (((0, 2), (44, 150)), ((1, 1), (44, 150))):
+        for d, n in zip(("spatial", "temporal"), targets):
+            a, t = arrays[f"latents_stream{si}_stack{z}_{d}"], ur.task_set(si, z)[d]
+            assert a.dtype == np.float32 and a.shape == (z * n, 2 * 2, 4)
+            assert np.array_equal(a, t["lat"][t["cm"][:, 0, 0] != 0].numpy())
+    bench.write_outputs(arrays, tmp_path / "full")
+    for name, a in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "full" / f"{name}.npy"), a)
+    total = sum(a.nbytes for a in arrays.values())
+    for rep in ("s1", "s2"):
+        bench.write_outputs(arrays, tmp_path / rep, budget=total // 4)
+    written = 0
+    for name, a in arrays.items():
+        s1, s2 = np.load(tmp_path / "s1" / f"{name}.npy"), np.load(tmp_path / "s2" / f"{name}.npy")
+        assert s1.dtype == np.float32 and s1.size == a.size // 4 and np.array_equal(s1, s2)
+        assert np.isin(s1, a.reshape(-1)).all()
+        written += s1.nbytes
+    assert written <= total // 4
+
+
+def test_plain_run_is_the_default(monkeypatch):
+    """Everything beyond the headline figure is opt-in (--full); --dump-outputs takes a directory."""
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (5, 2)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "out"
+
+
 def _worker(rank, world, port, outdir, task_batch=1):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     dist.init_process_group("gloo", rank=rank, world_size=world)

@@ -1,19 +1,18 @@
-"""CPU, build container only (needs /root/reference): the reference's OWN SlidingIterativeSampler + SamplingRunner
-(imported through oracle/refshim.py) against (a) oracle/sampler.py, the restatement the GPU test uses where the reference
-checkout is absent, and (b) this repo's product sampler + runner -- all three driving the same recording pipeline.
+"""CPU: the reference's OWN SlidingIterativeSampler + SamplingRunner -- their run on the recording pipeline below, kept in
+tests/golden/reference_protocol.pt (recorded through oracle/refshim.py by tests/golden/make_golden_protocol.py) -- against
+(a) oracle/sampler.py, the restatement the GPU test uses, and (b) this repo's product sampler + runner, both driving the same
+recording pipeline.
 
 What must be identical: the sequence of ``sliding_iterative_denoise`` calls (keyword names, tensor shapes / dtypes /
 devices, None-ness of ``latents``, scalar arguments) and the final grid (latents and timestep indices of every cell)."""
 import sys
 from pathlib import Path
 
-import pytest
 import torch
 
 ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
-HAVE_REF = Path("/root/reference/src/samplers/sliding_iterative_sampler.py").exists()
-pytestmark = pytest.mark.skipif(not HAVE_REF, reason="the reference checkout exists only in the build container")
+GOLDEN = ROOT / "tests" / "golden" / "reference_protocol.pt"
 
 from diffuman4d_amd.host.dataset import SyntheticSpaTemDataset  # noqa: E402
 from stubs import StubPipeline  # noqa: E402
@@ -49,21 +48,22 @@ def _grid(s):
             {c: dict(d) for c, d in s.timestep_indices.items()})
 
 
+class _Recorded:
+    """A recorded sampler (all_tasks, labels, latents, timestep_indices) or pipeline (trace, calls) of the reference."""
+
+    def __init__(self, d):
+        self.__dict__.update(d)
+
+
 def _run(kind, n_pipes=1):
     ds = SyntheticSpaTemDataset(height=16, width=16, num_cameras=48)
     pipes = [RecordingPipeline() for _ in range(n_pipes)]
-    if kind == "reference":
-        from oracle import refshim
-        refshim.install()
-        import src.samplers.sliding_iterative_sampler as ref_mod
-        from src.samplers.sampling_runner import SamplingRunner
-        import src.samplers.sampling_runner as run_mod
-        ref_mod.save_sampling_results = lambda *a, **k: None  # the writer is tested separately (tests/test_results.py)
-        ref_mod.check_sampling_results = lambda *a, **k: True
-        run_mod.check_sampling_results = lambda *a, **k: True
-        s = ref_mod.SlidingIterativeSampler(ds, pipes, "/tmp/dm4d_unused", **KW)
-        SamplingRunner(s).inference()
-    elif kind == "oracle":
+    if kind == "reference":  # the recorded run of the reference's own classes (tests/golden/make_golden_protocol.py)
+        g = torch.load(GOLDEN)
+        assert g["kw"] == KW, "tests/golden/reference_protocol.pt was recorded with other sampler arguments"
+        r = g[f"pipes{n_pipes}"]
+        return _Recorded(r), [_Recorded(dict(trace=t, calls=c)) for t, c in zip(r["traces"], r["calls"])]
+    if kind == "oracle":
         from oracle.sampler import OracleRunner, OracleSampler
         s = OracleSampler(ds, pipes, "/tmp/dm4d_unused", **KW)
         OracleRunner(s).inference()

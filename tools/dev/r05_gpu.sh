@@ -35,7 +35,7 @@ case $stage in
     timeout 1200 python tests/modelcheck.py fp16_unet_sd21 fp16_vae_sd fp16_demo3d fp16_multiround > $out/r05_modelcheck_fp16_sd.log 2>&1; quiet $out/r05_modelcheck_fp16_sd.log 600 | tail -24
     timeout 900 python tests/modelcheck.py par_unet_sd21_72x40_f24 par_unet_frame par_pipeline_shard par_pipeline_prune > $out/r05_modelcheck_par_holes.log 2>&1
     quiet $out/r05_modelcheck_par_holes.log 600 | tail -12
-    ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/r05_bench_a.json 2> $out/r05_bench_a.err ) 2> $out/r05_bench_a.time; tail -3 $out/r05_bench_a.time
+    ( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r05_bench_a.json 2> $out/r05_bench_a.err ) 2> $out/r05_bench_a.time; tail -3 $out/r05_bench_a.time
     bench_line $out/r05_bench_a.json "driver command:"
     tail -5 $out/r05_bench_a.err | cut -c1-300
     ;;
@@ -46,7 +46,7 @@ case $stage in
     timeout 1200 python tests/modelcheck.py fp16_unet_spatial fp16_vae fp16_pipeline_spatial fp16_unet_sd21 fp16_vae_sd fp16_demo3d fp16_multiround \
         fp16_unet_frame fp16_pipeline_shard par_unet_sd21_72x40_f24 par_unet_spatial par_pipeline_spatial > $out/r05_b_modelcheck.log 2>&1
     quiet $out/r05_b_modelcheck.log 600 | grep -v "RCCL\|HIP version\|ROCm version\|Hostname\|Librccl\|socket.cpp" | tail -30
-    ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/r05_bench_b.json 2> $out/r05_bench_b.err ) 2> $out/r05_bench_b.time; tail -3 $out/r05_bench_b.time
+    ( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r05_bench_b.json 2> $out/r05_bench_b.err ) 2> $out/r05_bench_b.time; tail -3 $out/r05_bench_b.time
     bench_line $out/r05_bench_b.json "driver command:"
     python - <<'PY'
 import json
@@ -63,7 +63,7 @@ PY
     cp diffuman4d_amd/libdm4d.so /tmp/cur.so
     for rep in 1 2; do for v in cur csouter ffabl; do
       if [ $v = cur ]; then cp /tmp/cur.so diffuman4d_amd/libdm4d.so; else cp tools/dev/libdm4d_$v.so diffuman4d_amd/libdm4d.so; fi
-      timeout 300 python bench.py $ab > $out/r05_ab_${v}_$rep.json 2>/dev/null; bench_line $out/r05_ab_${v}_$rep.json "A/B $v rep $rep:"
+      timeout 300 python bench.py --full $ab > $out/r05_ab_${v}_$rep.json 2>/dev/null; bench_line $out/r05_ab_${v}_$rep.json "A/B $v rep $rep:"
     done; done
     cp tools/dev/libdm4d_csouter.so diffuman4d_amd/libdm4d.so
     timeout 600 python tests/opcheck.py conv > $out/r05_ab_csouter_opcheck_conv.log 2>&1; tail -3 $out/r05_ab_csouter_opcheck_conv.log
@@ -73,7 +73,7 @@ PY
     timeout 900 python tests/opcheck.py h16_ conv_up2x > $out/r05_c_opcheck_h16.log 2>&1; quiet $out/r05_c_opcheck_h16.log | grep -v "^PASS" | tail -30
     timeout 1200 python tests/modelcheck.py fp16_ > $out/r05_c_modelcheck_fp16.log 2>&1
     quiet $out/r05_c_modelcheck_fp16.log 600 | grep -v "RCCL\|HIP version\|ROCm version\|Hostname\|Librccl\|socket.cpp\|^    \[golden\|^    \[pipeline" | tail -40
-    ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/r05_bench_c.json 2> $out/r05_bench_c.err ) 2> $out/r05_bench_c.time; tail -3 $out/r05_bench_c.time
+    ( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r05_bench_c.json 2> $out/r05_bench_c.err ) 2> $out/r05_bench_c.time; tail -3 $out/r05_bench_c.time
     bench_line $out/r05_bench_c.json "driver command:"
     python - <<'PY'
 import json
@@ -95,11 +95,11 @@ PY
     ab="--steps 9 --warmup 3 --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-latent128"
     for rep in 1 2; do for v in cur dot2; do
       if [ $v = cur ]; then cp /tmp/cur.so diffuman4d_amd/libdm4d.so; else cp tools/dev/libdm4d_$v.so diffuman4d_amd/libdm4d.so; fi
-      timeout 300 python bench.py $ab > $out/r05_dot2_${v}_$rep.json 2>/dev/null; bench_line $out/r05_dot2_${v}_$rep.json "A/B $v rep $rep:"
+      timeout 300 python bench.py --full $ab > $out/r05_dot2_${v}_$rep.json 2>/dev/null; bench_line $out/r05_dot2_${v}_$rep.json "A/B $v rep $rep:"
     done; done
     for v in cur dot2; do
       if [ $v = cur ]; then cp /tmp/cur.so diffuman4d_amd/libdm4d.so; else cp tools/dev/libdm4d_$v.so diffuman4d_amd/libdm4d.so; fi
-      timeout 300 python bench.py --latent 128x128 --steps 2 --warmup 1 --task-streams 1 --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128 > $out/r05_dot2_${v}_128.json 2>/dev/null
+      timeout 300 python bench.py --full --latent 128x128 --steps 2 --warmup 1 --task-streams 1 --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128 > $out/r05_dot2_${v}_128.json 2>/dev/null
       bench_line $out/r05_dot2_${v}_128.json "A/B $v 128x128:"
     done
     cp /tmp/cur.so diffuman4d_amd/libdm4d.so
@@ -110,23 +110,23 @@ PY
         > $out/r05_gnraw_modelcheck.log 2>&1; quiet $out/r05_gnraw_modelcheck.log 500 | grep "^PASS\|^FAIL\|^ERROR\|modelcheck:" | tail -12
     ab="--steps 12 --warmup 3 --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-latent128"
     for rep in 1 2; do for ts in 3 4 6; do
-      timeout 300 python bench.py $ab --task-streams $ts > $out/r05_ts${ts}_$rep.json 2>/dev/null; bench_line $out/r05_ts${ts}_$rep.json "task streams $ts rep $rep:"
+      timeout 300 python bench.py --full $ab --task-streams $ts > $out/r05_ts${ts}_$rep.json 2>/dev/null; bench_line $out/r05_ts${ts}_$rep.json "task streams $ts rep $rep:"
     done; done
     ;;
   final1)  # the whole GPU suite, smoke(), the driver command on the final tree
     ( time timeout 2400 python -m pytest tests -m gpu -q > $out/r05_pytest_gpu.log 2>&1 ) 2> $out/r05_pytest_gpu.time; tail -5 $out/r05_pytest_gpu.log; tail -3 $out/r05_pytest_gpu.time
     timeout 600 python -c "import __graft_entry__ as g; g.smoke()" > $out/r05_smoke.log 2>&1; tail -2 $out/r05_smoke.log | cut -c1-1500
-    ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
+    ( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
     bench_line $out/r05_bench.json "driver command:"
     ;;
   final2)  # the driver command once more on the final tree (bench.py gained the tolerance mode's evidence fields after final1), then the records: rocprofv3 kernel tables of the three precisions, PMC passes of the fast one, BASELINE configs[4], the CLI path in the fp16 precision
-    ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
+    ( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
     bench_line $out/r05_bench.json "driver command:"
     bash tools/profile_bench.sh r05 fast > $out/r05_profile.log 2>&1; tail -14 $out/r05_profile.log | cut -c1-220
     bash tools/profile_bench.sh r05_fp16 fp16 stats > $out/r05_profile_fp16.log 2>&1; tail -12 $out/r05_profile_fp16.log | cut -c1-200
     bash tools/profile_bench.sh r05_parity parity stats > $out/r05_profile_parity.log 2>&1; tail -8 $out/r05_profile_parity.log | cut -c1-200
-    timeout 600 python bench.py --config5 --steps 12 --warmup 3 --no-vae > $out/r05_bench_config5.json 2> $out/r05_bench_config5.err; bench_line $out/r05_bench_config5.json "config5 (48 x 225, sliding_default):"
-    timeout 600 python bench.py --config5 --precision fp16 --steps 12 --warmup 3 --no-vae > $out/r05_bench_config5_fp16.json 2>/dev/null; bench_line $out/r05_bench_config5_fp16.json "config5, fp16 precision:"
+    timeout 600 python bench.py --full --config5 --steps 12 --warmup 3 --no-vae > $out/r05_bench_config5.json 2> $out/r05_bench_config5.err; bench_line $out/r05_bench_config5.json "config5 (48 x 225, sliding_default):"
+    timeout 600 python bench.py --full --config5 --precision fp16 --steps 12 --warmup 3 --no-vae > $out/r05_bench_config5_fp16.json 2>/dev/null; bench_line $out/r05_bench_config5_fp16.json "config5, fp16 precision:"
     timeout 900 python tools/e2e_demo.py --exp demo_4d --fast-vae --prune --writers 2 --device-results --writer-processes 12 --host-threads 8 --depth 3 \
         sampler.plucker_on_device=true data.plucker=cameras model.precision=fp16 > $out/r05_e2e_demo4d_fp16.json 2> $out/r05_e2e_demo4d_fp16.err
     cat $out/r05_e2e_demo4d_fp16.json | cut -c1-600; tail -2 $out/r05_e2e_demo4d_fp16.err | cut -c1-300
@@ -135,7 +135,7 @@ PY
     ab="--steps 12 --warmup 6 --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
     for rep in 1 2; do
       for cfg in "1 3" "2 1" "2 2" "3 1" "3 2" "6 1"; do set -- $cfg
-        timeout 300 python bench.py $ab --task-batch $1 --task-streams $2 > $out/r05_batch_b$1_s$2_$rep.json 2>/dev/null; bench_line $out/r05_batch_b$1_s$2_$rep.json "task-batch $1 x streams $2 rep $rep:"
+        timeout 300 python bench.py --full $ab --task-batch $1 --task-streams $2 > $out/r05_batch_b$1_s$2_$rep.json 2>/dev/null; bench_line $out/r05_batch_b$1_s$2_$rep.json "task-batch $1 x streams $2 rep $rep:"
       done
     done
     ;;
@@ -145,12 +145,12 @@ PY
     ab="--steps 24 --warmup 12 --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
     for rep in 1 2; do
       for cfg in "1 3" "2 2" "3 2" "2 3" "4 2"; do set -- $cfg
-        timeout 300 python bench.py $ab --task-batch $1 --task-streams $2 > $out/r05_stack_b$1_s$2_$rep.json 2>$out/r05_stack_err.log || tail -5 $out/r05_stack_err.log
+        timeout 300 python bench.py --full $ab --task-batch $1 --task-streams $2 > $out/r05_stack_b$1_s$2_$rep.json 2>$out/r05_stack_err.log || tail -5 $out/r05_stack_err.log
         bench_line $out/r05_stack_b$1_s$2_$rep.json "batch $1 x streams $2 rep $rep:"
       done
     done
     for cfg in "1 3" "2 2" "3 2"; do set -- $cfg
-      timeout 300 python bench.py $ab --precision fp16 --task-batch $1 --task-streams $2 > $out/r05_stack_fp16_b$1_s$2.json 2>$out/r05_stack_err.log || tail -5 $out/r05_stack_err.log
+      timeout 300 python bench.py --full $ab --precision fp16 --task-batch $1 --task-streams $2 > $out/r05_stack_fp16_b$1_s$2.json 2>$out/r05_stack_err.log || tail -5 $out/r05_stack_err.log
       bench_line $out/r05_stack_fp16_b$1_s$2.json "fp16 precision, batch $1 x streams $2:"
     done
     for cfg in "1 3" "2 2" "3 2"; do set -- $cfg
@@ -163,7 +163,7 @@ PY
            # shapes, then the GPU tests of everything the change touched (pipeline / sampler / runner / bench) and smoke()
     timeout 600 python -m pytest tests/test_bench_gpu.py -q -x -k "default_task_streams" > $out/r05_pytest_canary.log 2>&1 || { tail -30 $out/r05_pytest_canary.log | cut -c1-300; exit 1; }
     tail -1 $out/r05_pytest_canary.log
-    ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
+    ( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
     bench_line $out/r05_bench.json "driver command:"; tail -3 $out/r05_bench.err | cut -c1-300
     bash tools/profile_bench.sh r05b fast > $out/r05b_profile.log 2>&1; tail -14 $out/r05b_profile.log | cut -c1-220
     ( time timeout 1500 python -m pytest tests/test_bench_gpu.py tests/test_e2e_gpu.py tests/test_reference_protocol_gpu.py tests/test_entry_gpu.py tests/test_model_gpu.py -q \
@@ -174,12 +174,12 @@ PY
   final4)  # the multi-round job in stacks against its task-by-task fixture, the UNet-call distance against the input state, the driver command
     timeout 900 python tests/modelcheck.py multiround par_multiround fp16_multiround > $out/r05_modelcheck_multiround_stacks.log 2>&1; grep "^PASS\|^FAIL\|^ERROR\|multi-round" $out/r05_modelcheck_multiround_stacks.log | cut -c1-330
     timeout 300 python tools/dev/parity_state_probe.py > $out/r05_parity_state_probe.log 2>&1; grep -v "^/opt\|warn" $out/r05_parity_state_probe.log | tail -12
-    ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
+    ( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
     bench_line $out/r05_bench.json "driver command:"; tail -3 $out/r05_bench.err | cut -c1-300
     ;;
   final5)  # the driver command with the stack-of-2 PMC records in profiles/ (roofline.traffic), then the CLI path on a 48 x 64 grid
            # (64 + 44 + 64 tasks) with the new runner defaults and with round 4's (the new ones FIRST: whatever runs first meets the colder chip)
-    ( time timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
+    ( time timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/r05_bench.json 2> $out/r05_bench.err ) 2> $out/r05_bench.time; tail -3 $out/r05_bench.time
     bench_line $out/r05_bench.json "driver command:"; tail -2 $out/r05_bench.err | cut -c1-300
     for cfg in "2 2" "1 3"; do set -- $cfg
       timeout 230 python tools/e2e_demo.py --exp demo_4d --fast-vae --prune --writers 2 --device-results --writer-processes 12 --host-threads 8 --depth 4 \
@@ -189,7 +189,7 @@ PY
     ;;
   final6)  # the driver command's GPU part with the final runner defaults (3 streams of 2-task stacks); the CPU baseline / parity objects of the
            # full command do not depend on the defaults (final5's record has them) and the round's GPU budget ends here
-    timeout 100 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity-precision --no-latent128 > $out/r05_bench_default_3x2.json 2> $out/r05_bench_default_3x2.err
+    timeout 100 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --no-parity-precision --no-latent128 > $out/r05_bench_default_3x2.json 2> $out/r05_bench_default_3x2.err
     bench_line $out/r05_bench_default_3x2.json "default (3 streams x 2-task stacks), no CPU legs:"; tail -2 $out/r05_bench_default_3x2.err | cut -c1-300
     ;;
   *) echo "unknown stage $stage"; exit 2;;

@@ -1,7 +1,7 @@
 #!/bin/bash
 # bench A/B inside one call: 8-wave attention kernel (DM4D_ATTN64=0) against attn64, fast and fp16 precisions
 export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
 for prec in fast fp16; do
 for a in 0 1; do

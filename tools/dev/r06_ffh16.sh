@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 {
 echo "=== opcheck"; timeout 900 python tests/opcheck.py h16_ff_proj h16_gemm_resid ff_proj_fused_128 2>&1 | grep -E "PASS|FAIL|ERROR|opcheck:|Error"
 echo "=== fp16 model cases"; timeout 1200 python tests/modelcheck.py fp16_unet_sd21 fp16_golden fp16_demo3d fp16_demo4dtiny fp16_multiround 2>&1 | grep -E "^\s+\[|PASS|FAIL|ERROR|modelcheck:"
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
 for a in 0 1; do
   DM4D_FF_PROJ_FUSED=$a timeout 600 python bench.py $Q --precision fp16 2>/dev/null | tail -1 | python -c "

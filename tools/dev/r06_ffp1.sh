@@ -14,7 +14,7 @@ for v in base ffp1d3 ffp1d4 ffp1d6; do
   if [ $v = base ]; then cp /tmp/base.so diffuman4d_amd/libdm4d.so; else cp tools/dev/libdm4d_$v.so diffuman4d_amd/libdm4d.so; fi
   echo "=== $v: opbench (round $round)"; timeout 300 python tests/opbench.py ffproj 2>&1 | grep "one launch"
 done; done
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
 for v in base ffp1d4 ffp1d6; do
   if [ $v = base ]; then cp /tmp/base.so diffuman4d_amd/libdm4d.so; else cp tools/dev/libdm4d_$v.so diffuman4d_amd/libdm4d.so; fi

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round-6 records on the final tree: stacks / streams A/B, rocprofv3 profiles (kernel table + PMC), the driver's bench command
 export TMPDIR=/tmp
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 [ -n "${SKIP_AB:-}" ] || {
 for round in 1 2; do
 for cfg in "3 2" "3 4" "2 4" "2 2"; do

@@ -7,7 +7,7 @@ echo "=== opcheck"; timeout 900 python tests/opcheck.py h16_gn h16_conv_l0 h16_c
 for a in 0 1; do
 echo "=== fp16 model cases, DM4D_H16_CONV1_F16=$a"; DM4D_H16_CONV1_F16=$a timeout 1200 python tests/modelcheck.py fp16_unet_sd21 fp16_golden_spatial fp16_golden_temporal_v fp16_golden_pose fp16_demo3d fp16_demo4dtiny fp16_multiround 2>&1 | grep -E "PASS|FAIL|ERROR|modelcheck:" | cut -c1-120
 done
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
 for a in 0 1; do
   DM4D_H16_CONV1_F16=$a timeout 600 python bench.py $Q --precision fp16 2>/dev/null | tail -1 | python -c "

@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 cp diffuman4d_amd/libdm4d.so /tmp/new.so
 {
 echo "=== parity (new)"; timeout 900 python tests/opcheck.py h16_gemm h16_conv h16_ff 2>&1 | grep -E "FAIL|ERROR|opcheck:|Error"
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
 for v in loop new; do
   if [ $v = new ]; then cp /tmp/new.so diffuman4d_amd/libdm4d.so; else cp tools/dev/libdm4d_h16loop.so diffuman4d_amd/libdm4d.so; fi

@@ -3,7 +3,7 @@
 # bank-conflict cycles, LDS-busy cycles, per launch (separate --pmc passes, kernel trace only)
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
-BENCH="python bench.py --steps 4 --warmup 2 --no-cpu-baseline --task-streams 1 --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+BENCH="python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --task-streams 1 --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 OUT=gpurun_out/prof_lds
 rm -rf "$OUT"

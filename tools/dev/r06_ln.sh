@@ -5,7 +5,7 @@ export TMPDIR=/tmp
 cp diffuman4d_amd/libdm4d.so /tmp/new.so
 {
 echo "=== parity (R = 2)"; timeout 600 python tests/opcheck.py layernorm ln h16_layernorm h16_ln par_ln par_layernorm 2>&1 | grep -E "PASS|FAIL|ERROR|opcheck:|Error" | cut -c1-110
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
 for prec in fast fp16; do
 for v in ln1 new ln4; do

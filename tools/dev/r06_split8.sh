@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 {
 echo "=== parity"; timeout 600 python tests/opcheck.py h16_split 2>&1 | grep -E "PASS|FAIL|ERROR|opcheck:|Error"
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
   timeout 600 python bench.py $Q --precision fp16 2>/dev/null | tail -1 | python -c "
 import json,sys

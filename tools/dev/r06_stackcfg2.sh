@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 cp diffuman4d_amd/libdm4d.so /tmp/new.so
 {
 echo "=== parity (new)"; timeout 900 python tests/opcheck.py conv_batch_invariance gemm_ conv_l0 h16_conv_l0 h16_gemm_qkv 2>&1 | grep -E "FAIL|ERROR|opcheck:|Error"
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
 for prec in fast fp16; do
 for v in base new; do

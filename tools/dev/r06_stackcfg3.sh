@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 cp diffuman4d_amd/libdm4d.so /tmp/new.so
 {
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
 for prec in fast fp16; do
 for v in base new; do

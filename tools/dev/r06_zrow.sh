@@ -10,7 +10,7 @@ for v in base new; do
   if [ $v = new ]; then cp /tmp/new.so diffuman4d_amd/libdm4d.so; else cp tools/dev/libdm4d_zrow0.so diffuman4d_amd/libdm4d.so; fi
   echo "=== $v: opbench conv (round $round)"; timeout 300 python tests/opbench.py conv 2>&1 | grep -E "B64|vae" | cut -c1-120
 done; done
-Q="--no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
+Q="--full --no-cpu-baseline --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128"
 for round in 1 2; do
 for prec in fast fp16; do
 for v in base new; do

@@ -18,7 +18,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 # kernel intervals of different stacks overlap in the trace.  --steps 4 --warmup 2: every pass of the run (set-up, warm-up, timed, prune,
 # roofline, breakdown) is then made of whole stacks of the default task_batch (2), so every launch of a kernel carries the same rows and the
 # trace's average duration per kernel is the average of ONE launch shape per layer
-BENCH="python bench.py --steps 4 --warmup 2 --no-cpu-baseline --task-streams 1 --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128 --precision $PREC"
+BENCH="python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --task-streams 1 --no-grid-secondary --no-vae --no-parity-precision --no-tolerance-mode --no-latent128 --precision $PREC"
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT"
 OUT=gpurun_out/prof_$TAG
 rm -rf "$OUT"

@@ -1,7 +1,7 @@
 #!/bin/bash
 # First contact with an 8-GPU MI355X node (none was available to rounds 1-6: RCCL has only ever run at world size 1 here).
 # Runs, in order and each to its own log under gpurun_out/scale/:
-#   1. the driver's scaling lines        python bench.py --gpus N --steps 20 --warmup 5        N = 1, 2, 4, 8   (grid mode at N > 1)
+#   1. the driver's scaling lines        python bench.py --full --gpus N --steps 20 --warmup 5 N = 1, 2, 4, 8   (grid mode at N > 1; --full: secondary.grid at N = 1)
 #   2. the same grid job, hybrid deal    python bench.py --gpus N --mode hybrid ...            N = 4, 8         (frame-sharded tail waves)
 #   3. the latency mode                  python bench.py --gpus N --mode frame-shard ...       N = 2, 4, 8      (BASELINE.json configs[3])
 #   4. the grid job without task stacks  python bench.py --gpus N --task-batch 1 ...           N = 8            (every line above runs the runner's
@@ -18,7 +18,7 @@ ngpu=$(python -c "import torch; print(torch.cuda.device_count())")
 echo "visible GPUs: $ngpu"
 run() {  # $1 = N, $2 = mode flag (may be empty), $3 = tag
   [ "$1" -le "$ngpu" ] || { echo "skip $3: needs $1 GPUs"; return; }
-  timeout 1200 python bench.py --gpus $1 --steps $steps --warmup $warm $2 > $out/$3.json 2> $out/$3.err || echo "$3: exit code $?"
+  timeout 1200 python bench.py --full --gpus $1 --steps $steps --warmup $warm $2 > $out/$3.json 2> $out/$3.err || echo "$3: exit code $?"
   python - "$out/$3.json" "$3" <<'PY'
 import json, sys
 try:

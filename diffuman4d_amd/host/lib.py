@@ -87,6 +87,10 @@ SIGNATURES = {
     "dm4d_layernorm_f32_f16_general": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _f]),
     "dm4d_softmax_rows_f32_f16": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _f]),
     "dm4d_attention_qscaled_kv_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i]),
+    "dm4d_attention_hd_qscaled_kv_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i]),
+    "dm4d_attention_hd_qscaled_kv_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _i]),
+    "dm4d_attention_hd_split_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i, _i, _i, _i, _f,
+                                          _i]),
     "dm4d_attn_out_ff_geglu_fused_f16": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i,
                                                _i]),
     "dm4d_pack_model_input_f32_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),

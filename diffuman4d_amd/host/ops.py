@@ -599,31 +599,51 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
 LOG2E = 1.4426950408889634
 
 
+HEAD_DIMS_HD = (40, 80, 160)  # head dimensions of the attention_hd.hip kernels (SD-1.x layout); 64 has attention.hip's own
+
+
+def _head_dim(width: int, heads: int, what: str) -> int:
+    """Head dimension of an operand `width` channels wide over `heads` heads: 64 or one of HEAD_DIMS_HD, else Dm4dError."""
+    d = width // heads if heads > 0 else 0
+    if heads <= 0 or d * heads != width or (d != 64 and d not in HEAD_DIMS_HD):
+        raise _l.Dm4dError(f"{what}: {width} channels over {heads} heads; supported head dimensions are 64, "
+                           + ", ".join(str(x) for x in HEAD_DIMS_HD))
+    return d
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, heads: int, seq: int,
               scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
               kv_seq: Optional[int] = None, q_scaled: bool = False) -> torch.Tensor:
-    """q/k/v: [batch*seq, >=heads*64] row-strided views (e.g. column slices of the fused QKV output).
+    """q/k/v: [batch*seq, >=heads*d] row-strided views (e.g. column slices of the fused QKV output), d = q.shape[1] // heads:
+    64 (attention.hip) or 40 / 80 / 160 (attention_hd.hip; pre-scaled Q only).
     kv_seq: keys per batch when K/V hold more tokens than Q (frame-sharded 3-D attention); default = seq.
     q_scaled: q already carries scale * LOG2E (folded into the to_q weights, unet._TransformerBlock)."""
     lib = _l.load()
     h16 = isinstance(q, torch.Tensor) and q.dtype == F16  # precision "fp16": fp16 Q (pre-scaled) / K / V -> fp16 O
     dt = F16 if h16 else BF16
     _req(q, "q", dt), _req(k, "k", dt), _req(v, "v", dt)
-    assert q.shape[0] == batch * seq and q.shape[1] == heads * 64, (q.shape, batch, seq, heads)
+    d = _head_dim(q.shape[1], heads, "attention")
+    assert q.shape[0] == batch * seq and q.shape[1] == heads * d, (q.shape, batch, seq, heads)
     kv_seq = seq if kv_seq is None else kv_seq
     assert k.shape[0] == batch * kv_seq and v.shape[0] == batch * kv_seq, (k.shape, batch, kv_seq)
     if out is None:
-        out = torch.empty((batch * seq, heads * 64), dtype=dt, device=q.device)
+        out = torch.empty((batch * seq, heads * d), dtype=dt, device=q.device)
     if h16 and not q_scaled:
         raise _l.Dm4dError("attention: fp16 operands need a pre-scaled Q (gemm(..., scale_cols=C, col_scale=scale * LOG2E))")
+    if d != 64 and not q_scaled:
+        raise _l.Dm4dError(f"attention: head dimension {d} needs a pre-scaled Q (gemm(..., scale_cols=C, col_scale=scale * LOG2E))")
     if scale is None:
-        scale = 0.125
+        scale = d ** -0.5
     prof = KERNEL_TIMER
     if prof is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-    with _Prof("attention", 4.0 * batch * heads * seq * kv_seq * 64, "flop", batch * seq):
-        if h16:
+    with _Prof("attention", 4.0 * batch * heads * seq * kv_seq * d, "flop", batch * seq):
+        if d != 64:
+            fn = lib.dm4d_attention_hd_qscaled_kv_f16 if h16 else lib.dm4d_attention_hd_qscaled_kv_bf16
+            rc = fn(_stream(), _p(q), _p(k), _p(v), _p(out), q.stride(0), k.stride(0), v.stride(0), out.stride(0), batch, heads, d, seq,
+                    kv_seq)
+        elif h16:
             rc = lib.dm4d_attention_qscaled_kv_f16(_stream(), _p(q), _p(k), _p(v), _p(out), q.stride(0), k.stride(0),
                                                    v.stride(0), out.stride(0), batch, heads, seq, kv_seq)
         elif q_scaled:
@@ -634,9 +654,9 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, hea
                                             v.stride(0), out.stride(0), batch, heads, seq, kv_seq, scale)
     if prof is not None:
         e1.record()
-        prof.append(("attn_kernel", 4.0 * batch * heads * seq * kv_seq * 64, e0, e1))
-    _l.check(rc, "dm4d_attention_kv_bf16")
-    if h16:
+        prof.append(("attn_kernel" if d == 64 else "attn_hd_kernel", 4.0 * batch * heads * seq * kv_seq * d, e0, e1))
+    _l.check(rc, "dm4d_attention_kv_bf16" if d == 64 else "dm4d_attention_hd_qscaled_kv")
+    if h16 or d != 64:  # oracle/replay.py recomputes the head_dim 64 launches only
         return out
     _trace("attention", out, q=q, k=k, v=v, batch=batch, heads=heads, seq=seq, kv_seq=kv_seq, scale=scale, q_scaled=q_scaled)
     return out
@@ -645,12 +665,17 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, hea
 def attention_split(qkv: Optional[torch.Tensor], batch: int, heads: int, seq: int, scale: Optional[float] = None, *,
                     q: Optional[torch.Tensor] = None, kv: Optional[torch.Tensor] = None, kv_seq: Optional[int] = None) -> torch.Tensor:
     """Parity precision: qkv [batch*seq, 6 C] = the planes gemm(split_out=True) leaves for a fused QKV projection
-    ([q_hi | k_hi | v_hi | q_lo | k_lo | v_lo], C = heads * 64) -> attention output as a two-term operand [batch*seq, 2 C].
+    ([q_hi | k_hi | v_hi | q_lo | k_lo | v_lo], C = heads * d) -> attention output as a two-term operand [batch*seq, 2 C].
     Frame-sharded form (qkv = None): q [batch*seq, 2 C] = [q_hi | q_lo] of the local queries, kv [batch*kv_seq, 4 C] =
     [k_hi | v_hi | k_lo | v_lo] of the all-gathered keys (the planes of gemm(n, w_kv, split_out=True)).
-    Three MFMAs per product, exact running-max softmax in fp32 (dm4d_attention_split_bf16)."""
+    Three MFMAs per product, exact running-max softmax in fp32 (dm4d_attention_split_bf16; head dimensions 40 / 80 / 160:
+    dm4d_attention_hd_split_bf16).  d comes from the operand widths: qkv.shape[1] // (6 heads), or q.shape[1] // (2 heads)."""
     lib = _l.load()
-    C = heads * 64
+    if qkv is not None:
+        d = _head_dim(qkv.shape[1] // 6 if qkv.shape[1] % 6 == 0 else -1, heads, "attention_split")
+    else:
+        d = _head_dim(q.shape[1] // 2 if q.shape[1] % 2 == 0 else -1, heads, "attention_split")
+    C = heads * d
     if qkv is not None:
         _req(qkv, "qkv")
         assert qkv.shape == (batch * seq, 6 * C), (qkv.shape, batch, seq, heads)
@@ -667,10 +692,15 @@ def attention_split(qkv: Optional[torch.Tensor], batch: int, heads: int, seq: in
         q_lo, k_lo, v_lo = C, 2 * C, 2 * C
         dev = q.device
     out = torch.empty((batch * seq, 2 * C), dtype=BF16, device=dev)
-    with _Prof("attention", 3 * 4.0 * batch * heads * seq * kv_seq * 64, "flop", batch * seq):  # three MFMA terms per product
-        rc = lib.dm4d_attention_split_bf16(_stream(), qp, kp, vp, _p(out), ldq, ldk, ldv, out.stride(0), q_lo, k_lo, v_lo, C, batch,
-                                           heads, seq, kv_seq, 0.125 if scale is None else scale)
-    _l.check(rc, "dm4d_attention_split_bf16")
+    scale = d ** -0.5 if scale is None else scale
+    with _Prof("attention", 3 * 4.0 * batch * heads * seq * kv_seq * d, "flop", batch * seq):  # three MFMA terms per product
+        if d == 64:
+            rc = lib.dm4d_attention_split_bf16(_stream(), qp, kp, vp, _p(out), ldq, ldk, ldv, out.stride(0), q_lo, k_lo, v_lo, C, batch,
+                                               heads, seq, kv_seq, scale)
+        else:
+            rc = lib.dm4d_attention_hd_split_bf16(_stream(), qp, kp, vp, _p(out), ldq, ldk, ldv, out.stride(0), q_lo, k_lo, v_lo, C,
+                                                  batch, heads, seq, kv_seq, scale, d)
+    _l.check(rc, "dm4d_attention_split_bf16" if d == 64 else "dm4d_attention_hd_split_bf16")
     return out
 
 

@@ -30,6 +30,11 @@ PRECISIONS = ("fast", "parity", "fp16")
 H16_CONV1_F16 = os.environ.get("DM4D_H16_CONV1_F16", "1") != "0"  # fp16 precision: conv1 -> fp16 -> norm2 (off: fp32 in between; A/B, tests)
 
 
+# head dimensions a checkpoint may give its self-attention blocks (channels / attention_head_dim): 64 (attention.hip) and the SD-1.x
+# layout's 40 / 80 / 160 (attention_hd.hip)
+HEAD_DIMS = (40, 64, 80, 160)
+
+
 def check_precision(precision: str) -> None:
     if precision not in PRECISIONS:
         raise ValueError(f"Unsupported precision: {precision}. Supported values are 'fast', 'parity' and 'fp16'.")
@@ -321,11 +326,13 @@ class _Transformer:
         while (pfx + f"transformer_blocks.{i}.norm1.weight") in W.sd:
             self.blocks.append(_TransformerBlock(W, pfx + f"transformer_blocks.{i}.", heads))
             i += 1
-        if (self.pob.shape[0] // heads) != 64:
+        d = self.pob.shape[0] // heads
+        if d * heads != self.pob.shape[0] or d not in HEAD_DIMS:
             raise NotImplementedError(
-                f"unet/config.json: block_out_channels / attention_head_dim give a head dimension of {self.pob.shape[0] // heads} at "
+                f"unet/config.json: block_out_channels / attention_head_dim give a head dimension of {d} at "
                 f"'{pfx[:-1]}' ({self.pob.shape[0]} channels over {heads} heads -- `attention_head_dim` is the NUMBER of heads, "
-                "unet_multiview_condition.py:222-228); the HIP attention kernels are built for head dimension 64 (SD-2.1 geometry)")
+                "unet_multiview_condition.py:222-228); the HIP attention kernels are built for head dimensions "
+                + ", ".join(str(x) for x in HEAD_DIMS) + " (64: SD-2.1 geometry; 40 / 80 / 160: SD-1.x, attention_head_dim = 8)")
 
     def __call__(self, x: torch.Tensor, num_frames: int, shard=None) -> torch.Tensor:
         B, H, Wd, C = x.shape

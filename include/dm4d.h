@@ -384,6 +384,23 @@ int dm4d_layernorm_f32_f16_general(void* stream, const float* X, int64_t ldx, co
 int dm4d_attention_qscaled_kv_f16(void* stream, const void* Q, const void* K, const void* V, void* O, int64_t ldq, int64_t ldk,
                                   int64_t ldv, int64_t ldo, int batch, int heads, int Lq, int Lk);
 
+/* Head dimensions 40, 80 and 160 (the SD-1.x UNet layout: attention_head_dim = 8 heads over 320 / 640 / 1280 channels; reference
+ *   unet_multiview_condition.py:184 and :222-228, attention.py:73-78).  Same contracts as the head_dim 64 entries they stand beside;
+ *   head_dim 64 is refused here (it has its own entries: dm4d_attention_qscaled_kv_bf16 / _f16, dm4d_attention_split_bf16).
+ *   Q / K / V / O are [batch * L, >= heads * head_dim] row-strided views (strides multiples of 8 elements, e.g. column slices of the
+ *   fused [M, 3 C] QKV output); the kernels read and write exactly the head's head_dim columns.  Exact running-max softmax per row, so
+ *   results do not depend on how query rows are grouped into workgroups (attention_hd.hip).
+ *   dm4d_attention_hd_qscaled_kv_bf16: as dm4d_attention_qscaled_kv_bf16 (Q carries scale * log2 e, softmax in base 2).
+ *   dm4d_attention_hd_qscaled_kv_f16:  as dm4d_attention_qscaled_kv_f16 (fp16 operands, fp16 O).
+ *   dm4d_attention_hd_split_bf16:      as dm4d_attention_split_bf16 (two-term operands, parity precision), head_dim last.          */
+int dm4d_attention_hd_qscaled_kv_bf16(void* stream, const void* Q, const void* K, const void* V, void* O, int64_t ldq, int64_t ldk,
+                                      int64_t ldv, int64_t ldo, int batch, int heads, int head_dim, int Lq, int Lk);
+int dm4d_attention_hd_qscaled_kv_f16(void* stream, const void* Q, const void* K, const void* V, void* O, int64_t ldq, int64_t ldk,
+                                     int64_t ldv, int64_t ldo, int batch, int heads, int head_dim, int Lq, int Lk);
+int dm4d_attention_hd_split_bf16(void* stream, const void* Q, const void* K, const void* V, void* O, int64_t ldq, int64_t ldk,
+                                 int64_t ldv, int64_t ldo, int64_t q_lo, int64_t k_lo, int64_t v_lo, int64_t o_lo, int batch,
+                                 int heads, int Lq, int Lk, float scale, int head_dim);
+
 /* The tail of a transformer block in one launch, precision "fp16" (dm4d_attn_out_ff_geglu_fused_bf16 above; attention.py:88-90 and
  *   :129-149): A0 [M, C] fp16 attention output, Wo / bo / LayerNorm vectors / b2 fp16, W1p / b1p / W2p = dm4d_ff_geglu_prepare_bf16 of
  *   the fp16 matrices (a permutation of 16-bit words), X [M, C] the fp32 residual stream (ldx in floats, a multiple of 4):

@@ -28,6 +28,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
 from diffuman4d_amd.host import config as cfglib  # noqa: E402
 from diffuman4d_amd.host.runner import DEFAULT_GPU_STREAMS, DEFAULT_TASK_BATCH, SamplingRunner  # noqa: E402
 from diffuman4d_amd.host.weights import write_synthetic_checkpoint  # noqa: E402
+from diffuman4d_amd.host.unet import UNetConfig  # noqa: E402
 
 
 def main():
@@ -48,13 +49,17 @@ def main():
     ap.add_argument("--writer-processes", type=int, default=0, help="runner.writer_processes: encode the packages in N processes")
     ap.add_argument("--host-threads", type=int, default=0, help="torch.set_num_threads for the host stages (0 = torch's default)")
     ap.add_argument("--timeline", default=None, help="write per-task stage intervals (load / denoise / save: start, end, thread) as JSON")
+    ap.add_argument("--unet-layout", choices=("sd21", "sd1x"), default="sd21",
+                    help="attention layout of the synthetic checkpoint: sd21 = attention_head_dim (5, 10, 20, 20), head dimension 64; "
+                         "sd1x = attention_head_dim 8, head dimensions 40 / 80 / 160")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("overrides", nargs="*")
     a = ap.parse_args()
     H, W = (int(v) for v in a.size.lower().split("x"))
     work = Path(a.workdir or tempfile.mkdtemp(prefix="dm4d_e2e_"))
     t0 = time.perf_counter()
-    ckpt = write_synthetic_checkpoint(work / "ckpt", device="cuda")
+    ucfg = UNetConfig(attention_head_dim=8) if a.unet_layout == "sd1x" else None  # SD-1.x: diffusers writes the int form
+    ckpt = write_synthetic_checkpoint(work / "ckpt", ucfg, device="cuda")
     t_ckpt = time.perf_counter() - t0
     cfg = cfglib.compose([f"exp={a.exp}", "model=diffuman4d_mi355x", "data=synthetic", f"model.model_dir={ckpt}",
                           "model.gpu_ids=[0]", f"data.height={H}", f"data.width={W}", f"result_dir={work / 'results'}"]

@@ -1,0 +1,333 @@
+"""``SpaTemDataset`` for captured scenes: nerfstudio cameras, Pillow decode on the host, crop + resize on the device.
+
+Same constructor keywords and ``get_item`` dict as the reference's dataset (``src/data/spatem_dataset.py``), built from its
+behaviour.  What the reference does per frame -- decode, crop to the mask's square box, Pillow's bicubic resize of image, mask and
+skeleton, ``to_tensor``, ``* 2 - 1`` and the white-background blend -- is split here:
+
+  * host, in a thread pool (Pillow releases the GIL while it decodes): decode, the mask's bounding box and the crop box, the
+    ``has_gt_target=False`` masks, the checks, and Pillow's coefficient tables (float64, once per distinct size pair per task);
+  * device, two launches per task (``dm4d_capture_crop_resize_f32``): the resize itself, bit-exact with Pillow, and the fp32 epilogue.
+
+Every task's uint8 planes, tables and frame descriptors go into one pinned staging buffer and up in one copy.  ``pixel_values``
+and ``skeletons`` come back as fp32 NCHW tensors on ``device``; cameras, Pluecker maps and masks stay on the host.
+"""
+from __future__ import annotations
+
+import json
+import logging
+import math
+import os
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from PIL import Image
+
+from . import ops
+from .dataset import plucker_maps, relative_poses
+
+log = logging.getLogger(__name__)
+
+FIELDS = 16  # int64 fields of one frame descriptor (include/dm4d.h DM4D_CAPTURE_FIELDS)
+PRECISION_BITS = 22  # Pillow's fixed-point coefficients for 8-bit images (libImaging/Resample.c)
+_ALIGN = 16
+
+
+def _bicubic(x: np.ndarray) -> np.ndarray:
+    """Pillow's bicubic kernel, a = -0.5, in its own order of operations."""
+    x = np.abs(x)
+    near = ((1.5 * x - 2.5) * x) * x + 1.0
+    far = (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5
+    return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
+
+
+def bicubic_table(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's coefficients for resizing an axis of `in_size` pixels (the crop) to `out_size`: ([out, 2] int32 window
+    {start, length}, [out, ksize] int32 weights with 22 fractional bits).  float64 throughout, the weights of a window summed left
+    to right (a pairwise sum can move a coefficient by one unit), each scaled by 1 / filterscale as a product."""
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = 2.0 * fs
+    ksize = int(math.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)  # C's (int) truncates
+    hi = np.minimum(np.trunc(center + support + 0.5), in_size).astype(np.int64)
+    n = hi - lo
+    t = np.arange(ksize)
+    w = _bicubic(((t[None, :] + lo[:, None]) - center[:, None] + 0.5) * (1.0 / fs))
+    w = np.where(t[None, :] < n[:, None], w, 0.0)
+    total = np.zeros(out_size)
+    for j in range(ksize):  # sequential sum; the zero tail adds nothing
+        total = total + w[:, j]
+    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
+    scaled = w * float(1 << PRECISION_BITS)
+    k = np.trunc(np.where(w < 0, -0.5 + scaled, 0.5 + scaled)).astype(np.int32)
+    return np.stack([lo, n], axis=1).astype(np.int32), k
+
+
+# -- cameras ----------------------------------------------------------------------------------------------------------------------
+def read_cameras(camera_path: str) -> Dict[str, Dict]:
+    """nerfstudio ``transforms.json`` -> {camera_label: {K, pose, height, width}} with OpenCV axes and normalised positions, in the
+    reference's float32 arithmetic (data/utils/camera_parser.py)."""
+    if os.path.isdir(camera_path) or camera_path.endswith(".yml"):
+        raise NotImplementedError(f"EasyVolcap cameras are not supported ({camera_path}): give a nerfstudio transforms.json")
+    if not camera_path.endswith(".json"):
+        raise ValueError(f"camera file must be a nerfstudio transforms.json: {camera_path}")
+    with open(camera_path) as f:
+        tfs = json.load(f)
+    labels, Ks, hws, poses = [], [], [], []
+    for fr in tfs["frames"]:
+        src = fr if all(k in fr for k in ("fl_x", "fl_y", "cx", "cy")) else tfs  # per-frame intrinsics, else the global ones
+        Ks.append(torch.tensor([src["fl_x"], 0, src["cx"], 0, src["fl_y"], src["cy"], 0, 0, 1]).reshape(3, 3))
+        hws.append((fr["h"], fr["w"]))
+        pose = torch.tensor(fr["transform_matrix"])
+        pose[:3, 1:3] *= -1  # OpenGL -> OpenCV camera axes
+        poses.append(pose)
+        labels.append(fr["camera_label"])
+    poses = torch.stack(poses)
+    # Scene normalisation.  The reference looks for f"{camera_path}/scene_norm.json", a path UNDER the JSON file, which therefore
+    # never exists: its centre and scale always come from the bounding box of the camera positions, and so do ours.
+    pos = poses[:, :3, 3]
+    lo, hi = torch.min(pos, dim=0).values, torch.max(pos, dim=0).values
+    center, scale = (lo + hi) / 2, 1 / torch.linalg.norm(hi - lo)
+    poses[:, :3, 3] = (poses[:, :3, 3] - center) * scale
+    return {lab: {"K": K, "pose": p, "height": hw[0], "width": hw[1]} for lab, K, hw, p in zip(labels, Ks, hws, poses)}
+
+
+# -- masks and crops --------------------------------------------------------------------------------------------------------------
+def mask_bbox(nonzero: np.ndarray) -> Optional[Tuple[int, int, int, int]]:
+    """(xmin, ymin, xmax, ymax) one pixel outside the nonzero pixels of a [h, w] bool map, or None when there are none."""
+    rows, cols = np.flatnonzero(nonzero.any(axis=1)), np.flatnonzero(nonzero.any(axis=0))
+    if rows.size == 0 or cols.size == 0:
+        return None
+    return int(cols[0]) - 1, int(rows[0]) - 1, int(cols[-1]) + 1, int(rows[-1]) + 1
+
+
+def crop_box(mask: np.ndarray, path: str = "") -> List[int]:
+    """The square crop around the mask (crop_utils.py mask_crop_aspect_ratio with its defaults) -> [top, left, height, width, h, w];
+    it may extend past the image.  The reference's padding is torch.randint(0, 1), always 0: no draw is made here."""
+    h, w = mask.shape
+    box = mask_bbox(mask != 0)
+    if box is None:
+        raise ValueError(f"foreground mask is empty: {path}")
+    xmin, ymin, xmax, ymax = box
+    xc, yc = (xmin + xmax) / 2, (ymin + ymax) / 2
+    size = max(2 * max(yc - ymin, ymax - yc, (xc - xmin) * 1.0, (xmax - xc) * 1.0), 0.7 * h)
+    cw = int(size / 1.0)
+    x0, y0 = math.floor(xc - cw / 2), math.floor(yc - size / 2)
+    x1, y1 = math.ceil(xc + cw / 2), math.ceil(yc + size / 2)
+    return [y0, x0, y1 - y0, x1 - x0, h, w]
+
+
+def skeleton_mask(skel: np.ndarray, path: str = "") -> np.ndarray:
+    """crop_utils.py skeleton_to_mask in float32: channel mean of to_tensor, the padded box of its nonzero pixels set to 1, then
+    mul(255) and a truncating byte() (to_pil_image).  [h, w, 3] uint8 -> [h, w] uint8."""
+    h, w = skel.shape[:2]
+    py, px = int(h * 0.03), int(w * 0.03)
+    pt = int(py * 3)
+    m = torch.from_numpy(np.array(skel)).permute(2, 0, 1).contiguous().to(torch.float32).div(255).mean(dim=0)
+    box = mask_bbox(m.numpy() != 0)
+    if box is None:
+        raise ValueError(f"skeleton is empty, no mask can be made from it: {path}")
+    xmin, ymin, xmax, ymax = box
+    xmin, ymin, xmax, ymax = max(xmin - px, 0), max(ymin - pt, 0), min(xmax + px, w), min(ymax + py, h)
+    m[ymin:ymax, xmin:xmax] = 1.0
+    return m.mul(255).byte().numpy()
+
+
+def _mask_mean_at_most(mask: np.ndarray, limit: float) -> bool:
+    """TF.to_tensor(mask).mean() <= limit, decided exactly: the float32 mean only where the exact mean is close to `limit`."""
+    exact = float(mask.sum(dtype=np.int64)) / (255.0 * mask.size)
+    if abs(exact - limit) > 1e-4:
+        return exact <= limit
+    return bool(torch.from_numpy(mask).to(torch.float32).div(255).mean() <= limit)
+
+
+def _open(path: str, mode: str) -> np.ndarray:
+    with Image.open(path) as im:
+        if im.mode != mode:
+            raise ValueError(f"{path}: image mode {im.mode!r}, expected {mode!r} (no conversion is made: it would change values)")
+        return np.asarray(im)
+
+
+def _intrinsic(K: torch.Tensor, crop: List[int], height: int) -> torch.Tensor:
+    """K of the cropped and resized view (spatem_dataset.py transform_intrinsic): float32, the scale multiplied as a scalar."""
+    top, left, ch = crop[0], crop[1], crop[2]
+    K = K.clone()
+    K[0, 2] = K[0, 2] - left
+    K[1, 2] = K[1, 2] - top
+    K = K * (height / ch)
+    K[2, 2] = 1.0
+    return K
+
+
+def _up(n: int) -> int:
+    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
+
+
+class SpaTemDataset:
+    """Captured-scene dataset with the reference's ``SpaTemDataset`` keywords and ``get_item`` contract.
+
+    Extension keywords: ``plucker`` ("host": full-resolution fp32 Pluecker maps, as the reference; "cameras": ``None`` and the
+    pipeline evaluates the rays on the device, as ``SyntheticSpaTemDataset``), ``device`` (where ``pixel_values`` / ``skeletons``
+    land; default: the calling thread's current HIP device), ``decode_threads`` (Pillow decode pool)."""
+
+    def __init__(self, data_dir: str, camera_path_pat: str = "{data_dir}/{scene_label}/transforms.json",
+                 image_path_pat: str = "{data_dir}/{scene_label}/images/{spa_label}/{tem_label}.webp",
+                 fmask_path_pat: str = "{data_dir}/{scene_label}/fmasks/{spa_label}/{tem_label}.png",
+                 skeleton_path_pat: str = "{data_dir}/{scene_label}/skeletons/{spa_label}/{tem_label}.webp",
+                 scene_label: Optional[str] = None, height: int = 1024, width: int = 1024, has_gt_target: bool = True,
+                 plucker: str = "host", device=None, decode_threads: int = 8):
+        if plucker not in ("host", "cameras"):
+            raise ValueError("plucker must be 'host' or 'cameras'")
+        if width % 4 != 0:
+            raise ValueError(f"width must be a multiple of 4 (dm4d_capture_crop_resize_f32), got {width}")
+        self.data_dir = os.path.expandvars(data_dir) if "$" in data_dir else data_dir
+        self.camera_path_pat, self.image_path_pat = camera_path_pat, image_path_pat
+        self.fmask_path_pat, self.skeleton_path_pat = fmask_path_pat, skeleton_path_pat
+        self.scene_label = "" if scene_label is None else scene_label
+        self.height, self.width, self.has_gt_target = height, width, has_gt_target
+        self.plucker, self.device, self.decode_threads = plucker, device, max(1, int(decode_threads))
+        camera_path = self.camera_path_pat.format(data_dir=self.data_dir, scene_label=self.scene_label)
+        self.cameras = {self.scene_label: read_cameras(camera_path)}
+        self._pool = ThreadPoolExecutor(max_workers=self.decode_threads, thread_name_prefix="dm4d-decode")
+        self._tls = threading.local()
+
+    def get_file_path(self, pat: str, scene_label: str, spa_label: str, tem_label: str) -> str:
+        return pat.format(data_dir=self.data_dir, scene_label=scene_label, spa_label=spa_label, tem_label=tem_label)
+
+    def nearest_input_camera(self, cam: int, input_cams: Sequence[int]) -> int:
+        """Integer-label form of the temporal conditioning-camera choice (runner.DistributedSamplingRunner asks for it)."""
+        labels = [f"{c:02d}" for c in input_cams]
+        return int(self._nearest(self.cameras[self.scene_label], f"{cam:02d}", labels))
+
+    @staticmethod
+    def _nearest(cameras: Dict, target: str, inputs: Sequence[str]) -> str:
+        """The input camera nearest to `target`: distances between normalised absolute positions (before relative poses)."""
+        pos = torch.stack([cameras[target]["pose"]] + [cameras[c]["pose"] for c in inputs])[:, :3, 3]
+        return inputs[torch.argmin(torch.norm(pos[1:] - pos[:1], dim=1)).item()]
+
+    # -- host half of one frame ----------------------------------------------------------------------------------------------
+    def _load_frame(self, label, input_spa_labels) -> Dict:
+        scene_label, spa, tem = label
+        skel_path = self.get_file_path(self.skeleton_path_pat, scene_label, spa, tem)
+        skel = _open(skel_path, "RGB")
+        if not self.has_gt_target and spa not in input_spa_labels:  # the skeleton serves as image, its box as mask
+            img, img_path, mask = None, skel_path, skeleton_mask(skel, skel_path)
+        else:
+            img_path = self.get_file_path(self.image_path_pat, scene_label, spa, tem)
+            fmask_path = self.get_file_path(self.fmask_path_pat, scene_label, spa, tem)
+            img, mask = _open(img_path, "RGB"), _open(fmask_path, "L")
+        crop = crop_box(mask, img_path)
+        size = lambda a: (a.shape[1], a.shape[0])  # PIL's (w, h)
+        isz = size(skel if img is None else img)
+        if not (isz == size(mask) == size(skel)):
+            raise AssertionError(f"Error: image size: {isz} != fmask size: {size(mask)} != skeleton size: {size(skel)}")
+        if self.has_gt_target and spa in input_spa_labels and _mask_mean_at_most(mask, 0.02):
+            raise AssertionError("Error: foreground mask < 2%. Please check the data.")
+        return {"img": img, "mask": mask, "skel": skel, "crop": crop}
+
+    def _stream(self, device: torch.device):
+        st = getattr(self._tls, "stream", None)
+        if st is None or st.device != device:
+            st = self._tls.stream = torch.cuda.Stream(device=device)
+        return st
+
+    def _resize_on_device(self, frames: List[Dict], device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Pack planes, tables and descriptors into one staging buffer, upload it, launch; -> (pixel_values, skeletons)."""
+        H, W = self.height, self.width
+        tables: Dict[Tuple[int, int], Tuple[int, int]] = {}  # (in, out) -> (offset in int32 units, ksize)
+        chunks: List[np.ndarray] = []
+        n_tab = 0
+        for fr in frames:
+            for key in ((fr["crop"][3], W), (fr["crop"][2], H)):
+                if key not in tables:
+                    b, k = bicubic_table(*key)
+                    tables[key] = (n_tab, k.shape[1])
+                    chunks += [b.reshape(-1), k.reshape(-1)]
+                    n_tab += b.size + k.size
+        tab = np.concatenate(chunks).astype(np.int32)
+        # layout: [frame planes | tables | descriptors], every region 16-byte aligned
+        off, plane_offs = 0, []
+        for fr in frames:
+            o = []
+            for name in ("img", "mask", "skel"):
+                a = fr[name]
+                if a is None:  # has_gt_target=False target: the image IS the skeleton
+                    o.append(None)
+                    continue
+                o.append(off)
+                off = _up(off + a.size)
+            plane_offs.append(o)
+        tab_off = off
+        desc_off = _up(tab_off + tab.nbytes)
+        total = desc_off + len(frames) * FIELDS * 8
+        desc = np.zeros((len(frames), FIELDS), dtype=np.int64)
+        scratch = 0
+        for i, (fr, (oi, om, os_)) in enumerate(zip(frames, plane_offs)):
+            top, left, ch, cw = fr["crop"][:4]
+            sh, sw = fr["skel"].shape[:2]
+            htab, hk = tables[(cw, W)]
+            vtab, vk = tables[(ch, H)]
+            vb = tab[vtab: vtab + 2 * H].reshape(H, 2)
+            y_first, y_last = int(vb[0, 0]), int(vb[-1, 0] + vb[-1, 1])  # crop rows the vertical windows read
+            desc[i] = [os_ if oi is None else oi, om, os_, sh, sw, top, left, ch, cw, htab, hk, vtab, vk, scratch, y_first,
+                       y_last - y_first]
+            scratch = _up(scratch + (y_last - y_first) * W * 8)
+        on_gpu = device.type == "cuda"
+        blob = torch.empty(total, dtype=torch.uint8, pin_memory=on_gpu)
+        host = blob.numpy()
+        jobs = [(o, fr[n]) for fr, offs in zip(frames, plane_offs) for o, n in zip(offs, ("img", "mask", "skel")) if o is not None]
+        list(self._pool.map(lambda j: np.copyto(host[j[0]: j[0] + j[1].size], j[1].reshape(-1)), jobs))
+        host[tab_off: tab_off + tab.nbytes] = tab.view(np.uint8)
+        host[desc_off: total] = desc.reshape(-1).view(np.uint8)
+        if not on_gpu:  # no device: the ops call decides (it refuses host tensors -- there is no CPU fallback)
+            return ops.capture_crop_resize(blob, blob, len(frames), desc_off, tab_off, tab.size, H, W)
+        st = self._stream(device)
+        with torch.cuda.device(device), torch.cuda.stream(st):
+            dev_blob = blob.to(device, non_blocking=True)
+            pix, skel = ops.capture_crop_resize(dev_blob, blob, len(frames), desc_off, tab_off, tab.size, H, W)
+        # get_item may run on a loader thread whose consumer is another stream (runner.run_round_pipelined): the tensors are
+        # complete when they are handed over, and the pinned buffer may be released.  This stalls the loader thread only.
+        st.synchronize()
+        return pix, skel
+
+    # -- the get_item contract (spatem_dataset.py:77-229) -------------------------------------------------------------------------
+    def get_item(self, scene_label: str, spa_labels: List[str], tem_labels: List[str], input_spa_labels: List[str]) -> Dict:
+        if len(spa_labels) > 1 and len(tem_labels) == 1:
+            domain = "spatial"
+        elif len(spa_labels) == 1 and len(tem_labels) > 1:
+            domain = "temporal"
+        else:
+            raise ValueError(f"Error: invalid spa_labels and tem_labels: {spa_labels} and {tem_labels}")
+        cameras = self.cameras[scene_label]
+        if domain == "spatial":
+            labels = [(scene_label, s, tem_labels[0]) for s in spa_labels]
+        else:  # the nearest input camera's frames first, then the target's
+            cams = [self._nearest(cameras, spa_labels[0], input_spa_labels)] + list(spa_labels)
+            labels = [(scene_label, s, t) for s in cams for t in tem_labels]
+
+        frames = list(self._pool.map(lambda lab: self._load_frame(lab, input_spa_labels), labels))
+        Ks = torch.stack([_intrinsic(cameras[s]["K"], fr["crop"], self.height) for (_, s, _), fr in zip(labels, frames)])
+        poses = relative_poses(torch.stack([cameras[s]["pose"] for _, s, _ in labels]))
+        hws = [(cameras[s]["height"], cameras[s]["width"]) for _, s, _ in labels]
+        crops = [fr["crop"] for fr in frames]
+        device = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        pixel_values, skeletons = self._resize_on_device(frames, device)
+        del frames
+
+        n = len(labels)
+        pl = plucker_maps(self.height, self.width, Ks, poses) if self.plucker == "host" else None
+        cond_masks = torch.ones(n, 1, self.height, self.width)
+        cond_masks[n // 2:] = 0.0
+        lo, hi = -1.0 - 1e-6, 1.0 + 1e-6  # check_output; pixel_values / skeletons lie in [-1, 1] by construction
+        if pl is not None and (lo > pl.min() or hi < pl.max()):
+            raise ValueError(f"Error: plucker embeds are out of range: {pl.min()} < {lo} or {pl.max()} > {hi}")
+        if lo > cond_masks.min() or hi < cond_masks.max():
+            raise ValueError(f"Error: cond masks are out of range: {cond_masks.min()} < {lo} or {cond_masks.max()} > {hi}")
+        return {"domain": domain, "labels": labels, "pixel_values": pixel_values, "plucker_embeds": pl, "skeletons": skeletons,
+                "cond_masks": cond_masks, "Ks": Ks, "hws": hws, "crops": crops, "poses": poses}

@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import copy
 import importlib
+import logging
 import os
 import re
 import time
@@ -26,6 +27,8 @@ from pathlib import Path
 from typing import Any, Dict, List, Optional
 
 import yaml
+
+log = logging.getLogger(__name__)
 
 _DATA_PATS = {
     "camera_path_pat": "{data_dir}/{scene_label}/transforms.json",
@@ -97,7 +100,7 @@ ROOT_BODY = {
     "sampling": True, "to_nerfstudio": True, "evaluating": False,
 }
 
-# reference `_target_` strings -> this package (a reference checkout on sys.path wins for the dataset)
+# reference `_target_` strings -> this package (for the dataset see NATIVE_FALLBACKS: a reference checkout on sys.path wins)
 TARGET_ALIASES = {
     "src.samplers.sliding_iterative_sampler.SlidingIterativeSampler": "diffuman4d_amd.host.sampler.SlidingIterativeSampler",
     "src.samplers.utils.sampling_utils.load_pipelines": "diffuman4d_amd.host.loader.load_pipelines",
@@ -268,10 +271,28 @@ def compose(overrides: List[str], config_dir: Optional[str] = None) -> Dict[str,
     return _resolve(cfg, choices)
 
 
-def locate(path: str):
-    path = TARGET_ALIASES.get(path, path)
+# reference classes with a native counterpart, used when the reference's own module does not import (no checkout on sys.path, or
+# its dependencies -- torchvision for the dataset -- missing)
+NATIVE_FALLBACKS = {"src.data.spatem_dataset.SpaTemDataset": "diffuman4d_amd.host.capture.SpaTemDataset"}
+
+
+def _import_attr(path: str):
     mod, _, name = path.rpartition(".")
     return getattr(importlib.import_module(mod), name)
+
+
+def locate(path: str):
+    path = TARGET_ALIASES.get(path, path)
+    if path in NATIVE_FALLBACKS:
+        try:
+            target = _import_attr(path)
+        except ImportError as e:
+            target = _import_attr(NATIVE_FALLBACKS[path])
+            log.info("%s does not import (%s): using %s", path, e, NATIVE_FALLBACKS[path])
+        else:
+            log.info("using the reference's %s", path)
+        return target
+    return _import_attr(path)
 
 
 def instantiate(node: Dict[str, Any], **kwargs):

@@ -1,8 +1,7 @@
 """Synthetic stand-in for ``SpaTemDataset`` with the same ``get_item`` output contract.
 
-The real dataset (``/root/reference/src/data/spatem_dataset.py``: PIL decode, mask-bbox crop, bicubic
-resize, camera parsing) is host-side file I/O and out of scope for this round.  This
-class produces tensors with the documented shapes and value ranges (``spatem_dataset.py:191-228``:
+Captured scenes are read by ``host/capture.py::SpaTemDataset`` (the reference's ``src/data/spatem_dataset.py``:
+PIL decode, mask-bbox crop, bicubic resize, camera parsing).  This class produces tensors with the documented shapes and value ranges (``spatem_dataset.py:191-228``:
 pixel / skeleton / Pluecker in [-1, 1], masks in {0, 1}) so the sampler, pipeline and CLI can be run
 and benchmarked without data: cameras on a ring looking at the origin, Pluecker maps [d, o x d].
 """

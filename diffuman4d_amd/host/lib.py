@@ -98,6 +98,8 @@ SIGNATURES = {
     "dm4d_tune_set_groupnorm_resident": (_i, [_i]),
     "dm4d_nchw_to_nhwc_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     "dm4d_nhwc_to_nchw_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
+    # captured frames: crop + Pillow-exact bicubic resize + the dataset's fp32 epilogue (host/capture.py)
+    "dm4d_capture_crop_resize_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i]),
 }
 
 EPI_GEGLU = 1

@@ -985,3 +985,29 @@ def postprocess_images(x: torch.Tensor, channels: int = 3) -> torch.Tensor:
     fn = lib.dm4d_postprocess_images_f32 if dt == F32 else lib.dm4d_postprocess_images_bf16
     _l.check(fn(_stream(), _p(x), _p(y), B, channels, H * W, ld), "dm4d_postprocess_images")
     return y
+
+
+CAPTURE_FIELDS = 16  # include/dm4d.h DM4D_CAPTURE_FIELDS
+
+
+def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: int, desc_off: int, tab_off: int, tab_len: int,
+                        H: int, W: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Crop + Pillow-exact bicubic resize + the dataset's fp32 epilogue of `n_frames` captured frames (host/capture.py) ->
+    (pixel_values, skeletons), fp32 [n_frames, 3, H, W] on blob's device.  `blob`: the device copy of the staging buffer
+    `blob_host` (uint8: frame planes | int32 tables at byte `tab_off` | int64 descriptors at byte `desc_off`); the library checks
+    every descriptor and table on the host copy before it launches."""
+    lib = _l.load()
+    _req(blob, "blob", torch.uint8)
+    if blob_host.device.type != "cpu" or blob_host.numel() != blob.numel():
+        raise _l.Dm4dError("blob_host: expected the host copy of blob")
+    desc = blob_host[desc_off: desc_off + n_frames * CAPTURE_FIELDS * 8].view(torch.int64).reshape(n_frames, CAPTURE_FIELDS)
+    tab = blob_host[tab_off: tab_off + tab_len * 4].view(torch.int32)
+    scratch_bytes = int((desc[:, 13] + desc[:, 15] * W * 8).max())
+    scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=blob.device)
+    pix = torch.empty((n_frames, 3, H, W), dtype=F32, device=blob.device)
+    skel = torch.empty((n_frames, 3, H, W), dtype=F32, device=blob.device)
+    base = blob.data_ptr()
+    rc = lib.dm4d_capture_crop_resize_f32(_stream(), base, blob.numel(), desc.data_ptr(), base + desc_off, n_frames, tab.data_ptr(),
+                                          base + tab_off, tab_len, _p(scratch), scratch.numel(), _p(pix), _p(skel), H, W)
+    _l.check(rc, "dm4d_capture_crop_resize_f32")
+    return pix, skel

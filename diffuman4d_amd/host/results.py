@@ -179,7 +179,8 @@ def save_sampling_results(sample: Dict[str, Any], output_dir: str = "./results",
     output_images = sample["images"].clone().float()  # the caller keeps its tensor (the reference edits it in place)
     input_indices = sample["input_indices"]
     target_indices = set(int(i) for i in sample["target_indices"])
-    input_images = sample["pixel_values"].float() * 0.5 + 0.5  # denorm_vae_tensor
+    # the captured-scene dataset leaves pixel_values / skeletons on the device (host/capture.py): the mosaic is made on the host
+    input_images = sample["pixel_values"].float().cpu() * 0.5 + 0.5  # denorm_vae_tensor
 
     if save_image_grid:
         errors = (output_images - input_images).abs().clamp(0, 1)
@@ -187,7 +188,7 @@ def save_sampling_results(sample: Dict[str, Any], output_dir: str = "./results",
         dimmed[input_indices] *= 0.2
         rows = [input_images, dimmed, errors]
         if sample.get("skeletons") is not None:
-            rows.insert(0, (sample["skeletons"].float() * 0.5 + 0.5) * 0.8 + input_images * 0.2)
+            rows.insert(0, (sample["skeletons"].float().cpu() * 0.5 + 0.5) * 0.8 + input_images * 0.2)
         mosaic = torch.cat(rows)
         n = len(output_images)
         max_size = min(max_image_size // n, max(mosaic.shape[-2:]))

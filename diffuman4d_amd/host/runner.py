@@ -41,6 +41,14 @@ def _denoise_group(sampler: SlidingIterativeSampler, group: List[dict], pipe_idx
     return sampler.denoise_stack(group, pipe_idx=pipe_idx)
 
 
+def _bind_device(sampler: SlidingIterativeSampler, pipe_idx: int) -> None:
+    """Make the pipeline's device the calling thread's current one, so that a dataset that loads onto "the current device"
+    (host/capture.py) loads onto the GPU this thread's tasks run on, not device 0."""
+    dev = sampler.pipelines[pipe_idx].device
+    if torch.cuda.is_available() and getattr(dev, "type", "cpu") == "cuda":
+        torch.cuda.set_device(dev)
+
+
 def _denoise_on_own_stream(sampler: SlidingIterativeSampler, group: List[dict], pipe_idx: int) -> List[dict]:
     """GPU-stage worker: every worker thread owns one HIP stream (created on first use), so the kernels of concurrently
     denoised tasks interleave on the device."""
@@ -102,6 +110,7 @@ def run_round_pipelined(sampler: SlidingIterativeSampler, tasks: List[dict], pip
     pin = torch.cuda.is_available() and getattr(sampler.pipelines[pipe_idx].device, "type", "cpu") == "cuda"
 
     def load(**task):
+        _bind_device(sampler, pipe_idx)
         sample = sampler.load_sample(**task)
         if pin:  # page-locked staging on the loader thread: the pipeline's H2D copies become plain DMA
             for k, v in sample.items():
@@ -197,6 +206,7 @@ class SamplingRunner:
         errors: List[BaseException] = []
 
         def _worker(q: Queue, pipe_idx: int):
+            _bind_device(self.sampler, pipe_idx)
             while True:
                 try:
                     task = q.get_nowait()

@@ -225,6 +225,22 @@ int dm4d_plucker_latent_bf16(void* stream, const float* cams, void* Y, int N, in
  *   triangle filter of support max(H / h, 1), normalised per axis.                                                            */
 int dm4d_resize_aa_nchw_f32(void* stream, const float* X, float* Y, int64_t planes, int H, int W, int h, int w);
 
+/* Crop + bicubic resize of captured frames (diffuman4d_amd/host/capture.py::SpaTemDataset; spatem_dataset.py:58-69 + 157-166):
+ *   Pillow's Image.crop((left, top, left + cw, top + ch)).resize((W, H), BICUBIC) byte for byte on each frame's image (RGB), mask (L)
+ *   and skeleton (RGB), then TF.to_tensor -> x * 2 - 1 and, for the image, apply_fmask(white, vae_normalized=True), each fp32
+ *   operation rounded on its own.  Two launches for all frames: the horizontal pass into `scratch` (8 bytes per pixel, uint8 as in
+ *   Pillow), the vertical pass + epilogue into pixel_values / skeletons [n_frames, 3, H, W] fp32.
+ *   staging: device copy of the frames' packed uint8 planes (HWC, rows tight).  desc: n_frames x DM4D_CAPTURE_FIELDS int64 =
+ *   {image, mask, skeleton byte offsets in staging | source h, w | crop top, left, height, width (may extend past the image) |
+ *   horizontal table offset, ksize | vertical table offset, ksize | scratch byte offset (16-aligned) | first crop row the vertical
+ *   windows read, number of such rows}.  tab: int32 tables; one table for n outputs = n x {window start, window length} followed by
+ *   n x ksize coefficients with 22 fractional bits.  desc_host / tab_host are host copies of the same bytes as desc_dev / tab_dev:
+ *   every offset, window and region is validated on them before anything is launched.  W % 4 == 0.                           */
+#define DM4D_CAPTURE_FIELDS 16
+int dm4d_capture_crop_resize_f32(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host,
+                                 const int64_t* desc_dev, int n_frames, const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len,
+                                 void* scratch, int64_t scratch_bytes, float* pixel_values, float* skeletons, int H, int W);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

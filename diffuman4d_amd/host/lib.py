@@ -100,6 +100,9 @@ SIGNATURES = {
     "dm4d_nhwc_to_nchw_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     # captured frames: crop + Pillow-exact bicubic resize + the dataset's fp32 epilogue (host/capture.py)
     "dm4d_capture_crop_resize_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i]),
+    # result evaluation: composite + nearest resize + mask crop + PSNR / SSIM of a batch of image pairs (host/metrics.py)
+    "dm4d_eval_ws_bytes": (C.c_size_t, [_i, _i, _i]),
+    "dm4d_eval_psnr_ssim_f64": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _i, _i]),
 }
 
 EPI_GEGLU = 1

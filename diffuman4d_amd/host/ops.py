@@ -1011,3 +1011,37 @@ def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: i
                                           base + tab_off, tab_len, _p(scratch), scratch.numel(), _p(pix), _p(skel), H, W)
     _l.check(rc, "dm4d_capture_crop_resize_f32")
     return pix, skel
+
+
+EVAL_FIELDS = 16  # include/dm4d.h DM4D_EVAL_FIELDS
+EVAL_OUT = 8      # include/dm4d.h DM4D_EVAL_OUT
+EVAL_IMAGE_F32, EVAL_MASK_F32, EVAL_CROP_MASKS, EVAL_BG_SHIFT = 1, 2, 4, 3
+
+
+def eval_psnr_ssim(blob: torch.Tensor, desc: torch.Tensor, desc_off: Optional[int] = None, debug: bool = False):
+    """PSNR / SSIM of a batch of image pairs (host/metrics.py; the reference's ImageEvaluator.__call__) -> (out [n, EVAL_OUT] fp64 =
+    {psnr, ssim, pred min, pred max, gt min, gt max, squared-error sum, SSIM-map sum}, boxes [n, 4] int32 = the crops used) on blob's
+    device, and with `debug` the cropped composites [n, 2, 3, max h, max w] fp32 as a third value.  `blob`: device bytes holding every
+    plane; `desc`: HOST int64 [n, EVAL_FIELDS] descriptors (include/dm4d.h), which the library checks before it launches; `desc_off`:
+    byte offset of the same descriptors inside blob (they went up with it), or None: they are uploaded here."""
+    lib = _l.load()
+    _req(blob, "blob", torch.uint8)
+    if desc.device.type != "cpu" or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != EVAL_FIELDS or not desc.is_contiguous():
+        raise _l.Dm4dError(f"desc: expected a contiguous host int64 [n, {EVAL_FIELDS}] tensor")
+    n = desc.shape[0]
+    if desc_off is None:
+        desc_dev = desc.to(blob.device)  # alive until the launches are queued: same-stream allocator order keeps it valid after
+        desc_ptr = desc_dev.data_ptr()
+    else:
+        if desc_off < 0 or desc_off % 8 or desc_off + desc.numel() * 8 > blob.numel():
+            raise _l.Dm4dError("desc_off: the descriptors lie outside the blob")
+        desc_ptr = blob.data_ptr() + desc_off
+    max_h, max_w = (int(desc[:, 6].max()), int(desc[:, 7].max())) if n else (0, 0)
+    ws = torch.empty(max(int(lib.dm4d_eval_ws_bytes(n, max_h, max_w)), 16), dtype=torch.uint8, device=blob.device)
+    out = torch.empty((n, EVAL_OUT), dtype=torch.float64, device=blob.device)
+    boxes = torch.empty((n, 4), dtype=torch.int32, device=blob.device)
+    dbg = torch.zeros((n, 2, 3, max(max_h, 1), max(max_w, 1)), dtype=F32, device=blob.device) if debug else None
+    rc = lib.dm4d_eval_psnr_ssim_f64(_stream(), blob.data_ptr(), blob.numel(), desc.data_ptr(), desc_ptr, n, _p(ws), ws.numel(), _p(out),
+                                     _p(boxes), _p(dbg), max_h, max_w)
+    _l.check(rc, "dm4d_eval_psnr_ssim_f64")
+    return (out, boxes, dbg) if debug else (out, boxes)

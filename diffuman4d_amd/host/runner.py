@@ -245,6 +245,25 @@ class SamplingRunner:
             if s.result_writer is not None and not check_sampling_results(s.spa_labels, s.tem_labels, s.output_dir):
                 raise ValueError("Sampling failed.")
 
+    def evaluate(self, gpu_ids=None, **extra) -> dict:
+        """PSNR / SSIM of the written target views against the captured ones -> ``{output_dir}/metrics.json`` (the reference's
+        ``evaluate``, sampling_runner.py:64-77: same paths and arguments; host/metrics.py).  `gpu_ids`: default the devices of the
+        sampler's pipelines (the reference takes every visible device; the job was given ``model.gpu_ids``)."""
+        from .metrics import evaluate_results
+        if gpu_ids is None:
+            devices = [getattr(p, "device", None) for p in self.sampler.pipelines]
+            gpu_ids = sorted({d.index for d in devices if isinstance(d, torch.device) and d.type == "cuda" and d.index is not None}) or None
+        return evaluate_results(gpu_ids=gpu_ids, **_evaluation_arguments(self.sampler), **extra)
+
+
+def _evaluation_arguments(s: SlidingIterativeSampler) -> dict:
+    """The reference's evaluate_results call (sampling_runner.py:65-77): predicted .jpg, captured .webp, mask .png, the target
+    cameras, white background, cropped to the masks."""
+    scene = f"{s.dataset.data_dir}/{s.dataset.scene_label}"
+    return dict(pred_images_dir=f"{s.output_dir}/images", gt_images_dir=f"{scene}/images", fmasks_dir=f"{scene}/fmasks",
+                pred_image_ext=".jpg", gt_image_ext=".webp", fmask_ext=".png", spa_labels=s.target_spa_labels, tem_labels=s.tem_labels,
+                out_metrics_path=f"{s.output_dir}/metrics.json", crop_with_fmask=True, background_color="white")
+
 
 class DistributedSamplingRunner:
     """One process per GPU.  Every rank builds the same sampler (same task lists); rank r executes
@@ -553,3 +572,22 @@ class DistributedSamplingRunner:
         if s.result_writer is not None and self.rank == 0:
             if not check_sampling_results(s.spa_labels, s.tem_labels, s.output_dir):
                 raise ValueError("Sampling failed.")
+
+    def evaluate(self, device=None, **extra):
+        """``SamplingRunner.evaluate`` over the ranks: after a barrier (every rank's writers have drained when its ``inference`` has
+        returned, so behind the barrier every image is on disk) rank r evaluates ``keys[r::world]`` on its own device, the values are
+        gathered to rank 0, which aggregates and writes ``metrics.json``.  -> the metrics on rank 0, None elsewhere."""
+        from .metrics import aggregate_metrics, evaluate_keys, evaluation_keys
+        kw = _evaluation_arguments(self.sampler)
+        self.dist.barrier(self.group)
+        keys = evaluation_keys(kw["pred_images_dir"], kw.pop("spa_labels"), kw.pop("tem_labels"))
+        out_path = kw.pop("out_metrics_path")
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
+        values = evaluate_keys(keys[self.rank::self.world], device, **kw, **extra)
+        gathered = [None] * self.world if self.rank == 0 else None
+        self.dist.gather_object(values, gathered, dst=self.dist.get_global_rank(self.group, 0) if self.group is not None else 0,
+                                group=self.group)
+        if self.rank != 0:
+            return None
+        return aggregate_metrics([v for part in gathered for v in part], out_path)

@@ -241,6 +241,34 @@ int dm4d_capture_crop_resize_f32(void* stream, const void* staging, int64_t stag
                                  const int64_t* desc_dev, int n_frames, const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len,
                                  void* scratch, int64_t scratch_bytes, float* pixel_values, float* skeletons, int H, int W);
 
+/* Result evaluation of n_pairs (predicted, ground-truth) images (diffuman4d_amd/host/metrics.py::ImageEvaluator; the reference's
+ *   ImageEvaluator.__call__, data/utils/metric_utils.py:98-137, called from evaluate_results :157-182 and sampling_runner.py:64-77):
+ *   apply_fmask (x * m + (1 - m) * bg, fp32, each operation rounded on its own), torchvision's nearest resize to the canvas
+ *   (src = min((int)floorf(dst * (float)in / out), in - 1)), mask_to_bbox(padding=8) of the union of the resized masks, the crop, then
+ *   PSNR = 10 log10(1 / mean((p - t)^2)) and torchmetrics' SSIM (11 x 11 Gaussian window, sigma 1.5, c1 = 1e-4, c2 = 9e-4, mean of the map
+ *   over the interior (h - 10) x (w - 10) of each channel) -- window sums and means in fp64, fixed summation order, no floating-point
+ *   atomics: a pair's result is bitwise the same on every run and in every batch.
+ *   blob: device bytes holding every plane.  desc: n_pairs x DM4D_EVAL_FIELDS int64 = {pred, gt byte offsets | pred mask, gt mask byte
+ *   offsets (-1: absent) | source h, w | resized h, w | flags | crop left, top, right, bottom in the resized image (right / bottom
+ *   exclusive; read when DM4D_EVAL_CROP_MASKS is not set) | 3 spare}.  Images: uint8 HWC (to_tensor's / 255 is applied) or, with
+ *   DM4D_EVAL_IMAGE_F32, fp32 CHW; masks: one uint8 or (DM4D_EVAL_MASK_F32) fp32 plane.  Background: flags >> DM4D_EVAL_BG_SHIFT =
+ *   0 black, 1 white, 2 grey.  desc_host is the host copy of desc_dev: every offset, size and box is validated on it before anything
+ *   is launched.  workspace: dm4d_eval_ws_bytes(n_pairs, max resized h, max resized w) bytes.
+ *   out [n_pairs, DM4D_EVAL_OUT] fp64 = {psnr, ssim, pred min, pred max, gt min, gt max (of the cropped composites: the reference's
+ *   "should be normalized" check), sum of squared errors, sum of the SSIM map}; boxes [n_pairs, 4] int32 = the crop used (an empty
+ *   mask gives 0, 0, 0, 0 and NaN results); debug (optional) [n_pairs, 2, 3, dbg_h, dbg_w] fp32 receives the cropped composites of
+ *   pred and gt at [.., :h, :w].                                                                                              */
+#define DM4D_EVAL_FIELDS 16
+#define DM4D_EVAL_OUT 8
+#define DM4D_EVAL_IMAGE_F32 1
+#define DM4D_EVAL_MASK_F32 2
+#define DM4D_EVAL_CROP_MASKS 4
+#define DM4D_EVAL_BG_SHIFT 3
+size_t dm4d_eval_ws_bytes(int n_pairs, int max_h, int max_w);
+int dm4d_eval_psnr_ssim_f64(void* stream, const void* blob, int64_t blob_bytes, const int64_t* desc_host, const int64_t* desc_dev,
+                            int n_pairs, void* workspace, int64_t workspace_bytes, double* out, int32_t* boxes, float* debug, int dbg_h,
+                            int dbg_w);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

@@ -58,8 +58,12 @@ def inference(cfg: dict):
     runner = DistributedSamplingRunner(sampler, mode=mode, **rk) if distributed else SamplingRunner(sampler, **rk)
     if cfg.get("sampling", True):
         runner.inference()
-    if cfg.get("to_nerfstudio") or cfg.get("evaluating"):
-        log.warning("to_nerfstudio / evaluating are post-processing steps of the reference that are out of scope here")
+    if cfg.get("evaluating"):
+        metrics = runner.evaluate()
+        if metrics is not None:  # every rank evaluates, rank 0 holds the result
+            log.info("Metrics: %s (per view: %s/metrics.json)", metrics["mean"], sampler.output_dir)
+    if cfg.get("to_nerfstudio"):
+        log.warning("to_nerfstudio is a post-processing step of the reference that is out of scope here")
 
 
 def main(argv=None):

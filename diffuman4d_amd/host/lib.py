@@ -103,6 +103,11 @@ SIGNATURES = {
     # result evaluation: composite + nearest resize + mask crop + PSNR / SSIM of a batch of image pairs (host/metrics.py)
     "dm4d_eval_ws_bytes": (C.c_size_t, [_i, _i, _i]),
     "dm4d_eval_psnr_ssim_f64": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _i, _i]),
+    # LPIPS-VGG: the steps around the VGG-16 convolutions (host/lpips.py)
+    "dm4d_lpips_input_split": (_i, [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp]),
+    "dm4d_lpips_relu_pool_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "dm4d_lpips_ws_bytes": (C.c_size_t, [_i, _i]),
+    "dm4d_lpips_tap_distance_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp]),
 }
 
 EPI_GEGLU = 1

@@ -12,9 +12,12 @@ to the canvas, the padded bounding box of the masks, the crop, torchmetrics' PSN
 Every batch's planes and descriptors go into one pinned staging buffer and up in one copy; uint8 planes stay uint8 on the way
 (4 x fewer bytes than ``to_tensor``'s floats).  There is no CPU path: a host tensor is uploaded, a missing library raises.
 
-LPIPS is not built (VGG-16 and the LPIPS weights are not part of this package).  ``ImageEvaluator(device, lpips=callable)`` leaves its
-place: the callable receives the cropped composites ``(gt[None], pred[None])`` on the device, as torchmetrics' module does.  Without
-it ``lpips`` is ``None`` in every result and ``null`` in metrics.json.
+LPIPS-VGG is built (``host/lpips.py::LpipsVGG``, csrc/lpips.hip: VGG-16 on the MFMA convolution with three-term bf16 products, fp64
+distances), but its weights are not part of this package and are never fetched: ``lpips_weights=(vgg16_path, lin_path)`` on
+``evaluate_keys`` / ``evaluate_results`` (torchvision's VGG-16 checkpoint and the LPIPS linear layers, the two files the reference's
+torchmetrics module loads) builds one ``LpipsVGG`` per worker.  ``ImageEvaluator(device, lpips=callable)`` takes that object or any
+other callable: it receives the cropped composites ``(gt[None], pred[None])`` on the device, as torchmetrics' module does.  Without
+either ``lpips`` is ``None`` in every result and ``null`` in metrics.json.
 """
 from __future__ import annotations
 
@@ -29,6 +32,7 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import lpips as _lpips
 from . import ops
 from .lib import Dm4dError
 
@@ -210,7 +214,11 @@ class ImageEvaluator:
             lp = None
             if self.lpips is not None:
                 crop = dbg[i, :, :, : b - t, : r - l]
-                lp = float(self.lpips(crop[1][None], crop[0][None]))
+                if self.device.type == "cuda":  # pairs run one after another on the stream the composites were made on
+                    with torch.cuda.device(self.device), torch.cuda.stream(self._stream()):
+                        lp = float(self.lpips(crop[1][None], crop[0][None]))
+                else:  # NOT a CPU path: only a stand-in for ops.eval_psnr_ssim (the non-GPU tests patch one in) gets this far without a device
+                    lp = float(self.lpips(crop[1][None], crop[0][None]))
             res.append((psnr, ssim, lp))
         return res
 
@@ -234,8 +242,13 @@ def evaluation_keys(pred_images_dir: str, spa_labels: Optional[List[str]] = None
 def evaluate_keys(keys: List[str], device, pred_images_dir: str, gt_images_dir: str, fmasks_dir: Optional[str] = None,
                   pred_image_ext: str = ".jpg", gt_image_ext: str = ".jpg", fmask_ext: str = ".png", crop_with_fmask: bool = True,
                   background_color: str = "black", canvas_size: int = 1024, lpips: Optional[Callable] = None, batch_size: int = 16,
-                  decode_threads: int = 8) -> List[Dict]:
-    """The reference's evaluate_on_single_gpu: [{key, psnr, ssim, lpips}] of `keys` on one device, `batch_size` pairs per launch."""
+                  decode_threads: int = 8, *, lpips_weights: Optional[Tuple[str, str]] = None) -> List[Dict]:
+    """The reference's evaluate_on_single_gpu: [{key, psnr, ssim, lpips}] of `keys` on one device, `batch_size` pairs per launch.
+    `lpips_weights` = (vgg16_path, lin_path): this worker builds its own ``LpipsVGG`` on `device` (instead of a `lpips` callable)."""
+    if lpips_weights is not None:
+        if lpips is not None:
+            raise ValueError("pass either lpips= (a callable) or lpips_weights= (the two weight files), not both")
+        lpips = _lpips.LpipsVGG(device, *lpips_weights)
     ev = ImageEvaluator(device, lpips=lpips, decode_threads=decode_threads)
     res = []
     try:
@@ -276,21 +289,27 @@ def evaluate_results(pred_images_dir: str, gt_images_dir: str, fmasks_dir: Optio
                      gt_image_ext: str = ".jpg", fmask_ext: str = ".png", spa_labels: Optional[List[str]] = None,
                      tem_labels: Optional[List[str]] = None, out_metrics_path: Optional[str] = None, crop_with_fmask: bool = True,
                      background_color: str = "black", gpu_ids: Optional[List[int]] = None, *, canvas_size: int = 1024,
-                     lpips: Optional[Callable] = None, batch_size: int = 16, decode_threads: int = 8) -> Dict:
+                     lpips: Optional[Callable] = None, batch_size: int = 16, decode_threads: int = 8,
+                     lpips_weights: Optional[Tuple[str, str]] = None) -> Dict:
     """The reference's ``evaluate_results`` (its keyword list, its key enumeration, its JSON): one thread per entry of `gpu_ids`
     (default: every visible device) over ``keys[i::n]``.  Keyword-only extensions: `canvas_size` (the reference always uses the
-    evaluator's default, 1024), `lpips` (a callable, see the module docstring), `batch_size` (pairs per launch), `decode_threads`."""
+    evaluator's default, 1024), `lpips` (a callable, see the module docstring) or `lpips_weights` = (vgg16_path, lin_path) (every worker
+    thread builds its own ``LpipsVGG`` on its device), `batch_size` (pairs per launch), `decode_threads`."""
+    if lpips is not None and lpips_weights is not None:
+        raise ValueError("pass either lpips= (a callable) or lpips_weights= (the two weight files), not both")
     keys = evaluation_keys(pred_images_dir, spa_labels, tem_labels)
     if gpu_ids is None:
         gpu_ids = list(range(torch.cuda.device_count()))
     if not gpu_ids:
         raise Dm4dError("evaluate_results: no HIP device (diffuman4d_amd has no CPU path)")
-    if lpips is None:
+    if lpips is None and lpips_weights is None:
         log.info("LPIPS is not built: \"lpips\" is null in the metrics (pass lpips=callable to fill it)")
     n = len(gpu_ids)
     kw = dict(pred_images_dir=pred_images_dir, gt_images_dir=gt_images_dir, fmasks_dir=fmasks_dir, pred_image_ext=pred_image_ext,
               gt_image_ext=gt_image_ext, fmask_ext=fmask_ext, crop_with_fmask=crop_with_fmask, background_color=background_color,
               canvas_size=canvas_size, lpips=lpips, batch_size=batch_size, decode_threads=decode_threads)
+    if lpips_weights is not None:
+        kw["lpips_weights"] = tuple(lpips_weights)
     with ThreadPoolExecutor(max_workers=n, thread_name_prefix="dm4d-eval") as ex:
         futures = [ex.submit(evaluate_keys, keys[i::n], _device_of(g), **kw) for i, g in enumerate(gpu_ids)]
         values = [v for f in futures for v in f.result()]

@@ -1045,3 +1045,55 @@ def eval_psnr_ssim(blob: torch.Tensor, desc: torch.Tensor, desc_off: Optional[in
                                      _p(boxes), _p(dbg), max_h, max_w)
     _l.check(rc, "dm4d_eval_psnr_ssim_f64")
     return (out, boxes, dbg) if debug else (out, boxes)
+
+
+LPIPS_TAPS = 5      # include/dm4d.h DM4D_LPIPS_TAPS
+LPIPS_IN_COLS = 64  # include/dm4d.h DM4D_LPIPS_IN_COLS
+
+
+def lpips_input(gt: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
+    """LPIPS' input scaling of one pair of cropped composites (fp32 [3, h, w] views with one row / plane stride, in [0, 1]) -> the operand
+    of VGG's first convolution, bf16 [2, h, w, LPIPS_IN_COLS] = [hi(3) | lo(3) | hi(3) | zeros] (0 = gt, 1 = pred)."""
+    lib = _l.load()
+    _req(gt, "gt", F32), _req(pred, "pred", F32)
+    if gt.dim() != 3 or gt.shape[0] != 3 or gt.shape != pred.shape:
+        raise _l.Dm4dError(f"lpips_input: expected two fp32 [3, h, w] images of one shape, got {tuple(gt.shape)} and {tuple(pred.shape)}")
+    if gt.stride() != pred.stride():
+        gt, pred = gt.contiguous(), pred.contiguous()
+    _, h, w = gt.shape
+    y = torch.empty((2, h, w, LPIPS_IN_COLS), dtype=BF16, device=gt.device)
+    rc = lib.dm4d_lpips_input_split(_stream(), _p(gt), _p(pred), gt.stride(0), gt.stride(1), h, w, _p(y))
+    _l.check(rc, "dm4d_lpips_input_split")
+    return y
+
+
+def lpips_relu_pool(x: torch.Tensor, pool: bool) -> torch.Tensor:
+    """ReLU (+ the 2 x 2 stride-2 floor max-pool) of a convolution's fp32 output [B, H, W, C] -> the pattern-1 operand of the next
+    convolution, bf16 [B, Ho, Wo, 3 C] = [hi | lo | hi]."""
+    lib = _l.load()
+    _req(x, "x", F32)
+    assert x.dim() == 4 and x.is_contiguous()
+    B, H, W, C = x.shape
+    Ho, Wo = (H // 2, W // 2) if pool else (H, W)
+    y = torch.empty((B, Ho, Wo, 3 * C), dtype=BF16, device=x.device)
+    with _Prof("lpips_relu_pool", 4.0 * x.numel() + 2.0 * y.numel(), "byte", B * Ho * Wo):
+        rc = lib.dm4d_lpips_relu_pool_split(_stream(), _p(x), _p(y), B, H, W, C, 1 if pool else 0)
+    _l.check(rc, "dm4d_lpips_relu_pool_split")
+    return y
+
+
+def lpips_ws(h: int, w: int, device) -> torch.Tensor:
+    """The workspace of lpips_tap_distance for taps of up to h x w pixels (one per forward: the taps run one after another)."""
+    return torch.empty(max(int(_l.load().dm4d_lpips_ws_bytes(h, w)), 16), dtype=torch.uint8, device=device)
+
+
+def lpips_tap_distance(f: torch.Tensor, lin: torch.Tensor, tap: int, out: torch.Tensor, ws: torch.Tensor) -> None:
+    """One LPIPS tap: f fp32 [2, H, W, C] (a convolution's output before ReLU), lin fp32 [C] -> out[tap] = the tap's distance (out: fp64
+    [LPIPS_TAPS] on the device); ws: lpips_ws(H, W) or larger."""
+    lib = _l.load()
+    _req(f, "f", F32), _req(lin, "lin", F32), _req(out, "out", torch.float64), _req(ws, "ws", torch.uint8)
+    assert f.dim() == 4 and f.shape[0] == 2 and f.is_contiguous() and lin.numel() == f.shape[3] and out.numel() == LPIPS_TAPS
+    _, H, W, C = f.shape
+    with _Prof("lpips_distance", 4.0 * f.numel(), "byte", H * W):
+        rc = lib.dm4d_lpips_tap_distance_f64(_stream(), _p(f), _p(lin), H, W, C, tap, _p(ws), ws.numel(), _p(out))
+    _l.check(rc, "dm4d_lpips_tap_distance_f64")

@@ -246,9 +246,10 @@ class SamplingRunner:
                 raise ValueError("Sampling failed.")
 
     def evaluate(self, gpu_ids=None, **extra) -> dict:
-        """PSNR / SSIM of the written target views against the captured ones -> ``{output_dir}/metrics.json`` (the reference's
-        ``evaluate``, sampling_runner.py:64-77: same paths and arguments; host/metrics.py).  `gpu_ids`: default the devices of the
-        sampler's pipelines (the reference takes every visible device; the job was given ``model.gpu_ids``)."""
+        """PSNR / SSIM (and LPIPS with ``lpips_weights=(vgg16_path, lin_path)``) of the written target views against the captured ones
+        -> ``{output_dir}/metrics.json`` (the reference's ``evaluate``, sampling_runner.py:64-77: same paths and arguments;
+        host/metrics.py).  `gpu_ids`: default the devices of the sampler's pipelines (the reference takes every visible device; the job
+        was given ``model.gpu_ids``).  `extra`: keyword-only extensions of ``evaluate_results`` (``lpips_weights``, ``canvas_size`` ...)."""
         from .metrics import evaluate_results
         if gpu_ids is None:
             devices = [getattr(p, "device", None) for p in self.sampler.pipelines]

@@ -269,6 +269,34 @@ int dm4d_eval_psnr_ssim_f64(void* stream, const void* blob, int64_t blob_bytes, 
                             int n_pairs, void* workspace, int64_t workspace_bytes, double* out, int32_t* boxes, float* debug, int dbg_h,
                             int dbg_w);
 
+/* LPIPS-VGG of one (ground-truth, predicted) pair of cropped composites (diffuman4d_amd/host/lpips.py::LpipsVGG; the reference's
+ *   ImageEvaluator.lpips = torchmetrics' LearnedPerceptualImagePatchSimilarity(net_type="vgg", normalize=True),
+ *   data/utils/metric_utils.py:14-19, called at :134-137).  The thirteen VGG-16 convolutions run on dm4d_conv3x3_nhwc_bf16_flags
+ *   (DM4D_EPI_F32OUT | DM4D_EPI_F32SIDE, the fp32 bias as its row bias) with three-term bf16 products: activations as pattern-1
+ *   operands [hi | lo | hi] (see dm4d_split_f32) against fp32 weights packed per tap as [w_hi | w_hi | w_lo]; the entries below are
+ *   the steps around them.  A pair is a batch of two images: 0 = ground truth, 1 = prediction.
+ *
+ * dm4d_lpips_input_split: the net's first lines (x = 2 img - 1; (x - shift) / scale, _LPIPS.forward with normalize=True and its
+ *   ScalingLayer).  gt / pred: fp32 planes [3, h, w] in [0, 1], element (c, y, x) at [c * chan_stride + y * row_stride + x] (the
+ *   evaluator's cropped composites are such views) -> Y bf16 [2, h, w, DM4D_LPIPS_IN_COLS] = [hi(3) | lo(3) | hi(3) | zeros]: the
+ *   operand of features.0, whose packed weights carry [w_hi(3) | w_hi(3) | w_lo(3) | zeros] per tap.
+ * dm4d_lpips_relu_pool_split: nn.ReLU (+ nn.MaxPool2d(2, 2), floor sizes, when pool != 0: torchvision's vgg16().features between the
+ *   convolutions) of a convolution's fp32 output X [B, H, W, C] -> Y bf16 [B, Ho, Wo, 3 C] = [hi(C) | lo(C) | hi(C)]; C % 8 == 0.
+ * dm4d_lpips_tap_distance_f64: one tap of _LPIPS.forward's loop: F fp32 [2, H, W, C] (BEFORE ReLU: it is applied on read) ->
+ *   n = f / sqrt(1e-8 + sum_c f^2) per pixel (_normalize_tensor), d = mean_{y,x} sum_c lin[c] (n_0 - n_1)^2 (NetLinLayer, spatial_average);
+ *   out[tap] = d (out: fp64 [DM4D_LPIPS_TAPS]; the value is the sum of the five, which the host takes in tap order).  fp64 sums in a
+ *   fixed order, no floating-point atomics: the same bits on every run, and for the two images swapped.
+ *   C: 64, 128, 256 or 512.  workspace: dm4d_lpips_ws_bytes(H, W) bytes (one fp64 partial per DM4D_LPIPS_DIST_PIXELS pixels).       */
+#define DM4D_LPIPS_TAPS 5
+#define DM4D_LPIPS_IN_COLS 64
+#define DM4D_LPIPS_DIST_PIXELS 256
+int dm4d_lpips_input_split(void* stream, const float* gt, const float* pred, int64_t chan_stride, int64_t row_stride, int h, int w,
+                           void* Y);
+int dm4d_lpips_relu_pool_split(void* stream, const float* X, void* Y, int B, int H, int W, int C, int pool);
+size_t dm4d_lpips_ws_bytes(int H, int W);
+int dm4d_lpips_tap_distance_f64(void* stream, const float* F, const float* lin, int H, int W, int C, int tap, void* workspace,
+                                int64_t workspace_bytes, double* out);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

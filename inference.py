@@ -59,7 +59,14 @@ def inference(cfg: dict):
     if cfg.get("sampling", True):
         runner.inference()
     if cfg.get("evaluating"):
-        metrics = runner.evaluate()
+        # evaluation.lpips_vgg16=PATH evaluation.lpips_lin=PATH: torchvision's VGG-16 checkpoint and the LPIPS linear layers (the two
+        # files the reference's torchmetrics module loads; never fetched here).  Both: "lpips" is filled; neither: it stays null
+        ev = cfg.get("evaluation") or {}
+        paths = {k: ev.get(k) for k in ("lpips_vgg16", "lpips_lin")}
+        missing = [k for k, v in paths.items() if not v]
+        if len(missing) == 1:
+            raise ValueError(f"evaluation.{missing[0]} is missing: LPIPS needs both evaluation.lpips_vgg16 and evaluation.lpips_lin")
+        metrics = runner.evaluate() if missing else runner.evaluate(lpips_weights=(str(paths["lpips_vgg16"]), str(paths["lpips_lin"])))
         if metrics is not None:  # every rank evaluates, rank 0 holds the result
             log.info("Metrics: %s (per view: %s/metrics.json)", metrics["mean"], sampler.output_dir)
     if cfg.get("to_nerfstudio"):

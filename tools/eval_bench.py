@@ -8,8 +8,12 @@ Writes a seeded result directory (predicted .jpg, captured .webp, mask .png at `
   evaluate    evaluate_results over the whole directory, decode included (wall) -> pairs/s
   torch cpu   the fp32 torch-CPU model of the same steps (tests/eval_model.py) on ``--cpu-threads`` threads, per pair, on files already
               decoded -- for scale: it is the arithmetic torchmetrics runs
+  lpips       with ``--lpips VGG16 LIN`` (torchvision's VGG-16 checkpoint and the LPIPS linear layers; ``python tests/lpips_model.py DIR``
+              writes a seeded full-width pair of such files when the real ones are not at hand -- the cost does not depend on the values):
+              ``evaluate_batch`` over ``--lpips-pairs`` pairs without and with ``LpipsVGG`` (wall, decode included, best of ``--reps``) and
+              the span of one LpipsVGG call (device events around its ~45 launches, their host-side gaps and the final read-back), per pair
 
-  python tools/eval_bench.py --src 2448x2048 --canvas 1024 --batch 64 --pairs 128 --threads 16
+  python tools/eval_bench.py --src 2448x2048 --canvas 1024 --batch 64 --pairs 128 --threads 16 [--lpips vgg16-397923af.pth vgg.pth]
 """
 from __future__ import annotations
 
@@ -62,6 +66,8 @@ def main(argv=None):
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--cpu-pairs", type=int, default=4)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--lpips", nargs=2, metavar=("VGG16", "LIN"), default=None, help="the two LPIPS weight files: also time LPIPS")
+    ap.add_argument("--lpips-pairs", type=int, default=8)
     args = ap.parse_args(argv)
     W, H = (int(v) for v in args.src.split("x"))
     cams, frames = 8, max(1, args.pairs // 8)
@@ -120,14 +126,48 @@ def main(argv=None):
         import eval_model as em
         from PIL import Image
         torch.set_num_threads(args.cpu_threads)
-        loaded = [{k: np.asarray(Image.open(v)) if isinstance(v, str) else v for k, v in kw.items()} for kw in pairs[: args.cpu_pairs]]
+        loaded = [{k: np.asarray(Image.open(v)) if k in ("pred", "gt", "pred_fmask", "gt_fmask") else v for k, v in kw.items()} for kw in pairs[: args.cpu_pairs]]
         t0 = time.perf_counter()
         cpu = [em.evaluate(dtype=torch.float32, **kw)[:2] for kw in loaded]
         t_cpu = (time.perf_counter() - t0) / len(loaded)
         res.update({"torch_cpu_fp32_threads": args.cpu_threads, "torch_cpu_fp32_s_per_pair": round(t_cpu, 3),
                     "torch_cpu_over_kernel": round(t_cpu / (t_kernel / len(batch)), 1),
                     "native_minus_cpu_pair_0": [float(out[0, 0]) - cpu[0][0], float(out[0, 1]) - cpu[0][1]]})
-        print(json.dumps(res))
+        print(json.dumps(res), flush=True)
+        if args.lpips:
+            print(json.dumps(lpips_report(dev, pairs[: args.lpips_pairs], args)))
+
+
+def lpips_report(dev, pairs, args) -> dict:
+    """Time per pair of evaluate_batch without and with LPIPS on the same pairs, and the event span of the LpipsVGG call alone (it
+    contains the host-side gaps between its launches: an upper bound of the kernel time, not the kernel time)."""
+    from diffuman4d_amd.host.lpips import LpipsVGG
+    lp = LpipsVGG(dev, *args.lpips)
+    events = []
+
+    def timed_lp(gt, pred):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        v = lp(gt, pred)
+        e.record()
+        events.append((s, e, tuple(gt.shape[2:])))
+        return v
+
+    def wall(ev):
+        best = float("inf")
+        for _ in range(args.reps + 1):  # the first call warms up
+            t0 = time.perf_counter()
+            out = ev.evaluate_batch(pairs)
+            best = min(best, time.perf_counter() - t0)
+        return best / len(pairs), out
+
+    t_plain, _ = wall(metrics.ImageEvaluator(dev, decode_threads=args.threads))
+    t_lpips, out = wall(metrics.ImageEvaluator(dev, lpips=timed_lp, decode_threads=args.threads))
+    torch.cuda.synchronize()
+    per_pair = [min(s.elapsed_time(e) for s, e, _ in events[i + len(pairs):: len(pairs)]) for i in range(len(pairs))]  # without the warm-up round
+    return {"lpips_pairs": len(pairs), "canvas": args.canvas, "crop_of_pair_0": list(events[0][2]),
+            "psnr_ssim_only_ms_per_pair": round(t_plain * 1e3, 2), "with_lpips_ms_per_pair": round(t_lpips * 1e3, 2),
+            "lpips_call_span_ms_per_pair": round(sum(per_pair) / len(per_pair), 2), "lpips_of_pair_0": out[0][2]}
 
 
 if __name__ == "__main__":

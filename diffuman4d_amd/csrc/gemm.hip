@@ -34,11 +34,15 @@
 // bias (time-embedding add), residual or scale follow -- so that every global store is a coalesced 16-byte row write.
 #include "common.h"
 #include "gemm_common.h"
+#include "gemm_select.h"
+#include <stdio.h>
 
 // Build switches that rounds 1-2 used for A/B and ablation runs (GEMM_FAST_EPI, GEMM_EPI_STRAIGHT, STRIP2_SCHED, GEGLU_ERF, GEMM_ABLATE,
 // STRIP2_NOWAIT) are resolved to the shipped values: shift / 32-bit-offset index arithmetic in the epilogue read-back loop, the
 // branch-free read-back of residual / row-bias blocks, sched_group_barrier placement of the fragment reads in the strip and
 // second-form loops, the erf form of GELU in the GEGLU epilogue (DESIGN.md section 4 has the measurements).
+// Host side: gemm_select.h (host-only, under a CPU test) decides which configuration a launch takes -- the tile heuristic choose_cfg and
+// the choice per precision; launch_by_id below turns the id into a kernel instantiation.
 
 namespace {
 
@@ -970,44 +974,37 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmParams p) {
   gemm_epilogue<MI, NI, TM, TN, EpiBudget<WM * WN, MI, NI, SMEM_BYTES>::STRAIGHT, PAR>(p, acc, reinterpret_cast<float*>(smem), m0, n0, wm, wn, wave, lane);
 }
 
+// Workgroups of a launch on BM x BN tiles; leaves the column-tile count in p.tiles_n, so call it BEFORE the launch statement that copies
+// p.  A GEGLU tile holds BN / 2 output columns (hidden and gate rows paired inside it; Linear layers only: no convolution entry takes the flag).
+template <int BM, int BN>
+unsigned tile_grid(GemmParams& p) {
+  const int bn_out = is_geglu(p) ? BN / 2 : BN;
+  p.tiles_n = (p.N + bn_out - 1) / bn_out;
+  return (unsigned)(((p.M + BM - 1) / BM) * p.tiles_n);
+}
+
 template <int BM, int BN, int WM, int WN, bool CONV, bool GLDS, int PAR = 0>
 int launch_cfg(hipStream_t st, GemmParams& p) {
-  const bool geglu = (p.flags & DM4D_EPI_GEGLU) != 0;
-  const int bn_out = geglu ? BN / 2 : BN;
-  const int tiles_m = (p.M + BM - 1) / BM;
-  p.tiles_n = (p.N + bn_out - 1) / bn_out;
+  const dim3 grid(tile_grid<BM, BN>(p));
   if constexpr (GLDS) {
-    hipLaunchKernelGGL((gemm_kernel_glds<BM, BN, WM, WN, CONV, PAR>), dim3(tiles_m * p.tiles_n), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((gemm_kernel_glds<BM, BN, WM, WN, CONV, PAR>), grid, dim3(256), 0, st, p);
   } else {
-    hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, CONV, PAR>), dim3(tiles_m * p.tiles_n), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((gemm_kernel<BM, BN, WM, WN, CONV, PAR>), grid, dim3(256), 0, st, p);
   }
   return dm4d_check_launch("gemm_kernel");
 }
 
 template <int BM, int BN, int WM, int WN, int NST, bool CONV, int BK = 32, int PAR = 0>
 int launch_pipe(hipStream_t st, GemmParams& p) {
-  const bool geglu = (p.flags & DM4D_EPI_GEGLU) != 0;
-  const int bn_out = geglu ? BN / 2 : BN;
-  const int tiles_m = (p.M + BM - 1) / BM;
-  p.tiles_n = (p.N + bn_out - 1) / bn_out;
-  hipLaunchKernelGGL((gemm_kernel_pipe<BM, BN, WM, WN, NST, CONV, BK, PAR>), dim3(tiles_m * p.tiles_n), dim3(WM * WN * 64), 0, st, p);
+  const dim3 grid(tile_grid<BM, BN>(p));
+  hipLaunchKernelGGL((gemm_kernel_pipe<BM, BN, WM, WN, NST, CONV, BK, PAR>), grid, dim3(WM * WN * 64), 0, st, p);
   return dm4d_check_launch("gemm_kernel_pipe");
-}
-
-// the second form addresses A, A2 and W with 32-bit byte offsets from a uniform base and walks K in slabs of 64
-__host__ inline bool lin2_ok(const GemmParams& p) {
-  return p.K % 64 == 0 && (!p.A2 || p.K1 % 64 == 0) && (uint64_t)p.M * (uint64_t)p.lda * 2u < (1ull << 32) &&
-         (!p.A2 || (uint64_t)p.M * (uint64_t)p.lda2 * 2u < (1ull << 32)) &&
-         (uint64_t)(2 * (uint64_t)p.N) * (uint64_t)p.ldw * 2u < (1ull << 32);
 }
 
 template <int BM, int BN, int WM, int WN, int NST, int BK = 64, int PAR = 0>
 int launch_lin2(hipStream_t st, GemmParams& p) {
-  const bool geglu = (p.flags & DM4D_EPI_GEGLU) != 0;
-  const int bn_out = geglu ? BN / 2 : BN;
-  const int tiles_m = (p.M + BM - 1) / BM;
-  p.tiles_n = (p.N + bn_out - 1) / bn_out;
-  hipLaunchKernelGGL((gemm_lin2_kernel<BM, BN, WM, WN, NST, BK, PAR>), dim3(tiles_m * p.tiles_n), dim3(WM * WN * 64), 0, st, p);
+  const dim3 grid(tile_grid<BM, BN>(p));
+  hipLaunchKernelGGL((gemm_lin2_kernel<BM, BN, WM, WN, NST, BK, PAR>), grid, dim3(WM * WN * 64), 0, st, p);
   return dm4d_check_launch("gemm_lin2_kernel");
 }
 
@@ -1076,28 +1073,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(GemmParams p) {
   }
 }
 
-// Split-K applies to stride-1 convolutions on small images (the 9x5 level of the UNet: M = B*45 rows against a
-// 11520- or 23040-deep K).  The rule looks at the per-image geometry only, never at the batch, so a frame-sharded
-// run (fewer frames per rank) sums in the same order as the unsharded one.
-__host__ inline bool strip_split_ok(const GemmParams& p) {
-  return p.H * p.W <= 64 && p.Cin >= 512 && (p.N & 7) == 0 && (p.ldc & 7) == 0 && (!p.res || (p.ld_res & 7) == 0) &&
-         (!p.rowbias || (p.ld_rb & 7) == 0) && (p.flags & ~(DM4D_EPI_F32OUT | DM4D_EPI_F32SIDE | DM4D_EPI_H16)) == 0 &&
-         ((p.flags & DM4D_EPI_H16) || p.flags == 0);  // the parity precision (F32OUT / F32SIDE without H16) never splits
-}
-
-// the strip kernel addresses A and W with 32-bit byte offsets from a uniform base
-__host__ inline bool strip2_ok(const GemmParams& p) {
-  return (uint64_t)p.M * (uint64_t)p.Cin * 2u < (1ull << 32) && (uint64_t)p.N * (uint64_t)p.ldw * 2u < (1ull << 32);
-}
-
 template <int BM, int BN, int WM, int WN, int PAR = 0>
 int launch_strip2(hipStream_t st, GemmParams& p) {
   if (!strip2_ok(p)) return DM4D_ERR_ARG;  // 4 GiB or more of input or weights: the gather kernels take such a launch
   if (BN % 64 != 0 && p.splits > 1) return DM4D_ERR_ARG;
-  const int tiles_m = (p.M + BM - 1) / BM;
-  p.tiles_n = (p.N + BN - 1) / BN;
   if (p.splits < 1) p.splits = 1;
-  hipLaunchKernelGGL((conv_strip2_kernel<BM, BN, WM, WN, 3, PAR>), dim3(tiles_m * p.tiles_n * p.splits), dim3(WM * WN * 64), 0, st, p);
+  const dim3 grid(tile_grid<BM, BN>(p) * p.splits);
+  hipLaunchKernelGGL((conv_strip2_kernel<BM, BN, WM, WN, 3, PAR>), grid, dim3(WM * WN * 64), 0, st, p);
   int rc = dm4d_check_launch("conv_strip2_kernel");
   if (rc || p.splits == 1) return rc;
   const int64_t nthreads = (int64_t)p.M * (p.N / 8);
@@ -1108,10 +1090,9 @@ int launch_strip2(hipStream_t st, GemmParams& p) {
 // Phase-decomposed x2 upsampling convolution: grid = 4 phases x tiles, weights [4][N][4 Cin] from up2x_prepare_kernel
 template <int BM, int BN, int WM, int WN, int PAR = 0>
 int launch_up2x(hipStream_t st, GemmParams& p) {
-  const int tiles_m = (p.M + BM - 1) / BM;
-  p.tiles_n = (p.N + BN - 1) / BN;
   p.splits = 1;
-  hipLaunchKernelGGL((conv_strip2_kernel<BM, BN, WM, WN, 2, PAR>), dim3(4 * tiles_m * p.tiles_n), dim3(WM * WN * 64), 0, st, p);
+  const dim3 grid(4 * tile_grid<BM, BN>(p));
+  hipLaunchKernelGGL((conv_strip2_kernel<BM, BN, WM, WN, 2, PAR>), grid, dim3(WM * WN * 64), 0, st, p);
   return dm4d_check_launch("conv_strip2_kernel<up2x>");
 }
 
@@ -1143,355 +1124,188 @@ __global__ __launch_bounds__(256) void up2x_prepare_kernel(const u16* W, u16* Wp
 
 int g_tune_cfg = 0;  // 0 = heuristic; otherwise a kernel-configuration id (tuning hook, dm4d_tune_set_gemm_config)
 
-// Kernel configurations.  glds: K-slab 64, 2 LDS stages, 4 waves.  pipe: K-slab 32, 3-4 stages, 4 or 8 waves.
+// Kernel configurations: the one place where an id (chosen in gemm_select.h, or forced by the tuning hook) becomes a template
+// instantiation.  glds: K-slab 64, 2 LDS stages, 4 waves.  pipe: K-slab 32, 3-4 stages, 4 or 8 waves.
+template <int ID, bool CONV, int PAR>
+int launch_id(hipStream_t st, GemmParams& p) {
+  constexpr bool STRIP = ID >= 31 && ID <= 37, LIN2 = ID >= 61;  // strip kernels: convolutions only; second form: Linear layers only
+  const bool geglu = is_geglu(p);
+  if constexpr ((STRIP && !CONV) || (LIN2 && CONV)) return DM4D_ERR_ARG;
+  else if ((ID <= 4 && !k64<CONV>(p)) || (STRIP && !strip_conv(p)) || (LIN2 && !lin2_ok(p))) return DM4D_ERR_ARG;
+  else if constexpr (ID == 1) return launch_cfg<128, 128, 2, 2, CONV, true, PAR>(st, p);
+  else if constexpr (ID == 2) return launch_cfg<256, 64, 4, 1, CONV, true, PAR>(st, p);
+  else if constexpr (ID == 3) return launch_cfg<128, 64, 4, 1, CONV, true, PAR>(st, p);
+  else if constexpr (ID == 4) return geglu ? DM4D_ERR_ARG : launch_cfg<64, 64, 2, 2, CONV, true, PAR>(st, p);
+  else if constexpr (ID == 13) return launch_pipe<256, 256, 2, 4, 4, CONV, 32, PAR>(st, p);
+  else if constexpr (ID == 14) return launch_pipe<256, 128, 4, 2, 3, CONV, 32, PAR>(st, p);
+  // 16 waves (one 1024-thread workgroup per CU, four waves per SIMD like two 8-wave workgroups) on a 256x256 tile: the
+  // per-wave work of id 14 (64x64) with 2/3 of its L2->LDS bytes per flop
+  else if constexpr (ID == 20) return launch_pipe<256, 256, 4, 4, 4, CONV, 32, PAR>(st, p);
+  // 320-wide tile (see id 35), K-slab 64, 2 stages = 144 KB; per-wave tile 64 x 160 = 5 column blocks: no GEGLU pairing
+  else if constexpr (ID == 46) return (k64<CONV>(p) && !geglu) ? launch_pipe<256, 320, 4, 2, 2, CONV, 64, PAR>(st, p) : DM4D_ERR_ARG;
+  // stride-1 3x3 convolutions on the strip kernel (same K order on every tile, so the choice never changes a result)
+  else if constexpr (ID == 31) return launch_strip2<128, 128, 2, 2, PAR>(st, p);
+  else if constexpr (ID == 32) return launch_strip2<256, 128, 4, 2, PAR>(st, p);
+  else if constexpr (ID == 33) return launch_strip2<128, 64, 4, 1, PAR>(st, p);
+  else if constexpr (ID == 34) return launch_strip2<256, 256, 2, 4, PAR>(st, p);
+  // every channel count of an SD-class UNet is a multiple of 320: a 320-wide tile reads the A strip once per
+  // kernel row for N = 320 (level 0) and feeds 40 MFMAs per wave between two barriers
+  else if constexpr (ID == 35) return launch_strip2<256, 320, 4, 2, PAR>(st, p);
+  // 160-wide tiles for N = 320 (two column tiles, no padding): 4 waves x (32 x 160) at 78 KB = two workgroups per CU, or 8 waves
+  else if constexpr (ID == 36) return launch_strip2<128, 160, 4, 1, PAR>(st, p);
+  else if constexpr (ID == 37) return launch_strip2<256, 160, 8, 1, PAR>(st, p);
+  // Linear layers on gemm_lin2_kernel: 61 = 256x128, 8 waves, K-slab 64, 3 stages; 63 = 128x128
+  // with 4 waves (2 workgroups per CU); 64 = 128x128 with 8 waves; 65 = 256x128, 8 waves, K-slab 32, 3 stages = 74 KB (two
+  // workgroups per CU); 67 = 256x256 on eight waves (128x64 per wave), K-slab 64, 2 stages = 128 KB
+  else if constexpr (ID == 67) return launch_lin2<256, 256, 2, 4, 2, 64, PAR>(st, p);
+  else if constexpr (ID == 65) return launch_lin2<256, 128, 4, 2, 3, 32, PAR>(st, p);
+  else if constexpr (ID == 61) return launch_lin2<256, 128, 4, 2, 3, 64, PAR>(st, p);
+  // N = 320 on a tall problem (level 0: proj_in, attention output, proj_out) without padded columns: 128x160 on 4 waves
+  // (32 x 160 per wave) at 74 KB = two workgroups per CU
+  else if constexpr (ID == 69) return geglu ? DM4D_ERR_ARG : launch_lin2<128, 160, 4, 1, 2, 64, PAR>(st, p);
+  else if constexpr (ID == 63) return launch_lin2<128, 128, 2, 2, 2, 64, PAR>(st, p);
+  else if constexpr (ID == 64) return launch_lin2<128, 128, 4, 2, 3, 64, PAR>(st, p);
+  else if constexpr (ID == 21) return launch_cfg<256, 128, 2, 2, CONV, false, PAR>(st, p);
+  else if constexpr (ID == 22) return launch_cfg<128, 128, 2, 2, CONV, false, PAR>(st, p);
+  else if constexpr (ID == 23) return launch_cfg<256, 64, 4, 1, CONV, false, PAR>(st, p);
+  else return launch_cfg<128, 64, 4, 1, CONV, false, PAR>(st, p);  // 24
+}
+
+// walks a list of gemm_select.h: the parity precision (PAR = 1) has kernels for the ids of ParIds only, the others for AllIds
+template <bool CONV, int PAR>
+int launch_from(IdList<>, int, hipStream_t, GemmParams&) { return DM4D_ERR_ARG; }  // an id the list does not hold
+template <bool CONV, int PAR, int ID, int... REST>
+int launch_from(IdList<ID, REST...>, int id, hipStream_t st, GemmParams& p) {
+  return id == ID ? launch_id<ID, CONV, PAR>(st, p) : launch_from<CONV, PAR>(IdList<REST...>{}, id, st, p);
+}
 template <bool CONV, int PAR = 0>
 int launch_by_id(int id, hipStream_t st, GemmParams& p) {
-  const bool geglu = (p.flags & DM4D_EPI_GEGLU) != 0;
-  const bool k64 = CONV ? (p.Cin % 64 == 0) : (p.K % 64 == 0 && (!p.A2 || p.K1 % 64 == 0));
-  if (id >= 1 && id <= 4 && !k64) return DM4D_ERR_ARG;
-  switch (id) {
-    case 1: return launch_cfg<128, 128, 2, 2, CONV, true, PAR>(st, p);
-    case 2: return launch_cfg<256, 64, 4, 1, CONV, true, PAR>(st, p);
-    case 3: return launch_cfg<128, 64, 4, 1, CONV, true, PAR>(st, p);
-    case 4: return geglu ? DM4D_ERR_ARG : launch_cfg<64, 64, 2, 2, CONV, true, PAR>(st, p);
-    case 13: return launch_pipe<256, 256, 2, 4, 4, CONV, 32, PAR>(st, p);
-    case 14: return launch_pipe<256, 128, 4, 2, 3, CONV, 32, PAR>(st, p);
-    // 16 waves (one 1024-thread workgroup per CU, four waves per SIMD like two 8-wave workgroups) on a 256x256 tile: the
-    // per-wave work of id 14 (64x64) with 2/3 of its L2->LDS bytes per flop
-    case 20: return launch_pipe<256, 256, 4, 4, 4, CONV, 32, PAR>(st, p);
-    // 320-wide tile (see id 35), K-slab 64, 2 stages = 144 KB; per-wave tile 64 x 160 = 5 column blocks: no GEGLU pairing
-    case 46: return (k64 && !geglu) ? launch_pipe<256, 320, 4, 2, 2, CONV, 64, PAR>(st, p) : DM4D_ERR_ARG;
-    // stride-1 3x3 convolutions on the strip kernel (same K order on every tile, so the choice never changes a result)
-    case 31: case 32: case 33: case 34: case 35: case 36: case 37:
-      if constexpr (CONV) {
-        if (!(k64 && p.stride == 1 && p.pad == 1 && !p.upsample && p.Ho == p.H && p.Wo == p.W)) return DM4D_ERR_ARG;
-        if (id == 31) return launch_strip2<128, 128, 2, 2, PAR>(st, p);
-        if (id == 32) return launch_strip2<256, 128, 4, 2, PAR>(st, p);
-        if (id == 33) return launch_strip2<128, 64, 4, 1, PAR>(st, p);
-        // every channel count of an SD-class UNet is a multiple of 320: a 320-wide tile reads the A strip once per
-        // kernel row for N = 320 (level 0) and feeds 40 MFMAs per wave between two barriers
-        if (id == 35) return launch_strip2<256, 320, 4, 2, PAR>(st, p);
-        // 160-wide tiles for N = 320 (two column tiles, no padding): 4 waves x (32 x 160) at 78 KB = two workgroups per CU, or 8 waves
-        if (id == 36) return launch_strip2<128, 160, 4, 1, PAR>(st, p);
-        if (id == 37) return launch_strip2<256, 160, 8, 1, PAR>(st, p);
-        return launch_strip2<256, 256, 2, 4, PAR>(st, p);
-      } else {
-        return DM4D_ERR_ARG;
-      }
-    // Linear layers on gemm_lin2_kernel: 61 = 256x128, 8 waves, K-slab 64, 3 stages; 63 = 128x128
-    // with 4 waves (2 workgroups per CU); 64 = 128x128 with 8 waves; 65 = 256x128, 8 waves, K-slab 32, 3 stages = 74 KB (two
-    // workgroups per CU); 67 = 256x256 on eight waves (128x64 per wave), K-slab 64, 2 stages = 128 KB
-    case 61: case 63: case 64: case 65: case 67: case 69:
-      if constexpr (!CONV) {
-        if (!lin2_ok(p)) return DM4D_ERR_ARG;
-        if (id == 67) return launch_lin2<256, 256, 2, 4, 2, 64, PAR>(st, p);
-        if (id == 65) return launch_lin2<256, 128, 4, 2, 3, 32, PAR>(st, p);
-        if (id == 61) return launch_lin2<256, 128, 4, 2, 3, 64, PAR>(st, p);
-        // N = 320 on a tall problem (level 0: proj_in, attention output, proj_out) without padded columns: 128x160 on 4 waves
-        // (32 x 160 per wave) at 74 KB = two workgroups per CU
-        if (id == 69) return geglu ? DM4D_ERR_ARG : launch_lin2<128, 160, 4, 1, 2, 64, PAR>(st, p);
-        if (id == 63) return launch_lin2<128, 128, 2, 2, 2, 64, PAR>(st, p);
-        return launch_lin2<128, 128, 4, 2, 3, 64, PAR>(st, p);
-      } else {
-        return DM4D_ERR_ARG;
-      }
-    case 21: return launch_cfg<256, 128, 2, 2, CONV, false, PAR>(st, p);
-    case 22: return launch_cfg<128, 128, 2, 2, CONV, false, PAR>(st, p);
-    case 23: return launch_cfg<256, 64, 4, 1, CONV, false, PAR>(st, p);
-    case 24: return launch_cfg<128, 64, 4, 1, CONV, false, PAR>(st, p);
-    default: return DM4D_ERR_ARG;
-  }
+  return launch_from<CONV, PAR>(std::conditional_t<PAR == 1, ParIds<CONV>, AllIds>{}, id, st, p);
 }
 
-// Heuristic (tuned on the UNet shapes at 72x40 latents, profiles/r01_gemm_tune.log)
-template <bool CONV>
-int choose_cfg(const GemmParams& p) {
-  const bool geglu = (p.flags & DM4D_EPI_GEGLU) != 0;
-  const bool k64 = CONV ? (p.Cin % 64 == 0) : (p.K % 64 == 0 && (!p.A2 || p.K1 % 64 == 0));
-  const bool n128 = geglu || (p.N % 128 == 0) || (p.N > 1024);
-  if (!k64) {  // K-slab 32 register-staged fallback
-    const long tiles_big = (long)((p.M + 255) / 256) * ((p.N + (geglu ? 63 : 127)) / (geglu ? 64 : 128));
-    if (n128) return tiles_big >= 384 ? 21 : 22;
-    return (long)((p.M + 255) / 256) * ((p.N + 63) / 64) >= 384 ? 23 : 24;
-  }
-  const int bn = geglu ? 64 : 128;  // output columns of a 128-wide B tile
-  const long tm256 = (p.M + 255) / 256, tm128 = (p.M + 127) / 128, tn = (p.N + bn - 1) / bn;
-  if (!CONV) {
-    // N = 320 on a tall problem (level 0: proj_in, attention output projection, proj_out; the feed-forward's output projection when
-    // the fused kernel is off): two 160-wide column tiles, no padded third tile -- cold-cache sweep profiles/r03_lin_160_tiles.log:
-    // 59.2 vs 70.0 us at K = 320 and CFG batch 32, 85.6 vs 92.8 at 48; 126 vs 141 / 197 vs 200 at K = 1280 (where the 320-wide
-    // tiles, ids 46 / 62 of round 2, used to be ahead; 46 stays for inputs the second form's 32-bit offsets cannot address)
-    if (!geglu && p.N == 320 && tm256 >= 256) {
-      if (lin2_ok(p)) return 69;
-      if (p.K >= 1024) return 46;
-    }
-#ifndef DM4D_NO_STACK_CFG  // (-DDM4D_NO_STACK_CFG: the table as tuned on single tasks, for the A/B)
-    // Round 6: the launches of a 2-task stack (CFG batch 64 / 96: 720 / 1080 row tiles of 256 at level 0) -- sweep of every id on those
-    // shapes, profiles/r06_gemm_tune_stacks.log: the level-0 QKV projection (N = 960, K = 320) on the 320-wide tile (three column tiles,
-    // no padded fourth: 209 -> 181 us, 301 -> 262 us), level 1's feed-forward output projection on the 160-wide one (197 -> 181, 288 -> 276)
-    if (!geglu && k64 && p.K == 320 && p.N == 960 && tm256 >= 700) return 46;
-    if (!geglu && p.N == 640 && p.K >= 2560 && tm256 >= 180 && lin2_ok(p)) return 69;
-#endif
-    // deep-K layers (K >= 1280): the second form (gemm_lin2_kernel), bit-identical, -4..-17 % per launch
-    // (profiles/r02_lin2_ab.log): 128x128 tiles with two workgroups per CU wherever they fill the chip, the 8-wave
-    // 3-stage 128x128 tile for the few-row, very deep output projections of the deepest level, and the 256x128 K-slab-64
-    // tile for that level's GEGLU projection.  Shorter K needs two resident workgroups (a tile is mostly prologue and
-    // epilogue): see id 65 below.
-    if (lin2_ok(p)) {
-      // 256x256 tiles on 8 waves (128x64 per wave: 6 fragment reads feed 8 MFMAs instead of 4 feeding 4), one workgroup per
-      // CU.  Chosen from TWO sweeps of every id (all bit-identical): the usual timing loop (profiles/r02_lin_tiles_256.log) and
-      // single launches after a cache flush with only the activations re-touched (profiles/r02_lin_cold.log) -- the state a
-      // layer meets inside a UNet pass, where this tile's exposed prologue costs more.  It wins both ways on the deep-K wide
-      // layers (K >= 1280: GEGLU projection of level 2 182 -> 156 us hot, 176 -> 156 cold; QKV of level 2 at CFG batch 48
-      // 95 -> 80 / 98 -> 82) and on the K = 640 ones only when the rounds of 256 tiles are nearly full; at K = 320 the
-      // two-workgroup 74 KB tile (id 65) is 8 % ahead cold and stays.
-      {
-        const long nw = geglu ? 2L * p.N : p.N, tn256 = (nw + 255) / 256, t = tm256 * tn256;
-        const double fill = (double)t / (double)(((t + 255) / 256) * 256) * (double)nw / (double)(tn256 * 256);
-        if (geglu && ((p.K >= 1280 && fill >= 0.85) || (p.K >= 640 && fill >= 0.95))) return 67;
-        // (round 6, second sweep of the stacked launches: id 67 for level 1's GEGLU projection at fill 0.94 and id 61 for level 2's K = 5120
-        // output projection were 6-8 % ahead per launch in the timing loop and 0.15 ms BEHIND over the Linear family of a bench step:
-        // profiles/r06_stackcfg2.log; not taken)
-        if (!geglu && p.K >= 640 && p.N >= 1280 && fill >= 0.85) return 67;
-        // one partial round (160-256 tiles) of the N = 1280 projections of level 2 at CFG batch 48: 42 vs 45 us, 122 vs 135 us
-        if (!geglu && p.K >= 1280 && p.N == 1280 && t >= 160 && t <= 256) return 67;
-      }
-      if (geglu) {
-        if (tm256 <= 12 && p.K >= 1280) return 61;
-      } else if (p.K >= 1280 && p.N >= 640) {
-        if (tm128 * ((p.N + 127) / 128) >= 256) return 63;
-        if (p.K >= 2560) return 64;
-      }
-    }
-    // Linear layers stream A once with little reuse (K = C or 4C): they are bound by L2->LDS bytes and DMA latency,
-    // so the 8-wave 256x128 tile with 2 slabs of DMA in flight wins whenever it still fills the chip (1.2-1.35x)
-    const long t = tm256 * tn;  // one 8-wave workgroup per CU => 256 slots per round; avoid a mostly empty last round
-    if (t >= 256 && 5 * t >= 4 * ((t + 255) / 256) * 256) {
-      // the same 74 KB geometry (two workgroups per CU) in the second form: -2..-9 % on the GEGLU projections of levels 0-2,
-      // -9..-16 % on the K = 640 layers of level 1, +-1 % on the narrow K = 320 layers; the wide K = 320 QKV projection
-      // (N = 960) is the one shape where it is not ahead at both batch sizes (profiles/r02_lin2_ab.log, id 65 vs auto)
-      // (id 61, the 147 KB three-stage tile, for the residual layers with K <= 640 -- ahead in the cold sweep, behind in the timing
-      // loop -- measured in a bench step: Linear family 27.6 -> 27.8 ms, profiles/r02_lin_heuristic_cold_ab.log; not taken)
-      if (lin2_ok(p) && (geglu || p.K >= 640 || p.N <= 640)) return 65;
-      return 14;
-    }
-  } else {
-    // stride-1 convs: the strip kernels stage A once per kernel row (profiles/r01_conv_strip.log)
-    if (p.stride == 1 && p.pad == 1 && !p.upsample && p.Ho == p.H && p.Wo == p.W && strip2_ok(p)) {
-      if (!n128) {
-        // N = 320 on a tall problem (level 0 of the UNet): two 160-wide column tiles, no padded columns and a third of the A re-reads
-        // of the 64-wide tile -- 8 waves on 256 rows when the last round of 256 workgroups is at least half full, else 4 waves on
-        // 128 rows with two workgroups per CU (-6..-12 % per launch against ids 33 / 35 at CFG batch 32 and 48, cold-cache sweep
-        // profiles/r03_strip_160_tiles.log); same K order as every strip kernel, so the choice never changes a result
-        if (p.N == 320 && tm256 >= 256) {
-#ifndef DM4D_NO_STACK_CFG
-          // round 6, stacked launches (profiles/r06_gemm_tune_stacks.log): with 720 / 1080 row tiles the 320-wide tile -- the A strip staged
-          // once per kernel row for all of N -- is ahead of the 160-wide ones: 320 -> 320 292 -> 269 us, 960 -> 320 845 -> 758 / 1298 -> 1196,
-          // 640 -> 320 570 -> 510 / 874 -> 817 (at CFG batch 32 / 48 the 160-wide tiles stay: r03_strip_160_tiles.log)
-          if (tm256 >= 700) return 35;
-#endif
-          const long t2 = tm256 * 2, last = t2 % 256;
-          return (last == 0 || last >= 128) ? 37 : 36;
-        }
-        if (tm128 * ((p.N + 63) / 64) >= 256) return 33;
-      } else {
-        const long t = tm256 * tn;
-        // (round 6, second sweep of the stacked launches, two passes of 12 launches, profiles/r06_gemm_tune_stacks_p1.log / _p2.log: the
-        // 160-wide tiles for level 1 (N = 640) and 256x128 for level 2 at CFG batch 96 are 4-7 % ahead per launch and take 0.7 ms off the
-        // convolution family of a one-stack-at-a-time pass -- and ADD 0.2-0.3 ms to the bench step with three stacks in flight
-        // (profiles/r06_stackcfg3.log): not taken)
-        // N = 640 (level 1) when two 320-wide column tiles make ONE nearly full round of 256 workgroups (CFG batch 32: 180): the A strip
-        // is read twice instead of five times, -3..-9 % per launch in both cold sweeps (r02_strip_cold.log, r03_strip_160_tiles.log);
-        // at batch 48 the same tile needs a second, nearly empty round and loses 20 %
-        if (p.N == 640 && p.Cin >= 640 && tm256 * 2 >= 160 && tm256 * 2 <= 256) return 35;
-        if (p.N % 256 == 0 && tm256 * (p.N / 256) >= 160) return 34;
-        // one partial round of 256x128 tiles against a nearly full round of 128x128 tiles at two workgroups per CU (level 2 at CFG
-        // batch 32: 230 vs 450 of 512): the small tile is 4-6 % ahead in both cold-cache sweeps (r02_strip_cold.log, r03_strip_160_tiles.log)
-        if (t <= 256 && tm128 * tn >= 384 && tm128 * tn <= 512) return 31;
-        if (t >= 200 && 5 * t >= 4 * ((t + 255) / 256) * 256) return 32;
-        if (tm128 * tn >= 256) return 31;
-      }
-    }
-    // upsample-fused convs (Upsample2D): the gather reads every input pixel four times, so tiles that cut the A traffic
-    // win: 320-wide for N = 640 (578 vs 698-760 us), 16-wave 256x256 for N = 1280 (634 vs 685-740 us); all of these walk K
-    // in the same (ky, kx, ci) order as the other gather kernels
-    if (p.upsample && k64) {
-      if (p.N % 320 == 0 && p.N <= 640 && tm256 >= 64) return 46;
-      if (p.N % 256 == 0 && tm256 * (p.N / 256) >= 256) return 20;
-    }
-    // other convs: 128x128 / 2 workgroups per CU is best except for wide, tall problems
-    if (!geglu && p.N % 256 == 0 && tm256 * (p.N / 256) >= 384) return 13;
-  }
-  if (n128) {
-    if (tm128 * tn >= 256) return 1;
-    if (geglu) return 3;
-    return tm128 * tn >= 200 ? 3 : 4;  // deepest UNet level: shrink the tile until the grid covers the 256 CUs
-  }
-  return tm256 * ((p.N + 63) / 64) >= 384 ? 2 : 3;
-}
-
-#ifndef DM4D_GEMM_H16_TU
-// Parity-precision launches (DM4D_EPI_F32SIDE / DM4D_EPI_SPLITOUT: fp32 side inputs, two-term output) run on their own
-// instantiations of a few tile geometries (PAR = true), chosen by the tail of the heuristic above; every kernel of this file walks
-// K in the same order, so the choice never changes a result.  The fast kernels do not carry that epilogue code.
-template <bool CONV>
-int launch_par(hipStream_t st, GemmParams& p) {
-  const bool geglu = (p.flags & DM4D_EPI_GEGLU) != 0;
-  const bool k64 = CONV ? (p.Cin % 64 == 0) : (p.K % 64 == 0 && (!p.A2 || p.K1 % 64 == 0));
-  const bool n128 = geglu || (p.N % 128 == 0) || (p.N > 1024);
-  const long tm128 = (p.M + 127) / 128, tm256 = (p.M + 255) / 256, tn = (p.N + (geglu ? 63 : 127)) / (geglu ? 64 : 128);
-  if constexpr (CONV) {
-    if (k64 && p.stride == 1 && p.pad == 1 && !p.upsample && p.Ho == p.H && p.Wo == p.W && strip2_ok(p)) {
-      if (!n128) return launch_strip2<128, 64, 4, 1, true>(st, p);
-      if (tm256 * tn >= 200) return launch_strip2<256, 128, 4, 2, true>(st, p);
-      return launch_strip2<128, 128, 2, 2, true>(st, p);
-    }
-    if (!k64) return dm4d_set_error(DM4D_ERR_ARG, "conv3x3: parity-precision launches need Cin % 64 == 0 (a two-term operand of Cin / 2 channels)");
-  } else {
-    if (!k64) {  // K-slab 32, register staged (P V of the VAE mid block: K = 3 Lp with Lp a multiple of 32)
-      if (n128) return launch_cfg<128, 128, 2, 2, false, false, true>(st, p);
-      return launch_cfg<128, 64, 4, 1, false, false, true>(st, p);
-    }
-    // Linear layers: the tiles the fast precision picks for this shape (K here is the doubled K of the two-term operand), PAR epilogue
-    if (lin2_ok(p)) {
-      switch (choose_cfg<false>(p)) {
-        case 67: return launch_lin2<256, 256, 2, 4, 2, 64, true>(st, p);
-        case 65: return launch_lin2<256, 128, 4, 2, 3, 32, true>(st, p);
-        case 61: return launch_lin2<256, 128, 4, 2, 3, 64, true>(st, p);
-        case 69: if (!geglu) return launch_lin2<128, 160, 4, 1, 2, 64, true>(st, p); break;
-        case 63: return launch_lin2<128, 128, 2, 2, 2, 64, true>(st, p);
-        case 64: return launch_lin2<128, 128, 4, 2, 3, 64, true>(st, p);
-        default: break;
-      }
-    }
-  }
-  if (n128) {
-    if (tm128 * tn >= 256 || geglu) return launch_cfg<128, 128, 2, 2, CONV, true, true>(st, p);
-    return tm128 * tn >= 200 ? launch_cfg<128, 64, 4, 1, CONV, true, true>(st, p) : launch_cfg<64, 64, 2, 2, CONV, true, true>(st, p);
-  }
-  return launch_cfg<128, 64, 4, 1, CONV, true, true>(st, p);
-}
-
-template <bool CONV>
+// One precision per translation unit: H16 = false here (fast; parity, on its own PAR = 1 instantiations, for the launches that carry
+// DM4D_EPI_F32SIDE / SPLITOUT), H16 = true in gemm_h16.hip (precision "fp16": every tile geometry of the fast precision with fp16
+// operands, chosen by the same heuristic -- the shapes are the fast precision's, K is not doubled; the entries set DM4D_EPI_H16).
+template <bool CONV, bool H16>
 int launch(hipStream_t st, GemmParams& p) {
-  p.splits = 1;
-  if (p.flags & (DM4D_EPI_F32SIDE | DM4D_EPI_SPLITOUT)) return launch_par<CONV>(st, p);
-  if (g_tune_cfg) {
-    int rc = launch_by_id<CONV>(g_tune_cfg, st, p);
-    if (rc == DM4D_ERR_ARG) return dm4d_set_error(DM4D_ERR_ARG, "gemm: forced configuration does not support this shape");
-    return rc;
-  }
-  if constexpr (CONV) {
-    if (p.ws && p.stride == 1 && p.pad == 1 && !p.upsample && p.Ho == p.H && p.Wo == p.W && p.Cin % 64 == 0 &&
-        strip_split_ok(p) && strip2_ok(p)) {
-      p.splits = 3;
-      return launch_by_id<CONV>(31, st, p);  // 128x128 strip tiles x 3 kernel rows
-    }
-  }
-  return launch_by_id<CONV>(choose_cfg<CONV>(p), st, p);
+  const bool par = !H16 && (p.flags & (DM4D_EPI_F32SIDE | DM4D_EPI_SPLITOUT)) != 0, forced = !H16 && !par && g_tune_cfg != 0;
+  const GemmChoice c = forced ? GemmChoice{g_tune_cfg, 1} : select_cfg<CONV>(p, H16 ? PREC_H16 : par ? PREC_PAR : PREC_FAST);
+  if (!c.id) return dm4d_set_error(DM4D_ERR_ARG, "conv3x3: parity-precision launches need Cin % 64 == 0 (a two-term operand of Cin / 2 channels)");
+  p.splits = c.splits;
+  int rc;
+  if constexpr (H16) rc = launch_by_id<CONV, 2>(c.id, st, p);
+  else rc = par ? launch_by_id<CONV, 1>(c.id, st, p) : launch_by_id<CONV>(c.id, st, p);
+  if (forced && rc == DM4D_ERR_ARG) return dm4d_set_error(DM4D_ERR_ARG, "gemm: forced configuration does not support this shape");
+  return rc;
 }
 
-#else  // DM4D_GEMM_H16_TU: this translation unit (gemm_h16.hip) instantiates the PAR = 2 kernels only
-// Precision "fp16": every tile geometry of the fast precision with fp16 operands (v_mfma_f32_32x32x16_f16), chosen by the same
-// heuristic -- the problem shapes are the fast precision's (K is not doubled) -- including the split over the kernel rows at the
-// 9x5 level.  fp32 side inputs and outputs go through the general epilogue loop (gemm_common.h, PAR = 2).
-template <bool CONV>
-int launch_h16(hipStream_t st, GemmParams& p) {
-  p.splits = 1;
-  p.flags |= DM4D_EPI_H16;
-  if constexpr (CONV) {
-    if (p.ws && p.stride == 1 && p.pad == 1 && !p.upsample && p.Ho == p.H && p.Wo == p.W && p.Cin % 64 == 0 &&
-        strip_split_ok(p) && strip2_ok(p)) {
-      p.splits = 3;
-      return launch_by_id<CONV, 2>(31, st, p);
-    }
-  }
-  return launch_by_id<CONV, 2>(choose_cfg<CONV>(p), st, p);
+// The entry points of the two precisions share their argument checks and their GemmParams fill; `name` heads the messages.
+int arg_error(const char* name, const char* what) {
+  char msg[256];
+  snprintf(msg, sizeof(msg), "%s: %s", name, what);
+  return dm4d_set_error(DM4D_ERR_ARG, msg);
 }
-#endif
 
-}  // namespace
-
-#ifdef DM4D_GEMM_H16_TU
-extern "C" int dm4d_gemm_f16(void* stream, const void* A, int64_t lda, const void* A2, int64_t lda2, int K1, const void* W,
-                             int64_t ldw, void* C, int64_t ldc, int M, int N, int K, const void* bias, const void* rowbias,
-                             int64_t ld_rowbias, int rows_per_rowbias, const void* residual, int64_t ld_res, unsigned flags,
-                             float out_scale, int scale_cols, float col_scale) {
-  if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return dm4d_set_error(DM4D_ERR_ARG, "gemm_f16: null pointer or empty shape");
-  if (K % 32 != 0) return dm4d_set_error(DM4D_ERR_ARG, "gemm_f16: K must be a multiple of 32");
-  if ((lda & 7) || (ldw & 7)) return dm4d_set_error(DM4D_ERR_ARG, "gemm_f16: lda/ldw must be multiples of 8");
-  if (A2 && ((K1 % 32) != 0 || K1 <= 0 || K1 >= K || (lda2 & 7)))
-    return dm4d_set_error(DM4D_ERR_ARG, "gemm_f16: bad split-A arguments");
-  if (rowbias && rows_per_rowbias <= 0) return dm4d_set_error(DM4D_ERR_ARG, "gemm_f16: rows_per_rowbias <= 0");
-  if ((flags & DM4D_EPI_GEGLU) && (N % 32 != 0)) return dm4d_set_error(DM4D_ERR_ARG, "gemm_f16: GEGLU needs N % 32 == 0");
-  if (flags & ~(DM4D_EPI_GEGLU | DM4D_EPI_SILU | DM4D_EPI_F32OUT | DM4D_EPI_F32SIDE))
-    return dm4d_set_error(DM4D_ERR_ARG, "gemm_f16: only GEGLU, SILU, F32OUT and F32SIDE apply");
-  if (scale_cols < 0 || scale_cols > N || (scale_cols & 7)) return dm4d_set_error(DM4D_ERR_ARG, "gemm_f16: scale_cols must be a multiple of 8 in [0, N]");
+template <bool H16>
+int gemm_entry(const char* name, void* stream, const void* A, int64_t lda, const void* A2, int64_t lda2, int K1, const void* W, int64_t ldw, void* C,
+               int64_t ldc, int M, int N, int K, const void* bias, const void* rowbias, int64_t ld_rowbias, int rows_per_rowbias,
+               const void* residual, int64_t ld_res, unsigned flags, float out_scale, int scale_cols, float col_scale) {
+  if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return arg_error(name, "null pointer or empty shape");
+  if (K % 32 != 0) return arg_error(name, "K must be a multiple of 32");
+  if ((lda & 7) || (ldw & 7)) return arg_error(name, "lda/ldw must be multiples of 8");
+  if (A2 && ((K1 % 32) != 0 || K1 <= 0 || K1 >= K || (lda2 & 7))) return arg_error(name, "bad split-A arguments");
+  if (rowbias && rows_per_rowbias <= 0) return arg_error(name, "rows_per_rowbias <= 0");
+  if ((flags & DM4D_EPI_GEGLU) && (N % 32 != 0)) return arg_error(name, "GEGLU needs N % 32 == 0");
+  if (H16 && (flags & ~(DM4D_EPI_GEGLU | DM4D_EPI_SILU | DM4D_EPI_F32OUT | DM4D_EPI_F32SIDE)))
+    return arg_error(name, "only GEGLU, SILU, F32OUT and F32SIDE apply");
+  if (H16 && (scale_cols < 0 || scale_cols > N || (scale_cols & 7))) return arg_error(name, "scale_cols must be a multiple of 8 in [0, N]");
   GemmParams p{};
   p.A = (const u16*)A; p.lda = lda; p.A2 = (const u16*)A2; p.lda2 = lda2; p.K1 = K1;
   p.Wt = (const u16*)W; p.ldw = ldw; p.C = (u16*)C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
   p.bias = (const u16*)bias; p.rowbias = (const u16*)rowbias; p.ld_rb = ld_rowbias; p.rows_per_rb = rows_per_rowbias;
-  p.res = (const u16*)residual; p.ld_res = ld_res; p.flags = flags; p.out_scale = out_scale;
+  p.res = (const u16*)residual; p.ld_res = ld_res; p.flags = H16 ? flags | DM4D_EPI_H16 : flags; p.out_scale = out_scale;
   p.scale_cols = scale_cols; p.col_scale = col_scale;
-  return launch_h16<false>((hipStream_t)stream, p);
+  return launch<false, H16>((hipStream_t)stream, p);
 }
 
-extern "C" int dm4d_conv3x3_nhwc_f16(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y, int Ho,
-                                     int Wo, int Cout, int stride, int pad, int upsample, const void* bias, const void* rowbias,
-                                     int64_t ld_rowbias, const void* residual, int64_t ld_res, float out_scale, unsigned flags,
-                                     void* ws, size_t ws_bytes) {
-  if (!X || !Wt || !Y || B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv3x3_f16: null pointer or empty shape");
-  if (Cin % 32 != 0) return dm4d_set_error(DM4D_ERR_ARG, "conv3x3_f16: Cin must be a multiple of 32 (pad the input)");
-  if (stride != 1 && stride != 2) return dm4d_set_error(DM4D_ERR_ARG, "conv3x3_f16: stride must be 1 or 2");
-  if (upsample && stride != 1) return dm4d_set_error(DM4D_ERR_ARG, "conv3x3_f16: upsample needs stride 1");
-  if (flags & ~(DM4D_EPI_F32OUT | DM4D_EPI_F32SIDE))
-    return dm4d_set_error(DM4D_ERR_ARG, "conv3x3_f16: only DM4D_EPI_F32OUT and DM4D_EPI_F32SIDE apply to a convolution");
+template <bool H16>
+int conv3x3_entry(const char* name, void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y, int Ho, int Wo, int Cout,
+                  int stride, int pad, int upsample, const void* bias, const void* rowbias, int64_t ld_rowbias, const void* residual, int64_t ld_res,
+                  float out_scale, unsigned flags, void* ws, size_t ws_bytes) {
+  if (!X || !Wt || !Y || B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0) return arg_error(name, "null pointer or empty shape");
+  if (Cin % 32 != 0) return arg_error(name, "Cin must be a multiple of 32 (pad the input)");
+  if (stride != 1 && stride != 2) return arg_error(name, "stride must be 1 or 2");
+  if (upsample && stride != 1) return arg_error(name, "upsample needs stride 1");
+  if (flags & ~(DM4D_EPI_F32OUT | DM4D_EPI_F32SIDE)) return arg_error(name, "only DM4D_EPI_F32OUT and DM4D_EPI_F32SIDE apply to a convolution");
   if ((int64_t)B * H * W * Cin >= (int64_t)1 << 31 || (int64_t)B * Ho * Wo * Cout >= (int64_t)1 << 31)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv3x3_f16: tensors of 2^31 or more elements are not supported (split the batch)");
+    return arg_error(name, "tensors of 2^31 or more elements are not supported (split the batch)");
   GemmParams p{};
-  p.A = (const u16*)X; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.pad = pad;
-  p.upsample = upsample;
-  p.Wt = (const u16*)Wt; p.ldw = (int64_t)9 * Cin; p.C = (u16*)Y; p.ldc = Cout;
-  p.M = B * Ho * Wo; p.N = Cout; p.K = 9 * Cin;
+  p.A = (const u16*)X; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.pad = pad; p.upsample = upsample;
+  p.Wt = (const u16*)Wt; p.ldw = (int64_t)9 * Cin; p.C = (u16*)Y; p.ldc = Cout; p.M = B * Ho * Wo; p.N = Cout; p.K = 9 * Cin;
   p.bias = (const u16*)bias; p.rowbias = (const u16*)rowbias; p.ld_rb = ld_rowbias; p.rows_per_rb = Ho * Wo;
-  p.res = (const u16*)residual; p.ld_res = ld_res; p.flags = flags; p.out_scale = out_scale;
-  const bool strip = stride == 1 && pad == 1 && !upsample && Ho == H && Wo == W && Cin % 64 == 0;
-  GemmParams q = p;
-  q.flags |= DM4D_EPI_H16;
-  const size_t need = strip && strip_split_ok(q) ? (size_t)3 * B * Ho * Wo * Cout * sizeof(float) : 0;  // = dm4d_conv3x3_ws_bytes
-  p.ws = (ws && need && ws_bytes >= need) ? (float*)ws : nullptr;
-  return launch_h16<true>((hipStream_t)stream, p);
+  p.res = (const u16*)residual; p.ld_res = ld_res; p.flags = H16 ? flags | DM4D_EPI_H16 : flags; p.out_scale = out_scale;
+  const size_t need = strip_ws_bytes(p, B);
+  p.ws = (ws && need && ws_bytes >= need) ? (float*)ws : nullptr;  // without a workspace the un-split kernels run
+  return launch<true, H16>((hipStream_t)stream, p);
 }
 
-extern "C" int dm4d_conv_up2x_prepare_f16(void* stream, const void* W, void* Wp, int Cout, int Cin) {
-  if (!W || !Wp || Cout <= 0 || Cin <= 0) return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x_prepare_f16: null pointer or empty shape");
+template <bool H16>
+int conv_up2x_entry(const char* name, void* stream, const void* X, int B, int H, int W, int Cin, const void* Wp, void* Y, int Cout, const void* bias,
+                    unsigned flags) {
+  if (!X || !Wp || !Y || B <= 0 || H <= 0 || W <= 0 || Cout <= 0) return arg_error(name, "null pointer or empty shape");
+  if (Cin % 64 != 0 || (Cout & 7) != 0)
+    return arg_error(name, H16 ? "Cin must be a multiple of 64 and Cout of 8 (use conv3x3_f16 with upsample = 1)"
+                               : "Cin must be a multiple of 64 and Cout of 8 (use conv3x3 with upsample = 1)");
+  if (H16 && (flags & ~DM4D_EPI_F32OUT)) return arg_error(name, "only DM4D_EPI_F32OUT applies");
+  if ((int64_t)B * H * W * Cin >= (int64_t)1 << 31 || (int64_t)B * 4 * H * W * Cout >= (int64_t)1 << 31)
+    return arg_error(name, "tensors of 2^31 or more elements are not supported (split the batch)");
+  GemmParams p{};
+  p.A = (const u16*)X; p.H = H; p.W = W; p.Cin = Cin; p.Ho = H; p.Wo = W; p.stride = 1; p.pad = 1; p.upsample = 0;
+  p.Wt = (const u16*)Wp; p.ldw = (int64_t)4 * Cin; p.C = (u16*)Y; p.ldc = Cout; p.M = B * H * W; p.N = Cout; p.K = 4 * Cin;
+  p.bias = (const u16*)bias; p.rows_per_rb = H * W; p.flags = H16 ? flags | DM4D_EPI_H16 : flags; p.out_scale = 1.0f; p.up_w = W;
+  if (!strip2_ok(p)) return arg_error(name, "input or weights of 4 GiB or more");
+  constexpr int PAR = H16 ? 2 : 0;
+  hipStream_t st = (hipStream_t)stream;
+  switch (choose_up2x(p)) {
+    case 32: return launch_up2x<256, 128, 4, 2, PAR>(st, p);
+    case 31: return launch_up2x<128, 128, 2, 2, PAR>(st, p);
+    default: return launch_up2x<128, 64, 4, 1, PAR>(st, p);
+  }
+}
+
+template <bool H16>
+int conv_up2x_prepare_entry(const char* name, void* stream, const void* W, void* Wp, int Cout, int Cin) {
+  if (!W || !Wp || Cout <= 0 || Cin <= 0) return arg_error(name, "null pointer or empty shape");
   const int64_t total = (int64_t)16 * Cout * Cin;
-  hipLaunchKernelGGL(up2x_prepare_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(up2x_prepare_kernel<H16>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (const u16*)W, (u16*)Wp, Cout, Cin);
   return dm4d_check_launch("up2x_prepare_kernel");
 }
 
-extern "C" int dm4d_conv_up2x_nhwc_f16(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wp, void* Y, int Cout,
-                                       const void* bias, unsigned flags) {
-  if (!X || !Wp || !Y || B <= 0 || H <= 0 || W <= 0 || Cout <= 0)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x_f16: null pointer or empty shape");
-  if (Cin % 64 != 0 || (Cout & 7) != 0)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x_f16: Cin must be a multiple of 64 and Cout of 8 (use conv3x3_f16 with upsample = 1)");
-  if (flags & ~DM4D_EPI_F32OUT) return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x_f16: only DM4D_EPI_F32OUT applies");
-  if ((int64_t)B * H * W * Cin >= (int64_t)1 << 31 || (int64_t)B * 4 * H * W * Cout >= (int64_t)1 << 31)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x_f16: tensors of 2^31 or more elements are not supported (split the batch)");
-  GemmParams p{};
-  p.A = (const u16*)X; p.H = H; p.W = W; p.Cin = Cin; p.Ho = H; p.Wo = W; p.stride = 1; p.pad = 1; p.upsample = 0;
-  p.Wt = (const u16*)Wp; p.ldw = (int64_t)4 * Cin; p.C = (u16*)Y; p.ldc = Cout;
-  p.M = B * H * W; p.N = Cout; p.K = 4 * Cin;
-  p.bias = (const u16*)bias; p.rows_per_rb = H * W; p.flags = flags | DM4D_EPI_H16; p.out_scale = 1.0f; p.up_w = W;
-  if (!strip2_ok(p)) return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x_f16: input or weights of 4 GiB or more");
-  hipStream_t st = (hipStream_t)stream;
-  const long tm256 = (p.M + 255) / 256;  // tile choice as dm4d_conv_up2x_nhwc_bf16
-  if (Cout % 128 == 0 && tm256 * (Cout / 128) >= 200) return launch_up2x<256, 128, 4, 2, 2>(st, p);
-  if (Cout % 128 == 0) return launch_up2x<128, 128, 2, 2, 2>(st, p);
-  return launch_up2x<128, 64, 4, 1, 2>(st, p);
+}  // namespace
+
+#ifdef DM4D_GEMM_H16_TU  // this translation unit (gemm_h16.hip) instantiates the PAR = 2 kernels only
+extern "C" int dm4d_gemm_f16(void* stream, const void* A, int64_t lda, const void* A2, int64_t lda2, int K1, const void* W, int64_t ldw, void* C,
+                             int64_t ldc, int M, int N, int K, const void* bias, const void* rowbias, int64_t ld_rowbias, int rows_per_rowbias,
+                             const void* residual, int64_t ld_res, unsigned flags, float out_scale, int scale_cols, float col_scale) {
+  return gemm_entry<true>("gemm_f16", stream, A, lda, A2, lda2, K1, W, ldw, C, ldc, M, N, K, bias, rowbias, ld_rowbias, rows_per_rowbias, residual,
+                          ld_res, flags, out_scale, scale_cols, col_scale);
+}
+
+extern "C" int dm4d_conv3x3_nhwc_f16(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y, int Ho, int Wo, int Cout,
+                                     int stride, int pad, int upsample, const void* bias, const void* rowbias, int64_t ld_rowbias,
+                                     const void* residual, int64_t ld_res, float out_scale, unsigned flags, void* ws, size_t ws_bytes) {
+  return conv3x3_entry<true>("conv3x3_f16", stream, X, B, H, W, Cin, Wt, Y, Ho, Wo, Cout, stride, pad, upsample, bias, rowbias, ld_rowbias, residual,
+                             ld_res, out_scale, flags, ws, ws_bytes);
+}
+
+extern "C" int dm4d_conv_up2x_prepare_f16(void* stream, const void* W, void* Wp, int Cout, int Cin) {
+  return conv_up2x_prepare_entry<true>("conv_up2x_prepare_f16", stream, W, Wp, Cout, Cin);
+}
+
+extern "C" int dm4d_conv_up2x_nhwc_f16(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wp, void* Y, int Cout, const void* bias,
+                                       unsigned flags) {
+  return conv_up2x_entry<true>("conv_up2x_f16", stream, X, B, H, W, Cin, Wp, Y, Cout, bias, flags);
 }
 #else
 
@@ -1500,110 +1314,46 @@ extern "C" int dm4d_tune_set_gemm_config(int id) {
   return DM4D_OK;
 }
 
-extern "C" int dm4d_gemm_bf16(void* stream, const void* A, int64_t lda, const void* A2, int64_t lda2, int K1,
-                              const void* W, int64_t ldw, void* C, int64_t ldc, int M, int N, int K, const void* bias,
-                              const void* rowbias, int64_t ld_rowbias, int rows_per_rowbias, const void* residual,
-                              int64_t ld_res, unsigned flags, float out_scale) {
-  if (!A || !W || !C || M <= 0 || N <= 0 || K <= 0) return dm4d_set_error(DM4D_ERR_ARG, "gemm: null pointer or empty shape");
-  if (K % 32 != 0) return dm4d_set_error(DM4D_ERR_ARG, "gemm: K must be a multiple of 32");
-  if ((lda & 7) || (ldw & 7)) return dm4d_set_error(DM4D_ERR_ARG, "gemm: lda/ldw must be multiples of 8");
-  if (A2 && ((K1 % 32) != 0 || K1 <= 0 || K1 >= K || (lda2 & 7)))
-    return dm4d_set_error(DM4D_ERR_ARG, "gemm: bad split-A arguments");
-  if (rowbias && rows_per_rowbias <= 0) return dm4d_set_error(DM4D_ERR_ARG, "gemm: rows_per_rowbias <= 0");
-  if ((flags & DM4D_EPI_GEGLU) && (N % 32 != 0)) return dm4d_set_error(DM4D_ERR_ARG, "gemm: GEGLU needs N % 32 == 0");
+extern "C" int dm4d_gemm_bf16(void* stream, const void* A, int64_t lda, const void* A2, int64_t lda2, int K1, const void* W, int64_t ldw, void* C,
+                              int64_t ldc, int M, int N, int K, const void* bias, const void* rowbias, int64_t ld_rowbias, int rows_per_rowbias,
+                              const void* residual, int64_t ld_res, unsigned flags, float out_scale) {
+  return gemm_entry<false>("gemm", stream, A, lda, A2, lda2, K1, W, ldw, C, ldc, M, N, K, bias, rowbias, ld_rowbias, rows_per_rowbias, residual, ld_res,
+                           flags, out_scale, 0, 0.0f);
+}
+
+extern "C" size_t dm4d_conv3x3_ws_bytes(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int stride, int pad, int upsample) {
   GemmParams p{};
-  p.A = (const u16*)A; p.lda = lda; p.A2 = (const u16*)A2; p.lda2 = lda2; p.K1 = K1;
-  p.Wt = (const u16*)W; p.ldw = ldw; p.C = (u16*)C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
-  p.bias = (const u16*)bias; p.rowbias = (const u16*)rowbias; p.ld_rb = ld_rowbias; p.rows_per_rb = rows_per_rowbias;
-  p.res = (const u16*)residual; p.ld_res = ld_res; p.flags = flags; p.out_scale = out_scale;
-  return launch<false>((hipStream_t)stream, p);
+  p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.pad = pad; p.upsample = upsample; p.N = Cout; p.ldc = Cout;
+  return strip_ws_bytes(p, B);
 }
 
-extern "C" size_t dm4d_conv3x3_ws_bytes(int B, int H, int W, int Cin, int Ho, int Wo, int Cout, int stride, int pad,
-                                        int upsample) {
-  GemmParams p{};
-  p.H = H; p.W = W; p.Cin = Cin; p.N = Cout; p.ldc = Cout;
-  const bool strip = stride == 1 && pad == 1 && !upsample && Ho == H && Wo == W && Cin % 64 == 0;
-  return strip && strip_split_ok(p) ? (size_t)3 * B * Ho * Wo * Cout * sizeof(float) : 0;
+extern "C" int dm4d_conv3x3_nhwc_bf16(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y, int Ho, int Wo, int Cout,
+                                      int stride, int pad, int upsample, const void* bias, const void* rowbias, int64_t ld_rowbias,
+                                      const void* residual, int64_t ld_res, float out_scale) {
+  return conv3x3_entry<false>("conv3x3", stream, X, B, H, W, Cin, Wt, Y, Ho, Wo, Cout, stride, pad, upsample, bias, rowbias, ld_rowbias, residual,
+                              ld_res, out_scale, 0, nullptr, 0);
 }
 
-static int conv3x3_impl(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y, int Ho, int Wo,
-                        int Cout, int stride, int pad, int upsample, const void* bias, const void* rowbias,
-                        int64_t ld_rowbias, const void* residual, int64_t ld_res, float out_scale, void* ws,
-                        size_t ws_bytes, unsigned flags = 0) {
-  if (!X || !Wt || !Y || B <= 0 || H <= 0 || W <= 0 || Ho <= 0 || Wo <= 0 || Cout <= 0)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv3x3: null pointer or empty shape");
-  if (Cin % 32 != 0) return dm4d_set_error(DM4D_ERR_ARG, "conv3x3: Cin must be a multiple of 32 (pad the input)");
-  if (stride != 1 && stride != 2) return dm4d_set_error(DM4D_ERR_ARG, "conv3x3: stride must be 1 or 2");
-  if (upsample && stride != 1) return dm4d_set_error(DM4D_ERR_ARG, "conv3x3: upsample needs stride 1");
-  if ((int64_t)B * H * W * Cin >= (int64_t)1 << 31 || (int64_t)B * Ho * Wo * Cout >= (int64_t)1 << 31)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv3x3: tensors of 2^31 or more elements are not supported (split the batch)");
-  GemmParams p{};
-  p.A = (const u16*)X; p.H = H; p.W = W; p.Cin = Cin; p.Ho = Ho; p.Wo = Wo; p.stride = stride; p.pad = pad;
-  p.upsample = upsample;
-  p.Wt = (const u16*)Wt; p.ldw = (int64_t)9 * Cin; p.C = (u16*)Y; p.ldc = Cout;
-  p.M = B * Ho * Wo; p.N = Cout; p.K = 9 * Cin;
-  p.bias = (const u16*)bias; p.rowbias = (const u16*)rowbias; p.ld_rb = ld_rowbias; p.rows_per_rb = Ho * Wo;
-  p.res = (const u16*)residual; p.ld_res = ld_res; p.flags = flags; p.out_scale = out_scale;
-  const size_t need = dm4d_conv3x3_ws_bytes(B, H, W, Cin, Ho, Wo, Cout, stride, pad, upsample);
-  p.ws = (ws && need && ws_bytes >= need) ? (float*)ws : nullptr;  // without a workspace the un-split kernels run
-  return launch<true>((hipStream_t)stream, p);
+extern "C" int dm4d_conv3x3_nhwc_bf16_flags(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y, int Ho, int Wo,
+                                            int Cout, int stride, int pad, int upsample, const void* bias, const void* rowbias, int64_t ld_rowbias,
+                                            const void* residual, int64_t ld_res, float out_scale, unsigned flags) {
+  return conv3x3_entry<false>("conv3x3", stream, X, B, H, W, Cin, Wt, Y, Ho, Wo, Cout, stride, pad, upsample, bias, rowbias, ld_rowbias, residual,
+                              ld_res, out_scale, flags, nullptr, 0);
 }
 
-extern "C" int dm4d_conv3x3_nhwc_bf16(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y,
-                                      int Ho, int Wo, int Cout, int stride, int pad, int upsample, const void* bias,
-                                      const void* rowbias, int64_t ld_rowbias, const void* residual, int64_t ld_res,
-                                      float out_scale) {
-  return conv3x3_impl(stream, X, B, H, W, Cin, Wt, Y, Ho, Wo, Cout, stride, pad, upsample, bias, rowbias, ld_rowbias,
-                      residual, ld_res, out_scale, nullptr, 0);
-}
-
-extern "C" int dm4d_conv3x3_nhwc_bf16_flags(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y,
-                                            int Ho, int Wo, int Cout, int stride, int pad, int upsample, const void* bias,
-                                            const void* rowbias, int64_t ld_rowbias, const void* residual, int64_t ld_res,
-                                            float out_scale, unsigned flags) {
-  if (flags & ~(DM4D_EPI_F32OUT | DM4D_EPI_F32SIDE))
-    return dm4d_set_error(DM4D_ERR_ARG, "conv3x3: only DM4D_EPI_F32OUT and DM4D_EPI_F32SIDE apply to a convolution");
-  return conv3x3_impl(stream, X, B, H, W, Cin, Wt, Y, Ho, Wo, Cout, stride, pad, upsample, bias, rowbias, ld_rowbias,
-                      residual, ld_res, out_scale, nullptr, 0, flags);
+extern "C" int dm4d_conv3x3_nhwc_bf16_ws(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y, int Ho, int Wo, int Cout,
+                                         int stride, int pad, int upsample, const void* bias, const void* rowbias, int64_t ld_rowbias,
+                                         const void* residual, int64_t ld_res, float out_scale, void* ws, size_t ws_bytes) {
+  return conv3x3_entry<false>("conv3x3", stream, X, B, H, W, Cin, Wt, Y, Ho, Wo, Cout, stride, pad, upsample, bias, rowbias, ld_rowbias, residual,
+                              ld_res, out_scale, 0, ws, ws_bytes);
 }
 
 extern "C" int dm4d_conv_up2x_prepare_bf16(void* stream, const void* W, void* Wp, int Cout, int Cin) {
-  if (!W || !Wp || Cout <= 0 || Cin <= 0) return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x_prepare: null pointer or empty shape");
-  const int64_t total = (int64_t)16 * Cout * Cin;
-  hipLaunchKernelGGL(up2x_prepare_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const u16*)W, (u16*)Wp, Cout, Cin);
-  return dm4d_check_launch("up2x_prepare_kernel");
+  return conv_up2x_prepare_entry<false>("conv_up2x_prepare", stream, W, Wp, Cout, Cin);
 }
 
-extern "C" int dm4d_conv_up2x_nhwc_bf16(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wp, void* Y,
-                                        int Cout, const void* bias) {
-  if (!X || !Wp || !Y || B <= 0 || H <= 0 || W <= 0 || Cout <= 0)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x: null pointer or empty shape");
-  if (Cin % 64 != 0 || (Cout & 7) != 0)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x: Cin must be a multiple of 64 and Cout of 8 (use conv3x3 with upsample = 1)");
-  if ((int64_t)B * H * W * Cin >= (int64_t)1 << 31 || (int64_t)B * 4 * H * W * Cout >= (int64_t)1 << 31)
-    return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x: tensors of 2^31 or more elements are not supported (split the batch)");
-  GemmParams p{};
-  p.A = (const u16*)X; p.H = H; p.W = W; p.Cin = Cin; p.Ho = H; p.Wo = W; p.stride = 1; p.pad = 1; p.upsample = 0;
-  p.Wt = (const u16*)Wp; p.ldw = (int64_t)4 * Cin; p.C = (u16*)Y; p.ldc = Cout;
-  p.M = B * H * W; p.N = Cout; p.K = 4 * Cin;
-  p.bias = (const u16*)bias; p.rows_per_rb = H * W; p.flags = 0; p.out_scale = 1.0f; p.up_w = W;
-  if (!strip2_ok(p)) return dm4d_set_error(DM4D_ERR_ARG, "conv_up2x: input or weights of 4 GiB or more");
-  hipStream_t st = (hipStream_t)stream;
-  // tile choice as for the stride-1 strips: 256-row tiles where a phase alone fills the chip's 256 CUs
-  const long tm256 = (p.M + 255) / 256, tm128 = (p.M + 127) / 128;
-  if (Cout % 128 == 0 && tm256 * (Cout / 128) >= 200) return launch_up2x<256, 128, 4, 2>(st, p);
-  if (Cout % 128 == 0) return launch_up2x<128, 128, 2, 2>(st, p);
-  (void)tm128;
-  return launch_up2x<128, 64, 4, 1>(st, p);
-}
-
-extern "C" int dm4d_conv3x3_nhwc_bf16_ws(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wt, void* Y,
-                                         int Ho, int Wo, int Cout, int stride, int pad, int upsample, const void* bias,
-                                         const void* rowbias, int64_t ld_rowbias, const void* residual, int64_t ld_res,
-                                         float out_scale, void* ws, size_t ws_bytes) {
-  return conv3x3_impl(stream, X, B, H, W, Cin, Wt, Y, Ho, Wo, Cout, stride, pad, upsample, bias, rowbias, ld_rowbias,
-                      residual, ld_res, out_scale, ws, ws_bytes);
+extern "C" int dm4d_conv_up2x_nhwc_bf16(void* stream, const void* X, int B, int H, int W, int Cin, const void* Wp, void* Y, int Cout,
+                                        const void* bias) {
+  return conv_up2x_entry<false>("conv_up2x", stream, X, B, H, W, Cin, Wp, Y, Cout, bias, 0);
 }
 #endif  // DM4D_GEMM_H16_TU

@@ -2,7 +2,7 @@
 """Sweep every GEMM / conv kernel configuration over the UNet's shapes (72x40 latents, F = 16 and 24)
 through the tuning hook dm4d_tune_set_gemm_config and print the best id per shape.
 Run on a GPU box:  python tools/gemm_tune.py > gpurun_out/gemm_tune.log
-The heuristic in csrc/gemm.hip::choose_cfg is written from this table (profiles/r01_gemm_tune.log)."""
+The heuristic in csrc/gemm_select.h::choose_cfg is written from this table (profiles/r01_gemm_tune.log)."""
 from __future__ import annotations
 
 import math

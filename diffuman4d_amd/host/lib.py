@@ -108,6 +108,10 @@ SIGNATURES = {
     "dm4d_lpips_relu_pool_split": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i]),
     "dm4d_lpips_ws_bytes": (C.c_size_t, [_i, _i]),
     "dm4d_lpips_tap_distance_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp]),
+    # visual-hull carving: masks to bits, then flags + scan + gather per chunk of the voxel grid (host/vhull.py)
+    "dm4d_vhull_pack_masks": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "dm4d_vhull_ws_bytes": (C.c_size_t, [_i64]),
+    "dm4d_vhull_carve_chunk": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i64, _vp, _vp, _i64]),
 }
 
 EPI_GEGLU = 1

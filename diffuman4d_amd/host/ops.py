@@ -1097,3 +1097,56 @@ def lpips_tap_distance(f: torch.Tensor, lin: torch.Tensor, tap: int, out: torch.
     with _Prof("lpips_distance", 4.0 * f.numel(), "byte", H * W):
         rc = lib.dm4d_lpips_tap_distance_f64(_stream(), _p(f), _p(lin), H, W, C, tap, _p(ws), ws.numel(), _p(out))
     _l.check(rc, "dm4d_lpips_tap_distance_f64")
+
+
+VHULL_BLOCK = 256           # include/dm4d.h DM4D_VHULL_BLOCK
+VHULL_MAX_CHUNK = 1 << 26   # include/dm4d.h DM4D_VHULL_MAX_CHUNK
+
+
+def vhull_pack_masks(masks: torch.Tensor) -> torch.Tensor:
+    """Foreground masks bool or uint8 [B, H, W] (nonzero = foreground) -> bits int32 [B, H, ceil(W / 32)]: pixel x of a row is bit x & 31 of
+    its word x >> 5 (what vhull_carve_chunk reads)."""
+    lib = _l.load()
+    if isinstance(masks, torch.Tensor) and masks.dtype == torch.bool:
+        masks = masks.view(torch.uint8)
+    _req(masks, "masks", torch.uint8)
+    if masks.dim() != 3 or not masks.is_contiguous():
+        raise _l.Dm4dError(f"masks: expected a contiguous [B, H, W] tensor, got {tuple(masks.shape)}")
+    B, H, W = masks.shape
+    bits = torch.empty((B, H, (W + 31) // 32), dtype=torch.int32, device=masks.device)
+    _l.check(lib.dm4d_vhull_pack_masks(_stream(), _p(masks), _p(bits), B, H, W), "dm4d_vhull_pack_masks")
+    return bits
+
+
+def vhull_ws(n_voxels: int, device) -> torch.Tensor:
+    """The workspace of vhull_carve_chunk for chunks of up to n_voxels voxels (reused from chunk to chunk)."""
+    nbytes = int(_l.load().dm4d_vhull_ws_bytes(n_voxels))
+    if nbytes == 0:
+        raise _l.Dm4dError(f"vhull_ws: a chunk holds 1 to {VHULL_MAX_CHUNK} voxels, got {n_voxels}")
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device)
+
+
+def vhull_carve_chunk(xs: torch.Tensor, ys: torch.Tensor, zs: torch.Tensor, P: torch.Tensor, bits: torch.Tensor, hw: Tuple[int, int],
+                      min_views: int, first: int, n_voxels: int, ws: torch.Tensor, total: torch.Tensor, out: torch.Tensor) -> None:
+    """Carve the voxels [first, first + n_voxels) of the grid xs x ys x zs (fp32 axes, z fastest) against B views: P fp64 [B, 3, 4],
+    bits = vhull_pack_masks of the [B, H, W] masks, hw = (H, W); min_views 0 = every view.  The kept centres are appended to out (fp32
+    [capacity, 3]) at the running count total (int64 [1], zeroed by the caller before a frame's first chunk), which grows by their number
+    even where out is full.  Three launches on the current stream, no synchronisation."""
+    lib = _l.load()
+    for t, name in ((xs, "xs"), (ys, "ys"), (zs, "zs"), (out, "out")):
+        _req(t, name, F32)
+    _req(P, "P", torch.float64), _req(bits, "bits", torch.int32), _req(ws, "ws", torch.int64), _req(total, "total", torch.int64)
+    H, W = hw
+    B = P.shape[0]
+    if P.dim() != 3 or tuple(P.shape[1:]) != (3, 4) or not P.is_contiguous():
+        raise _l.Dm4dError(f"P: expected a contiguous [B, 3, 4] tensor, got {tuple(P.shape)}")
+    if tuple(bits.shape) != (B, H, (W + 31) // 32) or not bits.is_contiguous():
+        raise _l.Dm4dError(f"bits: expected a contiguous [{B}, {H}, {(W + 31) // 32}] tensor, got {tuple(bits.shape)}")
+    if xs.dim() != 1 or ys.dim() != 1 or zs.dim() != 1 or total.numel() != 1:
+        raise _l.Dm4dError("xs, ys, zs: expected one-dimensional axes; total: expected one element")
+    if out.dim() != 2 or out.shape[1] != 3 or not out.is_contiguous():
+        raise _l.Dm4dError(f"out: expected a contiguous [capacity, 3] tensor, got {tuple(out.shape)}")
+    rc = lib.dm4d_vhull_carve_chunk(_stream(), _p(xs), _p(ys), _p(zs), xs.numel(), ys.numel(), zs.numel(), _p(P), _p(bits), B, H, W,
+                                    int(min_views), int(first), int(n_voxels), _p(ws), ws.numel() * 8, _p(total),
+                                    _p(out) if out.shape[0] else None, out.shape[0])
+    _l.check(rc, "dm4d_vhull_carve_chunk")

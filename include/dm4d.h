@@ -297,6 +297,31 @@ size_t dm4d_lpips_ws_bytes(int H, int W);
 int dm4d_lpips_tap_distance_f64(void* stream, const float* F, const float* lin, int H, int W, int C, int tap, void* workspace,
                                 int64_t workspace_bytes, double* out);
 
+/* Visual-hull carving (diffuman4d_amd/host/vhull.py::carve_visual_hull; the reference's scripts/preprocess/carve_visual_hull.py:76-151,
+ *   the loop over batches of voxels with its ~20 torch operators).  Grid: xs [nx], ys [ny], zs [nz] fp32 on the device; voxel idx in
+ *   [0, nx ny nz), z fastest: iz = idx % nz, iy = (idx / nz) % ny, ix = idx / (ny nz); X = (xs[ix], ys[iy], zs[iz]) widened to fp64.
+ *   Per view b with P[b] (3 x 4 fp64, row-major; P: [B, 12] on the device): x_r = ((P[r][0] X0 + P[r][1] X1) + P[r][2] X2) + P[r][3], every
+ *   operation rounded on its own; z = x_2, u = rint(x_0 / max(z, 1e-8)), v = rint(x_1 / max(z, 1e-8)) (ties to even);
+ *   inside_b = z > 0 && 0 <= u < W && 0 <= v < H (tested in fp64, before any conversion) && mask[b][v][u].  A voxel is kept iff all B
+ *   views are inside (min_views == 0) or at least min_views are (min_views > B keeps nothing).
+ *
+ * dm4d_vhull_pack_masks: masks uint8 [B, H, W] (nonzero = foreground; a torch.bool tensor as it lies in memory) -> bits uint32
+ *   [B, H, (W + 31) / 32]: bit (x & 31) of word x >> 5 of row (b, y); the unused bits of a row's last word are 0.
+ * dm4d_vhull_carve_chunk: the voxels [first, first + n_voxels) of the grid, n_voxels <= DM4D_VHULL_MAX_CHUNK, in three launches (flags +
+ *   per-block counts, a one-block scan, gather).  *total (device int64) is the running number of kept points of the frame: the kept
+ *   centres of this chunk go to out[*total ...] (fp32 [capacity, 3]) in ascending idx and *total grows by their number; the caller
+ *   zeroes it before the first chunk and walks the chunks in ascending order on one stream.  Points at positions >= capacity are
+ *   counted and not written: *total is always the true count, and out holds min(*total, capacity) points.  Positions come from
+ *   ballots, popcounts and the scan, never from an atomic; no block waits for another.
+ *   workspace: dm4d_vhull_ws_bytes(n_voxels) bytes (0 for an n_voxels out of range), 8-byte aligned, reusable by the next chunk.  */
+#define DM4D_VHULL_BLOCK 256
+#define DM4D_VHULL_MAX_CHUNK (1ll << 26)
+int dm4d_vhull_pack_masks(void* stream, const void* masks, void* bits, int B, int H, int W);
+size_t dm4d_vhull_ws_bytes(int64_t n_voxels);
+int dm4d_vhull_carve_chunk(void* stream, const float* xs, const float* ys, const float* zs, int64_t nx, int64_t ny, int64_t nz,
+                           const double* P, const void* bits, int B, int H, int W, int min_views, int64_t first, int64_t n_voxels,
+                           void* workspace, int64_t workspace_bytes, int64_t* total, float* out, int64_t capacity);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

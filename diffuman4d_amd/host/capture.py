@@ -68,9 +68,10 @@ def bicubic_table(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
 
 
 # -- cameras ----------------------------------------------------------------------------------------------------------------------
-def read_cameras(camera_path: str) -> Dict[str, Dict]:
+def read_cameras(camera_path: str, normalize_scene: bool = True) -> Dict[str, Dict]:
     """nerfstudio ``transforms.json`` -> {camera_label: {K, pose, height, width}} with OpenCV axes and normalised positions, in the
-    reference's float32 arithmetic (data/utils/camera_parser.py)."""
+    reference's float32 arithmetic (data/utils/camera_parser.py).  normalize_scene=False leaves the positions as the file gives them
+    (parse_cameras(..., normalize_scene=False), what skeleton triangulation asks for)."""
     if os.path.isdir(camera_path) or camera_path.endswith(".yml"):
         raise NotImplementedError(f"EasyVolcap cameras are not supported ({camera_path}): give a nerfstudio transforms.json")
     if not camera_path.endswith(".json"):
@@ -89,10 +90,11 @@ def read_cameras(camera_path: str) -> Dict[str, Dict]:
     poses = torch.stack(poses)
     # Scene normalisation.  The reference looks for f"{camera_path}/scene_norm.json", a path UNDER the JSON file, which therefore
     # never exists: its centre and scale always come from the bounding box of the camera positions, and so do ours.
-    pos = poses[:, :3, 3]
-    lo, hi = torch.min(pos, dim=0).values, torch.max(pos, dim=0).values
-    center, scale = (lo + hi) / 2, 1 / torch.linalg.norm(hi - lo)
-    poses[:, :3, 3] = (poses[:, :3, 3] - center) * scale
+    if normalize_scene:
+        pos = poses[:, :3, 3]
+        lo, hi = torch.min(pos, dim=0).values, torch.max(pos, dim=0).values
+        center, scale = (lo + hi) / 2, 1 / torch.linalg.norm(hi - lo)
+        poses[:, :3, 3] = (poses[:, :3, 3] - center) * scale
     return {lab: {"K": K, "pose": p, "height": hw[0], "width": hw[1]} for lab, K, hw, p in zip(labels, Ks, hws, poses)}
 
 

@@ -112,6 +112,9 @@ SIGNATURES = {
     "dm4d_vhull_pack_masks": (_i, [_vp, _vp, _vp, _i, _i, _i]),
     "dm4d_vhull_ws_bytes": (C.c_size_t, [_i64]),
     "dm4d_vhull_carve_chunk": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i64, _vp, _vp, _i64]),
+    # skeleton triangulation: one wave per (frame, keypoint), and the projection of the points into cameras (host/triang.py)
+    "dm4d_triangulate_points_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "dm4d_project_points_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 EPI_GEGLU = 1

@@ -1150,3 +1150,54 @@ def vhull_carve_chunk(xs: torch.Tensor, ys: torch.Tensor, zs: torch.Tensor, P: t
                                     int(min_views), int(first), int(n_voxels), _p(ws), ws.numel() * 8, _p(total),
                                     _p(out) if out.shape[0] else None, out.shape[0])
     _l.check(rc, "dm4d_vhull_carve_chunk")
+
+
+TRIANG_MAX_VIEWS = 65536    # include/dm4d.h DM4D_TRIANG_MAX_VIEWS
+
+
+def _cameras(K: torch.Tensor, T: torch.Tensor) -> int:
+    _req(K, "K", torch.float64), _req(T, "T", torch.float64)
+    if K.dim() != 3 or tuple(K.shape[1:]) != (3, 3) or not K.is_contiguous():
+        raise _l.Dm4dError(f"K: expected a contiguous [n, 3, 3] tensor, got {tuple(K.shape)}")
+    if tuple(T.shape) != (K.shape[0], 4, 4) or not T.is_contiguous():
+        raise _l.Dm4dError(f"T: expected a contiguous [{K.shape[0]}, 4, 4] tensor, got {tuple(T.shape)}")
+    return K.shape[0]
+
+
+def triangulate_points(K: torch.Tensor, T: torch.Tensor, kp2d: torch.Tensor, score: torch.Tensor, thr: torch.Tensor,
+                       min_views: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """K fp64 [n, 3, 3], T fp64 [n, 4, 4] (world -> camera), kp2d fp64 [F, n, k, 2], score fp64 [F, n, k], thr fp64 [F, k] (the score
+    threshold of each frame and keypoint) -> kp3d fp64 [F, k, 3], reproj fp64 [F, k], n_views int32 [F, k]; -1e6 in kp3d and reproj where
+    fewer than min_views views reach the threshold.  One launch on the current stream."""
+    lib = _l.load()
+    n = _cameras(K, T)
+    _req(kp2d, "kp2d", torch.float64), _req(score, "score", torch.float64), _req(thr, "thr", torch.float64)
+    if kp2d.dim() != 4 or kp2d.shape[1] != n or kp2d.shape[3] != 2 or not kp2d.is_contiguous():
+        raise _l.Dm4dError(f"kp2d: expected a contiguous [F, {n}, k, 2] tensor, got {tuple(kp2d.shape)}")
+    F, _, k, _ = kp2d.shape
+    if tuple(score.shape) != (F, n, k) or not score.is_contiguous():
+        raise _l.Dm4dError(f"score: expected a contiguous [{F}, {n}, {k}] tensor, got {tuple(score.shape)}")
+    if tuple(thr.shape) != (F, k) or not thr.is_contiguous():
+        raise _l.Dm4dError(f"thr: expected a contiguous [{F}, {k}] tensor, got {tuple(thr.shape)}")
+    kp3d = torch.empty((F, k, 3), dtype=torch.float64, device=kp2d.device)
+    reproj = torch.empty((F, k), dtype=torch.float64, device=kp2d.device)
+    n_views = torch.empty((F, k), dtype=torch.int32, device=kp2d.device)
+    rc = lib.dm4d_triangulate_points_f64(_stream(), _p(K), _p(T), _p(kp2d), _p(score), _p(thr), F, n, k, int(min_views), _p(kp3d),
+                                         _p(reproj), _p(n_views))
+    _l.check(rc, "dm4d_triangulate_points_f64")
+    return kp3d, reproj, n_views
+
+
+def project_points(kp3d: torch.Tensor, K: torch.Tensor, T: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """kp3d fp64 [F, k, 3], K fp64 [m, 3, 3], T fp64 [m, 4, 4] -> kp2d fp64 [F, m, k, 2], depth fp64 [F, m, k]; a point holding -1e6 gives
+    -1e6 in both for every camera."""
+    lib = _l.load()
+    _req(kp3d, "kp3d", torch.float64)
+    m = _cameras(K, T)
+    if kp3d.dim() != 3 or kp3d.shape[2] != 3 or not kp3d.is_contiguous():
+        raise _l.Dm4dError(f"kp3d: expected a contiguous [F, k, 3] tensor, got {tuple(kp3d.shape)}")
+    F, k, _ = kp3d.shape
+    kp2d = torch.empty((F, m, k, 2), dtype=torch.float64, device=kp3d.device)
+    depth = torch.empty((F, m, k), dtype=torch.float64, device=kp3d.device)
+    _l.check(lib.dm4d_project_points_f64(_stream(), _p(kp3d), _p(K), _p(T), F, m, k, _p(kp2d), _p(depth)), "dm4d_project_points_f64")
+    return kp2d, depth

@@ -322,6 +322,31 @@ int dm4d_vhull_carve_chunk(void* stream, const float* xs, const float* ys, const
                            const double* P, const void* bits, int B, int H, int W, int min_views, int64_t first, int64_t n_voxels,
                            void* workspace, int64_t workspace_bytes, int64_t* total, float* out, int64_t capacity);
 
+/* Skeleton triangulation (diffuman4d_amd/host/triang.py::triangulate_points / project_points; the reference's
+ *   scripts/preprocess/utils/triang_utils.py, called from scripts/preprocess/triangulate_skeleton.py:149 and :158).  All tensors fp64 on
+ *   the device (n_views int32), row-major; K [.., 3, 3] intrinsics, T [.., 4, 4] world -> camera, P = K @ T[:3].
+ *
+ * dm4d_triangulate_points_f64 (triangulate_points -> triangulate_one_point per keypoint, triang_utils.py:53-126 and :129-175) for a
+ *   batch of F frames in one launch: K [n, 3, 3], T [n, 4, 4], kp2d [F, n, k, 2], score [F, n, k], thr [F, k] = the score threshold of
+ *   each (frame, keypoint) (the host's max(score_thr, percentile); the device only compares) -> kp3d [F, k, 3], reproj [F, k], n_views
+ *   [F, k].  View j is selected iff score >= thr; n_views counts them; with fewer than min_views, kp3d = reproj = -1e6 (INVALID).
+ *   Otherwise: the linear (DLT) start on rows scaled by sqrt(score), from the eigenvector of the smallest eigenvalue of the 4 x 4 normal
+ *   matrix (selected views with score <= 0, u < 0 or v < 0 give no rows to the start only), x[:3] / (x[3] + 1e-9); then the minimiser
+ *   of scipy's Huber cost 0.5 sum rho(r^2), r = (P X / (depth + 1e-9) - obs) sqrt(score) per scalar component, f_scale = 1, by a
+ *   damped Gauss-Newton iteration on the 3 x 3 system run to fp64 convergence (at most 64 evaluations; the last iterate is written
+ *   in any case); reproj = sum(err_px score) / (sum score + 1e-9) over the selected views.  One wave per (frame, keypoint), lanes over
+ *   views (any n up to DM4D_TRIANG_MAX_VIEWS), sums over views in a fixed order: bitwise repeatable, and a frame's result does not
+ *   depend on the batch around it.  No atomics; no block waits on another.
+ * dm4d_project_points_f64 (project_points -> project_one_point, triang_utils.py:7-23): kp3d [F, k, 3], K [m, 3, 3], T [m, 4, 4] ->
+ *   kp2d [F, m, k, 2] = xy / (depth + 1e-9), depth [F, m, k] = the third homogeneous coordinate; a point with any coordinate equal to
+ *   -1e6 gives -1e6 in kp2d and depth for every camera.                                                                            */
+#define DM4D_TRIANG_MAX_VIEWS 65536
+int dm4d_triangulate_points_f64(void* stream, const double* K, const double* T, const double* kp2d, const double* score,
+                                const double* thr, int F, int n, int k, int min_views, double* kp3d, double* reproj,
+                                int32_t* n_views);
+int dm4d_project_points_f64(void* stream, const double* kp3d, const double* K, const double* T, int F, int m, int k, double* kp2d,
+                            double* depth);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

@@ -1,10 +1,12 @@
 // Fused feed-forward of a transformer block (level 0 of the UNet, C = 320), with the LayerNorm in front of it (norm3) folded in and,
 // in the form the UNet calls (ff_proj_fused_kernel), the attention output projection + residual in front of that: a kernel that keeps
 // its ACTIVATION ROWS IN REGISTERS for the whole launch.  Shares the MFMA / epilogue helpers of gemm.hip through gemm_common.h.
-// (The transformer's proj_out as a post-projection of the same launch was built as well: bit-identical, no gain in a bench step,
-// removed -- profiles/r03_ff_proj_fused.log.  The same row-register structure was built for the K = 320 Linear layers -- QKV with norm1 folded in, output
-// projection, proj_in / proj_out -- bit-identical and SLOWER than layernorm + gemm on every shape, 217 vs 118 us for QKV: one
-// workgroup per CU has nothing to overlap its tile fetch, LayerNorm and epilogue with.  profiles/r03_lin320_rowreg_ab.log; removed.)
+// (The transformer's proj_out as a post-projection of the same launch was built twice: bit-identical, 60 us less kernel time per stacked
+// launch and no gain in a bench step either time, removed -- profiles/r03_ff_proj_fused.log, profiles/r07_l0_linear_fused.log.  The same
+// row-register structure was built in round 3 for the K = 320 Linear layers ONE AT A TIME -- QKV with norm1 folded in, output projection, proj_in /
+// proj_out -- bit-identical and SLOWER than layernorm + gemm on every shape, 217 vs 118 us for QKV: one workgroup per CU has nothing to
+// overlap its tile fetch, LayerNorm and epilogue with; profiles/r03_lin320_rowreg_ab.log, removed.  l0_head_kernel below is that structure
+// over proj_in + norm1 + QKV TOGETHER: what pays is the traffic it removes -- 3200 instead of 5120 bytes per row -- not its schedule.)
 #include "gemm_common.h"
 
 namespace {
@@ -98,6 +100,80 @@ __device__ __forceinline__ void rows_fragments(const char* tile, int wm, int lan
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks)
       xf[4 * t + ks] = *reinterpret_cast<const bf16x8_t*>(tile + t * (FF_BM * 128) + (wm * 32 + l31) * 128 + (((ks * 2 + lh) ^ sw) * 16));
+}
+
+// ------------------------------------------------------------------------------------------------
+// One K = CK product of a row tile held as fragments against a [CK, CK] row-major weight (the transformer's proj_in / proj_out, one
+// 320-row chunk of the fused QKV weight): the slab loop of the PROJ prologue below as a function.  The weight streams as CK / 64 slabs of
+// [CK rows][64 k] (128-byte row pieces, source-side swizzle) through two 40 KB buffers at the start of the LDS; slab t uses buffer
+// (B0 + t) & 1.  The caller has issued slab 0 (wslab_issue) and passed a vmcnt(0) + barrier since; with `Wnext` the last iteration issues
+// slab 0 of the NEXT product into the other buffer (its parity is then B0 + CK / 64), so a chain of products never waits for a cold slab.
+// Ascending 16-wide k steps into accumulators the caller has started (acc_init: the bias as the first k step): the order of gemm().
+// ------------------------------------------------------------------------------------------------
+template <int CK>
+__device__ __forceinline__ void wslab_issue(const u16* W, int t, uint32_t dst, int wave, int lane) {
+#pragma unroll
+  for (int i = 0; i < CK / 64; ++i) {
+    const int row = (wave + 8 * i) * 8 + (lane >> 3);
+    const uint32_t voff = (uint32_t)row * (CK * 2) + (uint32_t)((lane & 7) ^ ((row >> 1) & 7)) * 16u;
+    dma16_sv(W + t * 64, voff, dst + (wave + 8 * i) * 1024);
+  }
+}
+
+template <int CK, int B0>
+__device__ __forceinline__ void wslab_product(const u16* W, const u16* Wnext, const char* smem, uint32_t lds0, const bf16x8_t (&xf)[CK / 16],
+                                              f32x16_t (&hacc)[1][CK / 2 / 32], int wave, int lane, int wn) {
+  constexpr int NSLAB = CK / 64, NJ = CK / 2 / 32, SLAB = CK * 128;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int rd = (wn * (CK / 2) + l31) * 128, sw = (l31 >> 1) & 7;
+#pragma unroll
+  for (int t = 0; t < NSLAB; ++t) {
+    if (t + 1 < NSLAB) {
+      wslab_issue<CK>(W, t + 1, lds0 + ((B0 + t + 1) & 1) * SLAB, wave, lane);  // its buffer was last read in slab t - 1, a barrier ago
+    } else if (Wnext) {
+      wslab_issue<CK>(Wnext, 0, lds0 + ((B0 + NSLAB) & 1) * SLAB, wave, lane);
+    }
+    const char* wb = smem + ((B0 + t) & 1) * SLAB;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+      for (int j = 0; j < NJ; ++j) {
+        const bf16x8_t wf = *reinterpret_cast<const bf16x8_t*>(wb + rd + j * (32 * 128) + (((ks * 2 + lh) ^ sw) * 16));
+        hacc[0][j] = mfma_t<0>(xf[4 * t + ks], wf, hacc[0][j]);
+      }
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  }
+}
+
+// The accumulators of a wave (lane: row l31 of its 32, runs of four columns 32 j + 8 q + 4 lh ..) rounded once to bf16 and written to the
+// LDS row tile in the layout rows_fragments reads.
+template <int CK>
+__device__ __forceinline__ void acc_to_tile(const f32x16_t (&a)[1][CK / 2 / 32], char* tile, int wm, int wn, int lane) {
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int r = wm * 32 + l31, key = (r >> 1) & 7;
+  char* trow = tile + r * 128 + 8 * lh;
+#pragma unroll
+  for (int j = 0; j < CK / 2 / 32; ++j)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      uint2 pk;
+      pk.x = pack_bf2(a[0][j][4 * q + 0], a[0][j][4 * q + 1]);
+      pk.y = pack_bf2(a[0][j][4 * q + 2], a[0][j][4 * q + 3]);
+      const int n = wn * (CK / 2) + 32 * j + 8 * q;  // first of the four columns, before the + 4 lh
+      *reinterpret_cast<uint2*>(trow + (n >> 6) * (FF_BM * 128) + ((((n & 63) >> 3) ^ key) << 4)) = pk;
+    }
+}
+
+// The LDS row tile copied out as rows (the operator trace's view of a tensor that otherwise never leaves the chip).
+template <int CK>
+__device__ __forceinline__ void tile_store(const char* tile, u16* out, int64_t ld, int rows_valid, int tid) {
+  for (int id = tid; id < FF_BM * (CK / 8); id += 512) {
+    const int r = id / (CK / 8), c = id % (CK / 8);
+    const U4 v = *reinterpret_cast<const U4*>(tile + (c >> 3) * (FF_BM * 128) + r * 128 + (((c & 7) ^ ((r >> 1) & 7)) << 4));
+    if (r < rows_valid) stg16(out + (int64_t)r * ld + c * 8, v);
+  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -555,6 +631,162 @@ __global__ __launch_bounds__(512) void ff_proj_fused_kernel(GemmParams p, LnArgs
   ff_fused_body<CK, true>(p, ln, proj, W1p, b1p, W2p, nsteps);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The head of a level-0 transformer whose first block follows proj_in directly (transformer_multiview.py:160, attention.py:73-78):
+//     h = n Wpi^T + bpi        (proj_in: the block's residual stream, stored)
+//     n1 = LayerNorm(h)        (norm1: never stored -- unless the operator trace asks for it)
+//     qkv = n1 Wqkv^T          ([M, 3 CK], three chunks of CK columns)
+// in ONE launch.  A workgroup of 8 waves owns 128 rows as in ff_fused_body.  The n rows go through the LDS row tile into fragments;
+// product 1 is the slab loop of the PROJ prologue (bias first, ascending k); its fp32 sums are rounded once to bf16 IN THE REGISTERS
+// (h as gemm(n, Wpi, bias) stores it: bit-identical) and stored; norm1 is taken from those values in the accumulators (the FF_REG_LN
+// arithmetic: two-pass mean / variance, lane pair + 2 KB of LDS between the two waves of a row), rounded to bf16 into the row tile and
+// re-read as fragments; then three more slab loops, one per chunk of Wqkv, each followed by its stores.  Same products, k order and
+// rounding points as gemm, layernorm, gemm; only the order of norm1's fp32 row sums differs from ln_kernel<1>.
+// LDS: two 40 KB weight slabs + the 80 KB row tile, which also serves as the epilogues' staging area once the fragments are read (64
+// staging columns per wave: 68 KB), so the next chunk's first slab can land while a chunk is stored; the stores drain under that slab.
+// ------------------------------------------------------------------------------------------------
+struct HeadArgs {
+  const u16* Nrm;  // proj_in's input rows [M, CK] (the transformer's GroupNorm output)
+  int64_t ldn;
+  const u16* Wpi;  // [CK, CK] row-major
+  const u16* bpi;  // [CK] or nullptr
+  u16* H;          // [M, CK]
+  int64_t ldh;
+  const u16* Wqkv;  // [3 CK, CK] row-major, bias-free
+  u16* QKV;         // [M, 3 CK]
+  int64_t ldq;
+  u16* n1_out;  // nullptr, or where the n1 rows are stored as well (operator trace)
+  int64_t ldn1;
+  int M;
+};
+
+template <int CK>
+__device__ __forceinline__ void l0_head_body(const HeadArgs& a, const LnArgs& ln) {
+  constexpr int NJ = CK / 2 / 32, KS1 = CK / 16, SLAB = CK * 128, TILE_OFF = 2 * SLAB, TILE_BYTES = FF_BM * CK * 2;
+  constexpr int EPW = 64;  // staging columns per wave: 8 waves x 32 rows x 68 floats = 68 KB inside the row tile
+  static_assert(8 * 32 * (EPW + 4) * 4 <= TILE_BYTES && TILE_OFF + TILE_BYTES <= 160 * 1024, "does not fit the LDS");
+  static_assert(NJ == 5, "column groups of the epilogue below: 2 + 2 + 1 blocks");
+  __shared__ __attribute__((aligned(16))) char smem[TILE_OFF + TILE_BYTES];
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 1, wn = wave & 1;
+  const int m0 = blockIdx.x * FF_BM;
+  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+  float* stage = reinterpret_cast<float*>(smem + TILE_OFF);
+
+  GemmParams pe{};
+  pe.M = a.M; pe.N = CK; pe.K = CK; pe.flags = 0; pe.out_scale = 1.0f; pe.splits = 1; pe.rows_per_rb = 1; pe.tiles_n = 1;
+  // every wave stages through its own part of the row tile, whose readers are a barrier behind: no barrier of its own (SYNC = false)
+  auto store_rows = [&](f32x16_t (&acc)[1][NJ]) {
+    gemm_epilogue_impl<1, NJ, 32, CK / 2, 0, EPW, 0, 2, false, false, 0>(pe, acc, stage, m0, 0, wm, wn, wave, lane);
+    gemm_epilogue_impl<1, NJ, 32, CK / 2, 0, EPW, 2, 2, false, false, 0>(pe, acc, stage, m0, 0, wm, wn, wave, lane);
+    gemm_epilogue_impl<1, NJ, 32, CK / 2, 0, EPW, 4, 1, false, false, 0>(pe, acc, stage, m0, 0, wm, wn, wave, lane);
+  };
+
+  // ---- product 1: h = n Wpi^T + bpi ----
+  rows_issue<CK>(a.Nrm, a.ldn, a.M, m0, lds0 + TILE_OFF, wave, lane);
+  wslab_issue<CK>(a.Wpi, 0, lds0, wave, lane);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+  bf16x8_t xf[KS1];
+  rows_fragments<CK>(smem + TILE_OFF, wm, lane, xf);
+  f32x16_t hacc[1][NJ];
+  pe.bias = a.bpi;
+  acc_init<1, NJ, CK / 2, 0>(pe, hacc, 0, wn, lane, false);
+  wslab_product<CK, 0>(a.Wpi, a.Wqkv, smem, lds0, xf, hacc, wave, lane, wn);  // ... and the first slab of Wqkv into buffer 1
+  pe.bias = nullptr;
+  // h as the residual stream holds it: one rounding to bf16, kept as fp32 values
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t p01 = pack_bf2(hacc[0][j][4 * q + 0], hacc[0][j][4 * q + 1]);
+      const uint32_t p23 = pack_bf2(hacc[0][j][4 * q + 2], hacc[0][j][4 * q + 3]);
+      hacc[0][j][4 * q + 0] = bf2f((u16)(p01 & 0xffffu));
+      hacc[0][j][4 * q + 1] = bf2f((u16)(p01 >> 16));
+      hacc[0][j][4 * q + 2] = bf2f((u16)(p23 & 0xffffu));
+      hacc[0][j][4 * q + 3] = bf2f((u16)(p23 >> 16));
+    }
+  pe.C = a.H;
+  pe.ldc = a.ldh;
+  store_rows(hacc);
+
+  // ---- norm1 from the accumulators (the arithmetic of the block tail's norm3) ----
+  {
+    const int l31 = lane & 31, lh = lane >> 5;
+    const int r = wm * 32 + l31;
+    float* st = reinterpret_cast<float*>(smem);  // [pass][wn][FF_BM] in weight buffer 0: Wpi's last slab is read, Wqkv's second not yet issued
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) sum += hacc[0][j][e];
+    sum += __shfl_xor(sum, 32);
+    if (lh == 0) st[wn * FF_BM + r] = sum;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+    const float mu = (st[r] + st[FF_BM + r]) / (float)CK;
+    float sq = 0.f;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const float d = hacc[0][j][e] - mu;
+        sq += d * d;
+      }
+    sq += __shfl_xor(sq, 32);
+    if (lh == 0) st[(2 + wn) * FF_BM + r] = sq;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();  // (the second barrier since the h rows were staged: every wave's staging reads are done, the tile may be written)
+    asm volatile("" ::: "memory");
+    const float rs = rsqrtf((st[2 * FF_BM + r] + st[3 * FF_BM + r]) / (float)CK + ln.eps);
+    const u16* gp = ln.gamma + wn * (CK / 2) + 4 * lh;
+    const u16* bp = ln.beta + wn * (CK / 2) + 4 * lh;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const uint2 g2 = *reinterpret_cast<const uint2*>(gp + 32 * j + 8 * q), b2 = *reinterpret_cast<const uint2*>(bp + 32 * j + 8 * q);
+        const float g[4] = {bf2f((u16)(g2.x & 0xffffu)), bf2f((u16)(g2.x >> 16)), bf2f((u16)(g2.y & 0xffffu)), bf2f((u16)(g2.y >> 16))};
+        const float bt[4] = {bf2f((u16)(b2.x & 0xffffu)), bf2f((u16)(b2.x >> 16)), bf2f((u16)(b2.y & 0xffffu)), bf2f((u16)(b2.y >> 16))};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) hacc[0][j][4 * q + e] = (hacc[0][j][4 * q + e] - mu) * rs * g[e] + bt[e];
+      }
+    acc_to_tile<CK>(hacc, smem + TILE_OFF, wm, wn, lane);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the h stores stay in flight: they drain under the first slab of product 2)
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+  }
+  if (a.n1_out) tile_store<CK>(smem + TILE_OFF, a.n1_out + (int64_t)m0 * a.ldn1, a.ldn1, a.M - m0, tid);
+  rows_fragments<CK>(smem + TILE_OFF, wm, lane, xf);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();  // every wave has its n1 rows: the tile becomes the staging area again
+  asm volatile("" ::: "memory");
+
+  // ---- product 2: three chunks of CK output columns; a chunk's stores drain under the next chunk's first slab ----
+  pe.ldc = a.ldq;
+  acc_init<1, NJ, CK / 2, 0>(pe, hacc, 0, wn, lane, false);  // no bias: +0
+  wslab_product<CK, 1>(a.Wqkv, a.Wqkv + CK * CK, smem, lds0, xf, hacc, wave, lane, wn);
+  pe.C = a.QKV;
+  store_rows(hacc);
+  acc_init<1, NJ, CK / 2, 0>(pe, hacc, 0, wn, lane, false);
+  wslab_product<CK, 0>(a.Wqkv + CK * CK, a.Wqkv + 2 * CK * CK, smem, lds0, xf, hacc, wave, lane, wn);
+  pe.C = a.QKV + CK;
+  store_rows(hacc);
+  acc_init<1, NJ, CK / 2, 0>(pe, hacc, 0, wn, lane, false);
+  wslab_product<CK, 1>(a.Wqkv + 2 * CK * CK, nullptr, smem, lds0, xf, hacc, wave, lane, wn);
+  pe.C = a.QKV + 2 * CK;
+  store_rows(hacc);
+}
+
+template <int CK>
+__global__ __launch_bounds__(512) void l0_head_kernel(HeadArgs a, LnArgs ln) {
+  l0_head_body<CK>(a, ln);
+}
+
 // The same tail in precision "fp16" (PAR = 2): fp16 attention rows, weights and vectors, the fp32 residual stream X; the result is
 // h + ff(norm3(h)) as an fp32 tensor or (the block hands the transformer's proj_out its operand) rounded once to fp16.
 template <int CK>
@@ -611,6 +843,11 @@ int ff_launch_proj_fused_h16(hipStream_t st, const GemmParams& p, const LnArgs& 
   hipLaunchKernelGGL((ff_proj_fused_h16_kernel<320>), dim3((unsigned)((p.M + FF_BM - 1) / FF_BM)), dim3(512), 0, st, p, ln, proj, W1p,
                      b1p, W2p, nsteps);
   return dm4d_check_launch("ff_proj_fused_h16_kernel");
+}
+
+int l0_launch_head(hipStream_t st, const HeadArgs& a, const LnArgs& ln) {
+  hipLaunchKernelGGL((l0_head_kernel<320>), dim3((unsigned)((a.M + FF_BM - 1) / FF_BM)), dim3(512), 0, st, a, ln);
+  return dm4d_check_launch("l0_head_kernel");
 }
 
 }  // namespace
@@ -671,6 +908,28 @@ extern "C" int dm4d_attn_out_ff_geglu_fused_bf16(void* stream, const void* A0, i
   const LnArgs ln{(const u16*)ln_gamma, (const u16*)ln_beta, ln_eps};
   const ProjArgs proj{(const u16*)A0, lda0, (const u16*)Wo, (const u16*)bo, (const u16*)X, ldx};
   return ff_launch_proj_fused((hipStream_t)stream, p, ln, proj, (const u16*)W1p, (const u16*)b1p, (const u16*)W2p, hidden / FF_STEP);
+}
+
+extern "C" int dm4d_l0_linear_fused_supported(int C) { return C == 320 ? 1 : 0; }
+
+// proj_in + norm1 + QKV projection of a level-0 transformer in one launch (l0_head_kernel).
+extern "C" int dm4d_proj_in_ln_qkv_fused_bf16(void* stream, const void* N, int64_t ldn, const void* Wpi, const void* bpi, const void* ln_gamma,
+                                              const void* ln_beta, float ln_eps, const void* Wqkv, void* H, int64_t ldh, void* QKV,
+                                              int64_t ldq, void* n1_out, int64_t ldn1, int M, int C) {
+  if (!N || !Wpi || !ln_gamma || !ln_beta || !Wqkv || !H || !QKV || M <= 0)
+    return dm4d_set_error(DM4D_ERR_ARG, "proj_in_ln_qkv_fused: null pointer or empty shape");
+  if (!dm4d_l0_linear_fused_supported(C)) return dm4d_set_error(DM4D_ERR_ARG, "proj_in_ln_qkv_fused: built for C = 320 (use gemm, layernorm, gemm)");
+  if ((ldn & 7) || (ldh & 7) || (ldq & 7) || (n1_out && (ldn1 & 7)) || ldn < C || ldh < C || ldq < 3 * C || (n1_out && ldn1 < C) ||
+      ldh >= (1 << 24) || ldq >= (1 << 24) ||
+      ((((uintptr_t)N) | ((uintptr_t)Wpi) | ((uintptr_t)Wqkv) | ((uintptr_t)H) | ((uintptr_t)QKV) | ((uintptr_t)n1_out) | ((uintptr_t)ln_gamma) |
+        ((uintptr_t)ln_beta)) & 15))
+    return dm4d_set_error(DM4D_ERR_ARG, "proj_in_ln_qkv_fused: row strides must be multiples of 8 elements, pointers 16-byte aligned");
+  if ((uint64_t)M * (uint64_t)ldn * 2u >= (1ull << 32))
+    return dm4d_set_error(DM4D_ERR_ARG, "proj_in_ln_qkv_fused: input of 4 GiB or more (split the rows)");
+  if (H == N || QKV == N || H == QKV) return dm4d_set_error(DM4D_ERR_ARG, "proj_in_ln_qkv_fused: the outputs may not alias the input or each other");
+  const HeadArgs a{(const u16*)N, ldn, (const u16*)Wpi, (const u16*)bpi, (u16*)H, ldh, (const u16*)Wqkv, (u16*)QKV, ldq, (u16*)n1_out, ldn1, M};
+  const LnArgs ln{(const u16*)ln_gamma, (const u16*)ln_beta, ln_eps};
+  return l0_launch_head((hipStream_t)stream, a, ln);
 }
 
 // precision "fp16": see ff_proj_fused_h16_kernel.  W1p / b1p / W2p come from dm4d_ff_geglu_prepare_bf16 (a permutation of 16-bit words,

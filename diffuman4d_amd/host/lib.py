@@ -55,6 +55,8 @@ SIGNATURES = {
     "dm4d_ff_geglu_fused_bf16": (_i, [_vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i]),
     "dm4d_attn_out_ff_geglu_fused_bf16": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i,
                                                 _i]),
+    "dm4d_l0_linear_fused_supported": (_i, [_i]),
+    "dm4d_proj_in_ln_qkv_fused_bf16": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _f, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i, _i]),
     # parity precision (fp32 tensors between kernels, two-term bf16 operands)
     "dm4d_split_f32": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i64, _i, _vp, _i64, _i64, _i, _i, _f, _i]),
     "dm4d_groupnorm_f32_ws_bytes": (C.c_size_t, [_i, _i, _i]),

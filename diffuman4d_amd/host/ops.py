@@ -381,6 +381,70 @@ class FeedForward:
         return out
 
 
+# proj_in + norm1 + QKV projection of a level-0 transformer (C = 320) as one launch (proj_in_ln_qkv); off = gemm, layernorm, gemm (A/B, tests)
+L0_HEAD_FUSED = os.environ.get("DM4D_L0_HEAD_FUSED", "1") != "0"
+
+
+def _on_device(t: torch.Tensor) -> bool:
+    return t.is_cuda
+
+
+def _rows16(*ts) -> bool:
+    """2-D views whose rows start on 16-byte boundaries (row strides in multiples of 8 elements, contiguous columns)."""
+    return all(t.ndim == 2 and t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 and t.stride(1) == 1 for t in ts)
+
+
+def _l0_fusable(C: int, rows, weights, vectors) -> bool:
+    """The guards of FeedForward.after_attention for the level-0 head launch: bf16 device tensors, 16-byte-aligned rows, M * stride * 2 <
+    2^32 for the DMA-fetched input (rows[0]), contiguous 16-byte-aligned weights and vectors, and a channel count the kernels are built for."""
+    ts = tuple(rows) + tuple(weights) + tuple(v for v in vectors if v is not None)
+    return (all(isinstance(t, torch.Tensor) and t.dtype == BF16 and _on_device(t) for t in ts) and _rows16(*rows)
+            and all(t.shape[1] == C and t.stride(0) < (1 << 24) for t in rows)
+            and rows[0].shape[0] * rows[0].stride(0) * 2 < (1 << 32)
+            and all(w.is_contiguous() and w.data_ptr() % 16 == 0 for w in weights)
+            and all(v is None or (v.is_contiguous() and v.data_ptr() % 16 == 0) for v in vectors)
+            and bool(_l.load().dm4d_l0_linear_fused_supported(C)))
+
+
+def _launch_l0_head(n, wpi, bpi, ln, wqkv, h, qkv, n1) -> None:
+    M, C = n.shape
+    with _Prof("linear", 2.0 * M * (C + 3 * C) * C, "flop", M):
+        rc = _l.load().dm4d_proj_in_ln_qkv_fused_bf16(_stream(), _p(n), n.stride(0), _p(wpi), _p(bpi), _p(ln[0]), _p(ln[1]), float(ln[2]),
+                                                      _p(wqkv), _p(h), h.stride(0), _p(qkv), qkv.stride(0), _p(n1),
+                                                      n1.stride(0) if n1 is not None else 0, M, C)
+    _l.check(rc, "dm4d_proj_in_ln_qkv_fused_bf16")
+
+
+def proj_in_ln_qkv(n: torch.Tensor, wpi: torch.Tensor, bpi: Optional[torch.Tensor], ln, wqkv: torch.Tensor,
+                   qkv: Optional[torch.Tensor] = None):
+    """The head of a transformer whose first block follows proj_in (transformer_multiview.py:160, attention.py:73-78):
+    h = n wpi^T + bpi, qkv = LayerNorm(h) wqkv^T with ln = (gamma, beta, eps); returns (h, qkv).  One launch at C = 320 (L0_HEAD_FUSED:
+    LayerNorm(h) never leaves the chip), otherwise gemm, layernorm, gemm: the same products and bf16 rounding points, h bit-identical, the
+    LayerNorm's fp32 row sums in another order (one-ulp differences on isolated elements of qkv).  `qkv`: a [M, 3C] view to write into."""
+    M, C = n.shape[0], wpi.shape[0]
+    fused = (L0_HEAD_FUSED and wpi.shape == (C, C) and wqkv.shape == (3 * C, C) and n.shape[1] == C
+             and (qkv is None or (qkv.shape == (M, 3 * C) and _rows16(qkv) and qkv.dtype == BF16 and qkv.stride(0) < (1 << 24)))
+             and _l0_fusable(C, (n,), (wpi, wqkv), (bpi, ln[0], ln[1])))
+    if not fused:
+        h = gemm(n, wpi, bias=bpi)
+        return h, gemm(layernorm(h, ln[0], ln[1], ln[2]), wqkv, out=qkv)
+    h = torch.empty((M, C), dtype=BF16, device=n.device)
+    if qkv is None:
+        qkv = torch.empty((M, 3 * C), dtype=BF16, device=n.device)
+    # operator trace: the launch also stores LayerNorm(h), and is recorded part by part under the names of the separate launches
+    n1 = torch.empty((M, C), dtype=BF16, device=n.device) if TRACE is not None else None
+    _launch_l0_head(n, wpi, bpi, ln, wqkv, h, qkv, n1)
+    if TRACE is not None:
+        _trace("gemm", h, a=n, w=wpi, a2=None, bias=bpi, rowbias=None, rows_per_rowbias=1, residual=None, geglu=False, silu=False,
+               out_scale=1.0, out_f32=False, split_out=False)
+        _trace("layernorm", n1, x=h, gamma=ln[0], beta=ln[1], eps=ln[2])
+        _trace("gemm", qkv, a=n1, w=wqkv, a2=None, bias=None, rowbias=None, rows_per_rowbias=1, residual=None, geglu=False, silu=False,
+               out_scale=1.0, out_f32=False, split_out=False)
+    return h, qkv
+
+
+
+
 def conv_up2x_prepare(wt: torch.Tensor) -> torch.Tensor:
     """3x3 weights [Cout, 9*Cin] ((ky,kx,ci) order) -> the four 2x2 phase kernels [4, Cout, 4*Cin] of conv_up2x (once per
     layer: sums of the taps that read the same low-resolution pixel, fp32, rounded to bf16 once)."""

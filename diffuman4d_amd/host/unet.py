@@ -256,19 +256,23 @@ class _TransformerBlock:
                                       "cross_attention_dim is not null): not supported -- the reference never passes encoder_hidden_states "
                                       "(pipeline_diffuman4d.py:398-405)")
 
-    def __call__(self, h: torch.Tensor, batch: int, seq: int, shard=None, operand_out: bool = False) -> torch.Tensor:
+    def __call__(self, h: torch.Tensor, batch: int, seq: int, shard=None, operand_out: bool = False, qkv=None) -> torch.Tensor:
         """h [M, C] token-major; attention over `batch` sequences of `seq` tokens (attention.py:68-90).
         shard (parallel.FrameShard): `seq` is this rank's share of the frame-folded sequence; K/V are all-gathered.
         operand_out (wide precisions): the result leaves as the OPERAND of the next contraction (the transformer's proj_out, when this is
-        its last block) instead of an fp32 tensor: the same one rounding ops.split would apply to the stored fp32 sum, without storing it."""
+        its last block) instead of an fp32 tensor: the same one rounding ops.split would apply to the stored fp32 sum, without storing it.
+        qkv (fast precision without `shard`, from _Transformer): this block's QKV projection, already formed with proj_in
+        (ops.proj_in_ln_qkv)."""
         if self.wide:
             return self._call_wide(h, batch, seq, shard, operand_out)
         C = h.shape[1]
-        n = ops.layernorm(h, self.n1w, self.n1b, 1e-5)
         if shard is None:
-            qkv = ops.gemm(n, self.qkv)
+            if qkv is None:
+                qkv = ops.gemm(ops.layernorm(h, self.n1w, self.n1b, 1e-5), self.qkv)
             a = ops.attention(qkv[:, :C], qkv[:, C:2 * C], qkv[:, 2 * C:], batch, self.heads, seq, q_scaled=True)
         else:
+            assert qkv is None
+            n = ops.layernorm(h, self.n1w, self.n1b, 1e-5)
             kv = ops.gemm(n, self.qkv[C:])  # [M, 2C] contiguous so the collective needs no repack
             pending = shard.gather_kv_start(kv.view(batch, seq, 2 * C))
             q = ops.gemm(n, self.qkv[:C])  # runs while the K|V blocks travel
@@ -339,9 +343,16 @@ class _Transformer:
         M, HW = B * H * Wd, H * Wd
         P = self.wide
         n = ops.groupnorm(x, self.nw, self.nb, self.groups, 1e-6, silu=False)  # eps 1e-6: transformer_multiview.py:43-45
-        h = ops.gemm(n.view(M, -1), self.piw, bias=self.pib, out_f32=P)
+        qkv = None
+        if not P and shard is None and self.blocks:
+            # fast precision: proj_in + the first block's norm1 and QKV projection in one launch where the kernel is built for the channel
+            # count (level 0, C = 320); gemm, layernorm, gemm elsewhere
+            b0 = self.blocks[0]
+            h, qkv = ops.proj_in_ln_qkv(n.view(M, -1), self.piw, self.pib, (b0.n1w, b0.n1b, 1e-5), b0.qkv)
+        else:
+            h = ops.gemm(n.view(M, -1), self.piw, bias=self.pib, out_f32=P)
         for i, blk in enumerate(self.blocks):  # wide precisions: the last block hands proj_out its operand directly
-            h = blk(h, B // num_frames, num_frames * HW, shard, operand_out=P and i == len(self.blocks) - 1)
+            h = blk(h, B // num_frames, num_frames * HW, shard, operand_out=P and i == len(self.blocks) - 1, qkv=qkv if i == 0 else None)
         if P and not self.blocks:
             h = ops.split(h, h16=self.h16)
         return ops.gemm(h, self.pow, bias=self.pob, residual=x.view(M, C), out_f32=P).view(B, H, Wd, C)

@@ -380,6 +380,21 @@ int dm4d_attn_out_ff_geglu_fused_bf16(void* stream, const void* A0, int64_t lda0
                                       const void* b1p, const void* W2p, const void* b2, void* Out, int64_t ldo, int M, int C,
                                       int hidden);
 
+/* proj_in + norm1 + QKV projection of a level-0 transformer (C = 320) in one launch (transformer_multiview.py:160 proj_in;
+ * attention.py:73-78 norm1 and attn1's to_q / to_k / to_v; the block tail above covers attention.py:88-90, :129-149, and
+ * transformer_multiview.py:209 proj_out stays a dm4d_gemm_bf16 call):
+ *     H = N Wpi^T + bpi             (N [M, C] = the transformer's GroupNorm output, Wpi [C, C] row-major, bpi [C] or NULL)
+ *     QKV = LayerNorm(H) Wqkv^T     (Wqkv [3 C, C] row-major, bias-free; QKV [M, 3 C] with row stride ldq)
+ * H is rounded to bf16 once in the registers and stored: bit-identical to dm4d_gemm_bf16(N, Wpi, bias).  norm1 is taken from those
+ * values in the accumulators and never stored, unless n1_out is given (the operator trace: LayerNorm(H) as rounded to bf16, [M, C]).
+ * Same products, k order and rounding points as dm4d_gemm_bf16, dm4d_layernorm_bf16, dm4d_gemm_bf16; the fp32 row sums of the
+ * LayerNorm are added in another order (at most isolated one-ulp differences of a bf16 rounding in QKV).  The outputs may not alias
+ * the input or each other.  dm4d_l0_linear_fused_supported(C) says whether the kernel is built for the channel count (C = 320).   */
+int dm4d_l0_linear_fused_supported(int C);
+int dm4d_proj_in_ln_qkv_fused_bf16(void* stream, const void* N, int64_t ldn, const void* Wpi, const void* bpi, const void* ln_gamma,
+                                   const void* ln_beta, float ln_eps, const void* Wqkv, void* H, int64_t ldh, void* QKV, int64_t ldq,
+                                   void* n1_out, int64_t ldn1, int M, int C);
+
 /* ---- Parity precision -------------------------------------------------------------------------------------------------------
  * north_star (BASELINE.json) asks for decoded RGB within 1e-3 rel-L2 of the reference's fp32 CPU path
  * (pipeline_diffuman4d.py:439-559 run with fp32 modules).  bf16 MFMA operands alone cost 7e-3 on the judged UNet call, so the

@@ -6,23 +6,41 @@
 // row-register structure was built in round 3 for the K = 320 Linear layers ONE AT A TIME -- QKV with norm1 folded in, output projection, proj_in /
 // proj_out -- bit-identical and SLOWER than layernorm + gemm on every shape, 217 vs 118 us for QKV: one workgroup per CU has nothing to
 // overlap its tile fetch, LayerNorm and epilogue with; profiles/r03_lin320_rowreg_ab.log, removed.  l0_head_kernel below is that structure
-// over proj_in + norm1 + QKV TOGETHER: what pays is the traffic it removes -- 3200 instead of 5120 bytes per row -- not its schedule.)
+// over proj_in + norm1 + QKV TOGETHER: what pays is the traffic it removes -- 3200 instead of 5120 bytes per row -- not its schedule.
+// The block tail of rounds 3-5 -- h through the LDS tile, a row-by-row LayerNorm over it and the output buffer, kept behind a
+// compile-time switch through round 6 -- is gone as well: 348 against 318 us per launch, profiles/r06_ffregln.log.)
+// The block tail and the head share their parts: wslab_product (a K = 320 product against a row-major weight), acc_layernorm_to_tile
+// (LayerNorm taken from the accumulators), keep_as_bf16, tile_off, wait_barrier.
 #include "gemm_common.h"
 
 namespace {
 
 constexpr int FF_BM = 128, FF_STEP = 32;
-#ifdef FF_TILE_LN
-constexpr bool FF_REG_LN = false;  // round 3's form of the block tail: h through the LDS tile and the output buffer (A/B builds)
-#else
-constexpr bool FF_REG_LN = true;
-#endif
+
+// This wave's outstanding memory operations of the named counters (VM: loads, DMA pieces and stores; LGKM: LDS reads and stores) have
+// completed, then the workgroup's barrier; the compiler moves no memory access across either.
+template <bool VM, bool LGKM>
+__device__ __forceinline__ void wait_barrier() {
+  static_assert(VM || LGKM, "a bare barrier is not what the kernels of this file want");
+  if constexpr (VM && LGKM) {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  } else if constexpr (VM) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  } else {
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  }
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
+}
 
 // ------------------------------------------------------------------------------------------------
 // A tile of FF_BM rows x CK channels: HBM -> LDS by DMA as CK / 64 slabs of [FF_BM rows][64 k] (128-byte row pieces, the 16-byte
 // chunks of a row XOR-permuted on the source side like every A tile of gemm.hip), optionally LayerNorm'ed IN PLACE, then read
 // into registers as the MFMA fragments of the wave's 32 rows (CK / 16 k steps x 4 VGPRs).
 // ------------------------------------------------------------------------------------------------
+// Byte offset in the tile of row r's 16-byte chunk c (columns 8 c .. 8 c + 7): slab c >> 3, the chunk's place in the row piece XOR-permuted.
+__device__ __forceinline__ int tile_off(int r, int c) { return (c >> 3) * (FF_BM * 128) + r * 128 + (((c & 7) ^ ((r >> 1) & 7)) << 4); }
+
 struct LnArgs {
   const u16* gamma;  // nullptr: the rows are used as they are
   const u16* beta;
@@ -55,11 +73,10 @@ __device__ __forceinline__ void rows_issue(const u16* X, int64_t ldx, int M, int
 
 // LayerNorm of the tile in the LDS, in place: wave w normalises rows 16 w .. 16 w + 15 one after the other with lane l on the
 // row's 16-byte vector l -- the arrangement and the arithmetic of ln_kernel<1> (ln_row_stats / ln_row_apply), so the result is the
-// stand-alone LayerNorm launch bit for bit.  The caller puts a barrier on either side.
-// raw (ff_proj_fused_kernel): the un-normalised rows are also written to `raw` (row stride ldraw) on the way -- rows_valid of them.
-template <int CK, bool RAW = false>
-__device__ __forceinline__ void rows_layernorm(char* tile, const LnArgs& ln, int wave, int lane, u16* raw = nullptr, int64_t ldraw = 0,
-                                               int rows_valid = FF_BM) {
+// stand-alone LayerNorm launch bit for bit.  The caller puts a barrier on either side.  (ff_fused_kernel only: the block tail and the
+// head take their LayerNorm from the accumulators, acc_layernorm_to_tile.)
+template <int CK>
+__device__ __forceinline__ void rows_layernorm(char* tile, const LnArgs& ln, int wave, int lane) {
   static_assert(CK / 8 <= 64, "one vector per lane");
   const bool on[1] = {lane < CK / 8};
   float g[8], bt[8];
@@ -67,17 +84,12 @@ __device__ __forceinline__ void rows_layernorm(char* tile, const LnArgs& ln, int
     unpack8(ldg16(ln.gamma + lane * 8), g);
     unpack8(ldg16(ln.beta + lane * 8), bt);
   }
-  const int t = lane >> 3, c = lane & 7;
   for (int i = 0; i < FF_BM / 8; ++i) {
     const int r = wave * (FF_BM / 8) + i;
-    char* a = tile + t * (FF_BM * 128) + r * 128 + ((c ^ ((r >> 1) & 7)) << 4);
+    char* a = tile + tile_off(r, lane);
     float v[1][8];
     if (on[0]) {
-      const U4 rawv = *reinterpret_cast<const U4*>(a);
-      if constexpr (RAW) {
-        if (r < rows_valid) stg16(raw + (int64_t)r * ldraw + lane * 8, rawv);
-      }
-      unpack8(rawv, v[0]);
+      unpack8(*reinterpret_cast<const U4*>(a), v[0]);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) v[0][e] = 0.f;
@@ -94,6 +106,8 @@ __device__ __forceinline__ void rows_layernorm(char* tile, const LnArgs& ln, int
 
 template <int CK>
 __device__ __forceinline__ void rows_fragments(const char* tile, int wm, int lane, bf16x8_t (&xf)[CK / 16]) {
+  // (tile_off(wm * 32 + l31, 8 * t + 2 * ks + lh) written out, the XOR key taken from l31 alone: through tile_off the block-tail kernels
+  // need more registers -- ff_proj_fused_kernel spills 22 dwords instead of 7, ff_proj_fused_h16_kernel takes 246 VGPRs instead of 239)
   const int l31 = lane & 31, lh = lane >> 5, sw = (l31 >> 1) & 7;
 #pragma unroll
   for (int t = 0; t < CK / 64; ++t)
@@ -103,8 +117,8 @@ __device__ __forceinline__ void rows_fragments(const char* tile, int wm, int lan
 }
 
 // ------------------------------------------------------------------------------------------------
-// One K = CK product of a row tile held as fragments against a [CK, CK] row-major weight (the transformer's proj_in / proj_out, one
-// 320-row chunk of the fused QKV weight): the slab loop of the PROJ prologue below as a function.  The weight streams as CK / 64 slabs of
+// One K = CK product of a row tile held as fragments against a [CK, CK] row-major weight (the attention output projection of the block
+// tail, the transformer's proj_in, one 320-row chunk of the fused QKV weight) in the operand type of PAR.  The weight streams as CK / 64 slabs of
 // [CK rows][64 k] (128-byte row pieces, source-side swizzle) through two 40 KB buffers at the start of the LDS; slab t uses buffer
 // (B0 + t) & 1.  The caller has issued slab 0 (wslab_issue) and passed a vmcnt(0) + barrier since; with `Wnext` the last iteration issues
 // slab 0 of the NEXT product into the other buffer (its parity is then B0 + CK / 64), so a chain of products never waits for a cold slab.
@@ -120,10 +134,13 @@ __device__ __forceinline__ void wslab_issue(const u16* W, int t, uint32_t dst, i
   }
 }
 
-template <int CK, int B0>
+template <int CK>
+constexpr int WSLAB_BYTES = CK * 128;
+
+template <int CK, int B0, int PAR = 0>
 __device__ __forceinline__ void wslab_product(const u16* W, const u16* Wnext, const char* smem, uint32_t lds0, const bf16x8_t (&xf)[CK / 16],
                                               f32x16_t (&hacc)[1][CK / 2 / 32], int wave, int lane, int wn) {
-  constexpr int NSLAB = CK / 64, NJ = CK / 2 / 32, SLAB = CK * 128;
+  constexpr int NSLAB = CK / 64, NJ = CK / 2 / 32, SLAB = WSLAB_BYTES<CK>;
   const int l31 = lane & 31, lh = lane >> 5;
   const int rd = (wn * (CK / 2) + l31) * 128, sw = (l31 >> 1) & 7;
 #pragma unroll
@@ -139,30 +156,79 @@ __device__ __forceinline__ void wslab_product(const u16* W, const u16* Wnext, co
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const bf16x8_t wf = *reinterpret_cast<const bf16x8_t*>(wb + rd + j * (32 * 128) + (((ks * 2 + lh) ^ sw) * 16));
-        hacc[0][j] = mfma_t<0>(xf[4 * t + ks], wf, hacc[0][j]);
+        hacc[0][j] = mfma_t<PAR>(xf[4 * t + ks], wf, hacc[0][j]);
       }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    wait_barrier<true, true>();
   }
 }
 
-// The accumulators of a wave (lane: row l31 of its 32, runs of four columns 32 j + 8 q + 4 lh ..) rounded once to bf16 and written to the
-// LDS row tile in the layout rows_fragments reads.
-template <int CK>
-__device__ __forceinline__ void acc_to_tile(const f32x16_t (&a)[1][CK / 2 / 32], char* tile, int wm, int wn, int lane) {
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int r = wm * 32 + l31, key = (r >> 1) & 7;
-  char* trow = tile + r * 128 + 8 * lh;
+// Four 16-bit values of the operand type of PAR (fp16 for PAR == 2, bf16 otherwise) as fp32.
+template <int PAR>
+__device__ __forceinline__ void unpack4(uint2 v, float (&f)[4]) {
+  const u16 h[4] = {(u16)(v.x & 0xffffu), (u16)(v.x >> 16), (u16)(v.y & 0xffffu), (u16)(v.y >> 16)};
 #pragma unroll
-  for (int j = 0; j < CK / 2 / 32; ++j)
+  for (int e = 0; e < 4; ++e) f[e] = PAR == 2 ? h2f(h[e]) : bf2f(h[e]);
+}
+
+// Four values as a bf16 tensor would hold them -- ONE rounding -- kept as fp32 in a[i .. i + 3]: h as the residual stream holds it,
+// the rounding point of the gemm launch whose result a fused kernel keeps in its accumulators.
+__device__ __forceinline__ void keep_as_bf16(f32x16_t& a, int i, float v0, float v1, float v2, float v3) {
+  float r[4];
+  unpack4<0>(make_uint2(pack_bf2(v0, v1), pack_bf2(v2, v3)), r);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) a[i + e] = r[e];
+}
+
+// LayerNorm of the rows a workgroup holds in its accumulators (lane: row l31 of its wave's 32, runs of four columns wn CK / 2 + 32 j +
+// 8 q + 4 lh ..), written to the LDS row tile in the layout rows_fragments reads; `hacc` is left as it is.  Row sums over the lane pair
+// l, l ^ 32 and, through the 2 KB at `st` ([pass][wn][FF_BM] floats, the caller's choice of a place nobody else uses meanwhile), over the
+// two waves that share a row: two-pass mean / variance in fp32 like ln_row_stats, y = (h - mu) * rs * g + b rounded ONCE to the operand
+// type of PAR (fp16 with the saturating conversion of ln_kernel<., 2>, bf16 otherwise).  Same arithmetic as the stand-alone LayerNorm
+// launch, the row sums in another order.  Two barriers inside; the wait + barrier that makes the tile readable is the caller's.
+template <int CK, int PAR>
+__device__ __forceinline__ void acc_layernorm_to_tile(const f32x16_t (&hacc)[1][CK / 2 / 32], float* st, char* tile, const LnArgs& ln, int wm,
+                                                      int wn, int lane) {
+  constexpr int NJ = CK / 2 / 32;
+  const int l31 = lane & 31, lh = lane >> 5;
+  const int r = wm * 32 + l31;
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) sum += hacc[0][j][e];
+  sum += __shfl_xor(sum, 32);
+  if (lh == 0) st[wn * FF_BM + r] = sum;
+  wait_barrier<false, true>();
+  const float mu = (st[r] + st[FF_BM + r]) / (float)CK;
+  float sq = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const float d = hacc[0][j][e] - mu;
+      sq += d * d;
+    }
+  sq += __shfl_xor(sq, 32);
+  if (lh == 0) st[(2 + wn) * FF_BM + r] = sq;
+  wait_barrier<false, true>();
+  const float rs = rsqrtf((st[2 * FF_BM + r] + st[3 * FF_BM + r]) / (float)CK + ln.eps);
+  const u16* gp = ln.gamma + wn * (CK / 2) + 4 * lh;
+  const u16* bp = ln.beta + wn * (CK / 2) + 4 * lh;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      uint2 pk;
-      pk.x = pack_bf2(a[0][j][4 * q + 0], a[0][j][4 * q + 1]);
-      pk.y = pack_bf2(a[0][j][4 * q + 2], a[0][j][4 * q + 3]);
+      float g[4], bt[4], y[4];
+      unpack4<PAR>(*reinterpret_cast<const uint2*>(gp + 32 * j + 8 * q), g);
+      unpack4<PAR>(*reinterpret_cast<const uint2*>(bp + 32 * j + 8 * q), bt);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        y[e] = (hacc[0][j][4 * q + e] - mu) * rs * g[e] + bt[e];
+        if constexpr (PAR == 2) y[e] = sat_h(y[e]);
+      }
+      const uint2 pk = PAR == 2 ? make_uint2(pack_h2(y[0], y[1]), pack_h2(y[2], y[3])) : make_uint2(pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]));
       const int n = wn * (CK / 2) + 32 * j + 8 * q;  // first of the four columns, before the + 4 lh
-      *reinterpret_cast<uint2*>(trow + (n >> 6) * (FF_BM * 128) + ((((n & 63) >> 3) ^ key) << 4)) = pk;
+      *reinterpret_cast<uint2*>(tile + tile_off(r, n >> 3) + 8 * lh) = pk;
     }
 }
 
@@ -171,7 +237,7 @@ template <int CK>
 __device__ __forceinline__ void tile_store(const char* tile, u16* out, int64_t ld, int rows_valid, int tid) {
   for (int id = tid; id < FF_BM * (CK / 8); id += 512) {
     const int r = id / (CK / 8), c = id % (CK / 8);
-    const U4 v = *reinterpret_cast<const U4*>(tile + (c >> 3) * (FF_BM * 128) + r * 128 + (((c & 7) ^ ((r >> 1) & 7)) << 4));
+    const U4 v = *reinterpret_cast<const U4*>(tile + tile_off(r, c));
     if (r < rows_valid) stg16(out + (int64_t)r * ld + c * 8, v);
   }
 }
@@ -209,7 +275,7 @@ __device__ __forceinline__ void ff_fused_body(const GemmParams& p, const LnArgs&
   constexpr int SMEM_MAIN = (H_OFF + 2 * H_BYTES) > (Y_OFF + Y_BYTES) ? (H_OFF + 2 * H_BYTES) : (Y_OFF + Y_BYTES);
   constexpr int SMEM_EPI = 8 * 32 * (EpiGeom<CK / 2>::EPW + 4) * 4;
   // projection prologue (PROJ): two Wo slabs of [CK rows][64 k] in front, the attention rows tile behind them -- all of the LDS
-  constexpr int WO_SLAB = CK * 128, A0_OFF = 2 * WO_SLAB, SMEM_PROJ = PROJ ? A0_OFF + Y_BYTES : 0;
+  constexpr int A0_OFF = 2 * WSLAB_BYTES<CK>, SMEM_PROJ = PROJ ? A0_OFF + Y_BYTES : 0;
   constexpr int SMEM_1 = SMEM_MAIN > SMEM_EPI ? SMEM_MAIN : SMEM_EPI;
   constexpr int SMEM_BYTES = SMEM_1 > SMEM_PROJ ? SMEM_1 : SMEM_PROJ;
   static_assert(SMEM_BYTES <= 160 * 1024, "does not fit the LDS");
@@ -247,26 +313,12 @@ __device__ __forceinline__ void ff_fused_body(const GemmParams& p, const LnArgs&
   bf16x8_t xf[KS1];
   f32x16_t acc[1][NJ];
   if constexpr (PROJ) {
-    // ---- projection prologue: h = A0 Wo^T + bo + X for this workgroup's 128 rows, into the LDS tile at Y_OFF (and, from
-    // rows_layernorm, out to p.C: the epilogue's residual).  The products and their order are those of gemm(A0, Wo, bias, residual):
-    // bias as the first k step, ascending 16-wide k steps, the residual added to the fp32 sum, one rounding to bf16 -- bit-identical
-    // to that launch.  A0 rows -> LDS behind the two Wo buffers -> registers; Wo streams as NSLAB slabs of [CK rows][64 k] = 40 KB
-    // straight from its row-major layout (128-byte row pieces, source-side swizzle), double buffered.
-    uint32_t wo_voff[CK / 64];
-#pragma unroll
-    for (int i = 0; i < CK / 64; ++i) {
-      const int row = (wave + 8 * i) * 8 + (lane >> 3);
-      wo_voff[i] = (uint32_t)row * (CK * 2) + (uint32_t)((lane & 7) ^ ((row >> 1) & 7)) * 16u;
-    }
-    auto issue_wo = [&](int t, int b) {
-#pragma unroll
-      for (int i = 0; i < CK / 64; ++i) dma16_sv(proj.Wo + t * 64, wo_voff[i], lds0 + b * WO_SLAB + (wave + 8 * i) * 1024);
-    };
+    // ---- projection prologue: h = A0 Wo^T + bo + X for this workgroup's 128 rows, in the accumulators.  The products and their order are
+    // those of gemm(A0, Wo, bias, residual): bias as the first k step, ascending 16-wide k steps (wslab_product), the residual added to
+    // the fp32 sum.  A0 rows -> LDS behind the two Wo buffers -> registers.
     rows_issue<CK>(proj.A0, proj.lda0, p.M, m0, lds0 + A0_OFF, wave, lane);
-    issue_wo(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    wslab_issue<CK>(proj.Wo, 0, lds0, wave, lane);
+    wait_barrier<true, false>();
     rows_fragments<CK>(smem + A0_OFF, wm, lane, xf);
     f32x16_t hacc[1][NJ];
     {
@@ -274,37 +326,20 @@ __device__ __forceinline__ void ff_fused_body(const GemmParams& p, const LnArgs&
       pb.bias = proj.bo;
       acc_init<1, NJ, CK / 2, PAR>(pb, hacc, 0, wn, lane, false);
     }
-    const int wo_rd = (wn * (CK / 2) + l31) * 128, wo_sw = (l31 >> 1) & 7;
-#pragma unroll
-    for (int t = 0; t < NSLAB; ++t) {
-      if (t + 1 < NSLAB) issue_wo(t + 1, (t + 1) & 1);  // its buffer was last read in slab t - 1, a barrier ago
-      const char* wb = smem + (t & 1) * WO_SLAB;
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) {
-          const bf16x8_t wf = *reinterpret_cast<const bf16x8_t*>(wb + wo_rd + j * (32 * 128) + (((ks * 2 + lh) ^ wo_sw) * 16));
-          hacc[0][j] = mfma_t<PAR>(xf[4 * t + ks], wf, hacc[0][j]);
-        }
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-    }
-    // residual in the accumulators' own layout (lane: row l31 of its 32, runs of four columns): 8-byte loads, all issued first
+    wslab_product<CK, 0, PAR>(proj.Wo, nullptr, smem, lds0, xf, hacc, wave, lane, wn);
     issue_w1(0, 0);  // buffer 0 (Wo slab NSLAB - 1 was its last reader, behind the barrier above); lands while h is formed
-    if constexpr (PAR == 2 || FF_REG_LN) {
-      // Round 6, fast precision too (FF_REG_LN; -DFF_TILE_LN restores round 3's form for the A/B): the same structure on bf16 tensors --
-      // v = A0 Wo^T + bo + X is rounded to bf16 IN THE REGISTERS (the rounding point of gemm(A0, Wo, bias, residual): h as the residual
-      // stream holds it), norm3 is taken from those values, and they start the accumulators of the second product, so h is neither stored
-      // nor re-read and the serial row-by-row LayerNorm over the LDS tile (36 us of a 348 us launch at M = 92 160, profiles/r06_ffabl2.log)
-      // is gone.  Same products and rounding points as the four launches; the ORDER of fp32 additions differs (row statistics, h first in
-      // the output sum), so the two forms agree except for isolated one-ulp differences of a bf16 rounding (tests/opcheck.py ff_proj_fused_*).
+    {
+      // Fast precision: v = A0 Wo^T + bo + X is rounded to bf16 IN THE REGISTERS (the rounding point of gemm(A0, Wo, bias, residual): h as
+      // the residual stream holds it), norm3 is taken from those values (acc_layernorm_to_tile), and they start the accumulators of the
+      // second product, so h is neither stored nor re-read.  Same products and rounding points as the four launches; the ORDER of fp32
+      // additions differs (row statistics, h first in the output sum), so the two forms agree except for isolated one-ulp differences of
+      // a bf16 rounding (tests/opcheck.py ff_proj_fused_*).  (Rounds 3-5 sent h through the LDS tile, a serial row-by-row LayerNorm over
+      // it -- 36 us of a 348 us launch at M = 92 160, profiles/r06_ffabl2.log -- and the output buffer, from which the epilogue re-read it
+      // as its residual: 348 against 318 us per launch, profiles/r06_ffregln.log; that form was removed.)
       // Precision "fp16": the residual stream is fp32 and h = A0 Wo^T + bo + X is never rounded -- and never stored.  It stays in
-      // the accumulators it was formed in: norm3 is taken from them (row sums over the lane pair l, l ^ 32 and, through 2 KB of LDS,
-      // over the two waves that share a row: two-pass mean / variance in fp32 like ln_row_stats, y rounded once to fp16 with the
-      // saturating conversion of ln_kernel<., 2>), the fp16 y rows go to the LDS tile the fragments are read from, and the very same
-      // registers then become the accumulators of the second product: O = h + b2 + W2 H.  Against the separate launches of this
-      // precision (gemm -> fp32 h, layernorm, gemm GEGLU, gemm + fp32 residual) the 118 MB of h per launch are neither written nor
+      // the accumulators it was formed in: norm3 is taken from them, the fp16 y rows go to the LDS tile the fragments are read from, and
+      // the very same registers then become the accumulators of the second product: O = h + b2 + W2 H.  Against the separate launches of
+      // this precision (gemm -> fp32 h, layernorm, gemm GEGLU, gemm + fp32 residual) the 118 MB of h per launch are neither written nor
       // read twice; the sums differ from theirs only in the order of fp32 additions (h enters the output sum first instead of last,
       // the row statistics are added up in a different order): tests/opcheck.py h16_ff_proj_fused_*.
       // (lane-derived addresses of this block are formed HERE, from a copy of the lane id the compiler cannot see through, so that they do
@@ -314,7 +349,7 @@ __device__ __forceinline__ void ff_fused_body(const GemmParams& p, const LnArgs&
       asm volatile("" : "+v"(lane_b));
       const int l31 = lane_b & 31, lh = lane_b >> 5;
       const int r = wm * 32 + l31;
-      {
+      {  // the residual in the accumulators' own layout (lane: row l31 of its 32, runs of four columns): 16- or 8-byte loads
         int m = m0 + r;
         if (m > p.M - 1) m = p.M - 1;
         if constexpr (PAR == 2) {
@@ -338,73 +373,16 @@ __device__ __forceinline__ void ff_fused_body(const GemmParams& p, const LnArgs&
             for (int q = 0; q < 4; ++q) rx[q] = *reinterpret_cast<const uint2*>(xr + 32 * j + 8 * q);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-              const float x4[4] = {bf2f((u16)(rx[q].x & 0xffffu)), bf2f((u16)(rx[q].x >> 16)), bf2f((u16)(rx[q].y & 0xffffu)), bf2f((u16)(rx[q].y >> 16))};
-              // h as the residual stream holds it: one rounding to bf16, kept as an fp32 value
-              const uint32_t p01 = pack_bf2(hacc[0][j][4 * q + 0] + x4[0], hacc[0][j][4 * q + 1] + x4[1]);
-              const uint32_t p23 = pack_bf2(hacc[0][j][4 * q + 2] + x4[2], hacc[0][j][4 * q + 3] + x4[3]);
-              hacc[0][j][4 * q + 0] = bf2f((u16)(p01 & 0xffffu));
-              hacc[0][j][4 * q + 1] = bf2f((u16)(p01 >> 16));
-              hacc[0][j][4 * q + 2] = bf2f((u16)(p23 & 0xffffu));
-              hacc[0][j][4 * q + 3] = bf2f((u16)(p23 >> 16));
+              float x4[4];
+              unpack4<0>(rx[q], x4);
+              const f32x16_t& h = hacc[0][j];
+              keep_as_bf16(hacc[0][j], 4 * q, h[4 * q + 0] + x4[0], h[4 * q + 1] + x4[1], h[4 * q + 2] + x4[2], h[4 * q + 3] + x4[3]);
             }
           }
         }
       }
-      float* st = reinterpret_cast<float*>(smem + W1_BYTES);  // [pass][wn][FF_BM]: buffer 0's W2 area, first written in body 0
-      float sum = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) sum += hacc[0][j][e];
-      sum += __shfl_xor(sum, 32);
-      if (lh == 0) st[wn * FF_BM + r] = sum;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      const float mu = (st[r] + st[FF_BM + r]) / (float)CK;
-      float sq = 0.f;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const float d = hacc[0][j][e] - mu;
-          sq += d * d;
-        }
-      sq += __shfl_xor(sq, 32);
-      if (lh == 0) st[(2 + wn) * FF_BM + r] = sq;
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      __builtin_amdgcn_s_barrier();
-      asm volatile("" ::: "memory");
-      const float rs = rsqrtf((st[2 * FF_BM + r] + st[3 * FF_BM + r]) / (float)CK + ln.eps);
-      const u16* gp = ln.gamma + wn * (CK / 2) + 4 * lh;
-      const u16* bp = ln.beta + wn * (CK / 2) + 4 * lh;
-      const int key = (r >> 1) & 7;
-      char* trow = smem + Y_OFF + r * 128 + 8 * lh;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const uint2 g2 = *reinterpret_cast<const uint2*>(gp + 32 * j + 8 * q), b2 = *reinterpret_cast<const uint2*>(bp + 32 * j + 8 * q);
-          auto par = [](u16 v) { return PAR == 2 ? h2f(v) : bf2f(v); };
-          const float g[4] = {par((u16)(g2.x & 0xffffu)), par((u16)(g2.x >> 16)), par((u16)(g2.y & 0xffffu)), par((u16)(g2.y >> 16))};
-          const float bt[4] = {par((u16)(b2.x & 0xffffu)), par((u16)(b2.x >> 16)), par((u16)(b2.y & 0xffffu)), par((u16)(b2.y >> 16))};
-          float y[4];
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            y[e] = (hacc[0][j][4 * q + e] - mu) * rs * g[e] + bt[e];
-            if constexpr (PAR == 2) y[e] = sat_h(y[e]);
-          }
-          uint2 pk;
-          if constexpr (PAR == 2) {
-            pk.x = pack_h2(y[0], y[1]);
-            pk.y = pack_h2(y[2], y[3]);
-          } else {
-            pk.x = pack_bf2(y[0], y[1]);
-            pk.y = pack_bf2(y[2], y[3]);
-          }
-          const int n = wn * (CK / 2) + 32 * j + 8 * q;  // first of the four columns, before the + 4 lh
-          *reinterpret_cast<uint2*>(trow + (n >> 6) * (FF_BM * 128) + ((((n & 63) >> 3) ^ key) << 4)) = pk;
-        }
+      // statistics in buffer 0's W2 area, first written in body 0; lane_b: see above
+      acc_layernorm_to_tile<CK, PAR>(hacc, reinterpret_cast<float*>(smem + W1_BYTES), smem + Y_OFF, ln, wm, wn, lane_b);
       // b2 as one more k step on top of h: the accumulators of the second product
       const bf16x8_t one_h = k0_fragment(PAR == 2 ? 0x3c00 : 0x3f80, lh);
 #pragma unroll
@@ -412,63 +390,22 @@ __device__ __forceinline__ void ff_fused_body(const GemmParams& p, const LnArgs&
         const u16 bits = p.bias ? p.bias[wn * (CK / 2) + j * 32 + l31] : (u16)0;
         acc[0][j] = mfma_t<PAR>(one_h, k0_fragment(bits, lh), hacc[0][j]);
       }
-    } else {
-      int m = m0 + wm * 32 + l31;
-      if (m > p.M - 1) m = p.M - 1;
-      const u16* xr = proj.X + (int64_t)m * proj.ldx + wn * (CK / 2) + 4 * lh;
-      uint2 rx[NJ][4];
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) rx[j][q] = *reinterpret_cast<const uint2*>(xr + 32 * j + 8 * q);
-      const int r = wm * 32 + l31, key = (r >> 1) & 7;
-      char* trow = smem + Y_OFF + r * 128 + 8 * lh;
-#pragma unroll
-      for (int j = 0; j < NJ; ++j)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const float v0 = hacc[0][j][4 * q + 0] + bf2f((u16)(rx[j][q].x & 0xffffu));
-          const float v1 = hacc[0][j][4 * q + 1] + bf2f((u16)(rx[j][q].x >> 16));
-          const float v2 = hacc[0][j][4 * q + 2] + bf2f((u16)(rx[j][q].y & 0xffffu));
-          const float v3 = hacc[0][j][4 * q + 3] + bf2f((u16)(rx[j][q].y >> 16));
-          uint2 pk;
-          pk.x = pack_bf2(v0, v1);
-          pk.y = pack_bf2(v2, v3);
-          const int n = wn * (CK / 2) + 32 * j + 8 * q;  // first of the four columns, before the + 4 lh
-          *reinterpret_cast<uint2*>(trow + (n >> 6) * (FF_BM * 128) + ((((n & 63) >> 3) ^ key) << 4)) = pk;
-        }
     }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // W1(0) and the residual loads landed, the h tile is stored
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
+    wait_barrier<true, true>();  // W1(0) and the residual loads landed, the y tile is stored
   } else {
     // ---- prologue: y tile -> LDS (5 slabs of [128 rows][64 k]) beside the weights of step 0, then -> registers ----
     rows_issue<CK>(p.A, p.lda, p.M, m0, lds0 + Y_OFF, wave, lane);
     issue_w1(0, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  }
-  if (!(PROJ && (PAR == 2 || FF_REG_LN)) && ln.gamma) {  // norm3 folded in: the tile holds x, not LayerNorm(x) (bit-identical to the stand-alone launch, rows_layernorm)
-    if constexpr (PROJ) {
-      rows_layernorm<CK, true>(smem + Y_OFF, ln, wave, lane, p.C + (int64_t)m0 * p.ldc, p.ldc, p.M - m0);
-    } else {
+    wait_barrier<true, false>();
+    if (ln.gamma) {  // norm3 folded in: the tile holds x, not LayerNorm(x) (bit-identical to the stand-alone launch, rows_layernorm)
       rows_layernorm<CK>(smem + Y_OFF, ln, wave, lane);
+      wait_barrier<false, true>();
     }
-    // PROJ: rows_layernorm<RAW> has just stored h to Out with plain global stores, and the epilogue re-reads those rows as the
-    // residual (p.res == Out) from OTHER waves of this workgroup.  The stores are drained here (vmcnt(0) covers stores on gfx9-class
-    // parts) before the barrier, so that the dependency does not rest on a later interval's wait happening to come first.
-    if constexpr (PROJ) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
   }
   rows_fragments<CK>(smem + Y_OFF, wm, lane, xf);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();  // every wave has its y rows: buffer 1 and the H tile may be written
-  asm volatile("" ::: "memory");
+  wait_barrier<false, true>();  // every wave has its y rows: buffer 1 and the H tile may be written
 
-  if constexpr (!(PROJ && (PAR == 2 || FF_REG_LN))) acc_init<1, NJ, CK / 2>(p, acc, 0, wn, lane, false);  // b2 as the first k step of product 2
+  if constexpr (!PROJ) acc_init<1, NJ, CK / 2>(p, acc, 0, wn, lane, false);  // b2 as the first k step of product 2
   f32x16_t zero;
 #pragma unroll
   for (int r = 0; r < 16; ++r) zero[r] = 0.f;
@@ -495,7 +432,7 @@ __device__ __forceinline__ void ff_fused_body(const GemmParams& p, const LnArgs&
   // covers the LDS latency; removed.  Timing-only ablations of the same round (profiles/r06_ffabl.log, r06_ffabl2.log; M = 92 160, 348 us):
   // per step the kernel pays product 1 + product 2 + GEGLU + DMA issue + barrier IN SERIES (1690 + 835 + 780 + 500 + 335 cycles for 1984 cycles
   // of matrix pipe per SIMD); the launch without the steady loop is 121 us, of which the row-by-row LayerNorm over the LDS tile was 36 us
-  // and the epilogue 20 us -- hence FF_REG_LN above.
+  // and the epilogue 20 us -- hence the block tail's LayerNorm from the accumulators (acc_layernorm_to_tile).
   auto product1 = [&](int s, u16 bias_bits) {
     const char* wb = smem + (s & 1) * WBUF;
     f32x16_t sa = mfma_t<PAR>(one0, k0_fragment(bias_bits, lh), zero);
@@ -549,11 +486,7 @@ __device__ __forceinline__ void ff_fused_body(const GemmParams& p, const LnArgs&
     }
   };
   f32x16_t s_cur;
-  auto close_interval = [&]() {
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");  // this wave's DMA pieces have landed, its LDS reads and stores are done
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  };
+  auto close_interval = [] { wait_barrier<true, true>(); };  // this wave's DMA pieces have landed, its LDS reads and stores are done
 
   // Bias values (one bf16 per lane and step) are ordinary loads the compiler counts; the DMA statements are not.  A value
   // loaded in one body is settled at the top of the body that uses it, BEFORE that body's DMA goes out: the wait the compiler
@@ -622,9 +555,8 @@ __global__ __launch_bounds__(512) void ff_fused_kernel(GemmParams p, LnArgs ln, 
 }
 
 // The tail of a transformer block in one launch: attention output projection + residual, norm3, feed-forward + residual
-// (attention.py:88-90 and :129-149).  Round 6 (FF_REG_LN): h stays in registers from the projection to the end of the launch.
-// (-DFF_TILE_LN, rounds 3-5: p.res == p.C, the projection's result goes out once through rows_layernorm and comes back as the
-// epilogue's residual, element by element through the lane that overwrites it.)
+// (attention.py:88-90 and :129-149): h stays in registers from the projection to the end of the launch.  (Rounds 3-5 sent the projection's
+// result out once through rows_layernorm and read it back as the epilogue's residual; measured and removed, profiles/r06_ffregln.log.)
 template <int CK>
 __global__ __launch_bounds__(512) void ff_proj_fused_kernel(GemmParams p, LnArgs ln, ProjArgs proj, const u16* __restrict__ W1p,
                                                             const u16* __restrict__ b1p, const u16* __restrict__ W2p, int nsteps) {
@@ -637,10 +569,9 @@ __global__ __launch_bounds__(512) void ff_proj_fused_kernel(GemmParams p, LnArgs
 //     n1 = LayerNorm(h)        (norm1: never stored -- unless the operator trace asks for it)
 //     qkv = n1 Wqkv^T          ([M, 3 CK], three chunks of CK columns)
 // in ONE launch.  A workgroup of 8 waves owns 128 rows as in ff_fused_body.  The n rows go through the LDS row tile into fragments;
-// product 1 is the slab loop of the PROJ prologue (bias first, ascending k); its fp32 sums are rounded once to bf16 IN THE REGISTERS
-// (h as gemm(n, Wpi, bias) stores it: bit-identical) and stored; norm1 is taken from those values in the accumulators (the FF_REG_LN
-// arithmetic: two-pass mean / variance, lane pair + 2 KB of LDS between the two waves of a row), rounded to bf16 into the row tile and
-// re-read as fragments; then three more slab loops, one per chunk of Wqkv, each followed by its stores.  Same products, k order and
+// product 1 is wslab_product (bias first, ascending k); its fp32 sums are rounded once to bf16 IN THE REGISTERS (h as gemm(n, Wpi, bias)
+// stores it: bit-identical) and stored; norm1 is taken from those values in the accumulators (acc_layernorm_to_tile, as the block tail's
+// norm3), rounded to bf16 into the row tile and re-read as fragments; then three more slab loops, one per chunk of Wqkv, each followed by its stores.  Same products, k order and
 // rounding points as gemm, layernorm, gemm; only the order of norm1's fp32 row sums differs from ln_kernel<1>.
 // LDS: two 40 KB weight slabs + the 80 KB row tile, which also serves as the epilogues' staging area once the fragments are read (64
 // staging columns per wave: 68 KB), so the next chunk's first slab can land while a chunk is stored; the stores drain under that slab.
@@ -662,7 +593,7 @@ struct HeadArgs {
 
 template <int CK>
 __device__ __forceinline__ void l0_head_body(const HeadArgs& a, const LnArgs& ln) {
-  constexpr int NJ = CK / 2 / 32, KS1 = CK / 16, SLAB = CK * 128, TILE_OFF = 2 * SLAB, TILE_BYTES = FF_BM * CK * 2;
+  constexpr int NJ = CK / 2 / 32, KS1 = CK / 16, TILE_OFF = 2 * WSLAB_BYTES<CK>, TILE_BYTES = FF_BM * CK * 2;
   constexpr int EPW = 64;  // staging columns per wave: 8 waves x 32 rows x 68 floats = 68 KB inside the row tile
   static_assert(8 * 32 * (EPW + 4) * 4 <= TILE_BYTES && TILE_OFF + TILE_BYTES <= 160 * 1024, "does not fit the LDS");
   static_assert(NJ == 5, "column groups of the epilogue below: 2 + 2 + 1 blocks");
@@ -687,9 +618,7 @@ __device__ __forceinline__ void l0_head_body(const HeadArgs& a, const LnArgs& ln
   // ---- product 1: h = n Wpi^T + bpi ----
   rows_issue<CK>(a.Nrm, a.ldn, a.M, m0, lds0 + TILE_OFF, wave, lane);
   wslab_issue<CK>(a.Wpi, 0, lds0, wave, lane);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
+  wait_barrier<true, false>();
   bf16x8_t xf[KS1];
   rows_fragments<CK>(smem + TILE_OFF, wm, lane, xf);
   f32x16_t hacc[1][NJ];
@@ -697,74 +626,24 @@ __device__ __forceinline__ void l0_head_body(const HeadArgs& a, const LnArgs& ln
   acc_init<1, NJ, CK / 2, 0>(pe, hacc, 0, wn, lane, false);
   wslab_product<CK, 0>(a.Wpi, a.Wqkv, smem, lds0, xf, hacc, wave, lane, wn);  // ... and the first slab of Wqkv into buffer 1
   pe.bias = nullptr;
-  // h as the residual stream holds it: one rounding to bf16, kept as fp32 values
 #pragma unroll
   for (int j = 0; j < NJ; ++j)
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-      const uint32_t p01 = pack_bf2(hacc[0][j][4 * q + 0], hacc[0][j][4 * q + 1]);
-      const uint32_t p23 = pack_bf2(hacc[0][j][4 * q + 2], hacc[0][j][4 * q + 3]);
-      hacc[0][j][4 * q + 0] = bf2f((u16)(p01 & 0xffffu));
-      hacc[0][j][4 * q + 1] = bf2f((u16)(p01 >> 16));
-      hacc[0][j][4 * q + 2] = bf2f((u16)(p23 & 0xffffu));
-      hacc[0][j][4 * q + 3] = bf2f((u16)(p23 >> 16));
+      const f32x16_t& h = hacc[0][j];
+      keep_as_bf16(hacc[0][j], 4 * q, h[4 * q + 0], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]);
     }
   pe.C = a.H;
   pe.ldc = a.ldh;
   store_rows(hacc);
 
-  // ---- norm1 from the accumulators (the arithmetic of the block tail's norm3) ----
-  {
-    const int l31 = lane & 31, lh = lane >> 5;
-    const int r = wm * 32 + l31;
-    float* st = reinterpret_cast<float*>(smem);  // [pass][wn][FF_BM] in weight buffer 0: Wpi's last slab is read, Wqkv's second not yet issued
-    float sum = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) sum += hacc[0][j][e];
-    sum += __shfl_xor(sum, 32);
-    if (lh == 0) st[wn * FF_BM + r] = sum;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-    const float mu = (st[r] + st[FF_BM + r]) / (float)CK;
-    float sq = 0.f;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const float d = hacc[0][j][e] - mu;
-        sq += d * d;
-      }
-    sq += __shfl_xor(sq, 32);
-    if (lh == 0) st[(2 + wn) * FF_BM + r] = sq;
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // (the second barrier since the h rows were staged: every wave's staging reads are done, the tile may be written)
-    asm volatile("" ::: "memory");
-    const float rs = rsqrtf((st[2 * FF_BM + r] + st[3 * FF_BM + r]) / (float)CK + ln.eps);
-    const u16* gp = ln.gamma + wn * (CK / 2) + 4 * lh;
-    const u16* bp = ln.beta + wn * (CK / 2) + 4 * lh;
-#pragma unroll
-    for (int j = 0; j < NJ; ++j)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint2 g2 = *reinterpret_cast<const uint2*>(gp + 32 * j + 8 * q), b2 = *reinterpret_cast<const uint2*>(bp + 32 * j + 8 * q);
-        const float g[4] = {bf2f((u16)(g2.x & 0xffffu)), bf2f((u16)(g2.x >> 16)), bf2f((u16)(g2.y & 0xffffu)), bf2f((u16)(g2.y >> 16))};
-        const float bt[4] = {bf2f((u16)(b2.x & 0xffffu)), bf2f((u16)(b2.x >> 16)), bf2f((u16)(b2.y & 0xffffu)), bf2f((u16)(b2.y >> 16))};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) hacc[0][j][4 * q + e] = (hacc[0][j][4 * q + e] - mu) * rs * g[e] + bt[e];
-      }
-    acc_to_tile<CK>(hacc, smem + TILE_OFF, wm, wn, lane);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the h stores stay in flight: they drain under the first slab of product 2)
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-  }
+  // ---- norm1 from the accumulators.  Statistics in weight buffer 0: Wpi's last slab is read, Wqkv's second not yet issued.  The second
+  // barrier inside is the second since the h rows were staged: every wave's staging reads are done when the tile is written. ----
+  acc_layernorm_to_tile<CK, 0>(hacc, reinterpret_cast<float*>(smem), smem + TILE_OFF, ln, wm, wn, lane);
+  wait_barrier<false, true>();  // (the h stores stay in flight: they drain under the first slab of product 2)
   if (a.n1_out) tile_store<CK>(smem + TILE_OFF, a.n1_out + (int64_t)m0 * a.ldn1, a.ldn1, a.M - m0, tid);
   rows_fragments<CK>(smem + TILE_OFF, wm, lane, xf);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();  // every wave has its n1 rows: the tile becomes the staging area again
-  asm volatile("" ::: "memory");
+  wait_barrier<false, true>();  // every wave has its n1 rows: the tile becomes the staging area again
 
   // ---- product 2: three chunks of CK output columns; a chunk's stores drain under the next chunk's first slab ----
   pe.ldc = a.ldq;
@@ -898,12 +777,7 @@ extern "C" int dm4d_attn_out_ff_geglu_fused_bf16(void* stream, const void* A0, i
   if (Out == A0 || Out == X) return dm4d_set_error(DM4D_ERR_ARG, "attn_out_ff_geglu_fused: the output may not alias an input");
   GemmParams p{};
   p.A = (const u16*)A0; p.lda = lda0; p.C = (u16*)Out; p.ldc = ldo; p.M = M; p.N = C; p.K = hidden;
-  p.bias = (const u16*)b2; p.flags = 0; p.out_scale = 1.0f; p.splits = 1;
-  if (FF_REG_LN) {  // h starts the accumulators: the epilogue has no residual to add
-    p.res = nullptr; p.ld_res = 0;
-  } else {
-    p.res = (const u16*)Out; p.ld_res = ldo;
-  }
+  p.bias = (const u16*)b2; p.res = nullptr; p.ld_res = 0; p.flags = 0; p.out_scale = 1.0f; p.splits = 1;  // (h starts the accumulators: no residual)
   p.rows_per_rb = 1; p.tiles_n = 1;
   const LnArgs ln{(const u16*)ln_gamma, (const u16*)ln_beta, ln_eps};
   const ProjArgs proj{(const u16*)A0, lda0, (const u16*)Wo, (const u16*)bo, (const u16*)X, ldx};

@@ -1,0 +1,273 @@
+// Skeleton maps (scripts/preprocess/draw_skeleton.py): a frame's ordered list of thick lines and filled circles is painted on a canvas
+// of up to 2048 x 2048 pixels and the canvas is reduced with Pillow's Image.resize (BICUBIC) -- one launch for a batch of frames, and
+// the canvas never reaches memory: a workgroup owns one T x T tile of the OUTPUT and holds only the part of the canvas that the tile's
+// bicubic windows read (its footprint) in LDS.
+//
+//   cull        one lane per primitive: does its bounding box (grown by half the thickness, or the radius) meet the footprint?  A ballot
+//               per wave and the waves' counts give every kept primitive its place, so the list in LDS keeps the frame's order.  The list
+//               has room for all of a frame's primitives (DM4D_SKEL_MAX_PRIMS, checked on the host): nothing is ever left out.
+//   rasterise   one lane per footprint pixel: the list is walked from the back, the first primitive that covers the pixel gives its
+//               colour (= the last one painted wins), an uncovered pixel is black.  Coverage is the integer rule of dm4d.h, evaluated
+//               in int64: with coordinates in [-8192, 8191] and pixels in [0, 4096) the largest term, 4 (v x d)^2, stays below 2^61.
+//   horizontal  Pillow's pass along x over the footprint rows, rounded and clipped to uint8 (Resample.c), into LDS
+//   vertical    the pass along y over those bytes; the tile's RGB bytes are staged in LDS and stored row by row
+//
+// A tile with an empty list stores zeros and skips the passes (most of a map is black).  The result is a function of the frame's own
+// list only: no atomics, nothing depends on the order of blocks, on the batch or on the tile size.  Integer arithmetic throughout.
+#include <stdint.h>
+
+#include "common.h"
+#include "dm4d.h"
+#include "errors.h"
+
+namespace {
+
+constexpr int kPrecisionBits = 22;
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kLdsLimit = 64 * 1024;  // per workgroup: what a launch gets without asking for more; two or more tiles per CU
+constexpr int kMaxCanvas = 4096;
+constexpr int kMaxTaps = 4096;
+
+enum { P_KIND = 0, P_X1, P_Y1, P_X2, P_Y2, P_SIZE, P_COLOR };
+
+__device__ __forceinline__ uint32_t clip8(int32_t v) {
+  if (v >= (1 << kPrecisionBits << 8)) return 255u;
+  if (v <= 0) return 0u;
+  return (uint32_t)(v >> kPrecisionBits);
+}
+
+struct Prim {
+  int kind, x1, y1, x2, y2, size;
+  uint32_t color;
+};
+
+__device__ __forceinline__ Prim load_prim(const int32_t* p) {
+  const U4 a = *reinterpret_cast<const U4*>(p), b = *reinterpret_cast<const U4*>(p + 4);
+  return Prim{(int)a.x, (int)a.y, (int)a.z, (int)a.w, (int)b.x, (int)b.y, b.z};
+}
+
+// the coverage rule of dm4d.h ("Rasteriser")
+__device__ __forceinline__ bool covers(const Prim& p, int x, int y) {
+  const int64_t vx = x - p.x1, vy = y - p.y1, s = p.size;
+  const int64_t r1 = vx * vx + vy * vy;
+  if (p.kind == DM4D_SKEL_CIRCLE) return r1 <= s * s;
+  const int64_t t2 = s * s;
+  if (4 * r1 <= t2) return true;
+  const int64_t wx = x - p.x2, wy = y - p.y2;
+  if (4 * (wx * wx + wy * wy) <= t2) return true;
+  const int64_t dx = p.x2 - p.x1, dy = p.y2 - p.y1, l2 = dx * dx + dy * dy;
+  if (l2 == 0) return false;
+  const int64_t dot = vx * dx + vy * dy;
+  if (dot < 0 || dot > l2) return false;
+  const int64_t cr = vx * dy - vy * dx;
+  return 4 * cr * cr <= t2 * l2;
+}
+
+// LDS of one workgroup: the list, the footprint, the rows after the horizontal pass, the tile's bytes, the waves' counts
+__host__ __device__ inline size_t lds_bytes(int T, int cap, int fh, int fw) {
+  return (size_t)cap * DM4D_SKEL_FIELDS * 4 + (size_t)fh * fw * 4 + (size_t)fh * T * 4 + (size_t)T * T * 3 + 64;
+}
+
+template <int T>
+__global__ void __launch_bounds__(kThreads) skeleton_draw_kernel(const int32_t* __restrict__ prims, const int32_t* __restrict__ offsets,
+                                                                 const int32_t* __restrict__ htab, int hk, const int32_t* __restrict__ vtab,
+                                                                 int vk, int h, int w, int cap, int fh_max, int fw_max,
+                                                                 uint8_t* __restrict__ out) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  int32_t* s_list = reinterpret_cast<int32_t*>(smem);                      // [cap][DM4D_SKEL_FIELDS]
+  uint32_t* s_canvas = reinterpret_cast<uint32_t*>(s_list + (size_t)cap * DM4D_SKEL_FIELDS);  // [fh][fw] r | g << 8 | b << 16
+  uint32_t* s_rows = s_canvas + (size_t)fh_max * fw_max;                   // [fh][T] after the horizontal pass
+  uint8_t* s_tile = reinterpret_cast<uint8_t*>(s_rows + (size_t)fh_max * T);  // [T][3 T]
+  int* s_cnt = reinterpret_cast<int*>(s_tile + T * T * 3);                 // [kWaves]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int f = blockIdx.z;
+  const int ox0 = blockIdx.x * T, oy0 = blockIdx.y * T;
+  const int ncols = min(T, w - ox0), nrows = min(T, h - oy0);
+  const int32_t* hcoef = htab + 2 * w;
+  const int32_t* vcoef = vtab + 2 * h;
+  // window starts and ends do not decrease along an axis (checked on the host): the first and the last window bound the footprint
+  const int fx0 = htab[2 * ox0], fx1 = htab[2 * (ox0 + ncols - 1)] + htab[2 * (ox0 + ncols - 1) + 1];
+  const int fy0 = vtab[2 * oy0], fy1 = vtab[2 * (oy0 + nrows - 1)] + vtab[2 * (oy0 + nrows - 1) + 1];
+  const int fw = fx1 - fx0, fh = fy1 - fy0;
+
+  // cull, keeping the order
+  const int p0 = offsets[f], np = offsets[f + 1] - p0;
+  int n = 0;
+  for (int base = 0; base < np; base += kThreads) {
+    const int i = base + tid;
+    bool keep = false;
+    Prim p{};
+    if (i < np) {
+      p = load_prim(prims + (int64_t)(p0 + i) * DM4D_SKEL_FIELDS);
+      const int grow = p.kind == DM4D_SKEL_CIRCLE ? p.size : (p.size + 1) / 2;
+      keep = min(p.x1, p.x2) - grow < fx1 && max(p.x1, p.x2) + grow >= fx0 && min(p.y1, p.y2) - grow < fy1 && max(p.y1, p.y2) + grow >= fy0;
+    }
+    const uint64_t mask = __ballot(keep);
+    if (lane == 0) s_cnt[wave] = __popcll(mask);
+    __syncthreads();
+    int before = n, total = n;
+#pragma unroll
+    for (int k = 0; k < kWaves; ++k) {
+      const int c = s_cnt[k];
+      if (k < wave) before += c;
+      total += c;
+    }
+    if (keep) {
+      int32_t* dst = s_list + (size_t)(before + __popcll(mask & ((1ull << lane) - 1))) * DM4D_SKEL_FIELDS;
+      *reinterpret_cast<U4*>(dst) = U4{(uint32_t)p.kind, (uint32_t)p.x1, (uint32_t)p.y1, (uint32_t)p.x2};
+      *reinterpret_cast<U4*>(dst + 4) = U4{(uint32_t)p.y2, (uint32_t)p.size, p.color, 0u};
+    }
+    n = total;
+    __syncthreads();
+  }
+
+  uint8_t* tile_out = out + (((int64_t)f * h + oy0) * w + ox0) * 3;
+  const int row_bytes = ncols * 3;
+  if (n == 0) {  // the same for every thread
+    for (int i = tid; i < nrows * row_bytes; i += kThreads) tile_out[(int64_t)(i / row_bytes) * w * 3 + i % row_bytes] = 0;
+    return;
+  }
+
+  // rasterise the footprint
+  const int npx = fh * fw;
+  for (int base = 0; base < npx; base += kThreads) {
+    const int i = base + tid;
+    const int y = fy0 + i / fw, x = fx0 + i % fw;
+    bool open = i < npx;
+    uint32_t color = 0;
+    for (int k = n - 1; k >= 0; --k) {  // all lanes of a wave read the same record
+      const Prim p = load_prim(s_list + (size_t)k * DM4D_SKEL_FIELDS);
+      if (open && covers(p, x, y)) {
+        color = p.color;
+        open = false;
+      }
+      if (__ballot(open) == 0) break;
+    }
+    if (i < npx) s_canvas[i] = color;
+  }
+  __syncthreads();
+
+  // horizontal pass: rows of the footprint x columns of the tile
+  for (int i = tid; i < fh * T; i += kThreads) {
+    const int r = i / T, j = i % T;
+    if (j >= ncols) continue;
+    const int ox = ox0 + j;
+    const int xmin = htab[2 * ox] - fx0, cnt = htab[2 * ox + 1];
+    const int32_t* k = hcoef + (int64_t)ox * hk;
+    const uint32_t* src = s_canvas + r * fw + xmin;
+    int32_t a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
+    for (int t = 0; t < cnt; ++t) {
+      const uint32_t c = src[t];
+      const int32_t wt = k[t];
+      a0 += (int32_t)(c & 0xffu) * wt;
+      a1 += (int32_t)((c >> 8) & 0xffu) * wt;
+      a2 += (int32_t)((c >> 16) & 0xffu) * wt;
+    }
+    s_rows[r * T + j] = clip8(a0) | (clip8(a1) << 8) | (clip8(a2) << 16);
+  }
+  __syncthreads();
+
+  // vertical pass
+  for (int i = tid; i < T * T; i += kThreads) {
+    const int r = i / T, j = i % T;
+    if (r >= nrows || j >= ncols) continue;
+    const int oy = oy0 + r;
+    const int ymin = vtab[2 * oy] - fy0, cnt = vtab[2 * oy + 1];
+    const int32_t* k = vcoef + (int64_t)oy * vk;
+    int32_t a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
+    for (int t = 0; t < cnt; ++t) {
+      const uint32_t c = s_rows[(ymin + t) * T + j];
+      const int32_t wt = k[t];
+      a0 += (int32_t)(c & 0xffu) * wt;
+      a1 += (int32_t)((c >> 8) & 0xffu) * wt;
+      a2 += (int32_t)((c >> 16) & 0xffu) * wt;
+    }
+    uint8_t* dst = s_tile + (r * T + j) * 3;
+    dst[0] = (uint8_t)clip8(a0);
+    dst[1] = (uint8_t)clip8(a1);
+    dst[2] = (uint8_t)clip8(a2);
+  }
+  __syncthreads();
+  for (int i = tid; i < nrows * row_bytes; i += kThreads) {
+    const int r = i / row_bytes, c = i % row_bytes;
+    tile_out[(int64_t)r * w * 3 + c] = s_tile[r * T * 3 + c];
+  }
+}
+
+// host-side check of one coefficient table (n windows {start, length} then n x ksize weights): windows inside [0, in_size), at most
+// ksize long, starts and ends non-decreasing
+bool table_ok(const int32_t* tab, int n, int ksize, int in_size) {
+  int64_t prev_start = 0, prev_end = 0;
+  for (int i = 0; i < n; ++i) {
+    const int64_t start = tab[2 * i], cnt = tab[2 * i + 1];
+    if (start < 0 || cnt < 1 || cnt > ksize || start + cnt > in_size || start < prev_start || start + cnt < prev_end) return false;
+    prev_start = start;
+    prev_end = start + cnt;
+  }
+  return true;
+}
+
+// the largest footprint extent along one axis over tiles of T outputs
+int max_extent(const int32_t* tab, int n, int T) {
+  int best = 0;
+  for (int o0 = 0; o0 < n; o0 += T) {
+    const int last = (o0 + T < n ? o0 + T : n) - 1;
+    const int ext = tab[2 * last] + tab[2 * last + 1] - tab[2 * o0];
+    if (ext > best) best = ext;
+  }
+  return best;
+}
+
+template <int T>
+int launch(hipStream_t stream, const int32_t* prims, const int32_t* offsets, int n_frames, const int32_t* htab, int hk, const int32_t* vtab,
+           int vk, int h, int w, int cap, int fh, int fw, uint8_t* out) {
+  const dim3 grid((unsigned)((w + T - 1) / T), (unsigned)((h + T - 1) / T), (unsigned)n_frames);
+  hipLaunchKernelGGL(skeleton_draw_kernel<T>, grid, dim3(kThreads), lds_bytes(T, cap, fh, fw), stream, prims, offsets, htab, hk, vtab, vk, h,
+                     w, cap, fh, fw, out);
+  return dm4d_check_launch("skeleton_draw_kernel");
+}
+
+}  // namespace
+
+extern "C" int dm4d_skeleton_draw_u8(void* stream, const int32_t* prims_host, const int32_t* prims_dev, const int32_t* offsets_host,
+                                     const int32_t* offsets_dev, int n_frames, const int32_t* htab_host, const int32_t* htab_dev, int hk,
+                                     const int32_t* vtab_host, const int32_t* vtab_dev, int vk, int H, int W, int h, int w, uint8_t* out) {
+  if (!prims_host || !prims_dev || !offsets_host || !offsets_dev || !htab_host || !htab_dev || !vtab_host || !vtab_dev || !out)
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: null pointer");
+  if (n_frames <= 0 || n_frames > 65535 || H <= 0 || W <= 0 || H > kMaxCanvas || W > kMaxCanvas || h <= 0 || w <= 0 || h > (1 << 15) ||
+      w > (1 << 15) || hk < 1 || vk < 1 || hk > kMaxTaps || vk > kMaxTaps)
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: empty or oversized shape");
+  if (((uintptr_t)prims_dev & 15) || ((uintptr_t)offsets_dev & 3) || ((uintptr_t)htab_dev & 3) || ((uintptr_t)vtab_dev & 3))
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: the records must be 16-byte aligned, offsets and tables 4-byte aligned");
+  if (offsets_host[0] != 0) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: offsets[0] must be 0");
+  int cap = 1;
+  for (int f = 0; f < n_frames; ++f) {
+    const int64_t np = (int64_t)offsets_host[f + 1] - offsets_host[f];
+    if (np < 0 || np > DM4D_SKEL_MAX_PRIMS || offsets_host[f + 1] > (1 << 28))
+      return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a frame's primitive count is negative or above DM4D_SKEL_MAX_PRIMS");
+    if (np > cap) cap = (int)np;
+  }
+  for (int64_t i = 0; i < offsets_host[n_frames]; ++i) {
+    const int32_t* p = prims_host + i * DM4D_SKEL_FIELDS;
+    if (p[P_KIND] != DM4D_SKEL_LINE && p[P_KIND] != DM4D_SKEL_CIRCLE) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: unknown primitive kind");
+    for (int c = P_X1; c <= P_Y2; ++c)
+      if (p[c] < DM4D_SKEL_COORD_MIN || p[c] > DM4D_SKEL_COORD_MAX)
+        return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a coordinate lies outside [DM4D_SKEL_COORD_MIN, DM4D_SKEL_COORD_MAX]");
+    if (p[P_SIZE] < (p[P_KIND] == DM4D_SKEL_LINE ? 1 : 0) || p[P_SIZE] > DM4D_SKEL_MAX_SIZE)
+      return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a thickness below 1, a negative radius, or a size above DM4D_SKEL_MAX_SIZE");
+    if ((uint32_t)p[P_COLOR] >> 24) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a colour has bits above r | g << 8 | b << 16");
+  }
+  if (!table_ok(htab_host, w, hk, W) || !table_ok(vtab_host, h, vk, H))
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a coefficient table's windows leave the canvas, exceed ksize or are not ordered");
+  const hipStream_t s = (hipStream_t)stream;
+  for (int T : {32, 16, 8}) {
+    const int fw = max_extent(htab_host, w, T), fh = max_extent(vtab_host, h, T);
+    if (lds_bytes(T, cap, fh, fw) > (size_t)kLdsLimit || (w + T - 1) / T > 65535 || (h + T - 1) / T > 65535) continue;
+    if (T == 32) return launch<32>(s, prims_dev, offsets_dev, n_frames, htab_dev, hk, vtab_dev, vk, h, w, cap, fh, fw, out);
+    if (T == 16) return launch<16>(s, prims_dev, offsets_dev, n_frames, htab_dev, hk, vtab_dev, vk, h, w, cap, fh, fw, out);
+    return launch<8>(s, prims_dev, offsets_dev, n_frames, htab_dev, hk, vtab_dev, vk, h, w, cap, fh, fw, out);
+  }
+  return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: the canvas is too large for the output: an 8 x 8 tile's footprint does not fit in LDS");
+}

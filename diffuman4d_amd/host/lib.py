@@ -117,6 +117,8 @@ SIGNATURES = {
     # skeleton triangulation: one wave per (frame, keypoint), and the projection of the points into cameras (host/triang.py)
     "dm4d_triangulate_points_f64": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "dm4d_project_points_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    # skeleton maps: a batch of frames' draw calls rasterised per output tile in LDS + Pillow's bicubic resize (host/skeleton.py)
+    "dm4d_skeleton_draw_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
 }
 
 EPI_GEGLU = 1

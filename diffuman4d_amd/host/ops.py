@@ -1265,3 +1265,36 @@ def project_points(kp3d: torch.Tensor, K: torch.Tensor, T: torch.Tensor) -> Tupl
     depth = torch.empty((F, m, k), dtype=torch.float64, device=kp3d.device)
     _l.check(lib.dm4d_project_points_f64(_stream(), _p(kp3d), _p(K), _p(T), F, m, k, _p(kp2d), _p(depth)), "dm4d_project_points_f64")
     return kp2d, depth
+
+
+# include/dm4d.h DM4D_SKEL_*
+SKEL_FIELDS, SKEL_LINE, SKEL_CIRCLE, SKEL_MAX_PRIMS = 8, 0, 1, 512
+SKEL_COORD_MIN, SKEL_COORD_MAX = -8192, 8191
+
+
+def skeleton_draw(prims_host: torch.Tensor, prims: torch.Tensor, offsets_host: torch.Tensor, offsets: torch.Tensor, htab_host: torch.Tensor,
+                  htab: torch.Tensor, hk: int, vtab_host: torch.Tensor, vtab: torch.Tensor, vk: int, H: int, W: int, h: int,
+                  w: int) -> torch.Tensor:
+    """Skeleton maps of a batch of frames -> uint8 [B, h, w, 3] on prims' device, one launch on the current stream (host/skeleton.py).
+    prims int32 [n, SKEL_FIELDS] draw records, offsets int32 [B + 1] the frames' ranges in it, htab / vtab int32 bicubic tables of
+    the canvas (H, W) -> (h, w) with hk / vk taps per window; every *_host tensor is the host copy of its device twin, on which the
+    library checks counts, records and windows before it launches."""
+    lib = _l.load()
+    for name, dev, host in (("prims", prims, prims_host), ("offsets", offsets, offsets_host), ("htab", htab, htab_host), ("vtab", vtab, vtab_host)):
+        _req(dev, name, torch.int32)
+        if not isinstance(host, torch.Tensor) or host.device.type != "cpu" or host.dtype != torch.int32 or host.shape != dev.shape:
+            raise _l.Dm4dError(f"{name}_host: expected the host copy of {name}")
+        if not dev.is_contiguous() or not host.is_contiguous():
+            raise _l.Dm4dError(f"{name}: expected contiguous tensors")
+    if prims.dim() != 2 or prims.shape[1] != SKEL_FIELDS or prims.shape[0] < 1:
+        raise _l.Dm4dError(f"prims: expected [n >= 1, {SKEL_FIELDS}], got {tuple(prims.shape)}")
+    B = offsets.numel() - 1
+    if offsets.dim() != 1 or B < 1 or int(offsets_host[-1]) > prims.shape[0]:
+        raise _l.Dm4dError("offsets: expected [B + 1] with the last entry inside prims")
+    if htab.numel() != w * (2 + hk) or vtab.numel() != h * (2 + vk):
+        raise _l.Dm4dError(f"htab / vtab: expected {w} x (2 + {hk}) and {h} x (2 + {vk}) entries, got {htab.numel()} and {vtab.numel()}")
+    out = torch.empty((B, h, w, 3), dtype=torch.uint8, device=prims.device)
+    rc = lib.dm4d_skeleton_draw_u8(_stream(), prims_host.data_ptr(), _p(prims), offsets_host.data_ptr(), _p(offsets), B, htab_host.data_ptr(),
+                                   _p(htab), int(hk), vtab_host.data_ptr(), _p(vtab), int(vk), int(H), int(W), int(h), int(w), _p(out))
+    _l.check(rc, "dm4d_skeleton_draw_u8")
+    return out

@@ -1,0 +1,375 @@
+"""Skeleton maps: ``skeletons/{cam}/{frame}.webp`` from ``poses_2d/{cam}/{frame}.json``, the image the denoiser's pose encoder is
+conditioned on (host/capture.py reads it back).
+
+The reference's ``scripts/preprocess/draw_skeleton.py`` (the ``draw_skeleton`` action of ``preprocess.sh``) with the same function
+names, arguments and defaults, built from its behaviour.  The reference paints one frame at a time with OpenCV on a 2048-pixel
+canvas and reduces it with Pillow; here
+
+  * ``plan_draw_calls`` (numpy, no device, no library) turns one frame's keypoints into the ordered list of primitives the reference
+    hands to ``cv2.line`` / ``cv2.circle`` -- scores, scaling, rounding, colours, radii, the link filter and the paint order are the
+    reference's, pinned call for call by tests/golden/skel_reference.json;
+  * one launch (``dm4d_skeleton_draw_u8``) rasterises a batch of frames and applies Pillow's bicubic ``Image.resize`` byte for byte;
+    the 2048-pixel canvas exists only tile by tile in LDS;
+  * the host reads the JSON files and encodes the images (Pillow's ``Image.save(path, quality=...)``) in a thread pool.
+
+The rasteriser is NOT OpenCV's: a primitive covers the pixels given by the exact integer rule in DESIGN.md ("Skeleton maps"), which
+differs from OpenCV's edge walker in pixels on a primitive's rim only.  The colour and link tables are not part of this package: the
+caller names a palette file (``load_palette``).  There is no CPU path: a ``device`` that is not a HIP device is an error.
+"""
+from __future__ import annotations
+
+import json
+import logging
+import os
+import time
+from concurrent.futures import ThreadPoolExecutor
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import lib as _l
+from . import ops
+from .capture import bicubic_table
+from .triang import _hip_device
+
+log = logging.getLogger(__name__)
+
+DRAWING_SIZE = 2048        # the longer side of the canvas the reference paints on ("draw skeleton map at 2048p for anti-aliasing")
+X_LINKS = ((65, (5, 12)), (66, (6, 11)))  # "add x links for the body": left shoulder - right hip, right shoulder - left hip
+MAJOR_LINKS = 25           # link ids below this are painted at twice the radius and thickness
+COORD_MIN, COORD_MAX = ops.SKEL_COORD_MIN, ops.SKEL_COORD_MAX
+MIN_OUT, MAX_OUT = 256, 8192   # supported max(out_kpmap_shape): below, a tile's canvas footprint no longer fits in LDS
+MAX_HOST_THREADS = 16
+LAUNCH_BYTES = 1 << 28     # the frame axis is cut so that one launch's maps stay below this
+
+PALETTE_HELP = ("a palette is a JSON file {\"keypoint_colors\": [[r, g, b] | null, ...], \"links\": [{\"id\": 0, \"link\": [i1, i2], "
+                "\"color\": [r, g, b]}, ...], \"x_link_color\": [r, g, b]}: for the reference's drawing, write COCO_WHOLEBODY_KPTS_COLORS, "
+                "COCO_WHOLEBODY_SKELETON_INFO and BLUE of its sapiens/lite/demo/classes_and_palettes.py into one "
+                "(tests/golden/make_golden_skel.py does)")
+
+
+class Palette(NamedTuple):
+    keypoint_colors: List[Optional[List[int]]]
+    links: List[Dict]          # {"id", "link": (i1, i2), "color"} in the file's order
+    x_link_color: List[int]
+
+
+class DrawPlan(NamedTuple):
+    calls: List[Dict]                 # {"type": "line", "p1", "p2", "color", "thickness"} | {"type": "circle", "center", "radius", "color"}
+    canvas_shape: Tuple[int, int]     # (H, W) of the canvas the calls refer to
+    out_size: Tuple[int, int]         # (w, h) of the reduced map, Pillow's order
+    dropped_links: int                # links with an endpoint outside [COORD_MIN, COORD_MAX], not drawn
+
+
+# -- palette ------------------------------------------------------------------------------------------------------------------------
+def _rgb(c, what: str) -> List[int]:
+    if not isinstance(c, (list, tuple)) or len(c) != 3 or not all(isinstance(v, int) and 0 <= v <= 255 for v in c):
+        raise ValueError(f"palette: {what} must be [r, g, b] with integers in 0 .. 255, got {c!r}")
+    return [int(v) for v in c]
+
+
+def make_palette(data: Dict) -> Palette:
+    """The parsed content of a palette file -> Palette, validated."""
+    try:
+        colors, links, x_color = data["keypoint_colors"], data["links"], data["x_link_color"]
+    except (KeyError, TypeError):
+        raise ValueError(f"palette: expected the keys keypoint_colors, links and x_link_color; {PALETTE_HELP}") from None
+    n = len(colors)
+    colors = [None if c is None else _rgb(c, f"keypoint_colors[{i}]") for i, c in enumerate(colors)]
+    out, seen = [], set()
+    for k, l in enumerate(links):
+        i1, i2 = (int(v) for v in l["link"])
+        lid = int(l["id"])
+        if lid in seen or lid < 0:
+            raise ValueError(f"palette: links[{k}] has the id {lid}, which is negative or used twice")
+        seen.add(lid)
+        if not (0 <= i1 < n and 0 <= i2 < n):
+            raise ValueError(f"palette: links[{k}] joins keypoints {i1} and {i2}, but there are {n} keypoint colours")
+        out.append({"id": lid, "link": (i1, i2), "color": _rgb(l["color"], f"links[{k}].color")})
+    return Palette(colors, out, _rgb(x_color, "x_link_color"))
+
+
+def load_palette(path) -> Palette:
+    """Read a palette file.  The package ships no table of its own: without a file there is nothing to draw with."""
+    if path is None:
+        raise ValueError(f"no palette given: {PALETTE_HELP}")
+    if isinstance(path, Palette):
+        return path
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"palette {path!r} not found: {PALETTE_HELP}")
+    with open(path, "r") as f:
+        return make_palette(json.load(f))
+
+
+# -- the plan -----------------------------------------------------------------------------------------------------------------------
+def score_to_color(rgb, score, low=0.5, high=0.9) -> List[int]:
+    """A colour dimmed by its score: black at `low`, full at `high`, in float32, rounded half to even (draw_skeleton.py:18-23)."""
+    score = np.clip(score, low, high)
+    norm_score = (score - low) / (high - low)
+    rgb = np.array(rgb, dtype=np.float32) * norm_score
+    return np.round(rgb, decimals=0).astype(np.uint8).tolist()
+
+
+def plan_draw_calls(instance: Dict, score_instance: Optional[Dict], shapes, palette: Palette, low_thr=0.5, high_thr=0.9, radius=2,
+                    thickness=2, draw_face_keypoints: bool = False) -> DrawPlan:
+    """One frame's ``instance_info[0]`` -> the primitives the reference paints, in its order (draw_one_skeleton, draw_skeleton.py:49-161).
+
+    `shapes` = (kp2d_canvas_shape, out_kpmap_shape), both (h, w).  `score_instance`: the ``instance_info[0]`` of a score-override
+    file, or None.  Every array operation below has the operand types of the reference's, so that NumPy promotes and rounds as it
+    does there: float32 keypoints times a float64 ratio, float32 colour arithmetic, ``int(round(.))`` half to even.  Colours are RGB
+    (the reference reverses them for OpenCV and reverses the canvas back).  A link with an endpoint outside [-8192, 8191] is left out
+    with its two circles and counted in `dropped_links`: the device's coverage test is exact in 64-bit integers inside that range."""
+    if draw_face_keypoints:
+        raise NotImplementedError("draw_face_keypoints: the reference's own branch passes an array as a radius and fails; not built")
+    kp2d_canvas_shape, out_kpmap_shape = shapes
+    kpts = np.array(instance["keypoints"], dtype=np.float32)
+    if score_instance is not None:
+        scores = np.array(score_instance["keypoint_scores"], dtype=np.float32)
+    elif "keypoint_scores" in instance:
+        scores = np.array(instance["keypoint_scores"], dtype=np.float32)
+    else:
+        scores = np.ones(kpts.shape[0], dtype=np.float32)
+    if "keypoint_depths" in instance:
+        depths = np.array(instance["keypoint_depths"], dtype=np.float32)
+    else:
+        depths = np.zeros_like(scores)
+    scores[kpts.min(axis=1) < 0] = 0.0  # invalid keypoints
+
+    drawing_scale = DRAWING_SIZE / max(out_kpmap_shape)
+    canvas_shape = (np.array(out_kpmap_shape) * drawing_scale).astype(np.int32)
+    kp_shape = np.array(kp2d_canvas_shape)
+    scale_ratio = canvas_shape.min() / kp_shape.min()
+    kpts = kpts * scale_ratio
+    kp_shape = kp_shape * scale_ratio
+    kpts += (canvas_shape.min() - kp_shape.min()) / 2
+
+    if len(palette.keypoint_colors) != len(kpts):
+        raise ValueError(f"the length of kpt_color ({len(palette.keypoint_colors)}) does not matches that of keypoints ({len(kpts)})")
+    links = list(palette.links) + [{"id": lid, "link": link, "color": palette.x_link_color} for lid, link in X_LINKS
+                                   if all(l["id"] != lid for l in palette.links)]
+    if max(max(l["link"]) for l in links) >= len(kpts):
+        raise ValueError(f"a link joins keypoint {max(max(l['link']) for l in links)}, but the frame has {len(kpts)} keypoints")
+
+    # per-link radius and thickness, indexed by link id as in the reference
+    radius = int(round(radius * scale_ratio))
+    thickness = int(round(thickness * scale_ratio))
+    if thickness < 1:
+        raise ValueError(f"thickness rounds to {thickness} on the canvas (scale {float(scale_ratio):.4g}): a line needs at least 1")
+    if max(l["id"] for l in links) >= len(links):
+        raise ValueError(f"link ids must be below the number of links ({len(links)}): the per-link arrays are indexed by id")
+    radii = np.ones(len(links)) * radius
+    thicknesses = np.ones(len(links)) * thickness
+    radii[:MAJOR_LINKS] *= 2
+    thicknesses[:MAJOR_LINKS] *= 2
+    radii, thicknesses = radii.astype(np.int32), thicknesses.astype(np.int32)
+
+    # the links at once: the same float32 / float64 operations element by element as the reference's loop over links
+    i1, i2 = (np.array([l["link"][k] for l in links]) for k in (0, 1))
+    p1_score, p2_score = scores[i1], scores[i2]
+    line_score = np.minimum(p1_score, p2_score)
+    keep = ~(line_score < low_thr)
+    ends = np.concatenate([kpts[i1], kpts[i2]], axis=1)  # [links, 4]: x1, y1, x2, y2
+    if not np.isfinite(ends[keep]).all():
+        raise ValueError("a keypoint of a drawn link is not finite")
+    ends = np.rint(ends)  # int(round(.)): half to even
+    inside = ((ends >= COORD_MIN) & (ends <= COORD_MAX)).all(axis=1)
+    dropped = int((keep & ~inside).sum())
+    keep &= inside
+    ends = np.where(keep[:, None], ends, 0).astype(np.int64)
+    for l, k in zip(links, keep):
+        if k and (palette.keypoint_colors[l["link"][0]] is None or palette.keypoint_colors[l["link"][1]] is None):
+            raise ValueError(f"palette: link {l['id']} joins keypoints {l['link'][0]} and {l['link'][1]}, one of which has no colour")
+    kp_rgb = np.array([[0, 0, 0] if c is None else c for c in palette.keypoint_colors], dtype=np.float32)
+    link_rgb = np.array([l["color"] for l in links], dtype=np.float32)
+
+    def dimmed(rgb, score):  # score_to_color over rows
+        norm_score = (np.clip(score, low_thr, high_thr) - low_thr) / (high_thr - low_thr)
+        return np.round(rgb * norm_score[:, None], decimals=0).astype(np.uint8).tolist()
+
+    p1_color, p2_color, line_color = dimmed(kp_rgb[i1], p1_score), dimmed(kp_rgb[i2], p2_score), dimmed(link_rgb, line_score)
+    depth = ((depths[i1].astype(np.float64) + depths[i2].astype(np.float64)) / 2).tolist()
+    order = [k for k in range(len(links)) if keep[k]]
+    if (depths != 0.0).any():
+        order = sorted(order, key=lambda k: depth[k], reverse=True)  # far links first; sorted() is stable, also when reversed
+    elif (scores != 1.0).any():
+        score_key = line_score.tolist()
+        order = sorted(order, key=lambda k: score_key[k])
+    ends = ends.tolist()
+    calls = []
+    for k in order:
+        lid = links[k]["id"]
+        calls.append({"type": "line", "p1": ends[k][:2], "p2": ends[k][2:], "color": line_color[k], "thickness": int(thicknesses[lid])})
+        calls.append({"type": "circle", "center": ends[k][:2], "radius": int(radii[lid]), "color": p1_color[k]})
+        calls.append({"type": "circle", "center": ends[k][2:], "radius": int(radii[lid]), "color": p2_color[k]})
+    H, W = int(canvas_shape[0]), int(canvas_shape[1])
+    return DrawPlan(calls, (H, W), (int(W / drawing_scale), int(H / drawing_scale)), dropped)
+
+
+def pack_calls(calls: Sequence[Dict]) -> np.ndarray:
+    """Draw calls -> int32 [n, SKEL_FIELDS] records of include/dm4d.h: {kind, x1, y1, x2, y2, size, r | g << 8 | b << 16, 0}."""
+    rows = []
+    for c in calls:
+        r, g, b = c["color"]
+        if c["type"] == "line":
+            rows.append((ops.SKEL_LINE, *c["p1"], *c["p2"], c["thickness"], r | (g << 8) | (b << 16), 0))
+        else:
+            rows.append((ops.SKEL_CIRCLE, *c["center"], *c["center"], c["radius"], r | (g << 8) | (b << 16), 0))
+    return np.array(rows, dtype=np.int32).reshape(len(rows), ops.SKEL_FIELDS)
+
+
+# -- the launch ---------------------------------------------------------------------------------------------------------------------
+def _check_out_shape(out_kpmap_shape) -> None:
+    if len(out_kpmap_shape) != 2 or not MIN_OUT <= max(out_kpmap_shape) <= MAX_OUT or min(out_kpmap_shape) < 1:
+        raise ValueError(f"out_kpmap_shape {tuple(out_kpmap_shape)}: max(out_kpmap_shape) must lie in {MIN_OUT} .. {MAX_OUT} (the canvas is "
+                         f"{DRAWING_SIZE} pixels on its longer side, and below {MIN_OUT} an output tile's part of it does not fit in LDS)")
+
+
+def draw_plans(plans: Sequence[DrawPlan], device="cuda") -> np.ndarray:
+    """Plans of one canvas shape and output size -> uint8 [B, h, w, 3], one launch (cut along B where the maps pass 256 MiB)."""
+    if not plans:
+        raise ValueError("draw_plans: no frames")
+    (H, W), (w, h) = plans[0].canvas_shape, plans[0].out_size
+    if any(p.canvas_shape != (H, W) or p.out_size != (w, h) for p in plans):
+        raise ValueError("draw_plans: the frames of one batch must share the canvas shape and the output size")
+    dev = _hip_device(device, "draw_skeleton_maps")
+    hb, hk = bicubic_table(W, w)
+    vb, vk = bicubic_table(H, h)
+    htab = np.concatenate([hb.reshape(-1), hk.reshape(-1)]).astype(np.int32)
+    vtab = np.concatenate([vb.reshape(-1), vk.reshape(-1)]).astype(np.int32)
+    step = max(1, LAUNCH_BYTES // (h * w * 3))
+    out = []
+    with torch.cuda.device(dev):
+        htab_h, vtab_h = torch.from_numpy(htab), torch.from_numpy(vtab)
+        htab_d, vtab_d = htab_h.to(dev), vtab_h.to(dev)
+        for b0 in range(0, len(plans), step):
+            chunk = plans[b0:b0 + step]
+            recs = [pack_calls(p.calls) for p in chunk]
+            offsets = torch.from_numpy(np.concatenate([[0], np.cumsum([len(r) for r in recs])]).astype(np.int32))
+            prims = torch.from_numpy(np.concatenate(recs + [np.zeros((1, ops.SKEL_FIELDS), dtype=np.int32)]))  # never empty
+            maps = ops.skeleton_draw(prims, prims.to(dev), offsets, offsets.to(dev), htab_h, htab_d, hk.shape[1], vtab_h, vtab_d,
+                                     vk.shape[1], H, W, h, w)
+            out.append(maps.cpu().numpy())
+    return out[0] if len(out) == 1 else np.concatenate(out)
+
+
+def _read_instance(path) -> Optional[Dict]:
+    if path is None:
+        return None
+    with open(path, "r") as f:
+        return json.load(f)["instance_info"][0]  # "currently, we only support one instance per image"
+
+
+def draw_skeleton_maps(kp2d_paths: Sequence[str], kp2d_score_paths: Optional[Sequence[Optional[str]]] = None,
+                       kp2d_canvas_shape=(1024, 1024), out_kpmap_shape=(1024, 1024), low_thr=0.5, high_thr=0.9, radius=2, thickness=2,
+                       draw_face_keypoints: bool = False, palette=None, num_workers: int = 16, device="cuda", stats: Optional[Dict] = None,
+                       pool: Optional[ThreadPoolExecutor] = None) -> np.ndarray:
+    """The maps of many keypoint files -> uint8 [B, h, w, 3] (RGB), drawn in one launch; the files are read in a pool of `num_workers`
+    threads (at most 16).  `stats`, when given, receives dropped_links and the seconds spent reading, planning and on the device."""
+    palette = load_palette(palette)
+    _check_out_shape(out_kpmap_shape)
+    if kp2d_score_paths is None:
+        kp2d_score_paths = [None] * len(kp2d_paths)
+    own = pool is None
+    if own:
+        pool = ThreadPoolExecutor(max_workers=max(1, min(int(num_workers), MAX_HOST_THREADS)), thread_name_prefix="dm4d-skel")
+    try:
+        t0 = time.perf_counter()
+        instances = list(pool.map(_read_instance, kp2d_paths))
+        score_instances = list(pool.map(_read_instance, kp2d_score_paths))
+    finally:
+        if own:
+            pool.shutdown()
+    t1 = time.perf_counter()
+    plans = [plan_draw_calls(inst, sc, (kp2d_canvas_shape, out_kpmap_shape), palette, low_thr, high_thr, radius, thickness, draw_face_keypoints)
+             for inst, sc in zip(instances, score_instances)]
+    t2 = time.perf_counter()
+    maps = draw_plans(plans, device=device)
+    t3 = time.perf_counter()
+    if stats is not None:
+        stats["dropped_links"] = stats.get("dropped_links", 0) + sum(p.dropped_links for p in plans)
+        for key, dt in (("read", t1 - t0), ("plan", t2 - t1), ("launch", t3 - t2)):
+            stats[key] = stats.get(key, 0.0) + dt
+    return maps
+
+
+# -- a scene --------------------------------------------------------------------------------------------------------------------------
+def _valid_image(path: str) -> bool:
+    from PIL import Image
+    try:
+        Image.open(path).verify()
+        return True
+    except Exception as e:  # noqa: BLE001 -- whatever Pillow raises on a broken file: the reference redraws it
+        print(f"Error reading {path}: {e}")
+        return False
+
+
+def _save(path: str, arr: np.ndarray, quality: int) -> None:
+    from PIL import Image
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    Image.fromarray(arr).save(path, quality=quality)
+
+
+def draw_skeleton(kp2d_dir: str, out_kpmap_dir: str, kp2d_score_dir: Optional[str] = None, kp2d_canvas_shape=(1024, 1024),
+                  out_kpmap_shape=(1024, 1024), spa_labels=None, tem_labels=None, image_ext: str = ".webp", image_quality: int = 85,
+                  num_workers: int = 16, skip_exists: bool = False, palette=None, device="cuda") -> Dict:
+    """Draw every selected frame of a scene (draw_skeleton.py:182-226): reads ``kp2d_dir/{spa:02d}/{tem:06d}.json`` (and the scores of
+    the same path under `kp2d_score_dir`) and writes ``out_kpmap_dir/{spa:02d}/{tem:06d}{image_ext}``.  Labels are lists of integers or
+    default to the sorted listings of `kp2d_dir` and of its first camera, and the output path is the input path with `kp2d_dir`
+    replaced by `out_kpmap_dir` and ".json" by `image_ext`, all as in the reference.  With `skip_exists` a file that Pillow's
+    ``Image.open(path).verify()`` accepts is left untouched and a corrupt one is drawn again.
+
+    Frames are read by a pool of `num_workers` threads (at most 16), drawn (one launch per 256 MiB of maps) and encoded with
+    ``Image.save(path, quality=image_quality)`` by a second pool of as many; a batch is encoded while the next one is read and drawn.  host/imgwrite.py's package
+    writer is not used: it skips a path that exists, and a corrupt file has to be replaced here.  Returns counts: frames, skipped,
+    files, dropped_links (links left out because an endpoint lies outside [-8192, 8191] on the canvas; logged once), and seconds
+    per phase (read, plan, launch, and write = the time the run waited for the encoder)."""
+    palette = load_palette(palette)
+    _check_out_shape(out_kpmap_shape)
+    dev = _hip_device(device, "draw_skeleton")
+    if spa_labels is None:
+        spa_labels = sorted(os.listdir(kp2d_dir))
+    else:
+        spa_labels = [f"{spa_label:02d}" for spa_label in spa_labels]
+    if tem_labels is None:
+        tem_labels = [tem_label.split(".")[0] for tem_label in sorted(os.listdir(f"{kp2d_dir}/{spa_labels[0]}"))]
+    else:
+        tem_labels = [f"{tem_label:06d}" for tem_label in tem_labels]
+    kp2d_paths = [f"{kp2d_dir}/{spa_label}/{tem_label}.json" for spa_label in spa_labels for tem_label in tem_labels]
+    out_paths = [p.replace(kp2d_dir, out_kpmap_dir).replace(".json", image_ext) for p in kp2d_paths]
+    score_paths = [p.replace(kp2d_dir, kp2d_score_dir) for p in kp2d_paths] if kp2d_score_dir is not None else [None] * len(kp2d_paths)
+
+    todo = [i for i, p in enumerate(out_paths) if not (skip_exists and os.path.exists(p) and _valid_image(p))]
+    counts = {"frames": len(todo), "skipped": len(out_paths) - len(todo), "files": 0, "dropped_links": 0}
+    if not todo:
+        return counts
+    drawing_scale = DRAWING_SIZE / max(out_kpmap_shape)
+    h, w = (int(int(s * drawing_scale) / drawing_scale) for s in out_kpmap_shape)
+    step = max(1, LAUNCH_BYTES // (h * w * 3))
+    stats: Dict = {}
+    pending = []
+    threads = max(1, min(int(num_workers), MAX_HOST_THREADS))
+    # two pools: a batch's files are encoded (in Pillow, outside the interpreter lock) while the next batch is read, planned and drawn;
+    # in one pool the reads would queue behind the encodes
+    with ThreadPoolExecutor(max_workers=threads, thread_name_prefix="dm4d-skel-read") as readers, \
+            ThreadPoolExecutor(max_workers=threads, thread_name_prefix="dm4d-skel-write") as writers:
+        for b0 in range(0, len(todo), step):
+            idx = todo[b0:b0 + step]
+            maps = draw_skeleton_maps([kp2d_paths[i] for i in idx], [score_paths[i] for i in idx], kp2d_canvas_shape, out_kpmap_shape,
+                                      palette=palette, device=dev, stats=stats, pool=readers)
+            t0 = time.perf_counter()
+            for f in pending:  # the previous batch's files; at most two batches of maps are alive
+                f.result()
+            stats["write"] = stats.get("write", 0.0) + time.perf_counter() - t0
+            pending = [writers.submit(_save, out_paths[i], maps[k], image_quality) for k, i in enumerate(idx)]
+            counts["files"] += len(idx)
+        t0 = time.perf_counter()
+        for f in pending:
+            f.result()
+        stats["write"] = stats.get("write", 0.0) + time.perf_counter() - t0
+    counts["dropped_links"] = stats.pop("dropped_links", 0)
+    if counts["dropped_links"]:
+        log.warning("draw_skeleton: %d links have an endpoint outside [%d, %d] on the canvas and were not drawn", counts["dropped_links"],
+                    COORD_MIN, COORD_MAX)
+    counts["seconds"] = {k: round(v, 4) for k, v in stats.items()}
+    return counts

@@ -347,6 +347,34 @@ int dm4d_triangulate_points_f64(void* stream, const double* K, const double* T, 
 int dm4d_project_points_f64(void* stream, const double* kp3d, const double* K, const double* T, int F, int m, int k, double* kp2d,
                             double* depth);
 
+/* Skeleton maps (diffuman4d_amd/host/skeleton.py::draw_skeleton_maps; the reference's scripts/preprocess/draw_skeleton.py:158-178: the
+ *   loop of cv2.line / cv2.circle calls on a canvas of 2048 pixels, then Image.fromarray(canvas).resize((w, h))) for n_frames frames of
+ *   one shape in one launch.  prims: int32 records of DM4D_SKEL_FIELDS = {kind, x1, y1, x2, y2, size, r | g << 8 | b << 16, 0}, a frame's
+ *   records in paint order; kind DM4D_SKEL_LINE: the segment p1 p2 with thickness `size` >= 1; DM4D_SKEL_CIRCLE: the disc of radius
+ *   `size` >= 0 about p1 (p2 = p1).  offsets [n_frames + 1]: frame f owns records offsets[f] .. offsets[f + 1] - 1, at most
+ *   DM4D_SKEL_MAX_PRIMS of them.  Coordinates lie in [DM4D_SKEL_COORD_MIN, DM4D_SKEL_COORD_MAX], sizes in [0, DM4D_SKEL_MAX_SIZE].
+ *   Rasteriser (an exact integer rule, NOT OpenCV's edge walker, from which it differs on a primitive's rim only): a pixel is its integer
+ *   coordinate (x, y), 0 <= x < W, 0 <= y < H.  A circle covers (x - x1)^2 + (y - y1)^2 <= size^2.  A line, with d = p2 - p1, L2 = d . d,
+ *   v = (x, y) - p1, covers the union of {0 <= v . d <= L2 and 4 (v x d)^2 <= size^2 L2} (only when L2 > 0), 4 |(x, y) - p1|^2 <= size^2
+ *   and 4 |(x, y) - p2|^2 <= size^2.  A pixel takes the colour of the last record of its frame that covers it, black if none does.
+ *   Reduction: Pillow's Image.resize((w, h), BICUBIC) of the H x W RGB canvas, byte for byte: htab (W -> w) and vtab (H -> h) are tables
+ *   of n outputs = n x {window start, window length} followed by n x ksize int32 coefficients with 22 fractional bits (hk, vk = ksize);
+ *   the horizontal pass is rounded and clipped to uint8 before the vertical one.  The canvas is never stored: a workgroup paints the
+ *   part of it that one tile of the output reads, in LDS; the entry picks the largest tile (32, 16 or 8 outputs square) whose part fits
+ *   and refuses shapes where none does (canvas / output ratios above about 8).  out [n_frames, h, w, 3] uint8.
+ *   *_host are host copies of the bytes at *_dev: counts, records and windows are validated on them before anything is launched.
+ *   A frame's map is a function of its own records: bitwise repeatable, and independent of the batch.  No atomics.                  */
+#define DM4D_SKEL_FIELDS 8
+#define DM4D_SKEL_LINE 0
+#define DM4D_SKEL_CIRCLE 1
+#define DM4D_SKEL_MAX_PRIMS 512
+#define DM4D_SKEL_COORD_MIN (-8192)
+#define DM4D_SKEL_COORD_MAX 8191
+#define DM4D_SKEL_MAX_SIZE 16384
+int dm4d_skeleton_draw_u8(void* stream, const int32_t* prims_host, const int32_t* prims_dev, const int32_t* offsets_host,
+                          const int32_t* offsets_dev, int n_frames, const int32_t* htab_host, const int32_t* htab_dev, int hk,
+                          const int32_t* vtab_host, const int32_t* vtab_dev, int vk, int H, int W, int h, int w, uint8_t* out);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

@@ -1,0 +1,57 @@
+#!/usr/bin/env python
+"""Draw a scene's skeleton maps from its 2-D keypoints (diffuman4d_amd/host/skeleton.py), with the argument names of the reference's
+scripts/preprocess/draw_skeleton.py (the ``draw_skeleton`` action of preprocess.sh) plus ``--palette``.
+
+  python tools/draw_skeleton.py --kp2d_dir DATA/SCENE/poses_2d --out_kpmap_dir DATA/SCENE/skeletons --palette palette.json
+
+reads DATA/SCENE/poses_2d/{camera}/{frame}.json, writes DATA/SCENE/skeletons/{camera}/{frame}.webp and prints one JSON line with
+counts.  The palette (keypoint colours, links, the colour of the two "x" links) is not part of this package: see
+diffuman4d_amd.host.skeleton.load_palette for the file's layout.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+
+def _numbers(kind, count=None):
+    def parse(text: str):
+        parts = [p.strip() for p in text.strip("()[] ").split(",") if p.strip()]
+        if count is not None and len(parts) != count:
+            raise argparse.ArgumentTypeError(f"expected {count} comma-separated values, got {text!r}")
+        return [kind(p) for p in parts]
+    return parse
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--kp2d_dir", required=True, help="poses_2d/{camera}/{frame}.json")
+    ap.add_argument("--out_kpmap_dir", required=True, help="receives {camera}/{frame}{image_ext}")
+    ap.add_argument("--kp2d_score_dir", default=None, help="files of the same names whose keypoint_scores replace the frames' own")
+    ap.add_argument("--kp2d_canvas_shape", type=_numbers(int, 2), default=[1024, 1024], help="h,w of the image the keypoints refer to")
+    ap.add_argument("--out_kpmap_shape", type=_numbers(int, 2), default=[1024, 1024], help="h,w of the maps (the longer side 256 .. 8192)")
+    ap.add_argument("--spa_labels", type=_numbers(int), default=None, help="camera labels, e.g. 0,4,8 (default: the listing of kp2d_dir)")
+    ap.add_argument("--tem_labels", type=_numbers(int), default=None, help="frame labels (default: the listing of the first camera)")
+    ap.add_argument("--image_ext", default=".webp")
+    ap.add_argument("--image_quality", type=int, default=85)
+    ap.add_argument("--num_workers", type=int, default=16, help="threads that read the JSON files and encode the images (at most 16)")
+    ap.add_argument("--skip_exists", action="store_true", help="leave files that exist and that Pillow verifies")
+    ap.add_argument("--palette", required=True, help="JSON file with keypoint_colors, links and x_link_color")
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+    from diffuman4d_amd.host import skeleton
+    res = skeleton.draw_skeleton(args.kp2d_dir, args.out_kpmap_dir, kp2d_score_dir=args.kp2d_score_dir,
+                                 kp2d_canvas_shape=tuple(args.kp2d_canvas_shape), out_kpmap_shape=tuple(args.out_kpmap_shape),
+                                 spa_labels=args.spa_labels, tem_labels=args.tem_labels, image_ext=args.image_ext,
+                                 image_quality=args.image_quality, num_workers=args.num_workers, skip_exists=args.skip_exists,
+                                 palette=args.palette, device=args.device)
+    print(json.dumps(res))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -271,3 +271,193 @@ extern "C" int dm4d_skeleton_draw_u8(void* stream, const int32_t* prims_host, co
   }
   return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: the canvas is too large for the output: an 8 x 8 tile's footprint does not fit in LDS");
 }
+
+// Bounding box and box mask of drawn maps (crop_utils.py skeleton_to_mask on the maps above, for SpaTemDataset's has_gt_target=False
+// targets).  A pixel counts when any of its three bytes is non-zero.
+//
+//   extrema  grid (blocks per frame, frames): a block walks its share of the frame's 16-byte vectors (a scalar head of up to 15 bytes
+//            before the first aligned address and a tail of up to 15 after the last vector go to block 0); a vector that is all zero
+//            -- most of a map -- costs one load and one test, any other is walked byte by byte.  Shuffles reduce a wave, LDS the block,
+//            and thread 0 stores the block's {first column, first row, last column, last row} in the workspace.
+//   reduce   one wave per frame folds the frame's partials (a fixed assignment to lanes, then the shuffle tree) into boxes[f].
+//   fill     grid (blocks per frame, frames): 255 inside the padded and clamped rectangle, 0 outside, read from boxes[f] on the device.
+//
+// min and max of integers: no atomics, no block waits on another, and a frame's result does not depend on the batch it is in.
+namespace {
+
+constexpr int kBoxThreads = 256;
+constexpr int kBoxMaxBlocks = 256;       // per frame
+constexpr int kBoxVecsPerThread = 8;     // 32 KiB of a map per block before the grid stride sets in
+
+__host__ __device__ inline int box_blocks(int64_t frame_bytes) {
+  const int64_t per_block = (int64_t)kBoxThreads * kBoxVecsPerThread * 16;
+  const int64_t n = (frame_bytes + per_block - 1) / per_block;
+  return (int)(n < 1 ? 1 : n > kBoxMaxBlocks ? kBoxMaxBlocks : n);
+}
+
+struct Box {
+  int fc, fr, lc, lr;
+};
+
+__device__ __forceinline__ void box_add(Box& b, int col, int row) {
+  b.fc = min(b.fc, col);
+  b.fr = min(b.fr, row);
+  b.lc = max(b.lc, col);
+  b.lr = max(b.lr, row);
+}
+
+__device__ __forceinline__ void box_merge(Box& b, const Box& o) {
+  b.fc = min(b.fc, o.fc);
+  b.fr = min(b.fr, o.fr);
+  b.lc = max(b.lc, o.lc);
+  b.lr = max(b.lr, o.lr);
+}
+
+// the non-zero bytes among the `count` bytes of `word` (little endian) that start at byte `at` of the frame
+__device__ __forceinline__ void box_scan_word(Box& b, uint32_t word, int count, int64_t at, int row_bytes) {
+  if (word == 0) return;
+  int row = (int)(at / row_bytes), cb = (int)(at % row_bytes);
+  for (int j = 0; j < count; ++j) {
+    if ((word >> (8 * j)) & 0xffu) box_add(b, cb / 3, row);
+    if (++cb == row_bytes) {
+      cb = 0;
+      ++row;
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kBoxThreads) skeleton_box_partial_kernel(const uint8_t* __restrict__ maps, int64_t frame_bytes, int h, int w,
+                                                                           int32_t* __restrict__ partials) {
+  __shared__ int s_box[kBoxThreads / 64][4];
+  const int tid = threadIdx.x, f = blockIdx.y, nblocks = gridDim.x;
+  const uint8_t* src = maps + (int64_t)f * frame_bytes;
+  const int row_bytes = w * 3;
+  int64_t head = (16 - (int64_t)((uintptr_t)src & 15)) & 15;
+  if (head > frame_bytes) head = frame_bytes;
+  const int64_t nvec = (frame_bytes - head) / 16;
+  const int64_t tail0 = head + nvec * 16;
+  Box b{w, h, -1, -1};
+  for (int64_t v = (int64_t)blockIdx.x * kBoxThreads + tid; v < nvec; v += (int64_t)nblocks * kBoxThreads) {
+    const int64_t at = head + v * 16;
+    const U4 q = ldg16(src + at);
+    if ((q.x | q.y | q.z | q.w) == 0) continue;
+    box_scan_word(b, q.x, 4, at, row_bytes);
+    box_scan_word(b, q.y, 4, at + 4, row_bytes);
+    box_scan_word(b, q.z, 4, at + 8, row_bytes);
+    box_scan_word(b, q.w, 4, at + 12, row_bytes);
+  }
+  if (blockIdx.x == 0) {  // head and tail, a byte per thread
+    if (tid < head) box_scan_word(b, src[tid], 1, tid, row_bytes);
+    const int64_t t = tail0 + tid;
+    if (t < frame_bytes) box_scan_word(b, src[t], 1, t, row_bytes);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const Box o{__shfl_xor(b.fc, off), __shfl_xor(b.fr, off), __shfl_xor(b.lc, off), __shfl_xor(b.lr, off)};
+    box_merge(b, o);
+  }
+  if ((tid & 63) == 0) {
+    int* s = s_box[tid >> 6];
+    s[0] = b.fc, s[1] = b.fr, s[2] = b.lc, s[3] = b.lr;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < kBoxThreads / 64; ++k) box_merge(b, Box{s_box[k][0], s_box[k][1], s_box[k][2], s_box[k][3]});
+    int32_t* dst = partials + ((int64_t)f * nblocks + blockIdx.x) * 4;
+    dst[0] = b.fc, dst[1] = b.fr, dst[2] = b.lc, dst[3] = b.lr;
+  }
+}
+
+__global__ void __launch_bounds__(64) skeleton_box_reduce_kernel(const int32_t* __restrict__ partials, int nblocks, int h, int w,
+                                                                 int32_t* __restrict__ boxes) {
+  const int f = blockIdx.x, lane = threadIdx.x;  // one wave per frame
+  Box b{w, h, -1, -1};
+  const int32_t* p = partials + (int64_t)f * nblocks * 4;
+  for (int k = lane; k < nblocks; k += 64) box_merge(b, Box{p[4 * k], p[4 * k + 1], p[4 * k + 2], p[4 * k + 3]});
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const Box o{__shfl_xor(b.fc, off), __shfl_xor(b.fr, off), __shfl_xor(b.lc, off), __shfl_xor(b.lr, off)};
+    box_merge(b, o);
+  }
+  if (lane == 0) {
+    int32_t* dst = boxes + (int64_t)f * 4;
+    dst[0] = b.fc, dst[1] = b.fr, dst[2] = b.lc, dst[3] = b.lr;
+  }
+}
+
+__global__ void __launch_bounds__(kBoxThreads) skeleton_box_fill_kernel(const int32_t* __restrict__ boxes, int h, int w, int pad_top,
+                                                                        int pad_bottom, int pad_x, uint8_t* __restrict__ masks,
+                                                                        int64_t mask_stride) {
+  const int f = blockIdx.y;
+  const int32_t* bx = boxes + (int64_t)f * 4;
+  const int fc = bx[0], fr = bx[1], lc = bx[2], lr = bx[3];
+  int c0 = 0, c1 = 0, r0 = 0, r1 = 0;  // an all-zero map keeps an all-zero mask
+  if (lc >= 0) {
+    c0 = max(fc - 1 - pad_x, 0), c1 = min(lc + 1 + pad_x, w);
+    r0 = max(fr - 1 - pad_top, 0), r1 = min(lr + 1 + pad_bottom, h);
+  }
+  uint8_t* dst = masks + (int64_t)f * mask_stride;
+  const int64_t total = (int64_t)h * w;
+  int64_t head = (16 - (int64_t)((uintptr_t)dst & 15)) & 15;
+  if (head > total) head = total;
+  const int64_t nvec = (total - head) / 16;
+  const int64_t tail0 = head + nvec * 16;
+  auto value = [&](int row, int col) -> uint32_t { return (row >= r0 && row < r1 && col >= c0 && col < c1) ? 255u : 0u; };
+  for (int64_t v = (int64_t)blockIdx.x * kBoxThreads + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * kBoxThreads) {
+    const int64_t at = head + v * 16;
+    int row = (int)(at / w), col = (int)(at % w);
+    uint32_t q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        word |= value(row, col) << (8 * j);
+        if (++col == w) {
+          col = 0;
+          ++row;
+        }
+      }
+      q[k] = word;
+    }
+    stg16(dst + at, U4{q[0], q[1], q[2], q[3]});
+  }
+  if (blockIdx.x == 0) {
+    const int tid = threadIdx.x;
+    if (tid < head) dst[tid] = (uint8_t)value((int)(tid / w), (int)(tid % w));
+    const int64_t t = tail0 + tid;
+    if (t < total) dst[t] = (uint8_t)value((int)(t / w), (int)(t % w));
+  }
+}
+
+}  // namespace
+
+extern "C" size_t dm4d_skeleton_box_mask_ws_bytes(int n_frames, int h, int w) {
+  if (n_frames <= 0 || h <= 0 || w <= 0 || h > (1 << 15) || w > (1 << 15)) return 0;
+  return (size_t)n_frames * box_blocks((int64_t)h * w * 3) * 4 * sizeof(int32_t);
+}
+
+extern "C" int dm4d_skeleton_box_mask_u8(void* stream, const uint8_t* maps, int n_frames, int h, int w, int pad_top, int pad_bottom,
+                                         int pad_x, int32_t* boxes, uint8_t* masks, int64_t mask_stride, void* ws, int64_t ws_bytes) {
+  if (!maps || !boxes || !masks || !ws) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_box_mask: null pointer");
+  if (n_frames <= 0 || n_frames > 65535 || h <= 0 || w <= 0 || h > (1 << 15) || w > (1 << 15))
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_box_mask: empty or oversized shape");
+  if (pad_top < 0 || pad_bottom < 0 || pad_x < 0 || pad_top > (1 << 17) || pad_bottom > (1 << 17) || pad_x > (1 << 17))
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_box_mask: a padding is negative or oversized");
+  if (mask_stride < (int64_t)h * w) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_box_mask: mask_stride is below h * w: the slots overlap");
+  if (((uintptr_t)boxes & 3) || ((uintptr_t)ws & 3)) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_box_mask: boxes and workspace must be 4-byte aligned");
+  if (ws_bytes < 0 || (size_t)ws_bytes < dm4d_skeleton_box_mask_ws_bytes(n_frames, h, w))
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_box_mask: the workspace is smaller than dm4d_skeleton_box_mask_ws_bytes");
+  const hipStream_t s = (hipStream_t)stream;
+  const int64_t frame_bytes = (int64_t)h * w * 3;
+  const int nb = box_blocks(frame_bytes);
+  hipLaunchKernelGGL(skeleton_box_partial_kernel, dim3(nb, n_frames), dim3(kBoxThreads), 0, s, maps, frame_bytes, h, w, (int32_t*)ws);
+  int rc = dm4d_check_launch("skeleton_box_partial_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(skeleton_box_reduce_kernel, dim3(n_frames), dim3(64), 0, s, (const int32_t*)ws, nb, h, w, boxes);
+  rc = dm4d_check_launch("skeleton_box_reduce_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(skeleton_box_fill_kernel, dim3(box_blocks((int64_t)h * w), n_frames), dim3(kBoxThreads), 0, s, (const int32_t*)boxes, h, w,
+                     pad_top, pad_bottom, pad_x, masks, mask_stride);
+  return dm4d_check_launch("skeleton_box_fill_kernel");
+}

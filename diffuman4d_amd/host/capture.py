@@ -10,9 +10,14 @@ skeleton, ``to_tensor``, ``* 2 - 1`` and the white-background blend -- is split 
 
 Every task's uint8 planes, tables and frame descriptors go into one pinned staging buffer and up in one copy.  ``pixel_values``
 and ``skeletons`` come back as fp32 NCHW tensors on ``device``; cameras, Pluecker maps and masks stay on the host.
+
+``skeleton_source="kp2d"`` (opt-in) reads no skeleton image: every frame's map is drawn on the device from its ``poses_2d`` keypoint
+file (host/skeleton.py, ``dm4d_skeleton_draw_u8``) straight into the device staging buffer, and for ``has_gt_target=False`` targets
+``dm4d_skeleton_box_mask_u8`` derives the box mask and the bounding box there as well; only the boxes (16 bytes per frame) come back.
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import logging
 import math
@@ -114,6 +119,11 @@ def crop_box(mask: np.ndarray, path: str = "") -> List[int]:
     box = mask_bbox(mask != 0)
     if box is None:
         raise ValueError(f"foreground mask is empty: {path}")
+    return _crop_from_bbox(box, h, w)
+
+
+def _crop_from_bbox(box: Tuple[int, int, int, int], h: int, w: int) -> List[int]:
+    """crop_box from the mask's (xmin, ymin, xmax, ymax) of mask_bbox and its size."""
     xmin, ymin, xmax, ymax = box
     xc, yc = (xmin + xmax) / 2, (ymin + ymax) / 2
     size = max(2 * max(yc - ymin, ymax - yc, (xc - xmin) * 1.0, (xmax - xc) * 1.0), 0.7 * h)
@@ -137,6 +147,21 @@ def skeleton_mask(skel: np.ndarray, path: str = "") -> np.ndarray:
     xmin, ymin, xmax, ymax = max(xmin - px, 0), max(ymin - pt, 0), min(xmax + px, w), min(ymax + py, h)
     m[ymin:ymax, xmin:xmax] = 1.0
     return m.mul(255).byte().numpy()
+
+
+def skeleton_mask_pads(h: int, w: int) -> Tuple[int, int, int]:
+    """skeleton_mask's paddings for an [h, w] map -> (pad_top, pad_bottom, pad_x), as dm4d_skeleton_box_mask_u8 takes them."""
+    py, px = int(h * 0.03), int(w * 0.03)
+    return int(py * 3), py, px
+
+
+def skeleton_mask_rect(box: Sequence[int], h: int, w: int) -> Tuple[int, int, int, int]:
+    """skeleton_mask is a filled rectangle: from (first column, first row, last column, last row) of the pixels with a non-zero
+    channel -> (c0, r0, c1, r1), the mask is 255 on rows r0 .. r1 - 1 and columns c0 .. c1 - 1 and 0 elsewhere.  (The float32 channel
+    mean is non-zero exactly where a channel is, and mul(255).byte() of a mean outside the box, where every channel is 0, is 0.)"""
+    fc, fr, lc, lr = (int(v) for v in box)
+    pt, py, px = skeleton_mask_pads(h, w)
+    return max(fc - 1 - px, 0), max(fr - 1 - pt, 0), min(lc + 1 + px, w), min(lr + 1 + py, h)
 
 
 def _mask_mean_at_most(mask: np.ndarray, limit: float) -> bool:
@@ -169,21 +194,47 @@ def _up(n: int) -> int:
     return (n + _ALIGN - 1) // _ALIGN * _ALIGN
 
 
+SKELETON_SOURCES = ("files", "kp2d")
+KP2D_PATH_PAT = "{data_dir}/{scene_label}/poses_2d/{spa_label}/{tem_label}.json"
+
+
 class SpaTemDataset:
     """Captured-scene dataset with the reference's ``SpaTemDataset`` keywords and ``get_item`` contract.
 
     Extension keywords: ``plucker`` ("host": full-resolution fp32 Pluecker maps, as the reference; "cameras": ``None`` and the
     pipeline evaluates the rays on the device, as ``SyntheticSpaTemDataset``), ``device`` (where ``pixel_values`` / ``skeletons``
-    land; default: the calling thread's current HIP device), ``decode_threads`` (Pillow decode pool)."""
+    land; default: the calling thread's current HIP device), ``decode_threads`` (Pillow decode pool).
+
+    ``skeleton_source``: "files" reads ``skeleton_path_pat`` (the reference's route); "kp2d" draws every skeleton map on the device
+    from ``kp2d_path_pat`` (and the score override ``kp2d_score_path_pat``, the reference's ``draw_skeleton(kp2d_score_dir=...)``) with
+    ``palette`` (a path or a Palette, as ``skeleton.load_palette`` takes it), exactly as ``skeleton.draw_skeleton_maps([kp2d_path],
+    [score_path], kp2d_canvas_shape or the camera's (height, width), (h, w), palette=palette)[0]`` with (h, w) the decoded image's size
+    or, for a frame that loads none, the camera's.  No skeleton file is read and no map crosses PCIe.  The result equals the file
+    route's on skeleton files that hold those maps losslessly; it differs from it on lossy files by exactly the codec's loss."""
 
     def __init__(self, data_dir: str, camera_path_pat: str = "{data_dir}/{scene_label}/transforms.json",
                  image_path_pat: str = "{data_dir}/{scene_label}/images/{spa_label}/{tem_label}.webp",
                  fmask_path_pat: str = "{data_dir}/{scene_label}/fmasks/{spa_label}/{tem_label}.png",
                  skeleton_path_pat: str = "{data_dir}/{scene_label}/skeletons/{spa_label}/{tem_label}.webp",
                  scene_label: Optional[str] = None, height: int = 1024, width: int = 1024, has_gt_target: bool = True,
-                 plucker: str = "host", device=None, decode_threads: int = 8):
+                 plucker: str = "host", device=None, decode_threads: int = 8, skeleton_source: str = "files",
+                 kp2d_path_pat: str = KP2D_PATH_PAT, kp2d_score_path_pat: Optional[str] = None,
+                 kp2d_canvas_shape: Optional[Tuple[int, int]] = None, palette=None):
         if plucker not in ("host", "cameras"):
             raise ValueError("plucker must be 'host' or 'cameras'")
+        if skeleton_source not in SKELETON_SOURCES:
+            raise ValueError(f"skeleton_source must be one of {SKELETON_SOURCES}, got {skeleton_source!r}")
+        self.skeleton_source, self.kp2d_path_pat, self.kp2d_score_path_pat = skeleton_source, kp2d_path_pat, kp2d_score_path_pat
+        self.kp2d_canvas_shape = None if kp2d_canvas_shape is None else tuple(int(v) for v in kp2d_canvas_shape)
+        self.palette = None
+        if skeleton_source == "kp2d":
+            from . import skeleton as _sk  # here, not at the top: host/skeleton.py imports this module's bicubic_table
+            if palette is None:
+                raise ValueError("skeleton_source='kp2d' needs palette=: a path or a Palette, as skeleton.load_palette takes it (no colour "
+                                 f"or link table is part of this package); {_sk.PALETTE_HELP}")
+            if self.kp2d_canvas_shape is not None and (len(self.kp2d_canvas_shape) != 2 or min(self.kp2d_canvas_shape) < 1):
+                raise ValueError(f"kp2d_canvas_shape must be (height, width), got {kp2d_canvas_shape!r}")
+            self._sk, self.palette = _sk, _sk.load_palette(palette)
         if width % 4 != 0:
             raise ValueError(f"width must be a multiple of 4 (dm4d_capture_crop_resize_f32), got {width}")
         self.data_dir = os.path.expandvars(data_dir) if "$" in data_dir else data_dir
@@ -231,16 +282,41 @@ class SpaTemDataset:
             raise AssertionError("Error: foreground mask < 2%. Please check the data.")
         return {"img": img, "mask": mask, "skel": skel, "crop": crop}
 
-    def _stream(self, device: torch.device):
-        st = getattr(self._tls, "stream", None)
-        if st is None or st.device != device:
-            st = self._tls.stream = torch.cuda.Stream(device=device)
-        return st
+    # -- skeleton_source="kp2d": the host half of one frame -------------------------------------------------------------------
+    def _load_frame_kp2d(self, label, input_spa_labels) -> Dict:
+        """As _load_frame, without a skeleton image: the frame's draw plan instead.  A has_gt_target=False target has no mask and
+        no crop yet: both come from its map on the device (_resize_on_device_kp2d)."""
+        scene_label, spa, tem = label
+        sk, cam = self._sk, self.cameras[scene_label][spa]
+        kp_path = self.get_file_path(self.kp2d_path_pat, scene_label, spa, tem)
+        inst = sk._read_instance(kp_path)
+        score = None if self.kp2d_score_path_pat is None else sk._read_instance(self.get_file_path(self.kp2d_score_path_pat, scene_label, spa, tem))
+        if not self.has_gt_target and spa not in input_spa_labels:
+            img, mask, img_path, hw = None, None, kp_path, (int(cam["height"]), int(cam["width"]))
+        else:
+            img_path = self.get_file_path(self.image_path_pat, scene_label, spa, tem)
+            fmask_path = self.get_file_path(self.fmask_path_pat, scene_label, spa, tem)
+            img, mask = _open(img_path, "RGB"), _open(fmask_path, "L")
+            hw = img.shape[:2]
+        sk._check_out_shape(hw)
+        canvas = self.kp2d_canvas_shape or (int(cam["height"]), int(cam["width"]))
+        plan = sk.plan_draw_calls(inst, score, (canvas, hw), self.palette)
+        fr = {"img": img, "mask": mask, "plan": plan, "crop": None, "path": kp_path}
+        if mask is not None:
+            fr["crop"] = crop_box(mask, img_path)
+            size = lambda a: (a.shape[1], a.shape[0])  # PIL's (w, h)
+            if not (size(img) == size(mask) == plan.out_size):
+                raise AssertionError(f"Error: image size: {size(img)} != fmask size: {size(mask)} != skeleton size: {plan.out_size}")
+            if self.has_gt_target and spa in input_spa_labels and _mask_mean_at_most(mask, 0.02):
+                raise AssertionError("Error: foreground mask < 2%. Please check the data.")
+        return fr
 
-    def _resize_on_device(self, frames: List[Dict], device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Pack planes, tables and descriptors into one staging buffer, upload it, launch; -> (pixel_values, skeletons)."""
+    # -- tables and descriptors of a task whose crops are known ----------------------------------------------------------------
+    def _tables(self, frames: List[Dict]) -> Tuple[Dict[Tuple[int, int], Tuple[int, int]], np.ndarray]:
+        """Pillow's coefficient tables of every distinct (crop size, output size) pair -> ({pair: (offset in int32 units, ksize)},
+        the int32 array that holds them)."""
         H, W = self.height, self.width
-        tables: Dict[Tuple[int, int], Tuple[int, int]] = {}  # (in, out) -> (offset in int32 units, ksize)
+        tables: Dict[Tuple[int, int], Tuple[int, int]] = {}
         chunks: List[np.ndarray] = []
         n_tab = 0
         for fr in frames:
@@ -250,7 +326,119 @@ class SpaTemDataset:
                     tables[key] = (n_tab, k.shape[1])
                     chunks += [b.reshape(-1), k.reshape(-1)]
                     n_tab += b.size + k.size
-        tab = np.concatenate(chunks).astype(np.int32)
+        return tables, np.concatenate(chunks).astype(np.int32)
+
+    def _descriptors(self, frames: List[Dict], plane_offs, shapes, tables, tab: np.ndarray) -> np.ndarray:
+        """int64 [n, FIELDS] frame descriptors (include/dm4d.h): plane_offs = (image, mask, skeleton) byte offsets per frame, image None
+        where the skeleton serves as image; shapes = the (h, w) of each frame's planes."""
+        H, W = self.height, self.width
+        desc = np.zeros((len(frames), FIELDS), dtype=np.int64)
+        scratch = 0
+        for i, (fr, (oi, om, os_), (sh, sw)) in enumerate(zip(frames, plane_offs, shapes)):
+            top, left, ch, cw = fr["crop"][:4]
+            htab, hk = tables[(cw, W)]
+            vtab, vk = tables[(ch, H)]
+            vb = tab[vtab: vtab + 2 * H].reshape(H, 2)
+            y_first, y_last = int(vb[0, 0]), int(vb[-1, 0] + vb[-1, 1])  # crop rows the vertical windows read
+            desc[i] = [os_ if oi is None else oi, om, os_, sh, sw, top, left, ch, cw, htab, hk, vtab, vk, scratch, y_first,
+                       y_last - y_first]
+            scratch = _up(scratch + (y_last - y_first) * W * 8)
+        return desc
+
+    def _resize_on_device_kp2d(self, frames: List[Dict], device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The device half in "kp2d" mode; fills in the crop of every has_gt_target=False target.  Staging buffer on the device:
+
+            [per group: n x h x w x 3 skeleton planes, tight | per group: one h x w mask per target | image planes and decoded masks]
+
+        The first two parts exist on the device only; the third goes up from the pinned buffer in one copy, queued while the device
+        draws.  Every size in it is known before the targets' crops are.  Tables and descriptors depend on those crops: they go up
+        afterwards in a small buffer of their own (the library takes them by pointer, they need not lie in the staging buffer)."""
+        sk = self._sk
+        H, W = self.height, self.width
+        n = len(frames)
+        # groups of one canvas shape and one map size; the targets (whose maps feed dm4d_skeleton_box_mask_u8) come first in each
+        groups: Dict[Tuple, List[int]] = {}
+        for i, fr in enumerate(frames):
+            groups.setdefault((fr["plan"].canvas_shape, fr["plan"].out_size), []).append(i)
+        cur, skel_offs, mask_offs, regions = 0, [None] * n, [None] * n, []
+        for (_, (w, h)), idx in groups.items():
+            idx = [i for i in idx if frames[i]["mask"] is None] + [i for i in idx if frames[i]["mask"] is not None]
+            for k, i in enumerate(idx):
+                skel_offs[i] = cur + k * h * w * 3
+            regions.append([idx, sum(frames[i]["mask"] is None for i in idx), h, w, cur, None])
+            cur += len(idx) * h * w * 3
+        for reg in regions:
+            idx, n_targets, h, w = reg[:4]
+            if n_targets:
+                reg[5] = cur
+                for k, i in enumerate(idx[:n_targets]):
+                    mask_offs[i] = cur + k * h * w
+                cur += n_targets * h * w
+        file_off = off = _up(cur)  # where the planes that come from files start
+        file_offs = []
+        for fr in frames:
+            o = []
+            for name in ("img", "mask"):
+                a = fr[name]
+                o.append(None if a is None else off)
+                off = off if a is None else _up(off + a.size)
+            file_offs.append(o)
+        total = off
+
+        on_gpu = device.type == "cuda"
+        blob = torch.empty(total - file_off, dtype=torch.uint8, pin_memory=on_gpu)
+        host = blob.numpy()
+        st = self._stream(device) if on_gpu else None
+        with (torch.cuda.device(device) if on_gpu else contextlib.nullcontext()), (torch.cuda.stream(st) if on_gpu else contextlib.nullcontext()):
+            dev_blob = torch.empty(total, dtype=torch.uint8, device=device)
+            boxes = []
+            for idx, nt, h, w, start, mask_start in regions:
+                maps = dev_blob[start: start + len(idx) * h * w * 3].view(len(idx), h, w, 3)
+                sk.draw_plans_into([frames[i]["plan"] for i in idx], maps)
+                if nt:
+                    masks = dev_blob[mask_start: mask_start + nt * h * w].view(nt, h, w)
+                    boxes.append((idx[:nt], h, w, ops.skeleton_box_mask(maps[:nt], skeleton_mask_pads(h, w), masks=masks)[0]))
+            # the image planes go into the pinned buffer, and up, while the device draws
+            jobs = [(o - file_off, fr[name]) for fr, offs in zip(frames, file_offs) for o, name in zip(offs, ("img", "mask")) if o is not None]
+            list(self._pool.map(lambda j: np.copyto(host[j[0]: j[0] + j[1].size], j[1].reshape(-1)), jobs))
+            if total > file_off:
+                dev_blob[file_off:].copy_(blob, non_blocking=True)
+            for idx, h, w, b in boxes:  # 16 bytes per target; .cpu() waits for the stream
+                for i, box in zip(idx, b.cpu().tolist()):
+                    if box[2] < 0:
+                        raise ValueError(f"skeleton is empty, no mask can be made from it: {frames[i]['path']}")
+                    c0, r0, c1, r1 = skeleton_mask_rect(box, h, w)
+                    frames[i]["crop"] = _crop_from_bbox((c0 - 1, r0 - 1, c1, r1), h, w)  # mask_bbox of the rectangle
+            tables, tab = self._tables(frames)
+            shapes = [(fr["plan"].out_size[1], fr["plan"].out_size[0]) for fr in frames]
+            plane_offs = [(oi, mask_offs[i] if om is None else om, skel_offs[i]) for i, (oi, om) in enumerate(file_offs)]
+            desc = self._descriptors(frames, plane_offs, shapes, tables, tab)
+            desc_off = _up(tab.nbytes)
+            meta = torch.empty(desc_off + desc.nbytes, dtype=torch.uint8, pin_memory=on_gpu)
+            meta.numpy()[:tab.nbytes] = tab.view(np.uint8)
+            meta.numpy()[desc_off:] = desc.reshape(-1).view(np.uint8)
+            meta_dev = meta.to(device, non_blocking=True)
+            pix, skel = ops.capture_crop_resize(dev_blob, meta, n, desc_off, 0, tab.size, H, W, meta=meta_dev)
+        if on_gpu:
+            st.synchronize()  # as _resize_on_device: the tensors are complete when handed over, the pinned buffers may be released
+        return pix, skel
+
+    def _device(self) -> torch.device:
+        device = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        return device
+
+    def _stream(self, device: torch.device):
+        st = getattr(self._tls, "stream", None)
+        if st is None or st.device != device:
+            st = self._tls.stream = torch.cuda.Stream(device=device)
+        return st
+
+    def _resize_on_device(self, frames: List[Dict], device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Pack planes, tables and descriptors into one staging buffer, upload it, launch; -> (pixel_values, skeletons)."""
+        H, W = self.height, self.width
+        tables, tab = self._tables(frames)
         # layout: [frame planes | tables | descriptors], every region 16-byte aligned
         off, plane_offs = 0, []
         for fr in frames:
@@ -266,18 +454,7 @@ class SpaTemDataset:
         tab_off = off
         desc_off = _up(tab_off + tab.nbytes)
         total = desc_off + len(frames) * FIELDS * 8
-        desc = np.zeros((len(frames), FIELDS), dtype=np.int64)
-        scratch = 0
-        for i, (fr, (oi, om, os_)) in enumerate(zip(frames, plane_offs)):
-            top, left, ch, cw = fr["crop"][:4]
-            sh, sw = fr["skel"].shape[:2]
-            htab, hk = tables[(cw, W)]
-            vtab, vk = tables[(ch, H)]
-            vb = tab[vtab: vtab + 2 * H].reshape(H, 2)
-            y_first, y_last = int(vb[0, 0]), int(vb[-1, 0] + vb[-1, 1])  # crop rows the vertical windows read
-            desc[i] = [os_ if oi is None else oi, om, os_, sh, sw, top, left, ch, cw, htab, hk, vtab, vk, scratch, y_first,
-                       y_last - y_first]
-            scratch = _up(scratch + (y_last - y_first) * W * 8)
+        desc = self._descriptors(frames, plane_offs, [fr["skel"].shape[:2] for fr in frames], tables, tab)
         on_gpu = device.type == "cuda"
         blob = torch.empty(total, dtype=torch.uint8, pin_memory=on_gpu)
         host = blob.numpy()
@@ -311,15 +488,17 @@ class SpaTemDataset:
             cams = [self._nearest(cameras, spa_labels[0], input_spa_labels)] + list(spa_labels)
             labels = [(scene_label, s, t) for s in cams for t in tem_labels]
 
-        frames = list(self._pool.map(lambda lab: self._load_frame(lab, input_spa_labels), labels))
+        if self.skeleton_source == "kp2d":  # the targets' crops come from the device: the resize runs before the bookkeeping
+            frames = list(self._pool.map(lambda lab: self._load_frame_kp2d(lab, input_spa_labels), labels))
+            pixel_values, skeletons = self._resize_on_device_kp2d(frames, self._device())
+        else:
+            frames = list(self._pool.map(lambda lab: self._load_frame(lab, input_spa_labels), labels))
         Ks = torch.stack([_intrinsic(cameras[s]["K"], fr["crop"], self.height) for (_, s, _), fr in zip(labels, frames)])
         poses = relative_poses(torch.stack([cameras[s]["pose"] for _, s, _ in labels]))
         hws = [(cameras[s]["height"], cameras[s]["width"]) for _, s, _ in labels]
         crops = [fr["crop"] for fr in frames]
-        device = torch.device(self.device) if self.device is not None else torch.device("cuda", torch.cuda.current_device())
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
-        pixel_values, skeletons = self._resize_on_device(frames, device)
+        if self.skeleton_source != "kp2d":
+            pixel_values, skeletons = self._resize_on_device(frames, self._device())
         del frames
 
         n = len(labels)

@@ -276,14 +276,24 @@ def compose(overrides: List[str], config_dir: Optional[str] = None) -> Dict[str,
 NATIVE_FALLBACKS = {"src.data.spatem_dataset.SpaTemDataset": "diffuman4d_amd.host.capture.SpaTemDataset"}
 
 
+# keywords of the native dataset beyond the reference's, with their defaults (host/capture.py)
+NATIVE_DATASET_KEYS = {"skeleton_source": "files", "palette": None, "kp2d_score_path_pat": None, "kp2d_canvas_shape": None,
+                       "kp2d_path_pat": "{data_dir}/{scene_label}/poses_2d/{spa_label}/{tem_label}.json"}
+
+
 def _import_attr(path: str):
     mod, _, name = path.rpartition(".")
     return getattr(importlib.import_module(mod), name)
 
 
-def locate(path: str):
+def locate(path: str, native: bool = False):
+    """The class or function a ``_target_`` names.  `native`: take the native counterpart of a reference class even where the
+    reference's own imports (for keywords only the native class knows)."""
     path = TARGET_ALIASES.get(path, path)
     if path in NATIVE_FALLBACKS:
+        if native:
+            log.info("using %s for %s: the node has keywords the reference's class does not know", NATIVE_FALLBACKS[path], path)
+            return _import_attr(NATIVE_FALLBACKS[path])
         try:
             target = _import_attr(path)
         except ImportError as e:
@@ -298,6 +308,13 @@ def locate(path: str):
 def instantiate(node: Dict[str, Any], **kwargs):
     """hydra.utils.instantiate for flat ``_target_`` nodes."""
     node = dict(node)
-    target = locate(node.pop("_target_"))
+    path = node.pop("_target_")
+    # data.skeleton_source / palette / kp2d_* are keywords of the native SpaTemDataset only: one that is set selects the native class even
+    # where the reference's imports; given at their defaults they ask for nothing new and are not handed to the reference's class
+    given = [k for k in NATIVE_DATASET_KEYS if k in node] if TARGET_ALIASES.get(path, path) in NATIVE_FALLBACKS else []
+    target = locate(path, native=any(node[k] != NATIVE_DATASET_KEYS[k] for k in given))
+    if given and target is not _import_attr(NATIVE_FALLBACKS[TARGET_ALIASES.get(path, path)]):
+        for k in given:
+            del node[k]
     node.update(kwargs)
     return target(**node)

@@ -119,6 +119,9 @@ SIGNATURES = {
     "dm4d_project_points_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     # skeleton maps: a batch of frames' draw calls rasterised per output tile in LDS + Pillow's bicubic resize (host/skeleton.py)
     "dm4d_skeleton_draw_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    # bounding box + box mask of drawn maps, for the dataset's skeleton-only targets (host/capture.py, skeleton_source="kp2d")
+    "dm4d_skeleton_box_mask_ws_bytes": (C.c_size_t, [_i, _i, _i]),
+    "dm4d_skeleton_box_mask_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64]),
 }
 
 EPI_GEGLU = 1

@@ -1055,23 +1055,30 @@ CAPTURE_FIELDS = 16  # include/dm4d.h DM4D_CAPTURE_FIELDS
 
 
 def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: int, desc_off: int, tab_off: int, tab_len: int,
-                        H: int, W: int) -> Tuple[torch.Tensor, torch.Tensor]:
+                        H: int, W: int, meta: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """Crop + Pillow-exact bicubic resize + the dataset's fp32 epilogue of `n_frames` captured frames (host/capture.py) ->
     (pixel_values, skeletons), fp32 [n_frames, 3, H, W] on blob's device.  `blob`: the device copy of the staging buffer
     `blob_host` (uint8: frame planes | int32 tables at byte `tab_off` | int64 descriptors at byte `desc_off`); the library checks
-    every descriptor and table on the host copy before it launches."""
+    every descriptor and table on the host copy before it launches.  With `meta` (uint8, on blob's device) the tables and the
+    descriptors are read from it instead, at the same two offsets, `blob_host` is the host copy of `meta`, and `blob` holds
+    planes only, some of which may never have been on the host."""
     lib = _l.load()
     _req(blob, "blob", torch.uint8)
-    if blob_host.device.type != "cpu" or blob_host.numel() != blob.numel():
-        raise _l.Dm4dError("blob_host: expected the host copy of blob")
+    where = blob if meta is None else _req(meta, "meta", torch.uint8)
+    if blob_host.device.type != "cpu" or blob_host.dtype != torch.uint8 or blob_host.numel() != where.numel():
+        raise _l.Dm4dError("blob_host: expected the host copy of " + ("blob" if meta is None else "meta"))
+    if min(desc_off, tab_off) < 0 or desc_off % 8 or tab_off % 4 or max(desc_off + n_frames * CAPTURE_FIELDS * 8, tab_off + tab_len * 4) > where.numel():
+        raise _l.Dm4dError("desc_off / tab_off: the tables or the descriptors lie outside the buffer, or are not aligned")
+    if where.device != blob.device or not where.is_contiguous() or not blob.is_contiguous():
+        raise _l.Dm4dError("meta: expected a contiguous tensor on blob's device")
     desc = blob_host[desc_off: desc_off + n_frames * CAPTURE_FIELDS * 8].view(torch.int64).reshape(n_frames, CAPTURE_FIELDS)
     tab = blob_host[tab_off: tab_off + tab_len * 4].view(torch.int32)
     scratch_bytes = int((desc[:, 13] + desc[:, 15] * W * 8).max())
     scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=blob.device)
     pix = torch.empty((n_frames, 3, H, W), dtype=F32, device=blob.device)
     skel = torch.empty((n_frames, 3, H, W), dtype=F32, device=blob.device)
-    base = blob.data_ptr()
-    rc = lib.dm4d_capture_crop_resize_f32(_stream(), base, blob.numel(), desc.data_ptr(), base + desc_off, n_frames, tab.data_ptr(),
+    base = where.data_ptr()
+    rc = lib.dm4d_capture_crop_resize_f32(_stream(), blob.data_ptr(), blob.numel(), desc.data_ptr(), base + desc_off, n_frames, tab.data_ptr(),
                                           base + tab_off, tab_len, _p(scratch), scratch.numel(), _p(pix), _p(skel), H, W)
     _l.check(rc, "dm4d_capture_crop_resize_f32")
     return pix, skel
@@ -1274,11 +1281,12 @@ SKEL_COORD_MIN, SKEL_COORD_MAX = -8192, 8191
 
 def skeleton_draw(prims_host: torch.Tensor, prims: torch.Tensor, offsets_host: torch.Tensor, offsets: torch.Tensor, htab_host: torch.Tensor,
                   htab: torch.Tensor, hk: int, vtab_host: torch.Tensor, vtab: torch.Tensor, vk: int, H: int, W: int, h: int,
-                  w: int) -> torch.Tensor:
+                  w: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Skeleton maps of a batch of frames -> uint8 [B, h, w, 3] on prims' device, one launch on the current stream (host/skeleton.py).
     prims int32 [n, SKEL_FIELDS] draw records, offsets int32 [B + 1] the frames' ranges in it, htab / vtab int32 bicubic tables of
     the canvas (H, W) -> (h, w) with hk / vk taps per window; every *_host tensor is the host copy of its device twin, on which the
-    library checks counts, records and windows before it launches."""
+    library checks counts, records and windows before it launches.  `out`: a contiguous uint8 [B, h, w, 3] tensor on prims' device to
+    draw into (a view of a larger buffer is fine: no alignment is asked of it); by default one is allocated."""
     lib = _l.load()
     for name, dev, host in (("prims", prims, prims_host), ("offsets", offsets, offsets_host), ("htab", htab, htab_host), ("vtab", vtab, vtab_host)):
         _req(dev, name, torch.int32)
@@ -1293,8 +1301,41 @@ def skeleton_draw(prims_host: torch.Tensor, prims: torch.Tensor, offsets_host: t
         raise _l.Dm4dError("offsets: expected [B + 1] with the last entry inside prims")
     if htab.numel() != w * (2 + hk) or vtab.numel() != h * (2 + vk):
         raise _l.Dm4dError(f"htab / vtab: expected {w} x (2 + {hk}) and {h} x (2 + {vk}) entries, got {htab.numel()} and {vtab.numel()}")
-    out = torch.empty((B, h, w, 3), dtype=torch.uint8, device=prims.device)
+    if out is None:
+        out = torch.empty((B, h, w, 3), dtype=torch.uint8, device=prims.device)
+    else:
+        _req(out, "out", torch.uint8)
+        if tuple(out.shape) != (B, h, w, 3) or not out.is_contiguous() or out.device != prims.device:
+            raise _l.Dm4dError(f"out: expected a contiguous [{B}, {h}, {w}, 3] tensor on {prims.device}, got {tuple(out.shape)} on {out.device}")
     rc = lib.dm4d_skeleton_draw_u8(_stream(), prims_host.data_ptr(), _p(prims), offsets_host.data_ptr(), _p(offsets), B, htab_host.data_ptr(),
                                    _p(htab), int(hk), vtab_host.data_ptr(), _p(vtab), int(vk), int(H), int(W), int(h), int(w), _p(out))
     _l.check(rc, "dm4d_skeleton_draw_u8")
     return out
+
+
+def skeleton_box_mask(maps: torch.Tensor, pads: Tuple[int, int, int], masks: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Bounding boxes and box masks of drawn maps (crop_utils.py skeleton_to_mask; host/capture.py) -> (boxes int32 [B, 4] = {first
+    column, first row, last column, last row} of the pixels with a non-zero channel, {w, h, -1, -1} for a map without one; masks uint8
+    [B, h, w]: 255 inside the box grown by 1 + pads and clamped to the map, 0 outside), both on maps' device.  maps: contiguous uint8
+    [B, h, w, 3]; pads = (pad_top, pad_bottom, pad_x); `masks`: a contiguous uint8 [B, h, w] tensor to fill (a view of a larger buffer
+    is fine), by default one is allocated.  Three launches on the current stream; nothing is read back."""
+    lib = _l.load()
+    _req(maps, "maps", torch.uint8)
+    if maps.dim() != 4 or maps.shape[3] != 3 or maps.shape[0] < 1 or not maps.is_contiguous():
+        raise _l.Dm4dError(f"maps: expected a contiguous [B >= 1, h, w, 3] tensor, got {tuple(maps.shape)}")
+    B, h, w, _ = maps.shape
+    if masks is None:
+        masks = torch.empty((B, h, w), dtype=torch.uint8, device=maps.device)
+    else:
+        _req(masks, "masks", torch.uint8)
+        if tuple(masks.shape) != (B, h, w) or not masks.is_contiguous() or masks.device != maps.device:
+            raise _l.Dm4dError(f"masks: expected a contiguous [{B}, {h}, {w}] tensor on {maps.device}, got {tuple(masks.shape)} on {masks.device}")
+    pad_top, pad_bottom, pad_x = (int(v) for v in pads)
+    nbytes = int(lib.dm4d_skeleton_box_mask_ws_bytes(B, h, w))
+    if nbytes == 0:
+        raise _l.Dm4dError(f"skeleton_box_mask: shape {tuple(maps.shape)} is out of range")
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=maps.device)
+    boxes = torch.empty((B, 4), dtype=torch.int32, device=maps.device)
+    rc = lib.dm4d_skeleton_box_mask_u8(_stream(), _p(maps), B, h, w, pad_top, pad_bottom, pad_x, _p(boxes), _p(masks), h * w, _p(ws), nbytes)
+    _l.check(rc, "dm4d_skeleton_box_mask_u8")
+    return boxes, masks

@@ -18,6 +18,7 @@ caller names a palette file (``load_palette``).  There is no CPU path: a ``devic
 """
 from __future__ import annotations
 
+import contextlib
 import json
 import logging
 import os
@@ -225,21 +226,20 @@ def _check_out_shape(out_kpmap_shape) -> None:
                          f"{DRAWING_SIZE} pixels on its longer side, and below {MIN_OUT} an output tile's part of it does not fit in LDS)")
 
 
-def draw_plans(plans: Sequence[DrawPlan], device="cuda") -> np.ndarray:
-    """Plans of one canvas shape and output size -> uint8 [B, h, w, 3], one launch (cut along B where the maps pass 256 MiB)."""
+def _draw_chunks(plans: Sequence[DrawPlan], dev: torch.device, out: Optional[torch.Tensor] = None):
+    """The device half of draw_plans: yields (first frame, uint8 [b, h, w, 3] tensor on `dev`) launch by launch, on the current stream,
+    and reads nothing back.  With `out` ([B, h, w, 3] on `dev`) every launch writes its frames of it; without, a launch allocates its own."""
     if not plans:
         raise ValueError("draw_plans: no frames")
     (H, W), (w, h) = plans[0].canvas_shape, plans[0].out_size
     if any(p.canvas_shape != (H, W) or p.out_size != (w, h) for p in plans):
         raise ValueError("draw_plans: the frames of one batch must share the canvas shape and the output size")
-    dev = _hip_device(device, "draw_skeleton_maps")
     hb, hk = bicubic_table(W, w)
     vb, vk = bicubic_table(H, h)
     htab = np.concatenate([hb.reshape(-1), hk.reshape(-1)]).astype(np.int32)
     vtab = np.concatenate([vb.reshape(-1), vk.reshape(-1)]).astype(np.int32)
     step = max(1, LAUNCH_BYTES // (h * w * 3))
-    out = []
-    with torch.cuda.device(dev):
+    with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
         htab_h, vtab_h = torch.from_numpy(htab), torch.from_numpy(vtab)
         htab_d, vtab_d = htab_h.to(dev), vtab_h.to(dev)
         for b0 in range(0, len(plans), step):
@@ -247,9 +247,27 @@ def draw_plans(plans: Sequence[DrawPlan], device="cuda") -> np.ndarray:
             recs = [pack_calls(p.calls) for p in chunk]
             offsets = torch.from_numpy(np.concatenate([[0], np.cumsum([len(r) for r in recs])]).astype(np.int32))
             prims = torch.from_numpy(np.concatenate(recs + [np.zeros((1, ops.SKEL_FIELDS), dtype=np.int32)]))  # never empty
-            maps = ops.skeleton_draw(prims, prims.to(dev), offsets, offsets.to(dev), htab_h, htab_d, hk.shape[1], vtab_h, vtab_d,
-                                     vk.shape[1], H, W, h, w)
-            out.append(maps.cpu().numpy())
+            yield b0, ops.skeleton_draw(prims, prims.to(dev), offsets, offsets.to(dev), htab_h, htab_d, hk.shape[1], vtab_h, vtab_d,
+                                        vk.shape[1], H, W, h, w, out=None if out is None else out[b0:b0 + len(chunk)])
+
+
+def draw_plans_into(plans: Sequence[DrawPlan], out: torch.Tensor) -> torch.Tensor:
+    """Plans of one canvas shape and output size drawn into `out`, uint8 [B, h, w, 3] on the device (a view of a larger buffer is
+    fine), on the current stream; the maps stay where they are drawn (host/capture.py consumes them there).  Cut along B as draw_plans."""
+    (w, h) = plans[0].out_size if plans else (0, 0)
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) != (len(plans), h, w, 3):
+        raise ValueError(f"draw_plans_into: out must be [{len(plans)}, {h}, {w}, 3], got {tuple(getattr(out, 'shape', ()))}")
+    for _ in _draw_chunks(plans, out.device, out):
+        pass
+    return out
+
+
+def draw_plans(plans: Sequence[DrawPlan], device="cuda") -> np.ndarray:
+    """Plans of one canvas shape and output size -> uint8 [B, h, w, 3], one launch (cut along B where the maps pass 256 MiB)."""
+    if not plans:
+        raise ValueError("draw_plans: no frames")
+    dev = _hip_device(device, "draw_skeleton_maps")
+    out = [maps.cpu().numpy() for _, maps in _draw_chunks(plans, dev)]
     return out[0] if len(out) == 1 else np.concatenate(out)
 
 

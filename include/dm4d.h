@@ -375,6 +375,23 @@ int dm4d_skeleton_draw_u8(void* stream, const int32_t* prims_host, const int32_t
                           const int32_t* offsets_dev, int n_frames, const int32_t* htab_host, const int32_t* htab_dev, int hk,
                           const int32_t* vtab_host, const int32_t* vtab_dev, int vk, int H, int W, int h, int w, uint8_t* out);
 
+/* Bounding box and box mask of drawn skeleton maps (diffuman4d_amd/host/capture.py::SpaTemDataset, skeleton_source="kp2d"; the reference's
+ *   src/data/utils/crop_utils.py skeleton_to_mask, called from spatem_dataset.py:124-127 for has_gt_target=False targets).
+ *   maps [n_frames, h, w, 3] uint8, tight (what dm4d_skeleton_draw_u8 writes).  A pixel counts when any of its channels is non-zero.
+ *   boxes [n_frames, 4] int32 = {first column, first row, last column, last row} of the counting pixels, {w, h, -1, -1} for a map without
+ *   one.  Mask slot f = masks + f * mask_stride holds [h, w] uint8 (mask_stride >= h * w; slots need no alignment): 255 on rows
+ *   max(first row - 1 - pad_top, 0) .. min(last row + 1 + pad_bottom, h) - 1 and columns max(first column - 1 - pad_x, 0) ..
+ *   min(last column + 1 + pad_x, w) - 1, 0 elsewhere; all 0 for a map without a counting pixel.  With pad_bottom = pad_y = int(0.03 h),
+ *   pad_top = 3 pad_y and pad_x = int(0.03 w) this plane is skeleton_to_mask's result byte for byte (its float32 channel mean is non-zero
+ *   exactly where a channel is, and every pixel it leaves outside the box is zero).
+ *   Three launches on `stream`: per-block extrema over 16-byte loads (scalar head and tail where a frame does not start or end on a
+ *   16-byte address), one wave per frame that folds them (fixed lanes, then a shuffle tree), and the fill, which reads boxes on the device (no host
+ *   round trip in between).  Integers only, no atomics, no block waits on another: a frame's result is the same alone or in a batch.
+ *   ws: dm4d_skeleton_box_mask_ws_bytes(n_frames, h, w) bytes (0 for a shape out of range), 4-byte aligned.                          */
+size_t dm4d_skeleton_box_mask_ws_bytes(int n_frames, int h, int w);
+int dm4d_skeleton_box_mask_u8(void* stream, const uint8_t* maps, int n_frames, int h, int w, int pad_top, int pad_bottom, int pad_x,
+                              int32_t* boxes, uint8_t* masks, int64_t mask_stride, void* ws, int64_t ws_bytes);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

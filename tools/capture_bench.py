@@ -13,6 +13,17 @@ skeletons, PNG masks) at the source size of ``--src WxH``, then for each task re
   pillow     Pillow crop + resize (BICUBIC) of the same 3 planes per frame on the host, same thread count (the reference's path)
 
   python tools/capture_bench.py --src 2448x2048 --out 1024 --threads 8 [--plucker cameras]
+
+With ``--skeleton-source kp2d --palette PATH`` the dataset draws the skeleton maps on the device from keypoint files (the scene gets a
+``poses_2d`` file per frame either way) and the report gains
+  read_kp2d        reading the task's keypoint files in the dataset's pool (wall)
+  plan             plan_draw_calls of every frame, one thread (wall)
+  draw_kernel      the dm4d_skeleton_draw_u8 launches (device events)
+  box_mask_kernel  the dm4d_skeleton_box_mask_u8 launches, only with --no-gt-target (device events)
+and decode counts the files that route still reads.  ``--no-gt-target`` builds the dataset with has_gt_target=False.  The drawing
+reproduces a size only where s * 2048 / max(h, w) is an integer (a square source always): use such a --src with kp2d.
+
+  python tools/capture_bench.py --src 2048x2048 --out 1024 --skeleton-source kp2d --palette tests/golden/skel_palette.json --no-gt-target
 """
 from __future__ import annotations
 
@@ -62,6 +73,13 @@ def write_scene(root: Path, W: int, H: int, n_cams: int, n_frames: int, temporal
         img = np.clip(img.astype(np.int16) + rng.integers(-8, 9, img.shape), 0, 255).astype(np.uint8)
         skel = np.zeros_like(img)
         skel[int(cy) - H // 4: int(cy) + H // 4, int(cx) - 4: int(cx) + 4] = (200, 80, 40 + c)
+        # a 133-keypoint figure inside the mask's ellipse, deterministic: every link of a 133-keypoint palette gets drawn
+        ang = np.arange(133) * 2.399963
+        rad = 0.15 + 0.8 * ((np.arange(133) * 37) % 133) / 133
+        kp = np.stack([cx + 0.2 * W * rad * np.cos(ang), cy + 0.4 * H * rad * np.sin(ang)], -1)
+        kpath = root / "poses_2d" / f"{c:02d}" / f"{t:06d}.json"
+        kpath.parent.mkdir(parents=True, exist_ok=True)
+        kpath.write_text(json.dumps({"instance_info": [{"keypoints": kp.round(2).tolist(), "keypoint_scores": [1.0] * 133}]}))
         for sub, arr, ext in (("images", img, "webp"), ("skeletons", skel, "webp"), ("fmasks", mask, "png")):
             p = root / sub / f"{c:02d}" / f"{t:06d}.{ext}"
             p.parent.mkdir(parents=True, exist_ok=True)
@@ -83,36 +101,68 @@ def bench_task(ds, spa, tem, inputs, threads: int) -> dict:
         labels = [(scene, s, t) for s in [near] + spa for t in tem]
     paths = [[ds.get_file_path(p, *lab) for p in (ds.image_path_pat, ds.fmask_path_pat, ds.skeleton_path_pat)] for lab in labels]
     modes = ("RGB", "L", "RGB")
+    kp2d = ds.skeleton_source == "kp2d"
+    # the files the route reads: no skeleton file with kp2d, and with has_gt_target=False only the skeleton file of a target
+    target = [not ds.has_gt_target and lab[1] not in inputs for lab in labels]
+    read = [[(p, m) for k, (p, m) in enumerate(zip(ps, modes)) if (k < 2 and not tg) or (k == 2 and not kp2d)] for ps, tg in zip(paths, target)]
     t0 = time.perf_counter()
-    list(ds._pool.map(lambda ps: [capture._open(p, m) for p, m in zip(ps, modes)], paths))
+    list(ds._pool.map(lambda pm: [capture._open(p, m) for p, m in pm], read))
     t_decode = time.perf_counter() - t0
+    extra = {}
+    if kp2d:
+        from diffuman4d_amd.host import skeleton
+        kpaths = [ds.get_file_path(ds.kp2d_path_pat, *lab) for lab in labels]
+        t0 = time.perf_counter()
+        insts = list(ds._pool.map(skeleton._read_instance, kpaths))
+        extra["read_kp2d_s"] = round(time.perf_counter() - t0, 3)
+        t0 = time.perf_counter()
+        for lab, inst in zip(labels, insts):
+            cam = ds.cameras[scene][lab[1]]
+            hw = (cam["height"], cam["width"])
+            skeleton.plan_draw_calls(inst, None, (ds.kp2d_canvas_shape or hw, hw), ds.palette)
+        extra["plan_s"] = round(time.perf_counter() - t0, 3)
+    load = ds._load_frame_kp2d if kp2d else ds._load_frame
+    resize = ds._resize_on_device_kp2d if kp2d else ds._resize_on_device
     t0 = time.perf_counter()
-    frames = list(ds._pool.map(lambda lab: ds._load_frame(lab, inputs), labels))
+    frames = list(ds._pool.map(lambda lab: load(lab, inputs), labels))
     t_frames = time.perf_counter() - t0
     # the device half, with the kernel bracketed by events on the dataset's stream
     ev = {}
-    real = capture.ops.capture_crop_resize
+    names = {"k": "capture_crop_resize", "draw": "skeleton_draw", "box": "skeleton_box_mask"}
+    real = {key: getattr(capture.ops, name) for key, name in names.items()}
 
-    def timed(*a, **k):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        out = real(*a, **k)
-        e.record()
-        ev["k"] = (s, e)
-        return out
-    capture.ops.capture_crop_resize = timed
+    def timed(key):
+        def call(*a, **k):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            out = real[key](*a, **k)
+            e.record()
+            ev.setdefault(key, []).append((s, e))
+            return out
+        return call
+    for key, name in names.items():
+        setattr(capture.ops, name, timed(key))
     try:
-        ds._resize_on_device(frames, dev)  # warm-up (allocations, first launch)
+        resize(frames, dev)  # warm-up (allocations, first launch)
+        ev.clear()
         t0 = time.perf_counter()
-        ds._resize_on_device(frames, dev)
+        resize(frames, dev)
         t_device = time.perf_counter() - t0
     finally:
-        capture.ops.capture_crop_resize = real
-    t_kernel = ev["k"][0].elapsed_time(ev["k"][1]) / 1e3
-    planes = sum(fr[n].size for fr in frames for n in ("img", "mask", "skel") if fr[n] is not None)
+        for key, name in names.items():
+            setattr(capture.ops, name, real[key])
+    seconds = lambda key: sum(s.elapsed_time(e) for s, e in ev.get(key, [])) / 1e3
+    t_kernel = seconds("k")
+    if kp2d:
+        extra["draw_kernel_s"], extra["box_mask_kernel_s"] = round(seconds("draw"), 5), round(seconds("box"), 5)
+    planes = sum(fr[n].size for fr in frames for n in ("img", "mask", "skel") if fr.get(n) is not None)
+    if kp2d:  # the planes that exist on the device only are read by the kernel all the same, but never cross PCIe
+        device_only = sum(fr["plan"].out_size[0] * fr["plan"].out_size[1] * (3 if fr["mask"] is not None else 4) for fr in frames)
+    else:
+        device_only = 0
     H, W = ds.height, ds.width
     rows = sum(fr["crop"][2] for fr in frames)  # scratch rows: about the crop height (the crop rows the vertical windows read)
-    moved = planes + 2 * rows * W * 8 + len(frames) * 6 * H * W * 4
+    moved = planes + device_only + 2 * rows * W * 8 + len(frames) * 6 * H * W * 4
     # H2D of a pinned buffer of the staging size
     blob = torch.empty(planes, dtype=torch.uint8, pin_memory=True)
     dst = torch.empty(planes, dtype=torch.uint8, device=dev)
@@ -136,7 +186,8 @@ def bench_task(ds, spa, tem, inputs, threads: int) -> dict:
     t0 = time.perf_counter()
     list(ds._pool.map(pil, paths))
     t_pil = time.perf_counter() - t0
-    return {"frames": len(labels), "decode_s": round(t_decode, 3), "host_prep_s": round(t_frames - t_decode, 3),
+    return {"frames": len(labels), "skeleton_source": ds.skeleton_source, "has_gt_target": ds.has_gt_target, **extra,
+            "decode_s": round(t_decode, 3), "host_prep_s": round(t_frames - t_decode, 3),
             "pack_s": round(t_device - t_kernel - t_h2d, 3), "h2d_s": round(t_h2d, 4), "h2d_gb_per_s": round(planes / t_h2d / 1e9, 1),
             "kernel_s": round(t_kernel, 4), "kernel_tb_per_s": round(moved / t_kernel / 1e12, 2),
             "kernel_frac_of_hbm": round(moved / t_kernel / 1e12 / HBM_TBPS, 3), "get_item_s": round(t_get, 3),
@@ -151,6 +202,12 @@ def main(argv=None):
     ap.add_argument("--frames", type=int, default=150)
     ap.add_argument("--dir", default=None, help="scene directory (default: a temporary one)")
     ap.add_argument("--plucker", default="host", choices=("host", "cameras"), help="the dataset's plucker mode")
+    ap.add_argument("--reuse-scene", action="store_true", help="with --dir: keep the scene a previous run wrote there instead of writing it again")
+    ap.add_argument("--skeleton-source", default="files", choices=capture.SKELETON_SOURCES, help="the dataset's skeleton_source")
+    ap.add_argument("--palette", default=None, help="palette file (skeleton.load_palette), required with --skeleton-source kp2d")
+    ap.add_argument("--no-gt-target", action="store_true", help="has_gt_target=False: target cameras are skeleton-only")
+    ap.add_argument("--compare-files", action="store_true",
+                    help="with kp2d: also report the share of skeleton-tensor elements that differ from the file route on the scene's lossy files")
     args = ap.parse_args(argv)
     W, H = (int(v) for v in args.src.split("x"))
     tmp = tempfile.TemporaryDirectory() if args.dir is None else None
@@ -158,11 +215,31 @@ def main(argv=None):
     scene = root / "bench"
     inputs = ["01", "13", "25", "37"]
     t0 = time.perf_counter()
-    write_scene(scene, W, H, 48, args.frames, temporal_cams=["03", "01"], threads=16)
-    print(f"# scene {W}x{H} written in {time.perf_counter() - t0:.1f} s", flush=True)
+    if args.reuse_scene and (scene / "transforms.json").exists():
+        print(f"# scene {scene} reused", flush=True)
+    else:
+        write_scene(scene, W, H, 48, args.frames, temporal_cams=["03", "01"], threads=16)
+        print(f"# scene {W}x{H} written in {time.perf_counter() - t0:.1f} s", flush=True)
     ds = capture.SpaTemDataset(data_dir=str(root), scene_label="bench", height=args.out, width=args.out,
-                               decode_threads=args.threads, plucker=args.plucker)
+                               decode_threads=args.threads, plucker=args.plucker, has_gt_target=not args.no_gt_target,
+                               skeleton_source=args.skeleton_source, palette=args.palette)
     res = {"src": args.src, "out": args.out, "threads": args.threads, "plucker": args.plucker}
+    if args.compare_files and args.skeleton_source == "kp2d":
+        # skeletons_q85/*.webp: quality-85 encodings of the drawn maps (what draw_skeleton writes); the scene's skeletons/ stay as they are
+        from diffuman4d_amd.host import skeleton
+        t0 = time.perf_counter()
+        skeleton.draw_skeleton(str(scene / "poses_2d"), str(scene / "skeletons_q85"), kp2d_canvas_shape=(H, W), out_kpmap_shape=(H, W),
+                               palette=args.palette)
+        files = capture.SpaTemDataset(data_dir=str(root), scene_label="bench", height=args.out, width=args.out, decode_threads=args.threads,
+                                      plucker="cameras", skeleton_path_pat="{data_dir}/{scene_label}/skeletons_q85/{spa_label}/{tem_label}.webp")
+        spa = [f"{c:02d}" for c in range(48)]
+        drawn = capture.SpaTemDataset(data_dir=str(root), scene_label="bench", height=args.out, width=args.out, decode_threads=args.threads,
+                                      plucker="cameras", skeleton_source="kp2d", palette=args.palette)
+        a = files.get_item("bench", spa, ["000000"], inputs)["skeletons"]
+        b = drawn.get_item("bench", spa, ["000000"], inputs)["skeletons"]
+        res["lossy_files_vs_kp2d"] = {"elements": a.numel(), "differing_share": round(float((a != b).float().mean()), 6),
+                                      "max_abs": round(float((a - b).abs().max()), 6), "seconds": round(time.perf_counter() - t0, 1)}
+        print(json.dumps(res["lossy_files_vs_kp2d"]), flush=True)
     res["spatial"] = bench_task(ds, [f"{c:02d}" for c in range(48)], ["000000"], inputs, args.threads)
     print(json.dumps(res["spatial"]), flush=True)
     res["temporal"] = bench_task(ds, ["03"], [f"{t:06d}" for t in range(args.frames)], inputs, args.threads)

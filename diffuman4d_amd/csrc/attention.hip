@@ -65,12 +65,6 @@ constexpr int RING = 2, AHEAD = 1;
 // independent workgroups per CU, so that a wave waiting at its workgroup's barrier shares its SIMD with a wave that is not
 constexpr float RESCALE_THR = 8.0f;  // in log2 units
 
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_p;
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 // LDS-DMA pieces (global_load_lds_dwordx4: lane i's 16 bytes land at lds_dst + 16 i) as volatile asm.  The builtin form
 // makes hipcc put an s_waitcnt vmcnt(0) in front of the next ds_read of the same array (it cannot tell the stages
 // apart), i.e. right behind the issue; an asm DMA has no VGPR destination, so hiding it from the compiler's counter
@@ -90,16 +84,6 @@ __device__ __forceinline__ void dma16(const void* ptr, uint32_t lds_dst) {
                : "v"(ptr), "s"(lds_dst)
                : "memory");
 }
-__device__ __forceinline__ uint32_t lds_addr(const void* shared_ptr) {
-  return (uint32_t)(uintptr_t)(lptr_t)shared_ptr;  // byte offset inside the workgroup's LDS allocation
-}
-
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
-  f32x2_t v = {lo, hi};
-  bf16x2_t b = __builtin_convertvector(v, bf16x2_t);  // v_cvt_pk_bf16_f32
-  return *reinterpret_cast<uint32_t*>(&b);
-}
-
 // H16 (template parameter of the kernels; precision "fp16", dm4d_attention_qscaled_kv_f16): Q / K / V / O and the probabilities are
 // IEEE fp16 instead of bf16 -- v_mfma_f32_32x32x16_f16 and v_cvt_pk_f16_f32 in place of their bf16 twins, same rate and fragment
 // layouts, so the loop is the same instruction for instruction.  What changes is the range: fp16 stops at 65504, so the optimistic
@@ -113,17 +97,6 @@ constexpr float H16_OFF = 8.0f;
 // [65520, 65536) rounds to +inf while its fp32 sum can still sit below 2^16, so the bound that sends a workgroup to the exact loop is
 // 2^15: a row sum below it has no term above 32768, which fp16 holds.
 constexpr float H16_L_MAX = 0x1p15f;
-template <bool H16>
-__device__ __forceinline__ uint32_t cvt_pk(float lo, float hi) {
-  if constexpr (H16) return pack_h2(lo, hi);
-  else return cvt_pk_bf16(lo, hi);
-}
-template <bool H16>
-__device__ __forceinline__ f32x16_t mfma16(const bf16x8_t& a, const bf16x8_t& b, const f32x16_t& c) {
-  if constexpr (H16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8_t, a), __builtin_bit_cast(h16x8_t, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
 // ------------------------------------------------------------------------------------------------
 // "Optimistic" softmax variant (default).  tools/probes/issue_probe.hip shows that on a gfx950 SIMD a wave that
 // streams MFMAs starves its co-resident waves' VALU instructions, so a tile costs (MFMA cycles + VALU cycles), and at
@@ -176,7 +149,7 @@ __device__ __forceinline__ void kv_loop(const AttnParams& p, const u16* Kb, cons
 #pragma unroll
       for (int kb = 0; kb < 2; ++kb) {
         bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(Ks + (buf * KV + kb * 32 + l31) * LDS_LD + j * 16 + lh * 8);
-        s[kb] = mfma16<H16>(kf, qf[j], s[kb]);
+        s[kb] = mfma32<H16>(kf, qf[j], s[kb]);
       }
     if ((t == nt - 1) && (Lk % KV) != 0) {
 #pragma unroll
@@ -220,10 +193,10 @@ __device__ __forceinline__ void kv_loop(const AttnParams& p, const u16* Kb, cons
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
         U4 w;
-        w.x = cvt_pk<H16>(pv[jj * 8 + 0], pv[jj * 8 + 1]);
-        w.y = cvt_pk<H16>(pv[jj * 8 + 2], pv[jj * 8 + 3]);
-        w.z = cvt_pk<H16>(pv[jj * 8 + 4], pv[jj * 8 + 5]);
-        w.w = cvt_pk<H16>(pv[jj * 8 + 6], pv[jj * 8 + 7]);
+        w.x = pack2<H16>(pv[jj * 8 + 0], pv[jj * 8 + 1]);
+        w.y = pack2<H16>(pv[jj * 8 + 2], pv[jj * 8 + 3]);
+        w.z = pack2<H16>(pv[jj * 8 + 4], pv[jj * 8 + 5]);
+        w.w = pack2<H16>(pv[jj * 8 + 6], pv[jj * 8 + 7]);
         pf[jj] = *reinterpret_cast<bf16x8_t*>(&w);
       }
 #pragma unroll
@@ -235,7 +208,7 @@ __device__ __forceinline__ void kv_loop(const AttnParams& p, const u16* Kb, cons
           s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(vp + 8 * LDS_LDV));
           s16x8_t v01 = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
           bf16x8_t vf = *reinterpret_cast<bf16x8_t*>(&v01);
-          o[db] = mfma16<H16>(vf, pf[jj], o[db]);
+          o[db] = mfma32<H16>(vf, pf[jj], o[db]);
         }
     }
     if (t + 1 < nt) store_tile(buf ^ 1);
@@ -318,7 +291,7 @@ __device__ __forceinline__ void kv_loop_pipelined(const AttnParams& p, const u16
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(Ks + stage * TILE + kb * 32 * 64 + k_lane[j]);
-      s = mfma16<H16>(kf, qf[j], (FOLD && j == 0) ? negm : s);
+      s = mfma32<H16>(kf, qf[j], (FOLD && j == 0) ? negm : s);
     }
   };
   auto mask_tail = [&](int t, f32x16_t (&s)[2]) {
@@ -342,10 +315,10 @@ __device__ __forceinline__ void kv_loop_pipelined(const AttnParams& p, const u16
 #pragma unroll
     for (int jj = 0; jj < 2; ++jj) {
       U4 w;
-      w.x = cvt_pk<H16>(pv[jj * 8 + 0], pv[jj * 8 + 1]);
-      w.y = cvt_pk<H16>(pv[jj * 8 + 2], pv[jj * 8 + 3]);
-      w.z = cvt_pk<H16>(pv[jj * 8 + 4], pv[jj * 8 + 5]);
-      w.w = cvt_pk<H16>(pv[jj * 8 + 6], pv[jj * 8 + 7]);
+      w.x = pack2<H16>(pv[jj * 8 + 0], pv[jj * 8 + 1]);
+      w.y = pack2<H16>(pv[jj * 8 + 2], pv[jj * 8 + 3]);
+      w.z = pack2<H16>(pv[jj * 8 + 4], pv[jj * 8 + 5]);
+      w.w = pack2<H16>(pv[jj * 8 + 6], pv[jj * 8 + 7]);
       pf[jj] = *reinterpret_cast<bf16x8_t*>(&w);
     }
   };
@@ -359,7 +332,7 @@ __device__ __forceinline__ void kv_loop_pipelined(const AttnParams& p, const u16
         s16x4_t v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_p)(vp + 8 * 64));
         s16x8_t v01 = __builtin_shufflevector(v0, v1, 0, 1, 2, 3, 4, 5, 6, 7);
         bf16x8_t vf = *reinterpret_cast<bf16x8_t*>(&v01);
-        o[db] = mfma16<H16>(vf, pf[jj], o[db]);
+        o[db] = mfma32<H16>(vf, pf[jj], o[db]);
       }
   };
 
@@ -435,6 +408,31 @@ __device__ __forceinline__ void kv_loop_pipelined(const AttnParams& p, const u16
   }
 }
 
+// 32 rows of O^T (two d-blocks of one row block) * inv -> wave-private LDS tile (32 rows x 144 B) -> whole 128-byte rows, 4 dwordx4
+// stores per wave (per-lane stores at the row stride touch a different row per lane: 8 dwordx2 instructions whose every lane opens its
+// own line).  The caller's loop ended with a workgroup barrier, so the K/V stages under `Os` are free; the same wave reads back what it
+// wrote (the LDS executes a wave's accesses in order), so there is no barrier between the two halves.
+template <bool H16>
+__device__ __forceinline__ void store_rows32(const f32x16_t (&o)[2], float inv, u16* Os, u16* Ob, int64_t ldo, int q_first, int L, int lane,
+                                             int l31, int lh) {
+#pragma unroll
+  for (int db = 0; db < 2; ++db)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      uint2 w;
+      w.x = pack2<H16>(o[db][4 * g + 0] * inv, o[db][4 * g + 1] * inv);
+      w.y = pack2<H16>(o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
+      *reinterpret_cast<uint2*>(Os + l31 * LDS_LDO + db * 32 + 8 * g + 4 * lh) = w;
+    }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int row = 8 * k + (lane >> 3), ch = lane & 7;
+    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(Os + row * LDS_LDO + ch * 8);
+    const int q = q_first + row;
+    if (q < L) *reinterpret_cast<u32x4_t*>(Ob + (int64_t)q * ldo + ch * 8) = v;
+  }
+}
+
 template <bool FOLD, int NW, bool H16 = false>
 __global__ __launch_bounds__(NW * 64, 2) void attn_kernel(AttnParams p) {  // two waves per SIMD: 8-wave workgroup alone, or two 4-wave workgroups
   constexpr int SMEM_EXACT = 2 * KV * LDS_LD + 2 * KV * LDS_LDV, SMEM_RINGS = 2 * RING * TILE;  // u16 elements
@@ -489,28 +487,7 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_kernel(AttnParams p) {  // tw
     kv_loop<true, FOLD, NW, H16>(p, Kb, Vb, Ks, Vs, v_lane, qf, o, m_run, l_run, tid, l31, lh);
     l_tot = l_run + __shfl_xor(l_run, 32);
   }
-  // Both loops end with a workgroup barrier, so the K/V stages are free: O goes through a wave-private LDS tile
-  // (32 rows x 144 B) and leaves as whole 128-byte rows, 4 dwordx4 stores per wave (per-lane stores at the row
-  // stride touch a different row per lane: 8 dwordx2 instructions whose every lane opens its own line).
-  const float inv = 1.0f / l_tot;
-  u16* Os = smem + wave * (32 * LDS_LDO);
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      uint2 w;
-      w.x = cvt_pk<H16>(o[db][4 * g + 0] * inv, o[db][4 * g + 1] * inv);
-      w.y = cvt_pk<H16>(o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
-      *reinterpret_cast<uint2*>(Os + l31 * LDS_LDO + db * 32 + 8 * g + 4 * lh) = w;
-    }
-  // the same wave reads back what it wrote (the LDS executes a wave's accesses in order): no barrier
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int row = 8 * k + (lane >> 3), ch = lane & 7;
-    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(Os + row * LDS_LDO + ch * 8);
-    const int q = q_tile0 + row;
-    if (q < L) *reinterpret_cast<u32x4_t*>(Ob + (int64_t)q * p.ldo + ch * 8) = v;
-  }
+  store_rows32<H16>(o, 1.0f / l_tot, smem + wave * (32 * LDS_LDO), Ob, p.ldo, q_tile0, L, lane, l31, lh);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -518,51 +495,12 @@ __global__ __launch_bounds__(NW * 64, 2) void attn_kernel(AttnParams p) {  // tw
 // 512-register file per wave; the main loop is a single asm statement with its own register allocation (tools/attn64/gen.py writes
 // attn64_asm.inc: register map, schedule, counted waits, static hazard check; tools/attn64/sim.py executes the stream on a numpy model of
 // the workgroup -- tests/test_attn64_sim.py).  What the C++ side does: the lane-constant addresses the stream takes as operands, the
-// epilogue (accumulator file -> normalise -> wave-private LDS tile -> whole 128-byte rows), and the exact running-max loop as the
+// epilogue (the stream's declared results -> normalise -> wave-private LDS tile -> whole 128-byte rows), and the exact running-max loop as the
 // in-kernel fallback of the optimistic soft-max, run per 32-row block with the 8-wave kernel's kv_loop<SAFE>.
 // Pre-scaled Q only (FOLD); Lk must be a multiple of 64 and at least three tiles (attention_launch falls back to attn_kernel otherwise).
 // Row sums come from the matrix pipe: v_mfma_f32_16x16x32 of a constant ones pattern (lanes 0 / 32: row 0, lanes 17 / 49: row 1) against
 // the PACKED probabilities, so the normaliser is the sum of exactly the values the PV product used.
 // ------------------------------------------------------------------------------------------------
-template <int BASE>
-__device__ __forceinline__ void acc_read16(f32x16_t& x) {
-  float t[16];
-#define ATTN64_RD(i) asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(t[i]) : "n"(BASE + i));
-  ATTN64_RD(0) ATTN64_RD(1) ATTN64_RD(2) ATTN64_RD(3) ATTN64_RD(4) ATTN64_RD(5) ATTN64_RD(6) ATTN64_RD(7)
-  ATTN64_RD(8) ATTN64_RD(9) ATTN64_RD(10) ATTN64_RD(11) ATTN64_RD(12) ATTN64_RD(13) ATTN64_RD(14) ATTN64_RD(15)
-#undef ATTN64_RD
-#pragma unroll
-  for (int i = 0; i < 16; ++i) x[i] = t[i];
-}
-template <int BASE>
-__device__ __forceinline__ float acc_read1() {
-  float t;
-  asm volatile("v_accvgpr_read_b32 %0, a[%1]" : "=v"(t) : "n"(BASE));
-  return t;
-}
-
-// 32 rows of O^T (two d-blocks of one row block) * inv -> wave-private LDS tile -> 4 row-wide stores
-template <bool H16>
-__device__ __forceinline__ void store_rows32(const f32x16_t (&o)[2], float inv, u16* Os, u16* Ob, int64_t ldo, int q_first, int L, int lane,
-                                             int l31, int lh) {
-#pragma unroll
-  for (int db = 0; db < 2; ++db)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      uint2 w;
-      w.x = cvt_pk<H16>(o[db][4 * g + 0] * inv, o[db][4 * g + 1] * inv);
-      w.y = cvt_pk<H16>(o[db][4 * g + 2] * inv, o[db][4 * g + 3] * inv);
-      *reinterpret_cast<uint2*>(Os + l31 * LDS_LDO + db * 32 + 8 * g + 4 * lh) = w;
-    }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int row = 8 * k + (lane >> 3), ch = lane & 7;
-    const u32x4_t v = *reinterpret_cast<const u32x4_t*>(Os + row * LDS_LDO + ch * 8);
-    const int q = q_first + row;
-    if (q < L) *reinterpret_cast<u32x4_t*>(Ob + (int64_t)q * ldo + ch * 8) = v;
-  }
-}
-
 template <bool H16>
 __global__ __launch_bounds__(256, 1) void attn64_kernel(AttnParams p) {
   constexpr int SMEM_EXACT = 2 * KV * LDS_LD + 2 * KV * LDS_LDV, SMEM_RINGS = 2 * RING * TILE;  // u16 elements; >= 4 * 32 * LDS_LDO
@@ -581,6 +519,10 @@ __global__ __launch_bounds__(256, 1) void attn64_kernel(AttnParams p) {
   u16* Ob = p.O + (int64_t)batch * L * p.ldo + head * 64;
   u16* Ks = smem;
   u16* Vs = smem + RING * TILE;
+  // results of the stream, bound to the registers it leaves them in (ATTN64_RESULTS): O^T (db, qb) = a[16 (2 db + qb) ..], row sums of
+  // block qb = a[64 + 4 qb] (rows 0..15, lanes 0..15) and a[65 + 4 qb] (rows 16..31)
+  f32x16_t o[2][2];  // [qb][db]
+  f32x8_t l;
   {
     // operands of the stream (tools/attn64/sim.py::wave_inputs restates these): fragment byte addresses inside stage 0 of each ring,
     // DMA source offsets of this lane's two pieces per operand, the first-row pointers of the two row blocks, the ones pattern
@@ -616,8 +558,8 @@ __global__ __launch_bounds__(256, 1) void attn64_kernel(AttnParams p) {
 #ifdef ATTN64_TIMING
     uint32_t ts[6];
 #define ATTN64_STAMPS [ts0] "=s"(ts[0]), [ts1] "=s"(ts[1]), [ts2] "=s"(ts[2]), [ts3] "=s"(ts[3]), [ts4] "=s"(ts[4]), [ts5] "=s"(ts[5])
-    if constexpr (H16) asm volatile(ATTN64_ASM_F16 : ATTN64_STAMPS : ATTN64_OPERANDS : ATTN64_CLOBBERS);
-    else asm volatile(ATTN64_ASM_BF16 : ATTN64_STAMPS : ATTN64_OPERANDS : ATTN64_CLOBBERS);
+    if constexpr (H16) asm volatile(ATTN64_ASM_F16 : ATTN64_RESULTS(o, l), ATTN64_STAMPS : ATTN64_OPERANDS : ATTN64_CLOBBERS);
+    else asm volatile(ATTN64_ASM_BF16 : ATTN64_RESULTS(o, l), ATTN64_STAMPS : ATTN64_OPERANDS : ATTN64_CLOBBERS);
     if (p.dbg && lane == 0) {
       unsigned long long* d = p.dbg + ((size_t)blockIdx.x * 4 + wave) * 3;
 #pragma unroll
@@ -625,26 +567,19 @@ __global__ __launch_bounds__(256, 1) void attn64_kernel(AttnParams p) {
     }
 #undef ATTN64_STAMPS
 #else
-    if constexpr (H16) asm volatile(ATTN64_ASM_F16 : : ATTN64_OPERANDS : ATTN64_CLOBBERS);
-    else asm volatile(ATTN64_ASM_BF16 : : ATTN64_OPERANDS : ATTN64_CLOBBERS);
+    if constexpr (H16) asm volatile(ATTN64_ASM_F16 : ATTN64_RESULTS(o, l) : ATTN64_OPERANDS : ATTN64_CLOBBERS);
+    else asm volatile(ATTN64_ASM_BF16 : ATTN64_RESULTS(o, l) : ATTN64_OPERANDS : ATTN64_CLOBBERS);
 #endif
 #undef ATTN64_OPERANDS
   }
-  // the stream ends behind a workgroup barrier with every DMA landed: the rings are free.  O^T (db, qb) = a[16 (2 db + qb) ..],
-  // row sums of block qb = a[64 + 4 qb] (rows 0..15, lanes 0..15) and a[65 + 4 qb] (rows 16..31)
-  f32x16_t o[2][2];  // [qb][db]
-  acc_read16<0>(o[0][0]);
-  acc_read16<16>(o[1][0]);
-  acc_read16<32>(o[0][1]);
-  acc_read16<48>(o[1][1]);
+  // the stream ends behind a workgroup barrier with every DMA landed: the rings are free
   float l_tot[2];
   if constexpr (ATTN64_ROWSUM_VALU) {  // a schedule with VALU row sums (tools/attn64/gen.py rowsum = pk | add): each lane's half of its row
-    const float a = acc_read1<64>(), b = acc_read1<68>();
-    l_tot[0] = a + __shfl_xor(a, 32);
-    l_tot[1] = b + __shfl_xor(b, 32);
+    l_tot[0] = l[0] + __shfl_xor(l[0], 32);
+    l_tot[1] = l[4] + __shfl_xor(l[4], 32);
   } else {
-    const float a0 = __shfl(acc_read1<64>(), l31 & 15), a1 = __shfl(acc_read1<65>(), l31 & 15);
-    const float b0 = __shfl(acc_read1<68>(), l31 & 15), b1 = __shfl(acc_read1<69>(), l31 & 15);
+    const float a0 = __shfl(l[0], l31 & 15), a1 = __shfl(l[1], l31 & 15);
+    const float b0 = __shfl(l[4], l31 & 15), b1 = __shfl(l[5], l31 & 15);
     l_tot[0] = l31 < 16 ? a0 : a1;
     l_tot[1] = l31 < 16 ? b0 : b1;
   }

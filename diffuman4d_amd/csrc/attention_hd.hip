@@ -41,10 +41,6 @@ struct AttnHdParams {
   float c;  // SPLIT: scale * log2(e); the pre-scaled forms ignore it
 };
 
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_p;
-
 constexpr int NW = 8;  // waves per workgroup, 32 query rows each
 
 template <int D>
@@ -59,16 +55,6 @@ struct HdGeom {
   static_assert(LDV >= DO && ((LDV / 2) % 64 == 16 || (LDV / 2) % 64 == 48), "V rows: four rows tile the banks");
 };
 
-template <bool H16>
-__device__ __forceinline__ f32x16_t mma(const bf16x8_t& a, const bf16x8_t& b, const f32x16_t& c) {
-  if constexpr (H16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8_t, a), __builtin_bit_cast(h16x8_t, b), c, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-template <bool H16>
-__device__ __forceinline__ uint32_t pk2(float lo, float hi) {
-  if constexpr (H16) return pack_h2(lo, hi);
-  else return pack_bf2(lo, hi);
-}
 __device__ __forceinline__ bf16x8_t as_frag(const U4& v) { return __builtin_bit_cast(bf16x8_t, v); }
 
 template <int D, int MODE>
@@ -180,10 +166,10 @@ __global__ __launch_bounds__(NW * 64) void attn_hd_kernel(AttnHdParams p) {
         const bf16x8_t kh = *reinterpret_cast<const bf16x8_t*>(smem + off);
         if constexpr (SPLIT) {
           const bf16x8_t kl = *reinterpret_cast<const bf16x8_t*>(smem + KS + off);
-          s[kb] = mma<false>(kl, qf[0][j], s[kb]);
-          s[kb] = mma<false>(kh, qf[NP - 1][j], s[kb]);
+          s[kb] = mfma32<false>(kl, qf[0][j], s[kb]);
+          s[kb] = mfma32<false>(kh, qf[NP - 1][j], s[kb]);
         }
-        s[kb] = mma<H16>(kh, qf[0][j], s[kb]);
+        s[kb] = mfma32<H16>(kh, qf[0][j], s[kb]);
       }
     if ((t == nt - 1) && (Lk % KT) != 0) {
 #pragma unroll
@@ -226,10 +212,10 @@ __global__ __launch_bounds__(NW * 64) void attn_hd_kernel(AttnHdParams p) {
 #pragma unroll
       for (int jj = 0; jj < 2; ++jj) {
         U4 w;
-        w.x = pk2<H16>(pv[jj * 8 + 0], pv[jj * 8 + 1]);
-        w.y = pk2<H16>(pv[jj * 8 + 2], pv[jj * 8 + 3]);
-        w.z = pk2<H16>(pv[jj * 8 + 4], pv[jj * 8 + 5]);
-        w.w = pk2<H16>(pv[jj * 8 + 6], pv[jj * 8 + 7]);
+        w.x = pack2<H16>(pv[jj * 8 + 0], pv[jj * 8 + 1]);
+        w.y = pack2<H16>(pv[jj * 8 + 2], pv[jj * 8 + 3]);
+        w.z = pack2<H16>(pv[jj * 8 + 4], pv[jj * 8 + 5]);
+        w.w = pack2<H16>(pv[jj * 8 + 6], pv[jj * 8 + 7]);
         pf[0][jj] = as_frag(w);
         if constexpr (SPLIT) {
           float lo[8];
@@ -253,10 +239,10 @@ __global__ __launch_bounds__(NW * 64) void attn_hd_kernel(AttnHdParams p) {
             vf[pl] = __builtin_bit_cast(bf16x8_t, v01);
           }
           if constexpr (SPLIT) {
-            o[db] = mma<false>(vf[1], pf[0][jj], o[db]);
-            o[db] = mma<false>(vf[0], pf[1][jj], o[db]);
+            o[db] = mfma32<false>(vf[1], pf[0][jj], o[db]);
+            o[db] = mfma32<false>(vf[0], pf[1][jj], o[db]);
           }
-          o[db] = mma<H16>(vf[0], pf[0][jj], o[db]);
+          o[db] = mfma32<H16>(vf[0], pf[0][jj], o[db]);
         }
     }
     if (t + 1 < nt) store_tile(buf ^ 1);
@@ -277,8 +263,8 @@ __global__ __launch_bounds__(NW * 64) void attn_hd_kernel(AttnHdParams p) {
 #pragma unroll
           for (int e = 0; e < 4; ++e) v[e] = o[db][4 * g + e] * inv;
           uint2 w;
-          w.x = pk2<H16>(v[0], v[1]);
-          w.y = pk2<H16>(v[2], v[3]);
+          w.x = pack2<H16>(v[0], v[1]);
+          w.y = pack2<H16>(v[2], v[3]);
           *reinterpret_cast<uint2*>(orow + d0) = w;
           if constexpr (SPLIT) {
             float lo[4];

@@ -5,6 +5,7 @@
 
 typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x16_t __attribute__((ext_vector_type(16)));
+typedef float f32x8_t __attribute__((ext_vector_type(8)));
 typedef float f32x4_t __attribute__((ext_vector_type(4)));
 typedef unsigned short u16;
 
@@ -93,6 +94,28 @@ __device__ __forceinline__ U4 pack8h_sat(const float* f) {
   v.w = pack_h2(sat_h(f[6]), sat_h(f[7]));
   return v;
 }
+
+// The one 32x32x16 MFMA of every kernel here, on bf16 or (H16) fp16 values held in the same registers: same rate, same fragment layout
+template <bool H16>
+__device__ __forceinline__ f32x16_t mfma32(const bf16x8_t& a, const bf16x8_t& b, const f32x16_t& c) {
+  if constexpr (H16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8_t, a), __builtin_bit_cast(h16x8_t, b), c, 0, 0, 0);
+  else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
+}
+// ... and the packing of two fp32 values into its operand type
+template <bool H16>
+__device__ __forceinline__ uint32_t pack2(float lo, float hi) {
+  if constexpr (H16) return pack_h2(lo, hi);
+  else return pack_bf2(lo, hi);
+}
+
+// LDS: transposing-read fragments (ds_read_b64_tr_b16), 16-byte rows, and the byte offset of a __shared__ object inside the workgroup's
+// allocation (what M0 and the address operand of a hand-written ds_read / LDS-DMA statement take)
+typedef short s16x4_t __attribute__((ext_vector_type(4)));
+typedef short s16x8_t __attribute__((ext_vector_type(8)));
+typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_p;
+typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) void* lptr_t;
+__device__ __forceinline__ uint32_t lds_addr(const void* shared_ptr) { return (uint32_t)(uintptr_t)(lptr_t)shared_ptr; }
 
 __device__ __forceinline__ U4 ldg16(const void* p) { return *reinterpret_cast<const U4*>(p); }
 __device__ __forceinline__ void stg16(void* p, const U4& v) { *reinterpret_cast<U4*>(p) = v; }

@@ -286,7 +286,7 @@ __device__ __forceinline__ void ff_fused_body(const GemmParams& p, const LnArgs&
   const int wm = wave >> 1, wn = wave & 1;
   const int l31 = lane & 31, lh = lane >> 5;
   const int m0 = blockIdx.x * FF_BM;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+  const uint32_t lds0 = lds_addr(smem);
 
   // ---- weight DMA: lane offsets are loop invariant, the step enters through the uniform base ----
   // W1p[s]: NSLAB slabs of [64 rows][64 k]; this wave moves rows 8 wave .. 8 wave + 7 of every slab (one 1-KiB instruction each)
@@ -603,7 +603,7 @@ __device__ __forceinline__ void l0_head_body(const HeadArgs& a, const LnArgs& ln
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 1, wn = wave & 1;
   const int m0 = blockIdx.x * FF_BM;
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+  const uint32_t lds0 = lds_addr(smem);
   float* stage = reinterpret_cast<float*>(smem + TILE_OFF);
 
   GemmParams pe{};

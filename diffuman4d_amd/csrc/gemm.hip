@@ -116,7 +116,6 @@ __global__ __launch_bounds__(256) void gemm_kernel_glds(GemmParams p) {
   int ky = 0, kx = 0, ci0 = 0;  // conv tap of the NEXT slab to be issued
 
   typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   auto issue_slab = [&](int kt, int buf) {
     if constexpr (CONV) {
       if (ci0 == 0) {  // first slab of a (ky,kx) tap: the only place the gather geometry is evaluated
@@ -325,7 +324,7 @@ __global__ __launch_bounds__(WM* WN * 64, (BN % 64 != 0 ? 2 : 1)) void conv_stri
     if (n > p.N - 1) n = p.N - 1;
     w_voff[i] = ((uint32_t)n * (uint32_t)p.ldw + (uint32_t)chunk * 8u) * 2u;
   }
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+  const uint32_t lds0 = lds_addr(smem);
 
   // ---- fragment read addresses (LDS byte offsets) ------------------------------------------------------------------
   unsigned edge[MI];  // bit 0: x == 0, 1: x == W-1, 2: y == 0, 3: y == H-1 of this lane's output pixel in row block i
@@ -593,7 +592,6 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel_pipe(GemmParams p) {
   int ky = 0, kx = 0, ci0 = 0;
 
   typedef const __attribute__((address_space(1))) void* gptr_t;
-  typedef __attribute__((address_space(3))) void* lptr_t;
   auto issue_slab = [&](int kt, int st) {
     u16* As = smem + st * STAGE;
     u16* Bs = As + BM * BK;
@@ -728,7 +726,7 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_lin2_kernel(GemmParams p) {
     const int row = (wave + NW * i) * RPI + d_row;
     w_voff[i] = (uint32_t)weight_row<TN>(p, n0, row, geglu) * (uint32_t)(p.ldw * 2) + (uint32_t)(d_pos ^ key(row)) * 16u;
   }
-  const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)smem;
+  const uint32_t lds0 = lds_addr(smem);
   const uint32_t a_dst0 = lds0 + wave * 1024, b_dst0 = lds0 + BM * ROWB + wave * 1024;
   const int k1 = p.A2 ? p.K1 : p.K;  // slabs below k1 come from A, the others from A2 (split A: K1 % 64 == 0)
   auto issue_slab = [&](int kt, int st) {

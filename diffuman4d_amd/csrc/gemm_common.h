@@ -44,11 +44,7 @@ __device__ __forceinline__ int weight_row(const GemmParams& p, int n0, int r, bo
 // the same registers hold fp16 values and go through v_mfma_f32_32x32x16_f16 (same rate, same fragment layout).
 template <int PAR = 0>
 __device__ __forceinline__ f32x16_t mfma_t(const bf16x8_t& a_rows, const bf16x8_t& w_rows, const f32x16_t& c) {
-  if constexpr (PAR == 2) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(h16x8_t, w_rows), __builtin_bit_cast(h16x8_t, a_rows), c, 0, 0, 0);
-  } else {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(w_rows, a_rows, c, 0, 0, 0);
-  }
+  return mfma32<PAR == 2>(w_rows, a_rows, c);
 }
 
 // Stage one 32-row block of a wave (JN 32-column blocks of the transposed accumulators `a`, first one J0; the bias is

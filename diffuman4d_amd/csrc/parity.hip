@@ -453,10 +453,6 @@ struct AttnSplitParams {
   float c;  // scale * log2(e)
 };
 
-typedef short s16x4_t __attribute__((ext_vector_type(4)));
-typedef short s16x8_t __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) s16x4_t* lds_s16x4_p;
-typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int KV = 64;
 constexpr int LDK = 72;  // K rows: 64 + 8 pad bf16

@@ -14,7 +14,7 @@ produce (guide: a compiler-placed stream of the same multiset costs +10 %):
   probability group two rounds ahead and the fragment reads two rounds ahead as fillers in the MFMA gaps; the step barrier sits in
   front of the last round's MFMAs, so that the first fragment reads of the new stages are covered by register-only MFMAs.
 
-Registers (asm-owned, listed as clobbers of the statement):
+Registers (asm-owned: clobbers of the statement, except the results, which are its outputs -- RESULTS below):
   v[0:63], v[64:127]   S sets 0 / 1: block (kb, qb) = 16 registers, S^T[key][q] (swapped QK^T: a lane holds 16 scores of ITS row)
   v[128:159]           -m per row block (C operand of the first QK^T MFMA of a block)
   v[160:191]           P: 8 groups (kb, jj, qb) x 4 registers of packed bf16 / fp16
@@ -68,6 +68,12 @@ def O(db, qb):
 
 def L(qb):
     return L_BASE + 4 * qb
+
+
+# What the statement hands back: (C++ operand of ATTN64_RESULTS(o, l), first AGPR, registers).  Physical-register OUTPUTS of the asm
+# statement, so they are left out of its clobber list and the end of the stream counts as a VALU read of each (check_hazards).
+RESULTS = [(f"o[{qb}][{db}]", O(db, qb), 16) for db in range(2) for qb in range(2)] + [("l", L_BASE, 8)]
+RESULT_REGS = [("a", base + i) for _, base, n in RESULTS for i in range(n)]
 
 
 def Q(qb, j):
@@ -499,10 +505,11 @@ def insert_lgkm_waits(ins: List[Ins], strict=True):
 
 
 # ---- static hazard check ---------------------------------------------------------------------------------------------------
-def check_hazards(ins: List[Ins]):
+def check_hazards(ins: List[Ins], live_out: Sequence[Reg] = ()):
     """Software wait states of gfx950 that matter here (calibrated against what hipcc pads, tools/attn64/README.md):
     VALU write -> MFMA read 2; trans write -> non-trans VALU read 1; MFMA (8 pass) write -> VALU read / write 12; MFMA (4 pass) -> 8;
-    VALU write -> v_permlane 2; s_mov m0 -> LDS-DMA 1.  Linear scan (branches fall through; targets are preceded by waits)."""
+    VALU write -> v_permlane 2; s_mov m0 -> LDS-DMA 1.  Linear scan (branches fall through; targets are preceded by waits).
+    `live_out`: registers the compiler may read (v_accvgpr_read_b32 / v_mov_b32: VALU) in the first slot behind the stream."""
     errs = []
     last_valu_w, last_trans_w, last_mfma_w, last_m0 = {}, {}, {}, None
     pos = 0
@@ -545,6 +552,11 @@ def check_hazards(ins: List[Ins]):
         if x.sim and x.sim[0] == "s_mov_m0":
             last_m0 = pos
         pos += n
+    for r in live_out:
+        if r in last_mfma_w:
+            p0, need = last_mfma_w[r]
+            if pos - p0 - 1 < need:
+                errs.append(f"MFMA->VALU {r} live out at the end of the stream ({pos - p0 - 1} < {need})")
     return errs
 
 
@@ -560,12 +572,15 @@ def emit_file(opts=None) -> str:
              "#pragma once\n"]
     for h16 in (False, True):
         prog = Program(Variant(h16), **opts).build()
-        errs = check_hazards(prog.ins)
+        errs = check_hazards(prog.ins, live_out=RESULT_REGS)
         if errs:
             raise SystemExit("hazards:\n" + "\n".join(errs[:40]))
         parts.append(f"#define ATTN64_ASM_{prog.var.name} \\\n" + render(prog) + "\n\n")
     parts.append(f"#define ATTN64_ROWSUM_VALU {int(prog.rowsum != 'mfma')}  // 1: a[64] / a[68] hold each lane's half of its row's sum\n")
-    clob = ", ".join([f'"v{i}"' for i in range(N_VGPR_CLOBBER)] + [f'"a{i}"' for i in range(N_AGPR_CLOBBER)] + [f'"s{i}"' for i in SGPR_CLOBBER] + ['"scc"', '"memory"'])
+    outs = ", ".join(f'"={{{rng("a", base, n)}}}"({name})' for name, base, n in RESULTS)
+    parts.append(f"#define ATTN64_RESULTS(o, l) {outs}  // f32x16_t o[qb][db]: O^T blocks; f32x8_t l: row sums of block qb from l[4 qb]\n")
+    clob = ", ".join([f'"v{i}"' for i in range(N_VGPR_CLOBBER)] + [f'"a{i}"' for i in range(N_AGPR_CLOBBER) if ("a", i) not in RESULT_REGS] +
+                     [f'"s{i}"' for i in SGPR_CLOBBER] + ['"scc"', '"memory"'])
     parts.append(f"#define ATTN64_CLOBBERS {clob}\n")
     return "".join(parts)
 

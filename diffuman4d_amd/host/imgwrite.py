@@ -37,7 +37,8 @@ def restore_cropped_image(image, crop_param: Optional[Sequence[int]], ori_size=N
 
 def write_package(pkg: Dict[str, Any]) -> int:
     """Write one task's files.  pkg = {"grid": (path, uint8 [H, W, 3]) | None, "images": [(path, uint8 [H, W, 3], crop | None)],
-    "crops": [(path, crop | None)], "quality": int}.  Returns the number of image files written."""
+    "crops": [(path, crop | None)], "quality": int}; a package packed with ``device_jpeg`` carries "jpegs": [(path, bytes)], finished
+    files that are written verbatim, in place of "images".  Returns the number of image files written."""
     from PIL import Image
     grid = pkg.get("grid")
     if grid is not None:
@@ -50,6 +51,13 @@ def write_package(pkg: Dict[str, Any]) -> int:
             continue  # e.g. input views written by an earlier task (sampling_utils.py:105-106)
         os.makedirs(os.path.dirname(path), exist_ok=True)
         restore_cropped_image(Image.fromarray(arr), crop).save(path, quality=pkg.get("quality", 90))
+        written += 1
+    for path, data in pkg.get("jpegs", ()):
+        if os.path.isfile(path):
+            continue
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "wb") as f:
+            f.write(data)
         written += 1
     for path, crop in pkg.get("crops", ()):
         os.makedirs(os.path.dirname(path), exist_ok=True)

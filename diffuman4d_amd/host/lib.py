@@ -122,6 +122,11 @@ SIGNATURES = {
     # bounding box + box mask of drawn maps, for the dataset's skeleton-only targets (host/capture.py, skeleton_source="kp2d")
     "dm4d_skeleton_box_mask_ws_bytes": (C.c_size_t, [_i, _i, _i]),
     "dm4d_skeleton_box_mask_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64]),
+    # result images: crop restore onto a white canvas and the baseline JPEG scan of a batch of images (host/jpeg.py)
+    "dm4d_restore_crop_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i64]),
+    "dm4d_jpeg_scan_bound": (C.c_size_t, [_i, _i]),
+    "dm4d_jpeg_ws_bytes": (C.c_size_t, [_i64, _i]),
+    "dm4d_jpeg_encode_rgb_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
 }
 
 EPI_GEGLU = 1

@@ -1339,3 +1339,102 @@ def skeleton_box_mask(maps: torch.Tensor, pads: Tuple[int, int, int], masks: Opt
     rc = lib.dm4d_skeleton_box_mask_u8(_stream(), _p(maps), B, h, w, pad_top, pad_bottom, pad_x, _p(boxes), _p(masks), h * w, _p(ws), nbytes)
     _l.check(rc, "dm4d_skeleton_box_mask_u8")
     return boxes, masks
+
+
+JPEG_FIELDS = 8             # include/dm4d.h DM4D_JPEG_FIELDS
+RESTORE_FIELDS = 16         # include/dm4d.h DM4D_RESTORE_FIELDS
+JPEG_MCU_UNSTUFFED = 1248   # include/dm4d.h DM4D_JPEG_MCU_UNSTUFFED
+JPEG_CHUNK = 4096           # include/dm4d.h DM4D_JPEG_CHUNK
+
+
+def restore_crops(pixels: torch.Tensor, items, device) -> Tuple[torch.Tensor, list]:
+    """``imgwrite.restore_cropped_image`` of a batch on the device (dm4d_restore_crop_u8, two launches): items = [(byte offset of the
+    uint8 [H, W, 3] image in `pixels`, H, W, (ct, cl, ch, cw), (canvas h, canvas w))] -> (uint8 buffer of the canvases, their byte
+    offsets in it).  The coefficient tables are Pillow's (host/capture.py bicubic_table)."""
+    from .capture import bicubic_table
+    lib = _l.load()
+    _req(pixels, "pixels", torch.uint8)
+    desc = torch.zeros((len(items), RESTORE_FIELDS), dtype=torch.int64)
+    tabs, tab_at, tab_len, scratch_len, canvas_len, places = [], {}, 0, 0, 0, []
+
+    def table(n_in: int, n_out: int) -> Tuple[int, int]:
+        nonlocal tab_len
+        if (n_in, n_out) not in tab_at:
+            bounds, k = bicubic_table(n_in, n_out)
+            tab_at[(n_in, n_out)] = (tab_len, k.shape[1])
+            tabs.extend([torch.from_numpy(bounds.reshape(-1).copy()), torch.from_numpy(k.reshape(-1).copy())])
+            tab_len += bounds.size + k.size
+        return tab_at[(n_in, n_out)]
+
+    for i, (src, H, W, (ct, cl, ch, cw), (h, w)) in enumerate(items):
+        htab, hk = table(W, cw)
+        vtab, vk = table(H, ch)
+        desc[i, :15] = torch.tensor([src, H, W, ct, cl, ch, cw, h, w, htab, hk, vtab, vk, scratch_len, canvas_len])
+        places.append(canvas_len)
+        scratch_len += (H * cw * 3 + 15) // 16 * 16
+        canvas_len += (h * w * 3 + 15) // 16 * 16
+    tab = torch.cat(tabs).to(torch.int32).contiguous()
+    scratch = torch.empty(scratch_len, dtype=torch.uint8, device=device)
+    canvases = torch.empty(canvas_len, dtype=torch.uint8, device=device)
+    desc_dev, tab_dev = desc.to(device), tab.to(device)
+    rc = lib.dm4d_restore_crop_u8(_stream(), _p(pixels), pixels.numel(), desc.data_ptr(), _p(desc_dev), len(items), tab.data_ptr(),
+                                  _p(tab_dev), tab.numel(), _p(scratch), scratch.numel(), _p(canvases), canvases.numel())
+    _l.check(rc, "dm4d_restore_crop_u8")
+    return canvases, places
+
+
+def jpeg_encode_chunk(images, crops, sizes, qtab) -> list:
+    """Entropy-coded JPEG segments (bytes) of device uint8 [H, W, 3] tensors, each first restored onto its canvas where crops[k] is
+    not None (sizes[k] = the canvas' (h, w)); qtab: 128 integers, luma then chroma quantisation table in natural order.
+    Images that are views of one storage are read in place, otherwise they are gathered into one buffer first.  One host
+    synchronisation (the lengths) and one copy of exactly the bytes produced."""
+    lib = _l.load()
+    dev = images[0].device
+    for k, img in enumerate(images):
+        _req(img, f"images[{k}]", torch.uint8)
+        if img.device != dev or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
+            raise _l.Dm4dError(f"images[{k}]: expected a contiguous uint8 [H, W, 3] tensor on {dev}, got {tuple(img.shape)} on {img.device}")
+    with torch.cuda.device(dev):
+        base = images[0].untyped_storage().data_ptr()
+        if all(img.untyped_storage().data_ptr() == base for img in images):
+            pixels = torch.empty(0, dtype=torch.uint8, device=dev).set_(images[0].untyped_storage())
+            at = [img.data_ptr() - base for img in images]
+        else:
+            pixels = torch.cat([img.reshape(-1) for img in images])
+            at = [0]
+            for img in images[:-1]:
+                at.append(at[-1] + img.numel())
+        n = len(images)
+        cropped = [k for k in range(n) if crops[k] is not None]
+        canvases, places = None, {}
+        if cropped:
+            canvases, where = restore_crops(pixels, [(at[k], images[k].shape[0], images[k].shape[1], tuple(crops[k][:4]), sizes[k])
+                                                     for k in cropped], dev)
+            places = dict(zip(cropped, where))
+        desc = torch.zeros((n, JPEG_FIELDS), dtype=torch.int64)
+        mcu0 = chunk0 = bound = 0
+        for k, (h, w) in enumerate(sizes):
+            mcus = ((h + 15) // 16) * ((w + 15) // 16)
+            b = int(lib.dm4d_jpeg_scan_bound(h, w))
+            if b == 0:
+                raise _l.Dm4dError(f"images[{k}]: size {h} x {w} is out of range for the JPEG encoder")
+            desc[k, :6] = torch.tensor([1, places[k], h, w, mcu0, chunk0] if k in places else [0, at[k], h, w, mcu0, chunk0])
+            mcu0, chunk0, bound = mcu0 + mcus, chunk0 + (mcus * JPEG_MCU_UNSTUFFED + JPEG_CHUNK - 1) // JPEG_CHUNK, bound + b
+        nbytes = int(lib.dm4d_jpeg_ws_bytes(mcu0, n))
+        if nbytes == 0:
+            raise _l.Dm4dError(f"jpeg_encode_chunk: {n} images with {mcu0} MCUs are out of range for one call")
+        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+        blob = torch.empty(bound, dtype=torch.uint8, device=dev)
+        out = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        q = torch.tensor([int(v) for v in qtab], dtype=torch.int16)  # values 1..255: the same bytes as uint16
+        desc_dev, q_dev = desc.to(dev), q.to(dev)
+        rc = lib.dm4d_jpeg_encode_rgb_u8(_stream(), _p(pixels) if pixels.numel() else None, pixels.numel(), _p(canvases),
+                                         0 if canvases is None else canvases.numel(), desc.data_ptr(), _p(desc_dev), n, q.data_ptr(),
+                                         _p(q_dev), _p(ws), ws.numel() * 8, _p(blob), blob.numel(), _p(out))
+        _l.check(rc, "dm4d_jpeg_encode_rgb_u8")
+        where = out.cpu().tolist()  # the one synchronisation: n offsets, then n lengths
+        total = where[n - 1] + where[2 * n - 1]
+        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        host.copy_(blob[:total])
+        data = host.numpy().tobytes()
+    return [data[where[k]:where[k] + where[n + k]] for k in range(n)]

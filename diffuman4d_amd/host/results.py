@@ -82,12 +82,17 @@ def make_image_grid_device(images: torch.Tensor, nrow: int, padding: int = 2) ->
 @torch.no_grad()
 def pack_results_on_device(sample: Dict[str, Any], images: torch.Tensor, output_dir: str = "./results", save_image_grid: bool = True,
                            save_output_image: bool = True, save_crop_param: bool = False, image_ext: str = ".jpg",
-                           image_quality: int = 90, max_image_size: int = 8192, device=None) -> Dict[str, Any]:
+                           image_quality: int = 90, max_image_size: int = 8192, device=None, device_jpeg: bool = False) -> Dict[str, Any]:
     """``save_sampling_results`` up to (not including) the file encoding, evaluated on the device `images` lives on.
 
     images: the pipeline's decoded output [N, 3, H, W] in [0, 1], still on the GPU.  ``sample`` as the sampler builds it
     (``pixel_values`` / ``skeletons`` are the host tensors: they are uploaded once more in fp32, which is what the reference's
-    arithmetic reads).  Returns the package ``imgwrite.write_package`` consumes: uint8 HWC numpy arrays + paths + crop tuples."""
+    arithmetic reads).  Returns the package ``imgwrite.write_package`` consumes: uint8 HWC numpy arrays + paths + crop tuples.
+
+    device_jpeg: the crop restore and the JPEG encoding of the saved views run on the device as well (host/jpeg.py); the package then
+    carries ``"jpegs": [(path, file bytes)]`` instead of ``"images"``, the same bytes the writer would have produced."""
+    if device_jpeg and image_ext.lower() not in (".jpg", ".jpeg"):
+        raise ValueError(f"device_jpeg encodes JPEG files only: image_ext {image_ext!r} is neither '.jpg' nor '.jpeg'")
     # `device`: where the arithmetic runs (the sampler passes the pipeline's).  With decode_policy "denoised" a task of an early round
     # returns a zero-stride HOST placeholder for its images (nothing was decoded): the packer must not follow it onto the CPU -- 194 of
     # the 344 tasks of demo_4d then built their mosaics with host arithmetic, 130 s of a 303 s run (profiles/r04_e2e_demo_4d_fast.json)
@@ -99,7 +104,7 @@ def pack_results_on_device(sample: Dict[str, Any], images: torch.Tensor, output_
     input_indices = sample["input_indices"].to(dev)
     target_indices = set(int(i) for i in sample["target_indices"])
     inp = sample["pixel_values"].to(dev, non_blocking=True).float() * 0.5 + 0.5  # denorm_vae_tensor
-    pkg: Dict[str, Any] = {"grid": None, "images": [], "crops": [], "quality": int(image_quality)}
+    pkg: Dict[str, Any] = {"grid": None, "jpegs" if device_jpeg else "images": [], "crops": [], "quality": int(image_quality)}
     staged = []  # (device uint8 tensor, consumer) pairs: one synchronisation for all D2H copies
 
     if save_image_grid:
@@ -143,7 +148,12 @@ def pack_results_on_device(sample: Dict[str, Any], images: torch.Tensor, output_
         is_input[input_indices] = True
         sel = torch.where(is_input[idx][:, None, None, None], inp[idx], out[idx])  # input views are saved from the input images
         u8 = (sel.clamp(0, 1) * 255.0).to(torch.uint8).permute(0, 2, 3, 1).contiguous()  # to_pil_image: mul(255).byte()
-        staged.append((u8, ("images", meta)))
+        if device_jpeg:
+            from .jpeg import encode_jpeg_batch
+            files = encode_jpeg_batch(list(u8.unbind(0)), quality=int(image_quality), crops=[crop for _, crop in meta])
+            pkg["jpegs"] = [(path, data) for (path, _), data in zip(meta, files)]
+        else:
+            staged.append((u8, ("images", meta)))
     host = []
     for t, tag in staged:
         if dev.type == "cuda":

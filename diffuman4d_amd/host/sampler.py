@@ -12,7 +12,7 @@ What is organised differently here:
   * ``result_writer`` is injectable (the reference hard-wires ``save_sampling_results``);
   * ``partition(round, rank, world)`` exposes the per-round task sharding used by the one-process-per-GPU runner;
   * optional pipeline extensions (``vae_cache``, ``decode_policy``, ``prune_cond_rows``, ``plucker_on_device``,
-    ``device_results``), off by default.
+    ``device_results``, ``device_jpeg``), off by default.
 """
 from __future__ import annotations
 
@@ -63,7 +63,7 @@ class SlidingIterativeSampler:
                  spa_labels: Optional[Sequence[int]] = None, tem_labels: Optional[Sequence[int]] = None,
                  input_spa_labels: Sequence[int] = (1, 13, 25, 37), result_writer: Optional[Callable] = None,
                  vae_cache: bool = False, decode_policy: str = "all", prune_cond_rows: bool = False,
-                 plucker_on_device: bool = False, device_results: bool = False):
+                 plucker_on_device: bool = False, device_results: bool = False, device_jpeg: bool = False):
         self.dataset, self.pipelines, self.output_dir = dataset, pipelines, output_dir
         self.sweep = SweepConfig(window_size, sliding_stride, sliding_shift, bidirectional, num_denoising_steps,
                                  alternation_rounds, guidance_scale)
@@ -74,6 +74,11 @@ class SlidingIterativeSampler:
         # HIP device, the sampler keeps the reference's contract (float CPU `images` handed to the writer).
         on_hip = bool(pipelines) and all(getattr(getattr(p, "device", None), "type", "cpu") == "cuda" for p in pipelines)
         self.device_results = bool(device_results) and result_writer is None and on_hip and torch.cuda.is_available()
+        # device_jpeg: with device_results, the saved views leave the device as finished JPEG files (host/jpeg.py: crop restore and
+        # encoding on the GPU, the bytes Pillow would write); the writer only stores them
+        if device_jpeg and not device_results:
+            raise ValueError("device_jpeg needs device_results=True (the JPEG files are part of the device-side package)")
+        self.device_jpeg = bool(device_jpeg) and self.device_results
         if result_writer is None:
             if self.device_results:
                 from .results import write_packed_results as result_writer
@@ -259,7 +264,8 @@ class SlidingIterativeSampler:
         sample["fully_denoised"] = result["fully_denoised"].cpu()
         if self.device_results and on_gpu and self.result_writer is not None:  # (device_results is off for caller-supplied writers)
             from .results import pack_results_on_device
-            sample["_package"] = pack_results_on_device(sample, result["images"], output_dir=self.output_dir, device=pipe.device)
+            sample["_package"] = pack_results_on_device(sample, result["images"], output_dir=self.output_dir, device=pipe.device,
+                                                        device_jpeg=self.device_jpeg)
             sample["images"] = None  # the float images never leave the device (the package holds what gets written)
         elif getattr(self, "shard_follower", False):
             sample["images"] = None  # nothing was decoded on this rank and nothing will be written

@@ -392,6 +392,49 @@ size_t dm4d_skeleton_box_mask_ws_bytes(int n_frames, int h, int w);
 int dm4d_skeleton_box_mask_u8(void* stream, const uint8_t* maps, int n_frames, int h, int w, int pad_top, int pad_bottom, int pad_x,
                               int32_t* boxes, uint8_t* masks, int64_t mask_stride, void* ws, int64_t ws_bytes);
 
+/* Result images on the device (jpeg.hip): the two host steps of the reference's result writer, sampling_utils.py:95-114
+ *   (`restore_cropped_image(to_pil_image(img), crop).save(path, quality=90)`) and image_utils.py:62-93 (restore_cropped_image).
+ *
+ * dm4d_restore_crop_u8 (image_utils.py:62-93): per image, Pillow's Image.resize((cw, ch), BICUBIC) of the H x W RGB source (horizontal
+ *   pass rounded to uint8 into `scratch`, then the vertical pass: the arithmetic of dm4d_capture_crop_resize_f32) pasted at (cl, ct) of a
+ *   white canvas_h x canvas_w canvas, clipped to the canvas.  Two launches for all images.  desc: n x DM4D_RESTORE_FIELDS int64 = {source
+ *   byte offset in pixels | H, W | ct, cl, ch, cw | canvas_h, canvas_w | horizontal table offset, ksize | vertical table offset, ksize |
+ *   scratch byte offset (H x cw x 3 bytes) | canvas byte offset in canvases | 0}; tab as for dm4d_capture_crop_resize_f32 (W -> cw and
+ *   H -> ch).  desc_host / tab_host are host copies of desc_dev / tab_dev; every size, offset, window and region is validated on them
+ *   before anything is launched, and canvas regions may not overlap (they must be listed in ascending order).
+ *
+ * dm4d_jpeg_encode_rgb_u8 (sampling_utils.py:95-114, PIL's Image.save(path, quality=q) of an RGB image): the entropy-coded segment of
+ *   the baseline 4:2:0 JPEG libjpeg writes with the Annex-K Huffman tables, for n images of different sizes in one call, byte for byte.
+ *   Integer arithmetic only.  Eight launches for the whole batch and no workgroup waits for another: coefficients (colour conversion,
+ *   h2v2 downsample, jfdctint "islow", quantisation, zig-zag; one wave per 16 x 16 MCU), Huffman bit length of every MCU, a scan per
+ *   image, emission of the unstuffed bit stream (the MCU in which a byte starts writes it; the few trailing bits come from the next
+ *   MCU's "head bits" of the sizing pass), 0xFF counts per DM4D_JPEG_CHUNK bytes, their scan, the images' offsets, and the stuffed write.
+ *   An image's bytes do not depend on the rest of the batch.
+ *   desc: n x DM4D_JPEG_FIELDS int64 = {space: 0 = pixels, 1 = canvases | byte offset of the uint8 HWC image there (rows tight) |
+ *   h, w in 1..65535 | index of the image's first MCU = the MCUs of the images before it | index of its first stuffing chunk = the sum of
+ *   ceil(mcus * DM4D_JPEG_MCU_UNSTUFFED / DM4D_JPEG_CHUNK) before it | 0, 0}.  qtab: uint16 [2][64], the luma and chroma quantisation
+ *   tables in natural order, values 1..255.  desc_host / qtab_host are host copies, validated before anything is launched.
+ *   Bound per MCU: a block codes at most 20 bits of DC (9 + 11) and 63 x 26 bits of AC (16 + 10), so an MCU of six blocks is at most
+ *   9948 bits = 1244 bytes unstuffed (DM4D_JPEG_MCU_UNSTUFFED reserves 1248) and, were every byte 0xFF, DM4D_JPEG_MCU_BOUND = 2488 bytes
+ *   stuffed; the padded last byte is inside that count.  An MCU is never shorter than 32 bits (4 x (2 + 4) + 2 x (2 + 2)).
+ *   dm4d_jpeg_scan_bound(h, w) = mcus * DM4D_JPEG_MCU_BOUND (0 for a size outside 1..65535 or one whose bit count could pass 2^32).
+ *   blob: the n scans back to back; blob_bytes >= the sum of the images' bounds.  out: device int64 [2 n] = n byte offsets into blob,
+ *   then n lengths; the host reads them and copies blob[: offset[n - 1] + length[n - 1]].
+ *   workspace: dm4d_jpeg_ws_bytes(total MCUs, n) bytes, 16-byte aligned (0 for counts out of range).                                    */
+#define DM4D_RESTORE_FIELDS 16
+#define DM4D_JPEG_FIELDS 8
+#define DM4D_JPEG_MCU_UNSTUFFED 1248
+#define DM4D_JPEG_MCU_BOUND 2488
+#define DM4D_JPEG_CHUNK 4096
+int dm4d_restore_crop_u8(void* stream, const void* pixels, int64_t pixels_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
+                         const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len, void* scratch, int64_t scratch_bytes,
+                         void* canvases, int64_t canvases_bytes);
+size_t dm4d_jpeg_scan_bound(int h, int w);
+size_t dm4d_jpeg_ws_bytes(int64_t total_mcus, int n);
+int dm4d_jpeg_encode_rgb_u8(void* stream, const void* pixels, int64_t pixels_bytes, const void* canvases, int64_t canvases_bytes,
+                            const int64_t* desc_host, const int64_t* desc_dev, int n, const uint16_t* qtab_host, const uint16_t* qtab_dev,
+                            void* workspace, int64_t workspace_bytes, void* blob, int64_t blob_bytes, int64_t* out);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

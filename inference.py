@@ -42,6 +42,8 @@ def inference(cfg: dict):
     # every task's result is bitwise what it is alone); gpu_streams=1 task_batch=1 = the reference's one-task-at-a-time order
     # runner.writer_processes=N (default 0): with sampler.device_results=true the JPEG / WebP encoding of every task's uint8
     # package runs in N writer processes (host/imgwrite.py) instead of the writer threads
+    # sampler.device_jpeg=true (with sampler.device_results=true): crop restore and JPEG encoding on the GPU as well (host/jpeg.py); the
+    # writers then only store finished files
     rk = {k: int(v) for k, v in (cfg.get("runner") or {}).items()
           if k in ("prefetch_depth", "writers", "gpu_streams", "writer_processes", "task_batch")}
     # runner.host_threads=N: torch's intra-op CPU threads for the host-side stages (loader, writer).  The 256-thread GPU hosts

@@ -46,6 +46,9 @@ def main():
     ap.add_argument("--device-results", action="store_true",
                     help="sampler.device_results=true: the result writer's arithmetic (mosaic, |out - in|, down-scale, uint8) on the GPU, "
                          "one uint8 package per task over PCIe")
+    ap.add_argument("--device-jpeg", action="store_true",
+                    help="sampler.device_jpeg=true (needs --device-results): crop restore and JPEG encoding of the saved views on the GPU, "
+                         "finished file bytes over PCIe")
     ap.add_argument("--writer-processes", type=int, default=0, help="runner.writer_processes: encode the packages in N processes")
     ap.add_argument("--host-threads", type=int, default=0, help="torch.set_num_threads for the host stages (0 = torch's default)")
     ap.add_argument("--timeline", default=None, help="write per-task stage intervals (load / denoise / save: start, end, thread) as JSON")
@@ -65,7 +68,8 @@ def main():
                           "model.gpu_ids=[0]", f"data.height={H}", f"data.width={W}", f"result_dir={work / 'results'}"]
                          + (["sampler.vae_cache=true", "sampler.decode_policy=denoised"] if a.fast_vae else [])
                          + (["sampler.prune_cond_rows=true"] if a.prune else [])
-                         + (["sampler.device_results=true"] if a.device_results else []) + a.overrides)
+                         + (["sampler.device_results=true"] if a.device_results else [])
+                         + (["sampler.device_jpeg=true"] if a.device_jpeg else []) + a.overrides)
     if a.host_threads > 0:
         torch.set_num_threads(a.host_threads)
     t0 = time.perf_counter()
@@ -143,7 +147,7 @@ def main():
         "latents_per_s_end_to_end": round(n_lat / wall, 3),
         "stage_seconds": {k: round(v, 3) for k, v in acc.items()},
         "denoise_stage_busy_fraction": round(busy_any / wall, 4),
-        "device_results": a.device_results, "writer_processes": a.writer_processes, "host_threads": torch.get_num_threads(),
+        "device_results": a.device_results, "device_jpeg": a.device_jpeg, "writer_processes": a.writer_processes, "host_threads": torch.get_num_threads(),
         "checkpoint_write_s": round(t_ckpt, 2), "pipeline_load_s": round(t_load, 2),
     }), flush=True)
     if a.workdir is None:

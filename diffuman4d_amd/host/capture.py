@@ -35,7 +35,7 @@ from .dataset import plucker_maps, relative_poses
 
 log = logging.getLogger(__name__)
 
-FIELDS = 16  # int64 fields of one frame descriptor (include/dm4d.h DM4D_CAPTURE_FIELDS)
+FIELDS = ops.CAPTURE_FIELDS  # int64 fields of one frame descriptor: an alias of the one mirror in host/lib.py, not a second copy
 PRECISION_BITS = 22  # Pillow's fixed-point coefficients for 8-bit images (libImaging/Resample.c)
 _ALIGN = 16
 

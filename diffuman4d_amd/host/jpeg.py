@@ -14,6 +14,11 @@ from __future__ import annotations
 import struct
 from typing import List, Optional, Sequence, Tuple
 
+import torch
+
+from . import lib as _l
+from .ops import _p, _req, _stream
+
 # -- Annex K ------------------------------------------------------------------------------------------------------------------------
 QUANT_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
               18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100,
@@ -46,8 +51,6 @@ def _zigzag() -> Tuple[int, ...]:
 
 ZIGZAG = _zigzag()  # ZIGZAG[k] = natural (row-major) index of the k-th coefficient of the scan
 
-MCU_BOUND = 2488      # include/dm4d.h DM4D_JPEG_MCU_BOUND: bytes of stuffed scan per 16 x 16 MCU, worst case
-MCU_UNSTUFFED = 1248  # include/dm4d.h DM4D_JPEG_MCU_UNSTUFFED: workspace bytes of unstuffed scan per MCU
 DEFAULT_WORKSPACE = 1 << 30
 
 
@@ -98,10 +101,100 @@ def _pad16(n: int) -> int:
 def _image_bytes(img, crop, hw) -> int:
     """Device bytes one image of a batch needs: canvas + resize scratch + encoder workspace + its share of the blob."""
     m = _mcus(*hw)
-    n = m * (768 + 8 + MCU_UNSTUFFED + MCU_BOUND) + 64
+    n = m * (768 + 8 + _l.JPEG_MCU_UNSTUFFED + _l.JPEG_MCU_BOUND) + 64
     if crop is not None:
         n += _pad16(hw[0] * hw[1] * 3) + _pad16(img.shape[0] * int(crop[3]) * 3)
     return n
+
+
+def restore_crops(pixels: torch.Tensor, items, device) -> Tuple[torch.Tensor, list]:
+    """``imgwrite.restore_cropped_image`` of a batch on the device (dm4d_restore_crop_u8, two launches): items = [(byte offset of the
+    uint8 [H, W, 3] image in `pixels`, H, W, (ct, cl, ch, cw), (canvas h, canvas w))] -> (uint8 buffer of the canvases, their byte
+    offsets in it).  The coefficient tables are Pillow's (host/capture.py bicubic_table)."""
+    from .capture import bicubic_table
+    _req(pixels, "pixels", torch.uint8)
+    desc = torch.zeros((len(items), _l.RESTORE_FIELDS), dtype=torch.int64)
+    tabs, tab_at, tab_len, scratch_len, canvas_len, places = [], {}, 0, 0, 0, []
+
+    def table(n_in: int, n_out: int) -> Tuple[int, int]:
+        nonlocal tab_len
+        if (n_in, n_out) not in tab_at:
+            bounds, k = bicubic_table(n_in, n_out)
+            tab_at[(n_in, n_out)] = (tab_len, k.shape[1])
+            tabs.extend([torch.from_numpy(bounds.reshape(-1).copy()), torch.from_numpy(k.reshape(-1).copy())])
+            tab_len += bounds.size + k.size
+        return tab_at[(n_in, n_out)]
+
+    for i, (src, H, W, (ct, cl, ch, cw), (h, w)) in enumerate(items):
+        htab, hk = table(W, cw)
+        vtab, vk = table(H, ch)
+        desc[i, :15] = torch.tensor([src, H, W, ct, cl, ch, cw, h, w, htab, hk, vtab, vk, scratch_len, canvas_len])
+        places.append(canvas_len)
+        scratch_len += (H * cw * 3 + 15) // 16 * 16
+        canvas_len += (h * w * 3 + 15) // 16 * 16
+    tab = torch.cat(tabs).to(torch.int32).contiguous()
+    scratch = torch.empty(scratch_len, dtype=torch.uint8, device=device)
+    canvases = torch.empty(canvas_len, dtype=torch.uint8, device=device)
+    desc_dev, tab_dev = desc.to(device), tab.to(device)
+    _l.call("dm4d_restore_crop_u8", _stream(), _p(pixels), pixels.numel(), desc.data_ptr(), _p(desc_dev), len(items), tab.data_ptr(),
+            _p(tab_dev), tab.numel(), _p(scratch), scratch.numel(), _p(canvases), canvases.numel())
+    return canvases, places
+
+
+def jpeg_encode_chunk(images, crops, sizes, qtab) -> list:
+    """Entropy-coded JPEG segments (bytes) of device uint8 [H, W, 3] tensors, each first restored onto its canvas where crops[k] is
+    not None (sizes[k] = the canvas' (h, w)); qtab: 128 integers, luma then chroma quantisation table in natural order.
+    Images that are views of one storage are read in place, otherwise they are gathered into one buffer first.  One host
+    synchronisation (the lengths) and one copy of exactly the bytes produced."""
+    lib = _l.load()
+    dev = images[0].device
+    for k, img in enumerate(images):
+        _req(img, f"images[{k}]", torch.uint8)
+        if img.device != dev or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
+            raise _l.Dm4dError(f"images[{k}]: expected a contiguous uint8 [H, W, 3] tensor on {dev}, got {tuple(img.shape)} on {img.device}")
+    with torch.cuda.device(dev):
+        base = images[0].untyped_storage().data_ptr()
+        if all(img.untyped_storage().data_ptr() == base for img in images):
+            pixels = torch.empty(0, dtype=torch.uint8, device=dev).set_(images[0].untyped_storage())
+            at = [img.data_ptr() - base for img in images]
+        else:
+            pixels = torch.cat([img.reshape(-1) for img in images])
+            at = [0]
+            for img in images[:-1]:
+                at.append(at[-1] + img.numel())
+        n = len(images)
+        cropped = [k for k in range(n) if crops[k] is not None]
+        canvases, places = None, {}
+        if cropped:
+            canvases, where = restore_crops(pixels, [(at[k], images[k].shape[0], images[k].shape[1], tuple(crops[k][:4]), sizes[k])
+                                                     for k in cropped], dev)
+            places = dict(zip(cropped, where))
+        desc = torch.zeros((n, _l.JPEG_FIELDS), dtype=torch.int64)
+        mcu0 = chunk0 = bound = 0
+        for k, (h, w) in enumerate(sizes):
+            mcus = ((h + 15) // 16) * ((w + 15) // 16)
+            b = int(lib.dm4d_jpeg_scan_bound(h, w))
+            if b == 0:
+                raise _l.Dm4dError(f"images[{k}]: size {h} x {w} is out of range for the JPEG encoder")
+            desc[k, :6] = torch.tensor([1, places[k], h, w, mcu0, chunk0] if k in places else [0, at[k], h, w, mcu0, chunk0])
+            mcu0, chunk0, bound = mcu0 + mcus, chunk0 + (mcus * _l.JPEG_MCU_UNSTUFFED + _l.JPEG_CHUNK - 1) // _l.JPEG_CHUNK, bound + b
+        nbytes = int(lib.dm4d_jpeg_ws_bytes(mcu0, n))
+        if nbytes == 0:
+            raise _l.Dm4dError(f"jpeg_encode_chunk: {n} images with {mcu0} MCUs are out of range for one call")
+        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+        blob = torch.empty(bound, dtype=torch.uint8, device=dev)
+        out = torch.empty(2 * n, dtype=torch.int64, device=dev)
+        q = torch.tensor([int(v) for v in qtab], dtype=torch.int16)  # values 1..255: the same bytes as uint16
+        desc_dev, q_dev = desc.to(dev), q.to(dev)
+        _l.call("dm4d_jpeg_encode_rgb_u8", _stream(), _p(pixels) if pixels.numel() else None, pixels.numel(), _p(canvases),
+                0 if canvases is None else canvases.numel(), desc.data_ptr(), _p(desc_dev), n, q.data_ptr(), _p(q_dev), _p(ws),
+                ws.numel() * 8, _p(blob), blob.numel(), _p(out))
+        where = out.cpu().tolist()  # the one synchronisation: n offsets, then n lengths
+        total = where[n - 1] + where[2 * n - 1]
+        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+        host.copy_(blob[:total])
+        data = host.numpy().tobytes()
+    return [data[where[k]:where[k] + where[n + k]] for k in range(n)]
 
 
 def encode_jpeg_batch(images, quality: int = 90, crops: Optional[Sequence] = None, workspace_bytes: int = DEFAULT_WORKSPACE) -> List[bytes]:
@@ -110,9 +203,6 @@ def encode_jpeg_batch(images, quality: int = 90, crops: Optional[Sequence] = Non
     crops: per image None or the dataset's ``(ct, cl, ch, cw[, h, w])``: the image is first restored onto its white canvas on the
     device.  The batch is processed in chunks whose device memory stays below `workspace_bytes` (a chunk holds at least one image).
     One synchronisation and one device-to-host copy per chunk."""
-    import torch
-    from . import lib as _l
-    from . import ops
     q = _check_quality(quality)
     images = list(images)
     crops = [None] * len(images) if crops is None else [None if c is None else tuple(int(v) for v in c) for c in crops]
@@ -141,7 +231,7 @@ def encode_jpeg_batch(images, quality: int = 90, crops: Optional[Sequence] = Non
                 break
             used += need
             last += 1
-        scans = ops.jpeg_encode_chunk(images[first:last], crops[first:last], sizes[first:last], qtab)
+        scans = jpeg_encode_chunk(images[first:last], crops[first:last], sizes[first:last], qtab)
         files += [jpeg_header(hw[0], hw[1], q) + s + b"\xff\xd9" for hw, s in zip(sizes[first:last], scans)]
         first = last
     return files

@@ -129,11 +129,37 @@ SIGNATURES = {
     "dm4d_jpeg_encode_rgb_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
 }
 
+# The constants of include/dm4d.h that the host uses, under the header's names without the DM4D_ prefix.  This block is their ONLY
+# copy in Python (host/ops.py re-exports them); tests/test_abi.py reads the header and checks every value.
 EPI_GEGLU = 1
 EPI_SILU = 2
 EPI_F32OUT = 4
 EPI_F32SIDE = 8
 EPI_SPLITOUT = 16
+LOG2E = 1.4426950408889634
+CAPTURE_FIELDS = 16
+EVAL_FIELDS = 16
+EVAL_OUT = 8
+EVAL_IMAGE_F32 = 1
+EVAL_MASK_F32 = 2
+EVAL_CROP_MASKS = 4
+EVAL_BG_SHIFT = 3
+LPIPS_TAPS = 5
+LPIPS_IN_COLS = 64
+VHULL_BLOCK = 256
+VHULL_MAX_CHUNK = 1 << 26
+TRIANG_MAX_VIEWS = 65536
+SKEL_FIELDS = 8
+SKEL_LINE = 0
+SKEL_CIRCLE = 1
+SKEL_MAX_PRIMS = 512
+SKEL_COORD_MIN = -8192
+SKEL_COORD_MAX = 8191
+RESTORE_FIELDS = 16
+JPEG_FIELDS = 8
+JPEG_MCU_UNSTUFFED = 1248  # workspace bytes of unstuffed scan per 16 x 16 MCU
+JPEG_MCU_BOUND = 2488      # bytes of stuffed scan per MCU, worst case
+JPEG_CHUNK = 4096
 
 
 class Dm4dError(RuntimeError):
@@ -171,3 +197,10 @@ def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().dm4d_last_error()
         raise Dm4dError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
+
+
+def call(name: str, *args) -> None:
+    """Call the int-returning entry point `name`; a non-zero return raises Dm4dError under that same name."""
+    rc = getattr(load(), name)(*args)
+    if rc != 0:
+        check(rc, name)

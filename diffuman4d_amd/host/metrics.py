@@ -38,7 +38,6 @@ from .lib import Dm4dError
 
 log = logging.getLogger(__name__)
 
-FIELDS = ops.EVAL_FIELDS
 BACKGROUNDS = {"black": 0, "white": 1, "grey": 2}
 MIN_EDGE = 11  # the 11 x 11 SSIM window has to fit into the crop
 _ALIGN = 16
@@ -153,7 +152,7 @@ class ImageEvaluator:
         """Pack planes and descriptors into one staging buffer, upload it, launch -> (out [n, 8] fp64, boxes [n, 4], debug) on the host
         (debug stays on the device)."""
         off, jobs = 0, []
-        desc = np.zeros((len(items), FIELDS), dtype=np.int64)
+        desc = np.zeros((len(items), ops.EVAL_FIELDS), dtype=np.int64)
         for i, it in enumerate(items):
             offs = {}
             for name in ("pred", "gt", "pmask", "gmask"):

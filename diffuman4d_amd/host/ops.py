@@ -22,6 +22,9 @@ from typing import Optional, Tuple
 import torch
 
 from . import lib as _l
+from .lib import (CAPTURE_FIELDS, EVAL_BG_SHIFT, EVAL_CROP_MASKS, EVAL_FIELDS, EVAL_IMAGE_F32, EVAL_MASK_F32, EVAL_OUT,  # noqa: F401
+                  LOG2E, LPIPS_IN_COLS, LPIPS_TAPS, SKEL_CIRCLE, SKEL_COORD_MAX, SKEL_COORD_MIN, SKEL_FIELDS, SKEL_LINE, SKEL_MAX_PRIMS,
+                  TRIANG_MAX_VIEWS, VHULL_BLOCK, VHULL_MAX_CHUNK)
 
 BF16 = torch.bfloat16
 F16 = torch.float16
@@ -67,79 +70,45 @@ def gemm(a: torch.Tensor, w: torch.Tensor, *, a2: Optional[torch.Tensor] = None,
     fp16 (w is fp16): one fp16 plane [M, N].
     rowbias / residual may be fp32 tensors (wide precisions: both must then be fp32).
     scale_cols / col_scale (fp16 precision): output columns [0, scale_cols) are multiplied by col_scale before the one rounding."""
-    if isinstance(w, torch.Tensor) and w.dtype == F16:
-        return _gemm_f16(a, w, a2, bias, rowbias, rows_per_rowbias, residual, geglu, silu, out_scale, out, out_f32, scale_cols, col_scale)
-    assert scale_cols == 0
-    lib = _l.load()
-    _req(a, "a"), _req(w, "w")
+    h16 = isinstance(w, torch.Tensor) and w.dtype == F16  # precision "fp16": fp16 a / a2 / w / bias, fp16 (or fp32) result
+    dt = F16 if h16 else BF16
+    assert h16 or scale_cols == 0
+    _req(a, "a", dt), _req(w, "w", dt)
     M, K1 = a.shape
     K = w.shape[1]
     N = w.shape[0] // 2 if geglu else w.shape[0]
     if a2 is not None:
-        _req(a2, "a2")
+        _req(a2, "a2", dt)
         assert a2.shape[0] == M and K1 + a2.shape[1] == K
     else:
         assert K1 == K, (K1, K)
     if bias is not None:
-        _req(bias, "bias")
+        _req(bias, "bias", dt)
     side = [t for t in (rowbias, residual) if t is not None]
     f32_side = bool(side) and side[0].dtype == F32
     for t, n in ((rowbias, "rowbias"), (residual, "residual")):
         if t is not None:
-            _req(t, n, F32 if f32_side else BF16)
+            _req(t, n, F32 if f32_side else dt)
+    split_out = split_out and not h16  # the fp16 operand is the one plane this entry stores anyway
     assert not (out_f32 and split_out)
-    odt, ocols = (F32 if out_f32 else BF16), (2 * N if split_out else N)
+    odt, ocols = (F32 if out_f32 else dt), (2 * N if split_out else N)
     if out is None:
         out = torch.empty((M, ocols), dtype=odt, device=a.device)
     _req(out, "out", odt)
     assert out.shape[1] >= ocols or out.stride(0) >= ocols
     flags = ((_l.EPI_GEGLU if geglu else 0) | (_l.EPI_SILU if silu else 0) | (_l.EPI_F32OUT if out_f32 else 0)
              | (_l.EPI_F32SIDE if f32_side else 0) | (_l.EPI_SPLITOUT if split_out else 0))
+    args = (_stream(), _p(a), a.stride(0), _p(a2), a2.stride(0) if a2 is not None else 0, K1 if a2 is not None else 0, _p(w), w.stride(0),
+            _p(out), out.stride(0), M, N, K, _p(bias), _p(rowbias), rowbias.stride(0) if rowbias is not None else 0, rows_per_rowbias,
+            _p(residual), residual.stride(0) if residual is not None else 0, flags, out_scale)
     with _Prof("linear", 2.0 * M * w.shape[0] * K, "flop", M):
-        rc = lib.dm4d_gemm_bf16(_stream(), _p(a), a.stride(0), _p(a2), a2.stride(0) if a2 is not None else 0,
-                                K1 if a2 is not None else 0, _p(w), w.stride(0), _p(out), out.stride(0), M, N, K,
-                                _p(bias), _p(rowbias), rowbias.stride(0) if rowbias is not None else 0,
-                                rows_per_rowbias, _p(residual), residual.stride(0) if residual is not None else 0,
-                                flags, out_scale)
-    _l.check(rc, "dm4d_gemm_bf16")
-    _trace("gemm", out, a=a, w=w, a2=a2, bias=bias, rowbias=rowbias, rows_per_rowbias=rows_per_rowbias, residual=residual, geglu=geglu,
-           silu=silu, out_scale=out_scale, out_f32=out_f32, split_out=split_out)
-    return out
-
-
-def _gemm_f16(a, w, a2, bias, rowbias, rows_per_rowbias, residual, geglu, silu, out_scale, out, out_f32, scale_cols, col_scale):
-    """precision "fp16": fp16 a / a2 / w / bias, fp32 (or fp16) rowbias / residual, fp32 or fp16 result (dm4d_gemm_f16)."""
-    lib = _l.load()
-    _req(a, "a", F16), _req(w, "w", F16)
-    M, K1 = a.shape
-    K = w.shape[1]
-    N = w.shape[0] // 2 if geglu else w.shape[0]
-    if a2 is not None:
-        _req(a2, "a2", F16)
-        assert a2.shape[0] == M and K1 + a2.shape[1] == K
-    else:
-        assert K1 == K, (K1, K)
-    if bias is not None:
-        _req(bias, "bias", F16)
-    side = [t for t in (rowbias, residual) if t is not None]
-    f32_side = bool(side) and side[0].dtype == F32
-    for t, n in ((rowbias, "rowbias"), (residual, "residual")):
-        if t is not None:
-            _req(t, n, F32 if f32_side else F16)
-    odt = F32 if out_f32 else F16
-    if out is None:
-        out = torch.empty((M, N), dtype=odt, device=a.device)
-    _req(out, "out", odt)
-    assert out.shape[1] >= N or out.stride(0) >= N
-    flags = ((_l.EPI_GEGLU if geglu else 0) | (_l.EPI_SILU if silu else 0) | (_l.EPI_F32OUT if out_f32 else 0)
-             | (_l.EPI_F32SIDE if f32_side else 0))
-    with _Prof("linear", 2.0 * M * w.shape[0] * K, "flop", M):
-        rc = lib.dm4d_gemm_f16(_stream(), _p(a), a.stride(0), _p(a2), a2.stride(0) if a2 is not None else 0,
-                               K1 if a2 is not None else 0, _p(w), w.stride(0), _p(out), out.stride(0), M, N, K,
-                               _p(bias), _p(rowbias), rowbias.stride(0) if rowbias is not None else 0,
-                               rows_per_rowbias, _p(residual), residual.stride(0) if residual is not None else 0,
-                               flags, out_scale, int(scale_cols), float(col_scale))
-    _l.check(rc, "dm4d_gemm_f16")
+        if h16:
+            _l.call("dm4d_gemm_f16", *args, int(scale_cols), float(col_scale))
+        else:
+            _l.call("dm4d_gemm_bf16", *args)
+    if not h16:
+        _trace("gemm", out, a=a, w=w, a2=a2, bias=bias, rowbias=rowbias, rows_per_rowbias=rows_per_rowbias, residual=residual, geglu=geglu,
+               silu=silu, out_scale=out_scale, out_f32=out_f32, split_out=split_out)
     return out
 
 
@@ -154,63 +123,23 @@ def conv3x3(x: torch.Tensor, wt: torch.Tensor, *, bias=None, rowbias=None, resid
             pad: int = 1, pad_hi: Optional[int] = None, upsample: bool = False, out_scale: float = 1.0,
             out_f32: bool = False) -> torch.Tensor:
     """x [B,H,W,Cin] NHWC, wt [Cout, 9*Cin] ((ky,kx,ci) order) -> [B,Ho,Wo,Cout].
-    out_f32 (parity precision): fp32 output; rowbias / residual must then be fp32 as well (x is usually a two-term operand
-    and wt duplicated along Cin, which this function does not need to know)."""
+    out_f32 (wide precisions): fp32 output; rowbias / residual must then be fp32 as well (in the parity precision x is usually a two-term
+    operand and wt duplicated along Cin, which this function does not need to know).
+    fp16 x / wt / bias (precision "fp16"): rowbias / residual fp32 or fp16; an fp16 result may take an fp32 row bias (conv1 of a resnet,
+    whose fp32 sum is rounded once for norm2)."""
     lib = _l.load()
-    if isinstance(wt, torch.Tensor) and wt.dtype == F16:
-        return _conv3x3_f16(x, wt, bias, rowbias, residual, stride, pad, pad_hi, upsample, out_scale, out_f32)
-    _req(x, "x"), _req(wt, "wt")
+    h16 = isinstance(wt, torch.Tensor) and wt.dtype == F16
+    dt = F16 if h16 else BF16
+    _req(x, "x", dt), _req(wt, "wt", dt)
     assert x.is_contiguous() and wt.is_contiguous()
     B, H, W, Cin = x.shape
     Cout = wt.shape[0]
     assert wt.shape[1] == 9 * Cin, (wt.shape, Cin)
     Ho, Wo = conv_out_hw(H, W, stride, pad, upsample, pad_hi)
-    y = torch.empty((B, Ho, Wo, Cout), dtype=F32 if out_f32 else BF16, device=x.device)
-    side = F32 if out_f32 else BF16
-    if residual is not None:
-        _req(residual, "residual", side)
-        assert residual.numel() == y.numel() and residual.is_contiguous()
-    if rowbias is not None:
-        _req(rowbias, "rowbias", side)
-        assert rowbias.shape[0] == B
-    if out_f32:
-        with _Prof("conv3x3", 2.0 * B * Ho * Wo * 9 * Cin * Cout, "flop", B * Ho * Wo):
-            rc = lib.dm4d_conv3x3_nhwc_bf16_flags(_stream(), _p(x), B, H, W, Cin, _p(wt), _p(y), Ho, Wo, Cout, stride, pad,
-                                                  1 if upsample else 0, _p(bias), _p(rowbias),
-                                                  rowbias.stride(0) if rowbias is not None else 0, _p(residual),
-                                                  Cout if residual is not None else 0, out_scale, _l.EPI_F32OUT | _l.EPI_F32SIDE)
-        _l.check(rc, "dm4d_conv3x3_nhwc_bf16_flags")
-        _trace("conv3x3", y, x=x, wt=wt, bias=bias, rowbias=rowbias, residual=residual, stride=stride, pad=pad, pad_hi=pad_hi,
-               upsample=upsample, out_scale=out_scale, out_f32=True)
-        return y
-    # small images with a deep K (the 9x5 level) run split over the three kernel rows and need an fp32 workspace
-    ws_bytes = lib.dm4d_conv3x3_ws_bytes(B, H, W, Cin, Ho, Wo, Cout, stride, pad, 1 if upsample else 0)
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
-    with _Prof("conv3x3", 2.0 * B * Ho * Wo * 9 * Cin * Cout, "flop", B * Ho * Wo):
-        rc = lib.dm4d_conv3x3_nhwc_bf16_ws(_stream(), _p(x), B, H, W, Cin, _p(wt), _p(y), Ho, Wo, Cout, stride, pad,
-                                           1 if upsample else 0, _p(bias), _p(rowbias),
-                                           rowbias.stride(0) if rowbias is not None else 0, _p(residual),
-                                           Cout if residual is not None else 0, out_scale, _p(ws), ws_bytes)
-    _l.check(rc, "dm4d_conv3x3_nhwc_bf16_ws")
-    _trace("conv3x3", y, x=x, wt=wt, bias=bias, rowbias=rowbias, residual=residual, stride=stride, pad=pad, pad_hi=pad_hi,
-           upsample=upsample, out_scale=out_scale, out_f32=False)
-    return y
-
-
-def _conv3x3_f16(x, wt, bias, rowbias, residual, stride, pad, pad_hi, upsample, out_scale, out_f32) -> torch.Tensor:
-    """precision "fp16": x / wt / bias fp16; rowbias / residual fp32 (always with an fp32 result) or fp16; fp32 (out_f32) or fp16 result
-    (an fp16 result with an fp32 row bias: conv1 of a resnet, whose fp32 sum is rounded once for norm2)."""
-    lib = _l.load()
-    _req(x, "x", F16), _req(wt, "wt", F16)
-    assert x.is_contiguous() and wt.is_contiguous()
-    B, H, W, Cin = x.shape
-    Cout = wt.shape[0]
-    assert wt.shape[1] == 9 * Cin, (wt.shape, Cin)
-    Ho, Wo = conv_out_hw(H, W, stride, pad, upsample, pad_hi)
-    y = torch.empty((B, Ho, Wo, Cout), dtype=F32 if out_f32 else F16, device=x.device)
+    y = torch.empty((B, Ho, Wo, Cout), dtype=F32 if out_f32 else dt, device=x.device)
     sides = [t for t in (rowbias, residual) if t is not None]
-    side = F32 if (out_f32 or (sides and sides[0].dtype == F32)) else F16
-    if bias is not None:
+    side = F32 if (out_f32 or (h16 and sides and sides[0].dtype == F32)) else dt
+    if h16 and bias is not None:  # (a bf16 bias has always been taken as it comes)
         _req(bias, "bias", F16)
     if residual is not None:
         _req(residual, "residual", side)
@@ -218,15 +147,25 @@ def _conv3x3_f16(x, wt, bias, rowbias, residual, stride, pad, pad_hi, upsample, 
     if rowbias is not None:
         _req(rowbias, "rowbias", side)
         assert rowbias.shape[0] == B
-    ws_bytes = lib.dm4d_conv3x3_ws_bytes(B, H, W, Cin, Ho, Wo, Cout, stride, pad, 1 if upsample else 0)
-    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
+    up = 1 if upsample else 0
+    args = (_stream(), _p(x), B, H, W, Cin, _p(wt), _p(y), Ho, Wo, Cout, stride, pad, up, _p(bias), _p(rowbias),
+            rowbias.stride(0) if rowbias is not None else 0, _p(residual), Cout if residual is not None else 0, out_scale)
+    flags = (_l.EPI_F32OUT if out_f32 else 0) | (_l.EPI_F32SIDE if side == F32 else 0)
+    ws = ws_bytes = None
+    if h16 or not out_f32:
+        # small images with a deep K (the 9x5 level) run split over the three kernel rows and need an fp32 workspace
+        ws_bytes = lib.dm4d_conv3x3_ws_bytes(B, H, W, Cin, Ho, Wo, Cout, stride, pad, up)
+        ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=x.device) if ws_bytes else None
     with _Prof("conv3x3", 2.0 * B * Ho * Wo * 9 * Cin * Cout, "flop", B * Ho * Wo):
-        rc = lib.dm4d_conv3x3_nhwc_f16(_stream(), _p(x), B, H, W, Cin, _p(wt), _p(y), Ho, Wo, Cout, stride, pad,
-                                       1 if upsample else 0, _p(bias), _p(rowbias),
-                                       rowbias.stride(0) if rowbias is not None else 0, _p(residual),
-                                       Cout if residual is not None else 0, out_scale,
-                                       (_l.EPI_F32OUT if out_f32 else 0) | (_l.EPI_F32SIDE if side == F32 else 0), _p(ws), ws_bytes)
-    _l.check(rc, "dm4d_conv3x3_nhwc_f16")
+        if h16:
+            _l.call("dm4d_conv3x3_nhwc_f16", *args, flags, _p(ws), ws_bytes)
+        elif out_f32:
+            _l.call("dm4d_conv3x3_nhwc_bf16_flags", *args, flags)
+        else:
+            _l.call("dm4d_conv3x3_nhwc_bf16_ws", *args, _p(ws), ws_bytes)
+    if not h16:
+        _trace("conv3x3", y, x=x, wt=wt, bias=bias, rowbias=rowbias, residual=residual, stride=stride, pad=pad, pad_hi=pad_hi,
+               upsample=upsample, out_scale=out_scale, out_f32=bool(out_f32))
     return y
 
 
@@ -244,7 +183,6 @@ def split(x: torch.Tensor, x2: Optional[torch.Tensor] = None, *, cpad: Optional[
     """fp32 [..., C] (channel concat with x2) -> the OPERAND of a contraction.  Parity precision: two-term bf16 [..., 2 cpad] =
     [hi | lo] (pattern 1: [hi | lo | hi], 2: [hi | hi | lo], three planes); h16 (precision "fp16"): one fp16 plane [..., cpad].
     transposed: x is a 2-D view [K, M] read as its transpose (result [M, planes * K])."""
-    lib = _l.load()
     if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != F32:
         raise _l.Dm4dError("split: expected an fp32 tensor on a HIP device")
     planes = 1 if h16 else (2 if pattern == 0 else 3)
@@ -269,11 +207,10 @@ def split(x: torch.Tensor, x2: Optional[torch.Tensor] = None, *, cpad: Optional[
     y = torch.empty(lead + (planes * Cp,), dtype=F16 if h16 else BF16, device=x.device)
     with _Prof("split", 4.0 * M * (C1 + C2) + 2.0 * M * planes * Cp, "byte", M):  # fp32 in, 16-bit planes out
         if h16:
-            rc = lib.dm4d_to_f16_f32(_stream(), _p(x), rs1, cs1, C1, _p(x2), rs2, C2, _p(y), Cp, M, Cp, 1 if silu else 0, scale)
+            _l.call("dm4d_to_f16_f32", _stream(), _p(x), rs1, cs1, C1, _p(x2), rs2, C2, _p(y), Cp, M, Cp, 1 if silu else 0, scale)
         else:
-            rc = lib.dm4d_split_f32(_stream(), _p(x), rs1, cs1, C1, _p(x2), rs2, C2, _p(y), planes * Cp, M, Cp, 1 if silu else 0,
-                                    scale, pattern)
-    _l.check(rc, "dm4d_split_f32")
+            _l.call("dm4d_split_f32", _stream(), _p(x), rs1, cs1, C1, _p(x2), rs2, C2, _p(y), planes * Cp, M, Cp, 1 if silu else 0,
+                    scale, pattern)
     return y
 
 
@@ -296,65 +233,65 @@ class FeedForward:
         assert w1.shape == (2 * self.hidden, self.C)
         self.packed = None
         if w1.is_cuda and _l.load().dm4d_ff_geglu_supported(self.C, self.hidden):
-            lib = _l.load()
             _req(w1, "w1", w1.dtype), _req(w2, "w2", w1.dtype)  # bf16, or fp16 (precision "fp16": the packing permutes 16-bit words)
             with torch.cuda.device(w1.device):
                 w1p, b1p, w2p = torch.empty_like(w1), torch.empty(2 * self.hidden, dtype=w1.dtype, device=w1.device), torch.empty_like(w2)
-                _l.check(lib.dm4d_ff_geglu_prepare_bf16(_stream(), _p(w1.contiguous()), _p(b1), _p(w2.contiguous()), _p(w1p), _p(b1p),
-                                                        _p(w2p), self.C, self.hidden), "dm4d_ff_geglu_prepare_bf16")
+                _l.call("dm4d_ff_geglu_prepare_bf16", _stream(), _p(w1.contiguous()), _p(b1), _p(w2.contiguous()), _p(w1p), _p(b1p),
+                        _p(w2p), self.C, self.hidden)
                 torch.cuda.current_stream(w1.device).synchronize()
             self.packed = (w1p, b1p, w2p)
+
+    def _one_launch(self, dma: torch.Tensor, *others) -> bool:
+        """The guards every one-launch form shares: packed weights, the FF_FUSED switch, `dma` (the input the kernel fetches by DMA) below
+        4 GiB, and 16-byte-aligned starts and rows of `dma` and `others` (None passes).  Any other view takes the separate launches,
+        which accept 8-element-aligned strides."""
+        return (self.packed is not None and FF_FUSED and dma.shape[0] * dma.stride(0) * 2 < (1 << 32)
+                and all(t is None or (t.data_ptr() % 16 == 0 and (t.ndim < 2 or t.stride(0) * t.element_size() % 16 == 0))
+                        for t in (dma,) + others))
+
+    def _proj_one_launch(self, a: torch.Tensor, wo: torch.Tensor, *others) -> bool:
+        """_one_launch for the forms that start at the attention output projection: they also want a contiguous square weight."""
+        return FF_PROJ_FUSED and wo.shape == (self.C, self.C) and wo.is_contiguous() and self._one_launch(a, wo, *others)
+
+    def _launch(self, name: str, like: torch.Tensor, odt, cols: int, front, mid=(), flags=()) -> torch.Tensor:
+        """One launch of the entry `name`: (stream, *front, packed weights, b2, *mid, out, ldo, *flags, M, C, hidden) -> out [M, C] of
+        dtype odt next to `like`; cols = the weight rows the launch multiplies by, for the profile."""
+        M = like.shape[0]
+        out = torch.empty((M, self.C), dtype=odt, device=like.device)
+        w1p, b1p, w2p = self.packed
+        with _Prof("linear", 2.0 * M * cols * self.C, "flop", M):
+            _l.call(name, _stream(), *front, _p(w1p), _p(b1p), _p(w2p), _p(self.b2), *mid, _p(out), out.stride(0), *flags, M, self.C,
+                    self.hidden)
+        return out
 
     def __call__(self, n: torch.Tensor, residual: torch.Tensor, ln=None) -> torch.Tensor:
         """ln = (gamma, beta, eps): `n` is the un-normalised input and the LayerNorm in front of the feed-forward (norm3) is applied
         here -- inside the fused launch, or as its own launch in the two-GEMM form."""
-        # the one-launch form wants 16-byte aligned rows; any other view takes the two GEMMs, which accept 8-element-aligned strides
-        aligned = all(t is None or (t.data_ptr() % 16 == 0 and (t.ndim < 2 or t.stride(0) % 8 == 0))
-                      for t in (n, residual) + (tuple(ln[:2]) if ln is not None else ()))
-        if self.packed is None or not FF_FUSED or not aligned or n.shape[0] * n.stride(0) * 2 >= (1 << 32):
+        if not self._one_launch(n, residual, *(ln[:2] if ln is not None else ())):
             if ln is not None:
                 n = layernorm(n, ln[0], ln[1], ln[2])
             f = gemm(n, self.w1, bias=self.b1, geglu=True)
             return gemm(f, self.w2, bias=self.b2, residual=residual)
-        lib = _l.load()
         _req(n, "n"), _req(residual, "residual")
         if ln is not None:
             _req(ln[0], "gamma"), _req(ln[1], "beta")
-        M = n.shape[0]
-        out = torch.empty((M, self.C), dtype=BF16, device=n.device)
-        w1p, b1p, w2p = self.packed
-        with _Prof("linear", 2.0 * M * 3 * self.hidden * self.C, "flop", M):
-            rc = lib.dm4d_ff_geglu_fused_bf16(_stream(), _p(n), n.stride(0), _p(ln[0]) if ln is not None else None,
-                                              _p(ln[1]) if ln is not None else None, float(ln[2]) if ln is not None else 0.0, _p(w1p),
-                                              _p(b1p), _p(w2p), _p(self.b2), _p(residual), residual.stride(0), _p(out), out.stride(0), M,
-                                              self.C, self.hidden)
-        _l.check(rc, "dm4d_ff_geglu_fused_bf16")
+        gamma, beta, eps = (_p(ln[0]), _p(ln[1]), float(ln[2])) if ln is not None else (None, None, 0.0)
+        out = self._launch("dm4d_ff_geglu_fused_bf16", n, BF16, 3 * self.hidden, (_p(n), n.stride(0), gamma, beta, eps),
+                           mid=(_p(residual), residual.stride(0)))
         _trace("ff_fused", out, n=n, residual=residual, ln=ln, w1=self.w1, b1=self.b1, w2=self.w2, b2=self.b2)
         return out
-
 
     def after_attention(self, a: torch.Tensor, wo: torch.Tensor, bo: Optional[torch.Tensor], x: torch.Tensor, ln) -> torch.Tensor:
         """The tail of a transformer block: h = a wo^T + bo + x (attention output projection + residual), then ff(LayerNorm(h)) + h.
         One launch where the fused kernel is built for the shape (FF_PROJ_FUSED), gemm + __call__ otherwise: the same products and bf16
         rounding points either way (since round 6 the one-launch form adds its fp32 terms in another order: one-ulp differences on isolated
-        elements, tests/opcheck.py ff_proj_fused_*)."""
-        # the one-launch form wants 16-byte aligned rows (row strides in multiples of 8 elements) and a contiguous square weight; a
-        # column view of a wider tensor as `a` or `x` takes the separate launches, which accept any 8-element-aligned view
-        aligned = all(t.data_ptr() % 16 == 0 and t.stride(0) % 8 == 0 for t in (a, x)) and wo.data_ptr() % 16 == 0
-        if (self.packed is None or not FF_FUSED or not FF_PROJ_FUSED or ln is None or not aligned
-                or a.shape[0] * a.stride(0) * 2 >= (1 << 32) or wo.shape != (self.C, self.C) or not wo.is_contiguous()):
+        elements, tests/opcheck.py ff_proj_fused_*).  A column view of a wider tensor as `a` or `x` takes the separate launches."""
+        if ln is None or not self._proj_one_launch(a, wo, x):
             h = gemm(a, wo, bias=bo, residual=x)
             return self(h, h, ln=ln)
-        lib = _l.load()
         _req(a, "a"), _req(wo, "wo"), _req(x, "x"), _req(ln[0], "gamma"), _req(ln[1], "beta")
-        M = a.shape[0]
-        out = torch.empty((M, self.C), dtype=BF16, device=a.device)
-        w1p, b1p, w2p = self.packed
-        with _Prof("linear", 2.0 * M * (3 * self.hidden + self.C) * self.C, "flop", M):
-            rc = lib.dm4d_attn_out_ff_geglu_fused_bf16(_stream(), _p(a), a.stride(0), _p(wo), _p(bo), _p(x), x.stride(0), _p(ln[0]),
-                                                       _p(ln[1]), float(ln[2]), _p(w1p), _p(b1p), _p(w2p), _p(self.b2), _p(out),
-                                                       out.stride(0), M, self.C, self.hidden)
-        _l.check(rc, "dm4d_attn_out_ff_geglu_fused_bf16")
+        out = self._launch("dm4d_attn_out_ff_geglu_fused_bf16", a, BF16, 3 * self.hidden + self.C,
+                           (_p(a), a.stride(0), _p(wo), _p(bo), _p(x), x.stride(0), _p(ln[0]), _p(ln[1]), float(ln[2])))
         _trace("attn_out_ff_fused", out, a=a, wo=wo, bo=bo, x=x, ln=ln, w1=self.w1, b1=self.b1, w2=self.w2, b2=self.b2)
         return out
 
@@ -362,23 +299,14 @@ class FeedForward:
         """The same tail in precision "fp16": a fp16 [M, C], x the fp32 residual stream; the result is fp32 (out_f32) or the fp16 operand
         of the next contraction.  One launch (dm4d_attn_out_ff_geglu_fused_f16: h stays in the accumulators, never stored) where the kernel
         is built for the shape, otherwise gemm -> fp32 h, layernorm, gemm(GEGLU), gemm(+ h); the two forms agree to fp32 rounding."""
-        aligned = (all(t.data_ptr() % 16 == 0 for t in (a, x, wo, ln[0], ln[1])) and a.stride(0) % 8 == 0 and x.stride(0) % 4 == 0)
-        if (self.packed is None or not FF_FUSED or not FF_PROJ_FUSED or not aligned or a.shape[0] * a.stride(0) * 2 >= (1 << 32)
-                or wo.shape != (self.C, self.C) or not wo.is_contiguous()):
+        if not self._proj_one_launch(a, wo, x, ln[0], ln[1]):
             h = gemm(a, wo, bias=bo, residual=x, out_f32=True)
             f = gemm(layernorm(h, ln[0], ln[1], ln[2]), self.w1, bias=self.b1, geglu=True)
             return gemm(f, self.w2, bias=self.b2, residual=h, out_f32=out_f32)
-        lib = _l.load()
         _req(a, "a", F16), _req(wo, "wo", F16), _req(x, "x", F32), _req(ln[0], "gamma", F16), _req(ln[1], "beta", F16)
-        M = a.shape[0]
-        out = torch.empty((M, self.C), dtype=F32 if out_f32 else F16, device=a.device)
-        w1p, b1p, w2p = self.packed
-        with _Prof("linear", 2.0 * M * (3 * self.hidden + self.C) * self.C, "flop", M):
-            rc = lib.dm4d_attn_out_ff_geglu_fused_f16(_stream(), _p(a), a.stride(0), _p(wo), _p(bo), _p(x), x.stride(0), _p(ln[0]),
-                                                      _p(ln[1]), float(ln[2]), _p(w1p), _p(b1p), _p(w2p), _p(self.b2), _p(out),
-                                                      out.stride(0), 1 if out_f32 else 0, M, self.C, self.hidden)
-        _l.check(rc, "dm4d_attn_out_ff_geglu_fused_f16")
-        return out
+        return self._launch("dm4d_attn_out_ff_geglu_fused_f16", a, F32 if out_f32 else F16, 3 * self.hidden + self.C,
+                            (_p(a), a.stride(0), _p(wo), _p(bo), _p(x), x.stride(0), _p(ln[0]), _p(ln[1]), float(ln[2])),
+                            flags=(1 if out_f32 else 0,))
 
 
 # proj_in + norm1 + QKV projection of a level-0 transformer (C = 320) as one launch (proj_in_ln_qkv); off = gemm, layernorm, gemm (A/B, tests)
@@ -409,10 +337,8 @@ def _l0_fusable(C: int, rows, weights, vectors) -> bool:
 def _launch_l0_head(n, wpi, bpi, ln, wqkv, h, qkv, n1) -> None:
     M, C = n.shape
     with _Prof("linear", 2.0 * M * (C + 3 * C) * C, "flop", M):
-        rc = _l.load().dm4d_proj_in_ln_qkv_fused_bf16(_stream(), _p(n), n.stride(0), _p(wpi), _p(bpi), _p(ln[0]), _p(ln[1]), float(ln[2]),
-                                                      _p(wqkv), _p(h), h.stride(0), _p(qkv), qkv.stride(0), _p(n1),
-                                                      n1.stride(0) if n1 is not None else 0, M, C)
-    _l.check(rc, "dm4d_proj_in_ln_qkv_fused_bf16")
+        _l.call("dm4d_proj_in_ln_qkv_fused_bf16", _stream(), _p(n), n.stride(0), _p(wpi), _p(bpi), _p(ln[0]), _p(ln[1]), float(ln[2]),
+                _p(wqkv), _p(h), h.stride(0), _p(qkv), qkv.stride(0), _p(n1), n1.stride(0) if n1 is not None else 0, M, C)
 
 
 def proj_in_ln_qkv(n: torch.Tensor, wpi: torch.Tensor, bpi: Optional[torch.Tensor], ln, wqkv: torch.Tensor,
@@ -443,19 +369,15 @@ def proj_in_ln_qkv(n: torch.Tensor, wpi: torch.Tensor, bpi: Optional[torch.Tenso
     return h, qkv
 
 
-
-
 def conv_up2x_prepare(wt: torch.Tensor) -> torch.Tensor:
     """3x3 weights [Cout, 9*Cin] ((ky,kx,ci) order) -> the four 2x2 phase kernels [4, Cout, 4*Cin] of conv_up2x (once per
     layer: sums of the taps that read the same low-resolution pixel, fp32, rounded to bf16 once)."""
-    lib = _l.load()
     h16 = wt.dtype == F16  # precision "fp16": fp16 taps in, fp16 phase kernels out
     _req(wt, "wt", F16 if h16 else BF16)
     assert wt.is_contiguous() and wt.shape[1] % 9 == 0
     Cout, Cin = wt.shape[0], wt.shape[1] // 9
     wp = torch.empty((4, Cout, 4 * Cin), dtype=wt.dtype, device=wt.device)
-    fn = lib.dm4d_conv_up2x_prepare_f16 if h16 else lib.dm4d_conv_up2x_prepare_bf16
-    _l.check(fn(_stream(), _p(wt), _p(wp), Cout, Cin), "dm4d_conv_up2x_prepare")
+    _l.call("dm4d_conv_up2x_prepare_f16" if h16 else "dm4d_conv_up2x_prepare_bf16", _stream(), _p(wt), _p(wp), Cout, Cin)
     return wp
 
 
@@ -502,7 +424,6 @@ class Upsampler:
 def conv_up2x(x: torch.Tensor, wp: torch.Tensor, *, bias=None, out_f32: bool = False) -> torch.Tensor:
     """conv3x3(nearest_upsample_x2(x)) from the phase kernels of conv_up2x_prepare: x [B,H,W,Cin] -> [B,2H,2W,Cout].
     fp16 x / wp / bias (precision "fp16"): fp32 (out_f32) or fp16 result."""
-    lib = _l.load()
     h16 = wp.dtype == F16
     dt = F16 if h16 else BF16
     _req(x, "x", dt), _req(wp, "wp", dt)
@@ -514,10 +435,9 @@ def conv_up2x(x: torch.Tensor, wp: torch.Tensor, *, bias=None, out_f32: bool = F
     # credited with the multiply-adds it executes (4 taps per output pixel), not the 9 of the op it replaces
     with _Prof("conv3x3", 2.0 * B * 4 * H * W * 4 * Cin * Cout, "flop", B * 4 * H * W):
         if h16:
-            rc = lib.dm4d_conv_up2x_nhwc_f16(_stream(), _p(x), B, H, W, Cin, _p(wp), _p(y), Cout, _p(bias), _l.EPI_F32OUT if out_f32 else 0)
+            _l.call("dm4d_conv_up2x_nhwc_f16", _stream(), _p(x), B, H, W, Cin, _p(wp), _p(y), Cout, _p(bias), _l.EPI_F32OUT if out_f32 else 0)
         else:
-            rc = lib.dm4d_conv_up2x_nhwc_bf16(_stream(), _p(x), B, H, W, Cin, _p(wp), _p(y), Cout, _p(bias))
-    _l.check(rc, "dm4d_conv_up2x_nhwc")
+            _l.call("dm4d_conv_up2x_nhwc_bf16", _stream(), _p(x), B, H, W, Cin, _p(wp), _p(y), Cout, _p(bias))
     if not h16:
         _trace("conv_up2x", y, x=x, wp=wp, bias=bias)
     return y
@@ -527,7 +447,6 @@ def conv2d_direct(x: torch.Tensor, wt: torch.Tensor, *, ksize: int, bias=None, s
                   silu: bool = False) -> torch.Tensor:
     """Thin-layer convolution (PoseEncoder): x [B,H,W,Cin] NHWC, wt [Cout, ksize*ksize*Cin] ((ky,kx,ci) order).  bf16 tensors, or
     (parity precision) x, wt, bias and the result all fp32."""
-    lib = _l.load()
     dt = F32 if x.dtype == F32 else BF16
     _req(x, "x", dt), _req(wt, "wt", dt)
     if bias is not None:
@@ -538,9 +457,8 @@ def conv2d_direct(x: torch.Tensor, wt: torch.Tensor, *, ksize: int, bias=None, s
     assert wt.shape[1] == ksize * ksize * Cin, (wt.shape, ksize, Cin)
     Ho, Wo = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
     y = torch.empty((B, Ho, Wo, Cout), dtype=dt, device=x.device)
-    fn = lib.dm4d_conv2d_direct_nhwc_f32 if dt == F32 else lib.dm4d_conv2d_direct_nhwc_bf16
-    rc = fn(_stream(), _p(x), B, H, W, Cin, _p(wt), _p(bias), _p(y), Ho, Wo, Cout, ksize, stride, pad, 1 if silu else 0)
-    _l.check(rc, "dm4d_conv2d_direct_nhwc")
+    _l.call("dm4d_conv2d_direct_nhwc_f32" if dt == F32 else "dm4d_conv2d_direct_nhwc_bf16",
+            _stream(), _p(x), B, H, W, Cin, _p(wt), _p(bias), _p(y), Ho, Wo, Cout, ksize, stride, pad, 1 if silu else 0)
     return y
 
 
@@ -548,119 +466,76 @@ def groupnorm(x1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups:
               x2: Optional[torch.Tensor] = None, silu: bool = False, raw_out: bool = False):
     """GroupNorm(+SiLU) over the channel concat [x1 | x2]; x [B, HW, C] (any leading spatial shape).
     fp32 input (wide precisions): the result leaves as an operand -- parity: fp64 statistics, two-term [..., 2 C]; fp16 (fp16 gamma / beta):
-    one fp16 plane.  raw_out (fp16 precision): also returns fp16 of the un-normalised concat [x1 | x2] (the shortcut convolution's operand)
-    -> (y, raw)."""
+    one fp16 plane.  fp16 input (precision "fp16": an activation its producer left in fp16, conv1's output in front of norm2) -> one fp16
+    plane.  raw_out (fp16 precision, fp32 input): also returns fp16 of the un-normalised concat [x1 | x2] (the shortcut convolution's
+    operand) -> (y, raw)."""
     lib = _l.load()
-    if isinstance(x1, torch.Tensor) and x1.dtype == F32:
-        return _groupnorm_f32(x1, gamma, beta, groups, eps, x2, silu, raw_out)
-    assert not raw_out
-    if isinstance(x1, torch.Tensor) and x1.dtype == F16:
-        return _groupnorm_f16(x1, gamma, beta, groups, eps, x2, silu)
-    _req(x1, "x1"), _req(gamma, "gamma"), _req(beta, "beta")
+    xdt = x1.dtype if isinstance(x1, torch.Tensor) and x1.dtype in (F32, F16) else BF16
+    wide = xdt == F32
+    h16 = xdt == F16 or (wide and gamma.dtype == F16)  # precision "fp16": fp16 parameters, one fp16 plane out
+    pdt, planes = (F16 if h16 else BF16), (2 if wide and not h16 else 1)
+    assert wide or not raw_out
+    _req(x1, "x1", xdt), _req(gamma, "gamma", pdt), _req(beta, "beta", pdt)
     assert x1.is_contiguous()
     B, C1 = x1.shape[0], x1.shape[-1]
     HW = x1.numel() // (B * C1)
     C2 = 0
     if x2 is not None:
-        _req(x2, "x2")
+        _req(x2, "x2", xdt)
         assert x2.is_contiguous() and x2.shape[0] == B
         C2 = x2.shape[-1]
-    y = torch.empty(x1.shape[:-1] + (C1 + C2,), dtype=BF16, device=x1.device)
-    ws = torch.empty(lib.dm4d_groupnorm_ws_bytes(B, HW, groups) // 4, dtype=torch.float32, device=x1.device)
-    with _Prof("groupnorm", 2.0 * y.numel() * 2, "byte", B * HW):  # ALGORITHMIC bytes (SURVEY 8d): read once + write once; the
-        # statistics pass re-reads the input (mostly from L2 / Infinity Cache), so the device moves up to 1.5x this
-        rc = lib.dm4d_groupnorm_nhwc_bf16(_stream(), _p(x1), C1, _p(x2), C2, B, HW, groups, eps, _p(gamma), _p(beta),
-                                          _p(y), 1 if silu else 0, _p(ws))
-    _l.check(rc, "dm4d_groupnorm_nhwc_bf16")
-    _trace("groupnorm", y, x1=x1, x2=x2, gamma=gamma, beta=beta, groups=groups, eps=eps, silu=silu)
-    return y
-
-
-def _groupnorm_f32(x1, gamma, beta, groups, eps, x2, silu, raw_out=False):
-    lib = _l.load()
-    h16 = gamma.dtype == F16  # precision "fp16": fp16 parameters, one fp16 plane out
-    pdt = F16 if h16 else BF16
-    _req(x1, "x1", F32), _req(gamma, "gamma", pdt), _req(beta, "beta", pdt)
-    assert x1.is_contiguous()
-    B, C1 = x1.shape[0], x1.shape[-1]
-    HW = x1.numel() // (B * C1)
-    C2 = 0
-    if x2 is not None:
-        _req(x2, "x2", F32)
-        assert x2.is_contiguous() and x2.shape[0] == B
-        C2 = x2.shape[-1]
-    y = torch.empty(x1.shape[:-1] + ((1 if h16 else 2) * (C1 + C2),), dtype=pdt, device=x1.device)
-    ws = torch.empty(lib.dm4d_groupnorm_f32_ws_bytes(B, HW, groups) // 8, dtype=torch.float64, device=x1.device)
-    bpe = 6.0 if h16 else 8.0  # algorithmic bytes per element: fp32 in + the operand out (one fp16 plane, or hi + lo)
+    y = torch.empty(x1.shape[:-1] + (planes * (C1 + C2),), dtype=pdt, device=x1.device)
+    if wide:
+        ws = torch.empty(lib.dm4d_groupnorm_f32_ws_bytes(B, HW, groups) // 8, dtype=torch.float64, device=x1.device)
+    else:
+        ws = torch.empty(lib.dm4d_groupnorm_ws_bytes(B, HW, groups) // 4, dtype=torch.float32, device=x1.device)
+    # ALGORITHMIC bytes per element (SURVEY 8d): read once + write once (the operand out: one 16-bit plane, or hi + lo); the statistics
+    # pass re-reads the input (mostly from L2 / Infinity Cache), so the device moves up to 1.5x this
+    bpe = (4.0 if wide else 2.0) + 2.0 * planes
+    n_in = x1.numel() + (x2.numel() if x2 is not None else 0)
     if raw_out:
         if not h16:
             raise _l.Dm4dError("groupnorm: raw_out is a feature of the fp16 precision")
         fused = C1 % 8 == 0 and C2 % 8 == 0 and all(t is None or t.data_ptr() % 16 == 0 for t in (x1, x2))
         if not fused:  # shapes the vectorised kernels do not take: the operand from its own pass
             M = B * HW
-            return (_groupnorm_f32(x1, gamma, beta, groups, eps, x2, silu),
+            return (groupnorm(x1, gamma, beta, groups, eps, x2=x2, silu=silu),
                     split(x1.reshape(M, C1), x2.reshape(M, C2) if x2 is not None else None, h16=True).view(y.shape))
         raw = torch.empty_like(y)
-        with _Prof("groupnorm", (bpe + 2.0) * (x1.numel() + (x2.numel() if x2 is not None else 0)), "byte", B * HW):
-            rc = lib.dm4d_groupnorm_nhwc_f32_f16_raw(_stream(), _p(x1), C1, _p(x2), C2, B, HW, groups, eps, _p(gamma), _p(beta), _p(y), _p(raw),
-                                                     1 if silu else 0, _p(ws))
-        _l.check(rc, "dm4d_groupnorm_nhwc_f32_f16_raw")
+        with _Prof("groupnorm", (bpe + 2.0) * n_in, "byte", B * HW):
+            _l.call("dm4d_groupnorm_nhwc_f32_f16_raw", _stream(), _p(x1), C1, _p(x2), C2, B, HW, groups, eps, _p(gamma), _p(beta), _p(y),
+                    _p(raw), 1 if silu else 0, _p(ws))
         return y, raw
-    with _Prof("groupnorm", bpe * x1.numel() + (bpe * x2.numel() if x2 is not None else 0.0), "byte", B * HW):
-        fn = lib.dm4d_groupnorm_nhwc_f32_f16 if h16 else lib.dm4d_groupnorm_nhwc_f32_split
-        rc = fn(_stream(), _p(x1), C1, _p(x2), C2, B, HW, groups, eps, _p(gamma), _p(beta), _p(y), 1 if silu else 0, _p(ws))
-    _l.check(rc, "dm4d_groupnorm_nhwc_f32_split")
-    return y
-
-
-def _groupnorm_f16(x1, gamma, beta, groups, eps, x2, silu):
-    """precision "fp16", fp16 input (an activation its producer left in fp16: conv1's output in front of norm2) -> one fp16 plane."""
-    lib = _l.load()
-    _req(x1, "x1", F16), _req(gamma, "gamma", F16), _req(beta, "beta", F16)
-    assert x1.is_contiguous()
-    B, C1 = x1.shape[0], x1.shape[-1]
-    HW = x1.numel() // (B * C1)
-    C2 = 0
-    if x2 is not None:
-        _req(x2, "x2", F16)
-        assert x2.is_contiguous() and x2.shape[0] == B
-        C2 = x2.shape[-1]
-    y = torch.empty(x1.shape[:-1] + (C1 + C2,), dtype=F16, device=x1.device)
-    ws = torch.empty(lib.dm4d_groupnorm_ws_bytes(B, HW, groups) // 4, dtype=torch.float32, device=x1.device)
-    with _Prof("groupnorm", 2.0 * y.numel() * 2, "byte", B * HW):
-        rc = lib.dm4d_groupnorm_nhwc_f16_f16(_stream(), _p(x1), C1, _p(x2), C2, B, HW, groups, eps, _p(gamma), _p(beta), _p(y),
-                                             1 if silu else 0, _p(ws))
-    _l.check(rc, "dm4d_groupnorm_nhwc_f16_f16")
+    if wide:
+        name = "dm4d_groupnorm_nhwc_f32_f16" if h16 else "dm4d_groupnorm_nhwc_f32_split"
+    else:
+        name = "dm4d_groupnorm_nhwc_f16_f16" if h16 else "dm4d_groupnorm_nhwc_bf16"
+    with _Prof("groupnorm", bpe * n_in, "byte", B * HW):
+        _l.call(name, _stream(), _p(x1), C1, _p(x2), C2, B, HW, groups, eps, _p(gamma), _p(beta), _p(y), 1 if silu else 0, _p(ws))
+    if xdt == BF16:
+        _trace("groupnorm", y, x1=x1, x2=x2, gamma=gamma, beta=beta, groups=groups, eps=eps, silu=silu)
     return y
 
 
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
-    """fp32 input (parity precision): the result leaves as a two-term operand [..., 2 C]."""
-    lib = _l.load()
-    if isinstance(x, torch.Tensor) and x.dtype == F32:
-        h16 = gamma.dtype == F16  # precision "fp16": fp16 parameters, one fp16 plane out
-        pdt, planes = (F16, 1) if h16 else (BF16, 2)
-        _req(x, "x", F32), _req(gamma, "gamma", pdt), _req(beta, "beta", pdt)
-        x2 = x.reshape(-1, x.shape[-1])
-        C = x2.shape[1]
-        y = torch.empty((x2.shape[0], planes * C), dtype=pdt, device=x.device)
-        with _Prof("layernorm", (4.0 + 2.0 * planes) * x2.numel(), "byte", x2.shape[0]):
-            fn = lib.dm4d_layernorm_f32_f16 if h16 else lib.dm4d_layernorm_f32_split
-            rc = fn(_stream(), _p(x2), x2.stride(0), _p(gamma), _p(beta), _p(y), y.stride(0), x2.shape[0], C, eps)
-        _l.check(rc, "dm4d_layernorm_f32_split")
-        return y.view(x.shape[:-1] + (planes * C,))
-    _req(x, "x"), _req(gamma, "gamma"), _req(beta, "beta")
+    """fp32 input (wide precisions): the result leaves as an operand -- parity: two-term [..., 2 C]; fp16 (fp16 gamma / beta): one fp16
+    plane."""
+    wide = isinstance(x, torch.Tensor) and x.dtype == F32
+    h16 = wide and gamma.dtype == F16
+    pdt, planes = (F16 if h16 else BF16), (2 if wide and not h16 else 1)
+    _req(x, "x", F32 if wide else BF16), _req(gamma, "gamma", pdt), _req(beta, "beta", pdt)
     x2 = x.reshape(-1, x.shape[-1])
-    y = torch.empty_like(x2)
-    with _Prof("layernorm", 2.0 * y.numel() * 2, "byte", x2.shape[0]):
-        rc = lib.dm4d_layernorm_bf16(_stream(), _p(x2), x2.stride(0), _p(gamma), _p(beta), _p(y), y.stride(0), x2.shape[0],
-                                     x2.shape[1], eps)
-    _l.check(rc, "dm4d_layernorm_bf16")
-    _trace("layernorm", y, x=x2, gamma=gamma, beta=beta, eps=eps)
-    return y.view(x.shape)
-
-
-LOG2E = 1.4426950408889634
+    M, C = x2.shape
+    y = torch.empty((M, planes * C), dtype=pdt, device=x.device)
+    if wide:
+        name = "dm4d_layernorm_f32_f16" if h16 else "dm4d_layernorm_f32_split"
+    else:
+        name = "dm4d_layernorm_bf16"
+    with _Prof("layernorm", ((4.0 if wide else 2.0) + 2.0 * planes) * x2.numel(), "byte", M):
+        _l.call(name, _stream(), _p(x2), x2.stride(0), _p(gamma), _p(beta), _p(y), y.stride(0), M, C, eps)
+    if not wide:
+        _trace("layernorm", y, x=x2, gamma=gamma, beta=beta, eps=eps)
+    return y.view(x.shape[:-1] + (planes * C,))
 
 
 HEAD_DIMS_HD = (40, 80, 160)  # head dimensions of the attention_hd.hip kernels (SD-1.x layout); 64 has attention.hip's own
@@ -682,7 +557,6 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, hea
     64 (attention.hip) or 40 / 80 / 160 (attention_hd.hip; pre-scaled Q only).
     kv_seq: keys per batch when K/V hold more tokens than Q (frame-sharded 3-D attention); default = seq.
     q_scaled: q already carries scale * LOG2E (folded into the to_q weights, unet._TransformerBlock)."""
-    lib = _l.load()
     h16 = isinstance(q, torch.Tensor) and q.dtype == F16  # precision "fp16": fp16 Q (pre-scaled) / K / V -> fp16 O
     dt = F16 if h16 else BF16
     _req(q, "q", dt), _req(k, "k", dt), _req(v, "v", dt)
@@ -703,23 +577,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, batch: int, hea
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
     with _Prof("attention", 4.0 * batch * heads * seq * kv_seq * d, "flop", batch * seq):
+        args = (_stream(), _p(q), _p(k), _p(v), _p(out), q.stride(0), k.stride(0), v.stride(0), out.stride(0), batch, heads)
         if d != 64:
-            fn = lib.dm4d_attention_hd_qscaled_kv_f16 if h16 else lib.dm4d_attention_hd_qscaled_kv_bf16
-            rc = fn(_stream(), _p(q), _p(k), _p(v), _p(out), q.stride(0), k.stride(0), v.stride(0), out.stride(0), batch, heads, d, seq,
-                    kv_seq)
+            _l.call("dm4d_attention_hd_qscaled_kv_f16" if h16 else "dm4d_attention_hd_qscaled_kv_bf16", *args, d, seq, kv_seq)
         elif h16:
-            rc = lib.dm4d_attention_qscaled_kv_f16(_stream(), _p(q), _p(k), _p(v), _p(out), q.stride(0), k.stride(0),
-                                                   v.stride(0), out.stride(0), batch, heads, seq, kv_seq)
+            _l.call("dm4d_attention_qscaled_kv_f16", *args, seq, kv_seq)
         elif q_scaled:
-            rc = lib.dm4d_attention_qscaled_kv_bf16(_stream(), _p(q), _p(k), _p(v), _p(out), q.stride(0), k.stride(0),
-                                                    v.stride(0), out.stride(0), batch, heads, seq, kv_seq)
+            _l.call("dm4d_attention_qscaled_kv_bf16", *args, seq, kv_seq)
         else:
-            rc = lib.dm4d_attention_kv_bf16(_stream(), _p(q), _p(k), _p(v), _p(out), q.stride(0), k.stride(0),
-                                            v.stride(0), out.stride(0), batch, heads, seq, kv_seq, scale)
+            _l.call("dm4d_attention_kv_bf16", *args, seq, kv_seq, scale)
     if prof is not None:
         e1.record()
         prof.append(("attn_kernel" if d == 64 else "attn_hd_kernel", 4.0 * batch * heads * seq * kv_seq * d, e0, e1))
-    _l.check(rc, "dm4d_attention_kv_bf16" if d == 64 else "dm4d_attention_hd_qscaled_kv")
     if h16 or d != 64:  # oracle/replay.py recomputes the head_dim 64 launches only
         return out
     _trace("attention", out, q=q, k=k, v=v, batch=batch, heads=heads, seq=seq, kv_seq=kv_seq, scale=scale, q_scaled=q_scaled)
@@ -734,7 +603,6 @@ def attention_split(qkv: Optional[torch.Tensor], batch: int, heads: int, seq: in
     [k_hi | v_hi | k_lo | v_lo] of the all-gathered keys (the planes of gemm(n, w_kv, split_out=True)).
     Three MFMAs per product, exact running-max softmax in fp32 (dm4d_attention_split_bf16; head dimensions 40 / 80 / 160:
     dm4d_attention_hd_split_bf16).  d comes from the operand widths: qkv.shape[1] // (6 heads), or q.shape[1] // (2 heads)."""
-    lib = _l.load()
     if qkv is not None:
         d = _head_dim(qkv.shape[1] // 6 if qkv.shape[1] % 6 == 0 else -1, heads, "attention_split")
     else:
@@ -758,31 +626,23 @@ def attention_split(qkv: Optional[torch.Tensor], batch: int, heads: int, seq: in
     out = torch.empty((batch * seq, 2 * C), dtype=BF16, device=dev)
     scale = d ** -0.5 if scale is None else scale
     with _Prof("attention", 3 * 4.0 * batch * heads * seq * kv_seq * d, "flop", batch * seq):  # three MFMA terms per product
+        args = (_stream(), qp, kp, vp, _p(out), ldq, ldk, ldv, out.stride(0), q_lo, k_lo, v_lo, C, batch, heads, seq, kv_seq, scale)
         if d == 64:
-            rc = lib.dm4d_attention_split_bf16(_stream(), qp, kp, vp, _p(out), ldq, ldk, ldv, out.stride(0), q_lo, k_lo, v_lo, C, batch,
-                                               heads, seq, kv_seq, scale)
+            _l.call("dm4d_attention_split_bf16", *args)
         else:
-            rc = lib.dm4d_attention_hd_split_bf16(_stream(), qp, kp, vp, _p(out), ldq, ldk, ldv, out.stride(0), q_lo, k_lo, v_lo, C,
-                                                  batch, heads, seq, kv_seq, scale, d)
-    _l.check(rc, "dm4d_attention_split_bf16" if d == 64 else "dm4d_attention_hd_split_bf16")
+            _l.call("dm4d_attention_hd_split_bf16", *args, d)
     return out
 
 
 def softmax_rows_split(s: torch.Tensor, scale: float, n: Optional[int] = None, h16: bool = False) -> torch.Tensor:
     """Wide precisions: P = softmax(s * scale) over the first n columns of fp32 logits s [M, Np] -> parity: three planes
     [p_hi | p_lo | p_hi], bf16 [M, 3 Np]; h16 (precision "fp16"): one fp16 plane [M, Np] (columns n .. Np-1 of every plane zero)."""
-    lib = _l.load()
     _req(s, "s", F32)
     M, Np = s.shape
     n = Np if n is None else int(n)
-    if h16:
-        p = torch.empty((M, Np), dtype=F16, device=s.device)
-        _l.check(lib.dm4d_softmax_rows_f32_f16(_stream(), _p(s), s.stride(0), _p(p), p.stride(0), M, n, Np, scale),
-                 "dm4d_softmax_rows_f32_f16")
-        return p
-    p = torch.empty((M, 3 * Np), dtype=BF16, device=s.device)
-    _l.check(lib.dm4d_softmax_rows_f32_split(_stream(), _p(s), s.stride(0), _p(p), p.stride(0), M, n, Np, scale),
-             "dm4d_softmax_rows_f32_split")
+    p = torch.empty((M, Np if h16 else 3 * Np), dtype=F16 if h16 else BF16, device=s.device)
+    _l.call("dm4d_softmax_rows_f32_f16" if h16 else "dm4d_softmax_rows_f32_split", _stream(), _p(s), s.stride(0), _p(p), p.stride(0), M, n,
+            Np, scale)
     return p
 
 
@@ -819,7 +679,6 @@ def softmax_rows(s: torch.Tensor, scale: float, n: Optional[int] = None, out: Op
     """P = softmax(s * scale) per row, bf16; s bf16 or fp32 (logits from gemm(out_f32=True)).
     n (fp32 logits only): softmax over the first n columns of every row -- a key axis padded to the GEMM's K granularity; `out`
     (same shape as s) then keeps whatever it holds behind column n (the caller's zeros)."""
-    lib = _l.load()
     f32 = s.dtype == torch.float32
     _req(s, "s", torch.float32 if f32 else BF16)
     if n is not None and not f32:
@@ -828,30 +687,26 @@ def softmax_rows(s: torch.Tensor, scale: float, n: Optional[int] = None, out: Op
     _req(p, "out", BF16)
     if p.shape != s.shape:
         raise _l.Dm4dError(f"softmax_rows: out has shape {tuple(p.shape)}, the logits {tuple(s.shape)}")
-    fn = lib.dm4d_softmax_rows_f32in_bf16 if f32 else lib.dm4d_softmax_rows_bf16
-    rc = fn(_stream(), _p(s), s.stride(0), _p(p), p.stride(0), s.shape[0], s.shape[1] if n is None else int(n), scale)
-    _l.check(rc, "dm4d_softmax_rows_f32in_bf16" if f32 else "dm4d_softmax_rows_bf16")
+    _l.call("dm4d_softmax_rows_f32in_bf16" if f32 else "dm4d_softmax_rows_bf16", _stream(), _p(s), s.stride(0), _p(p), p.stride(0),
+            s.shape[0], s.shape[1] if n is None else int(n), scale)
     _trace("softmax_rows", p, s=s, scale=scale, n=n)
     return p
 
 
 def timestep_embedding(t: torch.Tensor, dim: int, flip_sin_to_cos: bool = True, freq_shift: float = 0.0,
                        out_f32: bool = False) -> torch.Tensor:
-    lib = _l.load()
     _req(t, "t", torch.float32)
     out = torch.empty((t.shape[0], dim), dtype=F32 if out_f32 else BF16, device=t.device)
-    fn = lib.dm4d_timestep_embedding_f32 if out_f32 else lib.dm4d_timestep_embedding_bf16
-    rc = fn(_stream(), _p(t), _p(out), t.shape[0], dim, 1 if flip_sin_to_cos else 0, freq_shift)
-    _l.check(rc, "dm4d_timestep_embedding")
+    _l.call("dm4d_timestep_embedding_f32" if out_f32 else "dm4d_timestep_embedding_bf16", _stream(), _p(t), _p(out), t.shape[0], dim,
+            1 if flip_sin_to_cos else 0, freq_shift)
     return out
 
 
 def silu(x: torch.Tensor) -> torch.Tensor:
-    lib = _l.load()
     _req(x, "x")
     assert x.is_contiguous()
     y = torch.empty_like(x)
-    _l.check(lib.dm4d_silu_bf16(_stream(), _p(x), _p(y), x.numel()), "dm4d_silu_bf16")
+    _l.call("dm4d_silu_bf16", _stream(), _p(x), _p(y), x.numel())
     _trace("silu", y, x=x)
     return y
 
@@ -861,7 +716,6 @@ def pack_model_input(latents, pv_lat, plucker, skel, mask, is_cond, cpad: int, u
     """Inputs NHWC [N, HW, c] (task level); is_cond int32 [F]; frame_idx int32 [F] selects the window's frames
     (None: F = N, identity).  Mutates the cond rows of `latents` (reference aliasing).
     fp32 task tensors (wide precisions): the result is conv_in's operand -- [hi | lo] bf16, or (h16) one fp16 plane."""
-    lib = _l.load()
     dt = F32 if latents.dtype == F32 else BF16  # fp32 task tensors = parity precision: the result is conv_in's two-term operand
     for t, n in ((latents, "latents"), (pv_lat, "pv_lat"), (plucker, "plucker"), (mask, "mask")):
         _req(t, n, dt)
@@ -878,27 +732,32 @@ def pack_model_input(latents, pv_lat, plucker, skel, mask, is_cond, cpad: int, u
     assert not h16 or dt == F32
     out = torch.empty(((2 if use_cfg else 1) * F, HW, 2 * cpad if (dt == F32 and not h16) else cpad), dtype=F16 if h16 else BF16,
                       device=latents.device)
-    fn = lib.dm4d_pack_model_input_f32_f16 if h16 else (lib.dm4d_pack_model_input_f32_split if dt == F32 else lib.dm4d_pack_model_input_bf16)
-    rc = fn(_stream(), _p(latents), _p(pv_lat), _p(plucker), _p(skel), _p(mask), _p(is_cond), _p(frame_idx), _p(out), F, HW, cpad,
+    if dt == F32:
+        name = "dm4d_pack_model_input_f32_f16" if h16 else "dm4d_pack_model_input_f32_split"
+    else:
+        name = "dm4d_pack_model_input_bf16"
+    _l.call(name, _stream(), _p(latents), _p(pv_lat), _p(plucker), _p(skel), _p(mask), _p(is_cond), _p(frame_idx), _p(out), F, HW, cpad,
             1 if use_cfg else 0)
-    _l.check(rc, "dm4d_pack_model_input")
     return out
+
+
+def _cfg_step_inputs(latents, noise_pred, coef, is_cond, frame_idx):
+    """What the three cfg_*_step wrappers ask of their common inputs -> (the tensors' dtype: fp32 in the wide precisions, F, HW)."""
+    dt = F32 if latents.dtype == F32 else BF16
+    _req(latents, "latents", dt), _req(noise_pred, "noise_pred", dt), _req(coef, "coef", torch.float32)
+    _req(is_cond, "is_cond", torch.int32)
+    if frame_idx is not None:
+        _req(frame_idx, "frame_idx", torch.int32)
+    return dt, is_cond.shape[0], latents.shape[1]
 
 
 def cfg_ddim_step(latents, noise_pred, coef, is_cond, use_cfg: bool, guidance_scale: float, v_prediction: bool,
                   frame_idx: Optional[torch.Tensor] = None):
     """In-place DDIM update of rows frame_idx of `latents` [N,HW,4] from noise_pred [cfg*F, HW, ldn]."""
-    lib = _l.load()
-    dt = F32 if latents.dtype == F32 else BF16
-    _req(latents, "latents", dt), _req(noise_pred, "noise_pred", dt), _req(coef, "coef", torch.float32)
-    _req(is_cond, "is_cond", torch.int32)
-    F, HW = is_cond.shape[0], latents.shape[1]
-    if frame_idx is not None:
-        _req(frame_idx, "frame_idx", torch.int32)
-    rc = (lib.dm4d_cfg_ddim_step_f32 if dt == F32 else lib.dm4d_cfg_ddim_step_bf16)(_stream(), _p(latents), _p(noise_pred), noise_pred.stride(-2), _p(coef),
-                                     _p(is_cond), _p(frame_idx), F, HW, 1 if use_cfg else 0, guidance_scale,
-                                     1 if v_prediction else 0)
-    _l.check(rc, "dm4d_cfg_ddim_step_bf16")
+    dt, F, HW = _cfg_step_inputs(latents, noise_pred, coef, is_cond, frame_idx)
+    _l.call("dm4d_cfg_ddim_step_f32" if dt == F32 else "dm4d_cfg_ddim_step_bf16", _stream(), _p(latents), _p(noise_pred),
+            noise_pred.stride(-2), _p(coef), _p(is_cond), _p(frame_idx), F, HW, 1 if use_cfg else 0, guidance_scale,
+            1 if v_prediction else 0)
     return latents
 
 
@@ -906,17 +765,11 @@ def cfg_linear_step(latents, x0_prev, noise_pred, coef, is_cond, use_cfg: bool, 
                     frame_idx: Optional[torch.Tensor] = None):
     """In-place linear multistep update (x' = a x + b m + c p; p' = d x + e m) of rows frame_idx of `latents` and `x0_prev`
     [N,HW,4] from noise_pred [cfg*F, HW, ldn]; coef [F,8] fp32 rows from scheduler.step_rows."""
-    lib = _l.load()
-    dt = F32 if latents.dtype == F32 else BF16
-    _req(latents, "latents", dt), _req(x0_prev, "x0_prev", dt), _req(noise_pred, "noise_pred", dt), _req(coef, "coef", torch.float32)
-    _req(is_cond, "is_cond", torch.int32)
+    dt, F, HW = _cfg_step_inputs(latents, noise_pred, coef, is_cond, frame_idx)
+    _req(x0_prev, "x0_prev", dt)
     assert x0_prev.shape == latents.shape and coef.shape[-1] == 8 and coef.is_contiguous()
-    F, HW = is_cond.shape[0], latents.shape[1]
-    if frame_idx is not None:
-        _req(frame_idx, "frame_idx", torch.int32)
-    rc = (lib.dm4d_cfg_linear_step_f32 if dt == F32 else lib.dm4d_cfg_linear_step_bf16)(_stream(), _p(latents), _p(x0_prev), _p(noise_pred), noise_pred.stride(-2), _p(coef),
-                                       _p(is_cond), _p(frame_idx), F, HW, 1 if use_cfg else 0, guidance_scale)
-    _l.check(rc, "dm4d_cfg_linear_step_bf16")
+    _l.call("dm4d_cfg_linear_step_f32" if dt == F32 else "dm4d_cfg_linear_step_bf16", _stream(), _p(latents), _p(x0_prev), _p(noise_pred),
+            noise_pred.stride(-2), _p(coef), _p(is_cond), _p(frame_idx), F, HW, 1 if use_cfg else 0, guidance_scale)
     return latents
 
 
@@ -925,94 +778,81 @@ def cfg_multistep_step(latents, states, noise_pred, coef, is_cond, use_cfg: bool
     """In-place general linear multistep update (UniPC with its corrector, DEIS; dm4d.h: dm4d_cfg_multistep_step_bf16) of rows frame_idx
     of `latents` and of the stored tensors `states` (a list of 1-3 tensors shaped like latents, zero at the start of a call) from
     noise_pred [cfg*F, HW, ldn]; coef [F,16] fp32 rows from scheduler.step_rows."""
-    lib = _l.load()
-    dt = F32 if latents.dtype == F32 else BF16
-    _req(latents, "latents", dt), _req(noise_pred, "noise_pred", dt), _req(coef, "coef", torch.float32), _req(is_cond, "is_cond", torch.int32)
+    dt, F, HW = _cfg_step_inputs(latents, noise_pred, coef, is_cond, frame_idx)
     assert 1 <= len(states) <= 3 and coef.shape[-1] == 16 and coef.is_contiguous()
     for t in states:
         _req(t, "state", dt)
         assert t.shape == latents.shape and t.is_contiguous()
-    F, HW = is_cond.shape[0], latents.shape[1]
-    if frame_idx is not None:
-        _req(frame_idx, "frame_idx", torch.int32)
     st = list(states) + [None] * (3 - len(states))
-    fn = lib.dm4d_cfg_multistep_step_f32 if dt == F32 else lib.dm4d_cfg_multistep_step_bf16
-    rc = fn(_stream(), _p(latents), _p(st[0]), _p(st[1]), _p(st[2]), _p(noise_pred), noise_pred.stride(-2), _p(coef), _p(is_cond),
-            _p(frame_idx), F, HW, 1 if use_cfg else 0, guidance_scale)
-    _l.check(rc, "dm4d_cfg_multistep_step")
+    _l.call("dm4d_cfg_multistep_step_f32" if dt == F32 else "dm4d_cfg_multistep_step_bf16", _stream(), _p(latents), _p(st[0]), _p(st[1]),
+            _p(st[2]), _p(noise_pred), noise_pred.stride(-2), _p(coef), _p(is_cond), _p(frame_idx), F, HW, 1 if use_cfg else 0,
+            guidance_scale)
     return latents
 
 
 def nchw_to_nhwc(x: torch.Tensor, cpad: Optional[int] = None) -> torch.Tensor:
-    lib = _l.load()
     _req(x, "x")
     assert x.is_contiguous()
     B, C, H, W = x.shape
     cpad = cpad or C
     y = torch.empty((B, H, W, cpad), dtype=BF16, device=x.device)
-    _l.check(lib.dm4d_nchw_to_nhwc_bf16(_stream(), _p(x), _p(y), B, C, H * W, cpad), "dm4d_nchw_to_nhwc_bf16")
+    _l.call("dm4d_nchw_to_nhwc_bf16", _stream(), _p(x), _p(y), B, C, H * W, cpad)
     return y
 
 
 def nhwc_to_nchw(x: torch.Tensor, C: Optional[int] = None) -> torch.Tensor:
-    lib = _l.load()
     dt = F32 if x.dtype == F32 else BF16
     _req(x, "x", dt)
     assert x.is_contiguous()
     B, H, W, ld = x.shape
     C = C or ld
     y = torch.empty((B, C, H, W), dtype=dt, device=x.device)
-    fn = lib.dm4d_nhwc_to_nchw_f32 if dt == F32 else lib.dm4d_nhwc_to_nchw_bf16
-    _l.check(fn(_stream(), _p(x), _p(y), B, C, H * W, ld), "dm4d_nhwc_to_nchw")
+    _l.call("dm4d_nhwc_to_nchw_f32" if dt == F32 else "dm4d_nhwc_to_nchw_bf16", _stream(), _p(x), _p(y), B, C, H * W, ld)
     return y
 
 
 def vae_sample(moments: torch.Tensor, noise: torch.Tensor, channels: int, scale: float) -> torch.Tensor:
     """moments [..., >=2C] (mean | logvar), noise [..., C] -> (mean + std * noise) * scale, [..., C]."""
-    lib = _l.load()
     dt = F32 if moments.dtype == F32 else BF16
     _req(moments, "moments", dt), _req(noise, "noise", dt)
     assert noise.is_contiguous() and noise.shape[-1] == channels
     M = noise.numel() // channels
     out = torch.empty_like(noise)
-    rc = (lib.dm4d_vae_sample_f32 if dt == F32 else lib.dm4d_vae_sample_bf16)(_stream(), _p(moments), moments.stride(-2), _p(noise), _p(out), M, channels, scale)
-    _l.check(rc, "dm4d_vae_sample_bf16")
+    _l.call("dm4d_vae_sample_f32" if dt == F32 else "dm4d_vae_sample_bf16", _stream(), _p(moments), moments.stride(-2), _p(noise), _p(out),
+            M, channels, scale)
     return out
 
 
 def scale_pad(x: torch.Tensor, cpad: int, scale: float) -> torch.Tensor:
-    lib = _l.load()
     _req(x, "x")
     C = x.shape[-1]
     M = x.numel() // C
     assert x.is_contiguous()
     y = torch.empty(x.shape[:-1] + (cpad,), dtype=BF16, device=x.device)
-    _l.check(lib.dm4d_scale_pad_bf16(_stream(), _p(x), C, _p(y), cpad, M, C, scale), "dm4d_scale_pad_bf16")
+    _l.call("dm4d_scale_pad_bf16", _stream(), _p(x), C, _p(y), cpad, M, C, scale)
     return y
 
 
 def resize_to_nhwc(x: torch.Tensor, size: Tuple[int, int], mode: str, out_f32: bool = False) -> torch.Tensor:
     """x fp32 NCHW on the device -> bf16 (out_f32: fp32) NHWC [B,h,w,C]; mode 'bilinear' | 'nearest' (F.interpolate semantics)."""
-    lib = _l.load()
     _req(x, "x", torch.float32)
     assert x.is_contiguous() and mode in ("bilinear", "nearest")
     B, C, H, W = x.shape
     h, w = size
     y = torch.empty((B, h, w, C), dtype=F32 if out_f32 else BF16, device=x.device)
-    rc = (lib.dm4d_resize_nchw_f32_to_nhwc_f32 if out_f32 else lib.dm4d_resize_nchw_f32_to_nhwc_bf16)(_stream(), _p(x), _p(y), B, C, H, W, h, w, 1 if mode == "bilinear" else 0)
-    _l.check(rc, "dm4d_resize_nchw_f32_to_nhwc_bf16")
+    _l.call("dm4d_resize_nchw_f32_to_nhwc_f32" if out_f32 else "dm4d_resize_nchw_f32_to_nhwc_bf16", _stream(), _p(x), _p(y), B, C, H, W,
+            h, w, 1 if mode == "bilinear" else 0)
     return y
 
 
 def resize_aa(x: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
     """F.interpolate(x, size=size, mode="bilinear", antialias=True) for fp32 NCHW on the device (the result writer's mosaic)."""
-    lib = _l.load()
     _req(x, "x", F32)
     assert x.is_contiguous() and x.ndim == 4
     N, C, H, W = x.shape
     h, w = size
     y = torch.empty((N, C, h, w), dtype=F32, device=x.device)
-    _l.check(lib.dm4d_resize_aa_nchw_f32(_stream(), _p(x), _p(y), N * C, H, W, h, w), "dm4d_resize_aa_nchw_f32")
+    _l.call("dm4d_resize_aa_nchw_f32", _stream(), _p(x), _p(y), N * C, H, W, h, w)
     return y
 
 
@@ -1029,29 +869,22 @@ def camera_rows(Ks: torch.Tensor, poses: torch.Tensor) -> torch.Tensor:
 def plucker_latents(Ks: torch.Tensor, poses: torch.Tensor, image_size: Tuple[int, int], latent_size: Tuple[int, int],
                     device, out_f32: bool = False) -> torch.Tensor:
     """Pluecker maps at latent resolution from the cameras -> bf16 (out_f32: fp32) NHWC [N, h, w, 6] on `device` (see dm4d.h)."""
-    lib = _l.load()
     cams = camera_rows(Ks, poses).to(device)
     (H, W), (h, w) = image_size, latent_size
     y = torch.empty((cams.shape[0], h, w, 6), dtype=F32 if out_f32 else BF16, device=device)
-    rc = (lib.dm4d_plucker_latent_f32 if out_f32 else lib.dm4d_plucker_latent_bf16)(_stream(), _p(cams), _p(y), cams.shape[0], H, W, h, w)
-    _l.check(rc, "dm4d_plucker_latent_bf16")
+    _l.call("dm4d_plucker_latent_f32" if out_f32 else "dm4d_plucker_latent_bf16", _stream(), _p(cams), _p(y), cams.shape[0], H, W, h, w)
     return y
 
 
 def postprocess_images(x: torch.Tensor, channels: int = 3) -> torch.Tensor:
     """NHWC [B,H,W,ld] -> NCHW [B,channels,H,W] with (x/2+0.5).clamp(0,1)."""
-    lib = _l.load()
     dt = F32 if x.dtype == F32 else BF16
     _req(x, "x", dt)
     assert x.is_contiguous()
     B, H, W, ld = x.shape
     y = torch.empty((B, channels, H, W), dtype=dt, device=x.device)
-    fn = lib.dm4d_postprocess_images_f32 if dt == F32 else lib.dm4d_postprocess_images_bf16
-    _l.check(fn(_stream(), _p(x), _p(y), B, channels, H * W, ld), "dm4d_postprocess_images")
+    _l.call("dm4d_postprocess_images_f32" if dt == F32 else "dm4d_postprocess_images_bf16", _stream(), _p(x), _p(y), B, channels, H * W, ld)
     return y
-
-
-CAPTURE_FIELDS = 16  # include/dm4d.h DM4D_CAPTURE_FIELDS
 
 
 def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: int, desc_off: int, tab_off: int, tab_len: int,
@@ -1062,7 +895,6 @@ def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: i
     every descriptor and table on the host copy before it launches.  With `meta` (uint8, on blob's device) the tables and the
     descriptors are read from it instead, at the same two offsets, `blob_host` is the host copy of `meta`, and `blob` holds
     planes only, some of which may never have been on the host."""
-    lib = _l.load()
     _req(blob, "blob", torch.uint8)
     where = blob if meta is None else _req(meta, "meta", torch.uint8)
     if blob_host.device.type != "cpu" or blob_host.dtype != torch.uint8 or blob_host.numel() != where.numel():
@@ -1078,15 +910,9 @@ def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: i
     pix = torch.empty((n_frames, 3, H, W), dtype=F32, device=blob.device)
     skel = torch.empty((n_frames, 3, H, W), dtype=F32, device=blob.device)
     base = where.data_ptr()
-    rc = lib.dm4d_capture_crop_resize_f32(_stream(), blob.data_ptr(), blob.numel(), desc.data_ptr(), base + desc_off, n_frames, tab.data_ptr(),
-                                          base + tab_off, tab_len, _p(scratch), scratch.numel(), _p(pix), _p(skel), H, W)
-    _l.check(rc, "dm4d_capture_crop_resize_f32")
+    _l.call("dm4d_capture_crop_resize_f32", _stream(), blob.data_ptr(), blob.numel(), desc.data_ptr(), base + desc_off, n_frames, tab.data_ptr(),
+            base + tab_off, tab_len, _p(scratch), scratch.numel(), _p(pix), _p(skel), H, W)
     return pix, skel
-
-
-EVAL_FIELDS = 16  # include/dm4d.h DM4D_EVAL_FIELDS
-EVAL_OUT = 8      # include/dm4d.h DM4D_EVAL_OUT
-EVAL_IMAGE_F32, EVAL_MASK_F32, EVAL_CROP_MASKS, EVAL_BG_SHIFT = 1, 2, 4, 3
 
 
 def eval_psnr_ssim(blob: torch.Tensor, desc: torch.Tensor, desc_off: Optional[int] = None, debug: bool = False):
@@ -1112,20 +938,14 @@ def eval_psnr_ssim(blob: torch.Tensor, desc: torch.Tensor, desc_off: Optional[in
     out = torch.empty((n, EVAL_OUT), dtype=torch.float64, device=blob.device)
     boxes = torch.empty((n, 4), dtype=torch.int32, device=blob.device)
     dbg = torch.zeros((n, 2, 3, max(max_h, 1), max(max_w, 1)), dtype=F32, device=blob.device) if debug else None
-    rc = lib.dm4d_eval_psnr_ssim_f64(_stream(), blob.data_ptr(), blob.numel(), desc.data_ptr(), desc_ptr, n, _p(ws), ws.numel(), _p(out),
-                                     _p(boxes), _p(dbg), max_h, max_w)
-    _l.check(rc, "dm4d_eval_psnr_ssim_f64")
+    _l.call("dm4d_eval_psnr_ssim_f64", _stream(), blob.data_ptr(), blob.numel(), desc.data_ptr(), desc_ptr, n, _p(ws), ws.numel(), _p(out),
+            _p(boxes), _p(dbg), max_h, max_w)
     return (out, boxes, dbg) if debug else (out, boxes)
-
-
-LPIPS_TAPS = 5      # include/dm4d.h DM4D_LPIPS_TAPS
-LPIPS_IN_COLS = 64  # include/dm4d.h DM4D_LPIPS_IN_COLS
 
 
 def lpips_input(gt: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
     """LPIPS' input scaling of one pair of cropped composites (fp32 [3, h, w] views with one row / plane stride, in [0, 1]) -> the operand
     of VGG's first convolution, bf16 [2, h, w, LPIPS_IN_COLS] = [hi(3) | lo(3) | hi(3) | zeros] (0 = gt, 1 = pred)."""
-    lib = _l.load()
     _req(gt, "gt", F32), _req(pred, "pred", F32)
     if gt.dim() != 3 or gt.shape[0] != 3 or gt.shape != pred.shape:
         raise _l.Dm4dError(f"lpips_input: expected two fp32 [3, h, w] images of one shape, got {tuple(gt.shape)} and {tuple(pred.shape)}")
@@ -1133,23 +953,20 @@ def lpips_input(gt: torch.Tensor, pred: torch.Tensor) -> torch.Tensor:
         gt, pred = gt.contiguous(), pred.contiguous()
     _, h, w = gt.shape
     y = torch.empty((2, h, w, LPIPS_IN_COLS), dtype=BF16, device=gt.device)
-    rc = lib.dm4d_lpips_input_split(_stream(), _p(gt), _p(pred), gt.stride(0), gt.stride(1), h, w, _p(y))
-    _l.check(rc, "dm4d_lpips_input_split")
+    _l.call("dm4d_lpips_input_split", _stream(), _p(gt), _p(pred), gt.stride(0), gt.stride(1), h, w, _p(y))
     return y
 
 
 def lpips_relu_pool(x: torch.Tensor, pool: bool) -> torch.Tensor:
     """ReLU (+ the 2 x 2 stride-2 floor max-pool) of a convolution's fp32 output [B, H, W, C] -> the pattern-1 operand of the next
     convolution, bf16 [B, Ho, Wo, 3 C] = [hi | lo | hi]."""
-    lib = _l.load()
     _req(x, "x", F32)
     assert x.dim() == 4 and x.is_contiguous()
     B, H, W, C = x.shape
     Ho, Wo = (H // 2, W // 2) if pool else (H, W)
     y = torch.empty((B, Ho, Wo, 3 * C), dtype=BF16, device=x.device)
     with _Prof("lpips_relu_pool", 4.0 * x.numel() + 2.0 * y.numel(), "byte", B * Ho * Wo):
-        rc = lib.dm4d_lpips_relu_pool_split(_stream(), _p(x), _p(y), B, H, W, C, 1 if pool else 0)
-    _l.check(rc, "dm4d_lpips_relu_pool_split")
+        _l.call("dm4d_lpips_relu_pool_split", _stream(), _p(x), _p(y), B, H, W, C, 1 if pool else 0)
     return y
 
 
@@ -1161,23 +978,16 @@ def lpips_ws(h: int, w: int, device) -> torch.Tensor:
 def lpips_tap_distance(f: torch.Tensor, lin: torch.Tensor, tap: int, out: torch.Tensor, ws: torch.Tensor) -> None:
     """One LPIPS tap: f fp32 [2, H, W, C] (a convolution's output before ReLU), lin fp32 [C] -> out[tap] = the tap's distance (out: fp64
     [LPIPS_TAPS] on the device); ws: lpips_ws(H, W) or larger."""
-    lib = _l.load()
     _req(f, "f", F32), _req(lin, "lin", F32), _req(out, "out", torch.float64), _req(ws, "ws", torch.uint8)
     assert f.dim() == 4 and f.shape[0] == 2 and f.is_contiguous() and lin.numel() == f.shape[3] and out.numel() == LPIPS_TAPS
     _, H, W, C = f.shape
     with _Prof("lpips_distance", 4.0 * f.numel(), "byte", H * W):
-        rc = lib.dm4d_lpips_tap_distance_f64(_stream(), _p(f), _p(lin), H, W, C, tap, _p(ws), ws.numel(), _p(out))
-    _l.check(rc, "dm4d_lpips_tap_distance_f64")
-
-
-VHULL_BLOCK = 256           # include/dm4d.h DM4D_VHULL_BLOCK
-VHULL_MAX_CHUNK = 1 << 26   # include/dm4d.h DM4D_VHULL_MAX_CHUNK
+        _l.call("dm4d_lpips_tap_distance_f64", _stream(), _p(f), _p(lin), H, W, C, tap, _p(ws), ws.numel(), _p(out))
 
 
 def vhull_pack_masks(masks: torch.Tensor) -> torch.Tensor:
     """Foreground masks bool or uint8 [B, H, W] (nonzero = foreground) -> bits int32 [B, H, ceil(W / 32)]: pixel x of a row is bit x & 31 of
     its word x >> 5 (what vhull_carve_chunk reads)."""
-    lib = _l.load()
     if isinstance(masks, torch.Tensor) and masks.dtype == torch.bool:
         masks = masks.view(torch.uint8)
     _req(masks, "masks", torch.uint8)
@@ -1185,7 +995,7 @@ def vhull_pack_masks(masks: torch.Tensor) -> torch.Tensor:
         raise _l.Dm4dError(f"masks: expected a contiguous [B, H, W] tensor, got {tuple(masks.shape)}")
     B, H, W = masks.shape
     bits = torch.empty((B, H, (W + 31) // 32), dtype=torch.int32, device=masks.device)
-    _l.check(lib.dm4d_vhull_pack_masks(_stream(), _p(masks), _p(bits), B, H, W), "dm4d_vhull_pack_masks")
+    _l.call("dm4d_vhull_pack_masks", _stream(), _p(masks), _p(bits), B, H, W)
     return bits
 
 
@@ -1203,7 +1013,6 @@ def vhull_carve_chunk(xs: torch.Tensor, ys: torch.Tensor, zs: torch.Tensor, P: t
     bits = vhull_pack_masks of the [B, H, W] masks, hw = (H, W); min_views 0 = every view.  The kept centres are appended to out (fp32
     [capacity, 3]) at the running count total (int64 [1], zeroed by the caller before a frame's first chunk), which grows by their number
     even where out is full.  Three launches on the current stream, no synchronisation."""
-    lib = _l.load()
     for t, name in ((xs, "xs"), (ys, "ys"), (zs, "zs"), (out, "out")):
         _req(t, name, F32)
     _req(P, "P", torch.float64), _req(bits, "bits", torch.int32), _req(ws, "ws", torch.int64), _req(total, "total", torch.int64)
@@ -1217,13 +1026,8 @@ def vhull_carve_chunk(xs: torch.Tensor, ys: torch.Tensor, zs: torch.Tensor, P: t
         raise _l.Dm4dError("xs, ys, zs: expected one-dimensional axes; total: expected one element")
     if out.dim() != 2 or out.shape[1] != 3 or not out.is_contiguous():
         raise _l.Dm4dError(f"out: expected a contiguous [capacity, 3] tensor, got {tuple(out.shape)}")
-    rc = lib.dm4d_vhull_carve_chunk(_stream(), _p(xs), _p(ys), _p(zs), xs.numel(), ys.numel(), zs.numel(), _p(P), _p(bits), B, H, W,
-                                    int(min_views), int(first), int(n_voxels), _p(ws), ws.numel() * 8, _p(total),
-                                    _p(out) if out.shape[0] else None, out.shape[0])
-    _l.check(rc, "dm4d_vhull_carve_chunk")
-
-
-TRIANG_MAX_VIEWS = 65536    # include/dm4d.h DM4D_TRIANG_MAX_VIEWS
+    _l.call("dm4d_vhull_carve_chunk", _stream(), _p(xs), _p(ys), _p(zs), xs.numel(), ys.numel(), zs.numel(), _p(P), _p(bits), B, H, W,
+            int(min_views), int(first), int(n_voxels), _p(ws), ws.numel() * 8, _p(total), _p(out) if out.shape[0] else None, out.shape[0])
 
 
 def _cameras(K: torch.Tensor, T: torch.Tensor) -> int:
@@ -1240,7 +1044,6 @@ def triangulate_points(K: torch.Tensor, T: torch.Tensor, kp2d: torch.Tensor, sco
     """K fp64 [n, 3, 3], T fp64 [n, 4, 4] (world -> camera), kp2d fp64 [F, n, k, 2], score fp64 [F, n, k], thr fp64 [F, k] (the score
     threshold of each frame and keypoint) -> kp3d fp64 [F, k, 3], reproj fp64 [F, k], n_views int32 [F, k]; -1e6 in kp3d and reproj where
     fewer than min_views views reach the threshold.  One launch on the current stream."""
-    lib = _l.load()
     n = _cameras(K, T)
     _req(kp2d, "kp2d", torch.float64), _req(score, "score", torch.float64), _req(thr, "thr", torch.float64)
     if kp2d.dim() != 4 or kp2d.shape[1] != n or kp2d.shape[3] != 2 or not kp2d.is_contiguous():
@@ -1253,16 +1056,14 @@ def triangulate_points(K: torch.Tensor, T: torch.Tensor, kp2d: torch.Tensor, sco
     kp3d = torch.empty((F, k, 3), dtype=torch.float64, device=kp2d.device)
     reproj = torch.empty((F, k), dtype=torch.float64, device=kp2d.device)
     n_views = torch.empty((F, k), dtype=torch.int32, device=kp2d.device)
-    rc = lib.dm4d_triangulate_points_f64(_stream(), _p(K), _p(T), _p(kp2d), _p(score), _p(thr), F, n, k, int(min_views), _p(kp3d),
-                                         _p(reproj), _p(n_views))
-    _l.check(rc, "dm4d_triangulate_points_f64")
+    _l.call("dm4d_triangulate_points_f64", _stream(), _p(K), _p(T), _p(kp2d), _p(score), _p(thr), F, n, k, int(min_views), _p(kp3d),
+            _p(reproj), _p(n_views))
     return kp3d, reproj, n_views
 
 
 def project_points(kp3d: torch.Tensor, K: torch.Tensor, T: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     """kp3d fp64 [F, k, 3], K fp64 [m, 3, 3], T fp64 [m, 4, 4] -> kp2d fp64 [F, m, k, 2], depth fp64 [F, m, k]; a point holding -1e6 gives
     -1e6 in both for every camera."""
-    lib = _l.load()
     _req(kp3d, "kp3d", torch.float64)
     m = _cameras(K, T)
     if kp3d.dim() != 3 or kp3d.shape[2] != 3 or not kp3d.is_contiguous():
@@ -1270,13 +1071,8 @@ def project_points(kp3d: torch.Tensor, K: torch.Tensor, T: torch.Tensor) -> Tupl
     F, k, _ = kp3d.shape
     kp2d = torch.empty((F, m, k, 2), dtype=torch.float64, device=kp3d.device)
     depth = torch.empty((F, m, k), dtype=torch.float64, device=kp3d.device)
-    _l.check(lib.dm4d_project_points_f64(_stream(), _p(kp3d), _p(K), _p(T), F, m, k, _p(kp2d), _p(depth)), "dm4d_project_points_f64")
+    _l.call("dm4d_project_points_f64", _stream(), _p(kp3d), _p(K), _p(T), F, m, k, _p(kp2d), _p(depth))
     return kp2d, depth
-
-
-# include/dm4d.h DM4D_SKEL_*
-SKEL_FIELDS, SKEL_LINE, SKEL_CIRCLE, SKEL_MAX_PRIMS = 8, 0, 1, 512
-SKEL_COORD_MIN, SKEL_COORD_MAX = -8192, 8191
 
 
 def skeleton_draw(prims_host: torch.Tensor, prims: torch.Tensor, offsets_host: torch.Tensor, offsets: torch.Tensor, htab_host: torch.Tensor,
@@ -1287,7 +1083,6 @@ def skeleton_draw(prims_host: torch.Tensor, prims: torch.Tensor, offsets_host: t
     the canvas (H, W) -> (h, w) with hk / vk taps per window; every *_host tensor is the host copy of its device twin, on which the
     library checks counts, records and windows before it launches.  `out`: a contiguous uint8 [B, h, w, 3] tensor on prims' device to
     draw into (a view of a larger buffer is fine: no alignment is asked of it); by default one is allocated."""
-    lib = _l.load()
     for name, dev, host in (("prims", prims, prims_host), ("offsets", offsets, offsets_host), ("htab", htab, htab_host), ("vtab", vtab, vtab_host)):
         _req(dev, name, torch.int32)
         if not isinstance(host, torch.Tensor) or host.device.type != "cpu" or host.dtype != torch.int32 or host.shape != dev.shape:
@@ -1307,9 +1102,8 @@ def skeleton_draw(prims_host: torch.Tensor, prims: torch.Tensor, offsets_host: t
         _req(out, "out", torch.uint8)
         if tuple(out.shape) != (B, h, w, 3) or not out.is_contiguous() or out.device != prims.device:
             raise _l.Dm4dError(f"out: expected a contiguous [{B}, {h}, {w}, 3] tensor on {prims.device}, got {tuple(out.shape)} on {out.device}")
-    rc = lib.dm4d_skeleton_draw_u8(_stream(), prims_host.data_ptr(), _p(prims), offsets_host.data_ptr(), _p(offsets), B, htab_host.data_ptr(),
-                                   _p(htab), int(hk), vtab_host.data_ptr(), _p(vtab), int(vk), int(H), int(W), int(h), int(w), _p(out))
-    _l.check(rc, "dm4d_skeleton_draw_u8")
+    _l.call("dm4d_skeleton_draw_u8", _stream(), prims_host.data_ptr(), _p(prims), offsets_host.data_ptr(), _p(offsets), B, htab_host.data_ptr(),
+            _p(htab), int(hk), vtab_host.data_ptr(), _p(vtab), int(vk), int(H), int(W), int(h), int(w), _p(out))
     return out
 
 
@@ -1336,105 +1130,5 @@ def skeleton_box_mask(maps: torch.Tensor, pads: Tuple[int, int, int], masks: Opt
         raise _l.Dm4dError(f"skeleton_box_mask: shape {tuple(maps.shape)} is out of range")
     ws = torch.empty(nbytes // 4, dtype=torch.int32, device=maps.device)
     boxes = torch.empty((B, 4), dtype=torch.int32, device=maps.device)
-    rc = lib.dm4d_skeleton_box_mask_u8(_stream(), _p(maps), B, h, w, pad_top, pad_bottom, pad_x, _p(boxes), _p(masks), h * w, _p(ws), nbytes)
-    _l.check(rc, "dm4d_skeleton_box_mask_u8")
+    _l.call("dm4d_skeleton_box_mask_u8", _stream(), _p(maps), B, h, w, pad_top, pad_bottom, pad_x, _p(boxes), _p(masks), h * w, _p(ws), nbytes)
     return boxes, masks
-
-
-JPEG_FIELDS = 8             # include/dm4d.h DM4D_JPEG_FIELDS
-RESTORE_FIELDS = 16         # include/dm4d.h DM4D_RESTORE_FIELDS
-JPEG_MCU_UNSTUFFED = 1248   # include/dm4d.h DM4D_JPEG_MCU_UNSTUFFED
-JPEG_CHUNK = 4096           # include/dm4d.h DM4D_JPEG_CHUNK
-
-
-def restore_crops(pixels: torch.Tensor, items, device) -> Tuple[torch.Tensor, list]:
-    """``imgwrite.restore_cropped_image`` of a batch on the device (dm4d_restore_crop_u8, two launches): items = [(byte offset of the
-    uint8 [H, W, 3] image in `pixels`, H, W, (ct, cl, ch, cw), (canvas h, canvas w))] -> (uint8 buffer of the canvases, their byte
-    offsets in it).  The coefficient tables are Pillow's (host/capture.py bicubic_table)."""
-    from .capture import bicubic_table
-    lib = _l.load()
-    _req(pixels, "pixels", torch.uint8)
-    desc = torch.zeros((len(items), RESTORE_FIELDS), dtype=torch.int64)
-    tabs, tab_at, tab_len, scratch_len, canvas_len, places = [], {}, 0, 0, 0, []
-
-    def table(n_in: int, n_out: int) -> Tuple[int, int]:
-        nonlocal tab_len
-        if (n_in, n_out) not in tab_at:
-            bounds, k = bicubic_table(n_in, n_out)
-            tab_at[(n_in, n_out)] = (tab_len, k.shape[1])
-            tabs.extend([torch.from_numpy(bounds.reshape(-1).copy()), torch.from_numpy(k.reshape(-1).copy())])
-            tab_len += bounds.size + k.size
-        return tab_at[(n_in, n_out)]
-
-    for i, (src, H, W, (ct, cl, ch, cw), (h, w)) in enumerate(items):
-        htab, hk = table(W, cw)
-        vtab, vk = table(H, ch)
-        desc[i, :15] = torch.tensor([src, H, W, ct, cl, ch, cw, h, w, htab, hk, vtab, vk, scratch_len, canvas_len])
-        places.append(canvas_len)
-        scratch_len += (H * cw * 3 + 15) // 16 * 16
-        canvas_len += (h * w * 3 + 15) // 16 * 16
-    tab = torch.cat(tabs).to(torch.int32).contiguous()
-    scratch = torch.empty(scratch_len, dtype=torch.uint8, device=device)
-    canvases = torch.empty(canvas_len, dtype=torch.uint8, device=device)
-    desc_dev, tab_dev = desc.to(device), tab.to(device)
-    rc = lib.dm4d_restore_crop_u8(_stream(), _p(pixels), pixels.numel(), desc.data_ptr(), _p(desc_dev), len(items), tab.data_ptr(),
-                                  _p(tab_dev), tab.numel(), _p(scratch), scratch.numel(), _p(canvases), canvases.numel())
-    _l.check(rc, "dm4d_restore_crop_u8")
-    return canvases, places
-
-
-def jpeg_encode_chunk(images, crops, sizes, qtab) -> list:
-    """Entropy-coded JPEG segments (bytes) of device uint8 [H, W, 3] tensors, each first restored onto its canvas where crops[k] is
-    not None (sizes[k] = the canvas' (h, w)); qtab: 128 integers, luma then chroma quantisation table in natural order.
-    Images that are views of one storage are read in place, otherwise they are gathered into one buffer first.  One host
-    synchronisation (the lengths) and one copy of exactly the bytes produced."""
-    lib = _l.load()
-    dev = images[0].device
-    for k, img in enumerate(images):
-        _req(img, f"images[{k}]", torch.uint8)
-        if img.device != dev or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
-            raise _l.Dm4dError(f"images[{k}]: expected a contiguous uint8 [H, W, 3] tensor on {dev}, got {tuple(img.shape)} on {img.device}")
-    with torch.cuda.device(dev):
-        base = images[0].untyped_storage().data_ptr()
-        if all(img.untyped_storage().data_ptr() == base for img in images):
-            pixels = torch.empty(0, dtype=torch.uint8, device=dev).set_(images[0].untyped_storage())
-            at = [img.data_ptr() - base for img in images]
-        else:
-            pixels = torch.cat([img.reshape(-1) for img in images])
-            at = [0]
-            for img in images[:-1]:
-                at.append(at[-1] + img.numel())
-        n = len(images)
-        cropped = [k for k in range(n) if crops[k] is not None]
-        canvases, places = None, {}
-        if cropped:
-            canvases, where = restore_crops(pixels, [(at[k], images[k].shape[0], images[k].shape[1], tuple(crops[k][:4]), sizes[k])
-                                                     for k in cropped], dev)
-            places = dict(zip(cropped, where))
-        desc = torch.zeros((n, JPEG_FIELDS), dtype=torch.int64)
-        mcu0 = chunk0 = bound = 0
-        for k, (h, w) in enumerate(sizes):
-            mcus = ((h + 15) // 16) * ((w + 15) // 16)
-            b = int(lib.dm4d_jpeg_scan_bound(h, w))
-            if b == 0:
-                raise _l.Dm4dError(f"images[{k}]: size {h} x {w} is out of range for the JPEG encoder")
-            desc[k, :6] = torch.tensor([1, places[k], h, w, mcu0, chunk0] if k in places else [0, at[k], h, w, mcu0, chunk0])
-            mcu0, chunk0, bound = mcu0 + mcus, chunk0 + (mcus * JPEG_MCU_UNSTUFFED + JPEG_CHUNK - 1) // JPEG_CHUNK, bound + b
-        nbytes = int(lib.dm4d_jpeg_ws_bytes(mcu0, n))
-        if nbytes == 0:
-            raise _l.Dm4dError(f"jpeg_encode_chunk: {n} images with {mcu0} MCUs are out of range for one call")
-        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
-        blob = torch.empty(bound, dtype=torch.uint8, device=dev)
-        out = torch.empty(2 * n, dtype=torch.int64, device=dev)
-        q = torch.tensor([int(v) for v in qtab], dtype=torch.int16)  # values 1..255: the same bytes as uint16
-        desc_dev, q_dev = desc.to(dev), q.to(dev)
-        rc = lib.dm4d_jpeg_encode_rgb_u8(_stream(), _p(pixels) if pixels.numel() else None, pixels.numel(), _p(canvases),
-                                         0 if canvases is None else canvases.numel(), desc.data_ptr(), _p(desc_dev), n, q.data_ptr(),
-                                         _p(q_dev), _p(ws), ws.numel() * 8, _p(blob), blob.numel(), _p(out))
-        _l.check(rc, "dm4d_jpeg_encode_rgb_u8")
-        where = out.cpu().tolist()  # the one synchronisation: n offsets, then n lengths
-        total = where[n - 1] + where[2 * n - 1]
-        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        host.copy_(blob[:total])
-        data = host.numpy().tobytes()
-    return [data[where[k]:where[k] + where[n + k]] for k in range(n)]

@@ -178,11 +178,9 @@ class _MidAttn:
 def _transpose(v: torch.Tensor, C: int) -> torch.Tensor:
     """v [L, C] row-strided view -> contiguous [C, L] via the NHWC->NCHW kernel."""
     from . import lib as _l
-    lib = _l.load()
     L = v.shape[0]
     y = torch.empty((C, L), dtype=BF16, device=v.device)
-    _l.check(lib.dm4d_nhwc_to_nchw_bf16(torch.cuda.current_stream().cuda_stream, v.data_ptr(), y.data_ptr(), 1, C, L,
-                                        v.stride(0)), "dm4d_nhwc_to_nchw_bf16")
+    _l.call("dm4d_nhwc_to_nchw_bf16", torch.cuda.current_stream().cuda_stream, v.data_ptr(), y.data_ptr(), 1, C, L, v.stride(0))
     return y
 
 

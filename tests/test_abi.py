@@ -106,3 +106,88 @@ def test_a_stale_library_is_not_blessed(monkeypatch, tmp_path):
     monkeypatch.setattr(build, "CSRC", build.ROOT / "csrc")
     monkeypatch.setattr(build, "STAMP", tmp_path / "absent")
     assert build.needs_build()
+
+
+# the constants of include/dm4d.h that diffuman4d_amd/host/lib.py mirrors (without the DM4D_ prefix): they size descriptor rows and
+# workspaces that the library indexes, so a mirror that is deleted or renamed must fail here, not on a device
+MIRRORED = ("EPI_GEGLU", "EPI_SILU", "EPI_F32OUT", "EPI_F32SIDE", "EPI_SPLITOUT", "LOG2E", "CAPTURE_FIELDS", "EVAL_FIELDS", "EVAL_OUT",
+            "EVAL_IMAGE_F32", "EVAL_MASK_F32", "EVAL_CROP_MASKS", "EVAL_BG_SHIFT", "LPIPS_TAPS", "LPIPS_IN_COLS", "VHULL_BLOCK",
+            "VHULL_MAX_CHUNK", "TRIANG_MAX_VIEWS", "SKEL_FIELDS", "SKEL_LINE", "SKEL_CIRCLE", "SKEL_MAX_PRIMS", "SKEL_COORD_MIN",
+            "SKEL_COORD_MAX", "RESTORE_FIELDS", "JPEG_FIELDS", "JPEG_MCU_UNSTUFFED", "JPEG_MCU_BOUND", "JPEG_CHUNK")
+
+
+def _constant(text: str):
+    """Value of a #define's replacement text: an integer literal (decimal or hex, u / l / ll suffixes), unary minus, `<<`, parentheses;
+    or a plain decimal float.  Anything else is a ValueError."""
+    integer = r"(?:0[xX][0-9a-fA-F]+|\d+)(?:[uU](?:ll|LL|l|L)?|(?:ll|LL|l|L)[uU]?)?"
+    real = r"\d+\.\d+(?:[eE][-+]?\d+)?"
+    tokens = re.findall(real + "|" + integer + r"|<<|[-()]|\S", text)
+    pos = 0
+
+    def peek():
+        return tokens[pos] if pos < len(tokens) else None
+
+    def take():
+        nonlocal pos
+        pos += 1
+        return tokens[pos - 1]
+
+    def unary():
+        tok = take() if peek() is not None else ""
+        if tok == "-":
+            return -unary()
+        if tok == "(":
+            v = shift()
+            if peek() != ")":
+                raise ValueError(text)
+            take()
+            return v
+        if re.fullmatch(real, tok):
+            return float(tok)
+        if re.fullmatch(integer, tok):
+            return int(tok.rstrip("uUlL"), 0)
+        raise ValueError(text)
+
+    def shift():
+        v = unary()
+        while peek() == "<<":
+            take()
+            n = unary()
+            if not (isinstance(v, int) and isinstance(n, int) and 0 <= n < 64):
+                raise ValueError(text)
+            v <<= n
+        return v
+
+    v = shift()
+    if pos != len(tokens):
+        raise ValueError(text)
+    return v
+
+
+def header_constants():
+    text = re.sub(r"/\*.*?\*/", "", HEADER, flags=re.S)
+    return {m.group(1): m.group(2).strip() for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+DM4D_(\w+)[ \t]+(\S[^\n]*)$", text, flags=re.M)}
+
+
+def test_constant_parser():
+    assert [_constant(t) for t in ("16", "4u", "(1ll << 26)", "(-8192)", "0x10", "-(2 << 3)", "1ULL<<4", "1.4426950408889634")] == [
+        16, 4, 1 << 26, -8192, 16, -16, 16, 1.4426950408889634]
+    for bad in ("", "1 +", "(1", "A", "1 2", "1.5 << 2", "sizeof(int)"):
+        with pytest.raises(ValueError):
+            _constant(bad)
+
+
+def test_mirrored_constants_match_header():
+    """Every DM4D_* constant that host/lib.py holds has the header's value, and host/lib.py holds at least the MIRRORED ones."""
+    from diffuman4d_amd.host import lib as L
+    consts = header_constants()
+    for name in MIRRORED:
+        assert name in consts, f"DM4D_{name} is not defined in include/dm4d.h"
+        assert hasattr(L, name), f"diffuman4d_amd/host/lib.py does not mirror DM4D_{name}"
+    checked = 0
+    for name, text in consts.items():
+        if hasattr(L, name):
+            want, got = _constant(text), getattr(L, name)
+            assert type(got) is type(want) and got == want, f"host/lib.py {name} = {got!r}, include/dm4d.h DM4D_{name} = {text}"
+            checked += 1
+    assert checked >= len(MIRRORED)

@@ -127,6 +127,10 @@ SIGNATURES = {
     "dm4d_jpeg_scan_bound": (C.c_size_t, [_i, _i]),
     "dm4d_jpeg_ws_bytes": (C.c_size_t, [_i64, _i]),
     "dm4d_jpeg_encode_rgb_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    # keypoint prediction around a caller-named pose network: composite + warp + normalise, mask box, UDP/DARK decode (host/pose.py)
+    "dm4d_pose_input_u8_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i, _i]),
+    "dm4d_pose_mask_box_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp]),
+    "dm4d_pose_udp_decode_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
 }
 
 # The constants of include/dm4d.h that the host uses, under the header's names without the DM4D_ prefix.  This block is their ONLY
@@ -160,6 +164,11 @@ JPEG_FIELDS = 8
 JPEG_MCU_UNSTUFFED = 1248  # workspace bytes of unstuffed scan per 16 x 16 MCU
 JPEG_MCU_BOUND = 2488      # bytes of stuffed scan per MCU, worst case
 JPEG_CHUNK = 4096
+POSE_FIELDS = 8
+POSE_MAX_SIDE = 16384
+POSE_MAX_HEATMAP_H = 4096
+POSE_MAX_HEATMAP_W = 1024
+POSE_TAB_LIMIT = 1 << 29
 
 
 class Dm4dError(RuntimeError):
@@ -197,6 +206,17 @@ def check(rc: int, what: str = ""):
     if rc != 0:
         msg = load().dm4d_last_error()
         raise Dm4dError(f"{what} failed (rc={rc}): {msg.decode() if msg else '?'}")
+
+
+def hip_device(device, what: str):
+    """`device` as a torch.device with an index, for the operator `what`; anything but an available HIP device is an error."""
+    import torch
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise Dm4dError(f"{what}: device {device!r} is not a HIP device (no CPU fallback in diffuman4d_amd)")
+    if not torch.cuda.is_available():
+        raise Dm4dError(f"{what}: no HIP device is available (no CPU fallback in diffuman4d_amd)")
+    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
 
 
 def call(name: str, *args) -> None:

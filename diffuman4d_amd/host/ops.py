@@ -1132,3 +1132,53 @@ def skeleton_box_mask(maps: torch.Tensor, pads: Tuple[int, int, int], masks: Opt
     boxes = torch.empty((B, 4), dtype=torch.int32, device=maps.device)
     _l.call("dm4d_skeleton_box_mask_u8", _stream(), _p(maps), B, h, w, pad_top, pad_bottom, pad_x, _p(boxes), _p(masks), h * w, _p(ws), nbytes)
     return boxes, masks
+
+
+def _pose_meta(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, rows: int, desc_off: int) -> None:
+    _req(blob, "blob", torch.uint8), _req(meta, "meta", torch.uint8)
+    if meta.device != blob.device or not blob.is_contiguous() or not meta.is_contiguous() or blob.numel() == 0:
+        raise _l.Dm4dError("blob / meta: expected contiguous non-empty tensors on one device")
+    if meta_host.device.type != "cpu" or meta_host.dtype != torch.uint8 or meta_host.numel() != meta.numel() or not meta_host.is_contiguous():
+        raise _l.Dm4dError("meta_host: expected the host copy of meta")
+    if rows < 1 or desc_off < 0 or desc_off % 8 or desc_off + rows * _l.POSE_FIELDS * 8 > meta.numel():
+        raise _l.Dm4dError("desc_off: the descriptors lie outside meta, or are not aligned")
+
+
+def pose_input(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, rows: int, desc_off: int, tab_off: int, tab_len: int,
+               H: int, W: int, norm: torch.Tensor) -> torch.Tensor:
+    """The pose network's input for `rows` (image, box) pairs (host/pose.py) -> fp32 [rows, 3, H, W] on blob's device, one launch on the
+    current stream.  `blob`: device uint8 holding the image and mask planes; `meta`: device uint8 holding int32 warp tables at byte
+    `tab_off` and int64 POSE_FIELDS descriptors at byte `desc_off`, `meta_host` its host copy, on which the library checks every
+    descriptor and table before it launches.  norm: host fp32 [6] = mean R, G, B | std R, G, B."""
+    _pose_meta(blob, meta, meta_host, rows, desc_off)
+    if tab_off < 0 or tab_off % 4 or tab_len < 1 or tab_off + tab_len * 4 > meta.numel():
+        raise _l.Dm4dError("tab_off: the tables lie outside meta, or are not aligned")
+    if norm.device.type != "cpu" or norm.dtype != F32 or norm.numel() != 6 or not norm.is_contiguous():
+        raise _l.Dm4dError("norm: expected a contiguous host fp32 tensor of 6 values")
+    out = torch.empty((rows, 3, H, W), dtype=F32, device=blob.device)
+    host, dev = meta_host.data_ptr(), meta.data_ptr()
+    _l.call("dm4d_pose_input_u8_f32", _stream(), _p(blob), blob.numel(), host + desc_off, dev + desc_off, rows, host + tab_off, dev + tab_off,
+            tab_len, norm.data_ptr(), _p(out), H, W)
+    return out
+
+
+def pose_mask_box(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int) -> torch.Tensor:
+    """[x1, y1, x2, y2] of the pixels >= 128 of the masks that `n` POSE_FIELDS descriptors at byte `desc_off` of meta name ({0, 0, w, h}
+    for a mask without one) -> int32 [n, 4] on blob's device; blob / meta / meta_host as for pose_input.  One launch on the current stream."""
+    _pose_meta(blob, meta, meta_host, n, desc_off)
+    boxes = torch.empty((n, 4), dtype=torch.int32, device=blob.device)
+    _l.call("dm4d_pose_mask_box_u8", _stream(), _p(blob), blob.numel(), meta_host.data_ptr() + desc_off, meta.data_ptr() + desc_off, n, _p(boxes))
+    return boxes
+
+
+def pose_udp_decode(heatmaps: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """UDP/DARK decode of heatmaps fp32 [n, K, Hh, Wh] (contiguous) -> (locs fp32 [n, K, 2] = refined (x, y) in heatmap pixels, (-1, -1)
+    for a map whose maximum is <= 0; scores fp32 [n, K] = each map's maximum), on the heatmaps' device.  One launch on the current stream."""
+    _req(heatmaps, "heatmaps", F32)
+    if heatmaps.dim() != 4 or not heatmaps.is_contiguous() or heatmaps.numel() == 0:
+        raise _l.Dm4dError(f"heatmaps: expected a contiguous non-empty [n, K, Hh, Wh] tensor, got {tuple(heatmaps.shape)}")
+    n, K, Hh, Wh = heatmaps.shape
+    locs = torch.empty((n, K, 2), dtype=F32, device=heatmaps.device)
+    scores = torch.empty((n, K), dtype=F32, device=heatmaps.device)
+    _l.call("dm4d_pose_udp_decode_f32", _stream(), _p(heatmaps), n, K, Hh, Wh, _p(scores), _p(locs))
+    return locs, scores

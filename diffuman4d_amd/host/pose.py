@@ -1,0 +1,386 @@
+"""2-D keypoint prediction around a caller-named pose network: the ``predict_keypoints`` action of the reference's preprocess.sh
+(scripts/preprocess/predict_keypoints.py -> sapiens/lite/demo/vis_pose.py, pose_utils.py), which writes
+``poses_sapiens/{camera}/{frame}.json``, the files ``host/triang.py`` reads.
+
+The network is not part of this package and is never downloaded: the caller names a checkpoint file (``load_pose_model``) or hands over
+any callable (``pose_model``).  Everything around it runs on the device (csrc/pose.hip):
+
+  * ``pose_inputs``: images (and foreground masks) are decoded with Pillow in a thread pool into pinned staging and uploaded once;
+    one launch composites each image over black through its mask, warps every person box to the network's input and normalises it.
+    The warp is an integer rule of this package ("Keypoint prediction"), modelled on OpenCV's bilinear warpAffine;
+  * ``decode_heatmaps``: one launch takes the heatmaps, which never visit the host, to refined keypoints (UDP / DARK decoding); the
+    last two linear maps to image pixels are done on the host in fp64, as the reference's numpy does.
+
+There is no CPU path: a ``device`` that is not a HIP device is an error.
+"""
+from __future__ import annotations
+
+import json
+import os
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from glob import glob
+from typing import Callable, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from PIL import Image
+
+from . import lib as _l
+from . import ops
+
+MEAN = (123.5, 116.5, 103.5)   # vis_pose.py:451-452, RGB order (preprocess_pose's two BGR swaps cancel)
+STD = (58.5, 57.0, 57.5)
+PADDING = 1.25                 # top_down_affine_transform's default
+MAX_HOST_THREADS = 16
+FIELDS = _l.POSE_FIELDS
+
+
+def _up(n: int) -> int:
+    return (n + 15) & ~15
+
+
+# -- boxes -> centre, scale, warp tables (host, numpy) -------------------------------------------------------------------------------
+def box_center_scale(bbox, shape: Tuple[int, int], padding: float = PADDING) -> Tuple[np.ndarray, np.ndarray]:
+    """[x1, y1, x2, y2] -> (center (2,), scale (2,)) float64 as top_down_affine_transform forms them (pose_utils.py:248-269): the box
+    grown by `padding`, then widened or heightened to the aspect of the network input `shape` = (H, W)."""
+    box = np.asarray(bbox, dtype=np.float64).reshape(4)
+    if not np.all(np.isfinite(box)) or box[2] <= box[0] or box[3] <= box[1]:
+        raise ValueError(f"bbox must be finite with x2 > x1 and y2 > y1, got {box.tolist()}")
+    H, W = shape
+    center = np.array([box[0] + box[2], box[1] + box[3]]) * 0.5
+    bw, bh = (box[2] - box[0]) * padding, (box[3] - box[1]) * padding
+    aspect = W / H
+    scale = np.array([bw, bw / aspect]) if bw > bh * aspect else np.array([bh * aspect, bh])
+    return center, scale
+
+
+def udp_warp_matrix(center: np.ndarray, scale: np.ndarray, shape: Tuple[int, int]) -> np.ndarray:
+    """The reference's UDP warp matrix without rotation (its get_udp_warp_matrix(center, scale, 0, (W, H))): 2 x 3 float32, image ->
+    network input.  The box corner ``center - scale / 2`` goes to (0, 0) and ``center + scale / 2`` to (W - 1, H - 1): a diagonal of
+    ``(last pixel) / scale`` and a translation of ``diagonal * (scale / 2 - center)``, formed in fp64 and rounded to float32 when stored."""
+    H, W = shape
+    gain = np.array([W - 1, H - 1], dtype=np.float64) / scale
+    mat = np.zeros((2, 3), dtype=np.float32)
+    mat[[0, 1], [0, 1]] = gain
+    mat[:, 2] = gain * (scale * 0.5 - center)
+    return mat
+
+
+def warp_tables(mat: np.ndarray, shape: Tuple[int, int]) -> np.ndarray:
+    """The int32 table {adelta[W] | bdelta[W] | X0[H] | Y0[H]} of include/dm4d.h (dm4d_pose_input_u8_f32) from the fp64 inverse of the
+    float32 matrix: everything of the warp that a float touches.  Raises ValueError for a box so small or so far away that an entry
+    leaves +-2^29."""
+    H, W = shape
+    m = mat.astype(np.float64)
+    det = m[0, 0] * m[1, 1] - m[0, 1] * m[1, 0]
+    d = 1.0 / det if det != 0 else 0.0
+    a00, a01, a10, a11 = m[1, 1] * d, m[0, 1] * -d, m[1, 0] * -d, m[0, 0] * d
+    a02 = -a00 * m[0, 2] - a01 * m[1, 2]
+    a12 = -a10 * m[0, 2] - a11 * m[1, 2]
+    xs, ys = np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        tab = np.concatenate([np.rint(a00 * xs * 1024), np.rint(a10 * xs * 1024), np.rint((a01 * ys + a02) * 1024) + 16,
+                              np.rint((a11 * ys + a12) * 1024) + 16])
+    if not np.all(np.abs(tab) <= _l.POSE_TAB_LIMIT):  # NaN included
+        raise ValueError("bbox: the warp leaves the fixed-point range (a degenerate or far-away box)")
+    return tab.astype(np.int32)
+
+
+# -- staging ---------------------------------------------------------------------------------------------------------------------------
+def _open(src):
+    """A path, a PIL image or an array -> a PIL image (not yet decoded for a path)."""
+    if isinstance(src, Image.Image):
+        return src
+    if isinstance(src, np.ndarray):
+        return Image.fromarray(src)
+    return Image.open(os.fspath(src))
+
+
+def _open_all(images, fmasks, pool: Optional[ThreadPoolExecutor]):
+    """Open (not yet decode) the images and masks and check them -> (PIL images or None, PIL masks with None entries or None).
+    `images` None: masks alone (``fmask_boxes``).  Needs no device."""
+    n = len(fmasks) if images is None else len(images)
+    if n < 1:
+        raise ValueError("images: at least one image")
+    if images is not None and fmasks is not None and len(fmasks) != n:
+        raise ValueError("fmask_paths and image_paths must have the same length")
+    run = (lambda fn, xs: list(pool.map(fn, xs))) if pool is not None else (lambda fn, xs: [fn(x) for x in xs])
+    ims = run(_open, images) if images is not None else None
+    mks = run(lambda m: None if m is None else _open(m), fmasks) if fmasks is not None else None
+    for k in range(n):
+        size = ims[k].size if ims is not None else mks[k].size
+        if not (1 <= size[1] <= _l.POSE_MAX_SIDE and 1 <= size[0] <= _l.POSE_MAX_SIDE):
+            raise ValueError(f"images[{k}]: size {size[0]} x {size[1]} is outside 1..{_l.POSE_MAX_SIDE}")
+        if mks is not None and mks[k] is not None:
+            if mks[k].mode not in ("L", "1"):
+                raise ValueError(f"fmasks[{k}]: mode {mks[k].mode!r}, expected 'L' or '1'")
+            if mks[k].size != size:
+                raise ValueError("images do not match")  # Pillow's text for Image.composite
+    return ims, mks
+
+
+class _Staged:
+    """Opened images and masks of one batch, decoded into pinned staging and uploaded: `blob` uint8 on the device (planes, 16-byte
+    aligned), sizes [(h, w)], image / mask byte offsets (-1: absent)."""
+
+    def __init__(self, ims, mks, device: torch.device, pool: Optional[ThreadPoolExecutor]):
+        n = len(ims) if ims is not None else len(mks)
+        run = (lambda fn, xs: list(pool.map(fn, xs))) if pool is not None else (lambda fn, xs: [fn(x) for x in xs])
+        self.sizes = [((ims if ims is not None else mks)[k].size[1], (ims if ims is not None else mks)[k].size[0]) for k in range(n)]
+        off, self.image_off, self.mask_off = 0, [], []
+        for k, (h, w) in enumerate(self.sizes):
+            if ims is not None:
+                self.image_off.append(off)
+                off = _up(off + h * w * 3)
+            else:
+                self.image_off.append(-1)
+            if mks is not None and mks[k] is not None:
+                self.mask_off.append(off)
+                off = _up(off + h * w)
+            else:
+                self.mask_off.append(-1)
+        host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
+        view = host.numpy()
+
+        def decode(k):
+            h, w = self.sizes[k]
+            o = self.image_off[k]
+            if o >= 0:
+                np.copyto(view[o: o + h * w * 3].reshape(h, w, 3), np.asarray(ims[k].convert("RGB")))
+            o = self.mask_off[k]
+            if o >= 0:
+                np.copyto(view[o: o + h * w].reshape(h, w), np.asarray(mks[k].convert("L")))
+        run(decode, range(n))
+        self.device = device
+        self.host = host  # pinned: alive until the consumer has synchronised
+        self.blob = host.to(device, non_blocking=True)
+
+    def meta(self, rows: Sequence[Tuple[int, int]], tab: Optional[np.ndarray]) -> Tuple[torch.Tensor, torch.Tensor, int, int]:
+        """rows: (image index, table offset in int32 elements) -> (meta on the device, its pinned host copy, tab_off, desc_off)."""
+        tab_bytes = 0 if tab is None else tab.nbytes
+        desc_off = _up(tab_bytes)
+        desc = np.zeros((len(rows), FIELDS), dtype=np.int64)
+        for r, (k, toff) in enumerate(rows):
+            desc[r, :5] = [self.image_off[k], self.mask_off[k], self.sizes[k][0], self.sizes[k][1], toff]
+        host = torch.empty(desc_off + desc.nbytes, dtype=torch.uint8, pin_memory=True)
+        view = host.numpy()
+        view[:] = 0
+        if tab is not None:
+            view[:tab_bytes] = tab.view(np.uint8)
+        view[desc_off:] = desc.reshape(-1).view(np.uint8)
+        return host.to(self.device, non_blocking=True), host, 0, desc_off
+
+
+def _mask_boxes(staged: _Staged) -> np.ndarray:
+    n = len(staged.sizes)
+    meta, meta_host, _, desc_off = staged.meta([(k, 0) for k in range(n)], None)
+    return ops.pose_mask_box(staged.blob, meta, meta_host, n, desc_off).cpu().numpy()
+
+
+def fmask_boxes(fmasks, device="cuda") -> np.ndarray:
+    """[n, 4] int32: per mask (path, PIL image or uint8 array; mode ``L`` or ``1``) the box [x1, y1, x2, y2] of its pixels >= 128, x2 and
+    y2 exclusive; the whole image for a mask without one.  One launch (dm4d_pose_mask_box_u8)."""
+    _, mks = _open_all(None, list(fmasks), None)
+    dev = _l.hip_device(device, "fmask_boxes")
+    with torch.cuda.device(dev):
+        return _mask_boxes(_Staged(None, mks, dev, None))
+
+
+def _boxes_of(b, h: int, w: int) -> List:
+    """An image's entry of `bboxes` -> its list of boxes: None (the whole image), one [x1, y1, x2, y2], or several, each of which may
+    again be None."""
+    whole = [0, 0, w, h]
+    if b is None:
+        return [whole]
+    if isinstance(b, (list, tuple)) and any(x is None or np.ndim(x) > 0 for x in b):
+        return [whole if x is None else np.asarray(x, dtype=np.float64).reshape(4) for x in b]
+    return list(np.asarray(b, dtype=np.float64).reshape(-1, 4))
+
+
+def pose_inputs(images, fmasks=None, bboxes=None, shape: Tuple[int, int] = (1024, 768), device="cuda", *, bbox_source: str = "image",
+                pool: Optional[ThreadPoolExecutor] = None) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
+    """The pose network's input for a batch of images -> (tensor fp32 [rows, 3, H, W] on `device`, centers [rows, 2], scales [rows, 2]
+    float64; rows in image order, an image's boxes in their order).
+
+    images: paths, PIL images or uint8 [h, w, 3] arrays, of any sizes.  fmasks: one per image, mode ``L`` or ``1`` (ValueError
+    otherwise), of the image's size, or None for an image without one; the image is composited over black through it, as
+    ``Image.composite(image, black, fmask)``.  bboxes: per image ``[x1, y1, x2, y2]`` or several of them, float, or None for the whole
+    image; bboxes=None: whole images, or, with ``bbox_source="fmask"``, the box of each mask's pixels >= 128.  shape: the network's
+    input (H, W)."""
+    if bbox_source not in ("image", "fmask"):
+        raise ValueError(f'bbox_source must be "image" or "fmask", got {bbox_source!r}')
+    H, W = int(shape[0]), int(shape[1])
+    ims, mks = _open_all(list(images), None if fmasks is None else list(fmasks), pool)
+    n = len(ims)
+    if bboxes is not None and len(bboxes) != n:
+        raise ValueError(f"bboxes: expected one entry per image ({n}), got {len(bboxes)}")
+    if bboxes is None and bbox_source == "fmask" and (mks is None or any(m is None for m in mks)):
+        raise ValueError('bbox_source="fmask" needs a mask for every image')
+    dev = _l.hip_device(device, "pose_inputs")
+    with torch.cuda.device(dev):
+        staged = _Staged(ims, mks, dev, pool)
+        if bboxes is None:
+            boxes = _mask_boxes(staged)[:, None, :] if bbox_source == "fmask" else [[[0, 0, w, h]] for h, w in staged.sizes]
+        else:
+            boxes = [_boxes_of(b, *staged.sizes[k]) for k, b in enumerate(bboxes)]
+        rows, tabs, centers, scales = [], [], [], []
+        per_row = 2 * (W + H)
+        for k in range(n):
+            for box in boxes[k]:
+                c, s = box_center_scale(box, (H, W))
+                tabs.append(warp_tables(udp_warp_matrix(c, s, (H, W)), (H, W)))
+                rows.append((k, (len(tabs) - 1) * per_row))
+                centers.append(c), scales.append(s)
+        if not rows:
+            raise ValueError("bboxes: no box at all")
+        tab = np.concatenate(tabs)
+        meta, meta_host, tab_off, desc_off = staged.meta(rows, tab)
+        out = ops.pose_input(staged.blob, meta, meta_host, len(rows), desc_off, tab_off, tab.size, H, W, torch.tensor(MEAN + STD, dtype=torch.float32))
+        torch.cuda.current_stream().synchronize()  # the pinned buffers may go; the tensor is complete when it is handed over
+    return out, np.stack(centers), np.stack(scales)
+
+
+def decode_heatmaps(heatmaps: torch.Tensor, input_size: Tuple[int, int], centers, scales) -> Tuple[np.ndarray, np.ndarray]:
+    """heatmaps [n, K, Hh, Wh] on the device, input_size = (W, H) of the network input, centers / scales [n, 2] from ``pose_inputs`` ->
+    (keypoints [n, K, 2] float64 in image pixels, scores [n, K] float32).  One launch (dm4d_pose_udp_decode_f32), then
+    ``kp / [Wh - 1, Hh - 1] * input_size`` and ``(kp / input_size) * scale + center - 0.5 * scale`` in fp64 (pose_utils.py:177-178,
+    vis_pose.py:107).  A map whose maximum is <= 0 is not refined: its heatmap location is (-1, -1)."""
+    if not isinstance(heatmaps, torch.Tensor) or heatmaps.device.type != "cuda":
+        raise _l.Dm4dError("heatmaps: expected a tensor on a HIP device (no CPU fallback in diffuman4d_amd)")
+    if heatmaps.dim() != 4:
+        raise ValueError(f"heatmaps: expected [n, K, Hh, Wh], got {tuple(heatmaps.shape)}")
+    n, K, Hh, Wh = heatmaps.shape
+    centers, scales = np.asarray(centers, dtype=np.float64).reshape(-1, 2), np.asarray(scales, dtype=np.float64).reshape(-1, 2)
+    if len(centers) != n or len(scales) != n:
+        raise ValueError(f"centers / scales: expected {n} rows, got {len(centers)} and {len(scales)}")
+    with torch.cuda.device(heatmaps.device):
+        locs, scores = ops.pose_udp_decode(heatmaps.float().contiguous())
+        locs, scores = locs.cpu().numpy(), scores.cpu().numpy()
+    size = np.asarray(input_size, dtype=np.int64)
+    kp = locs / np.array([Wh - 1, Hh - 1]) * size
+    kp = (kp / size) * scales[:, None, :] + centers[:, None, :] - 0.5 * scales[:, None, :]
+    return kp, scores
+
+
+# -- the stage -------------------------------------------------------------------------------------------------------------------------
+def load_pose_model(path: str, device) -> Callable:
+    """The caller's pose checkpoint, by the reference's rule (vis_pose.py:188-212): ``torch.jit.load`` when the file name contains
+    ``_torchscript``, else ``torch.export.load(path).module()``.  Nothing is ever downloaded.
+
+    The module is used as loaded and must accept fp32 ``[n, 3, H, W]``: ``predict_keypoints`` feeds fp32 and converts the heatmaps to
+    fp32.  The reference instead converts an exported module to bfloat16 and feeds bfloat16 under autocast; a checkpoint exported for
+    bfloat16 input needs a wrapper of the caller's (``pose_model=lambda x: module(x.bfloat16())``).  This path has not been run with a
+    real Sapiens checkpoint: none is at hand, and the tests go through ``pose_model``."""
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"pose checkpoint {path!r} does not exist (it is never downloaded: name a local file)")
+    if "_torchscript" in os.path.basename(path):
+        return torch.jit.load(path, map_location=device).eval()
+    return torch.export.load(path).module().to(device)
+
+
+def list_inputs(images_dir: str, fmasks_dir: Optional[str]) -> Tuple[List[str], Optional[List[str]]]:
+    """``**/*.jpg`` + ``**/*.webp`` under images_dir and ``**/*.png`` under fmasks_dir, each sorted; paired by index (vis_pose.py:367-376)."""
+    images = sorted(glob(f"{images_dir}/**/*.jpg", recursive=True) + glob(f"{images_dir}/**/*.webp", recursive=True))
+    fmasks = None
+    if fmasks_dir is not None and fmasks_dir != "None":
+        fmasks = sorted(glob(f"{fmasks_dir}/**/*.png", recursive=True))
+        if len(fmasks) != len(images):
+            raise ValueError("fmask_paths and image_paths must have the same length")
+    return images, fmasks
+
+
+def output_path(out_kp2d_dir: str, image_path: str) -> str:
+    """out_kp2d_dir/<last two components of image_path>.json (vis_pose.py:410-412)."""
+    tail = os.path.join(*os.path.normpath(image_path).split(os.sep)[-2:])
+    return os.path.join(out_kp2d_dir, os.path.splitext(tail)[0] + ".json")
+
+
+def _parses(path: str) -> bool:
+    try:
+        with open(path, "r") as f:
+            json.load(f)
+        return True
+    except Exception:
+        return False
+
+
+def write_instances(path: str, keypoints: np.ndarray, scores: np.ndarray) -> None:
+    """``{"instance_info": [{"keypoints", "keypoint_scores"}, ...]}``, one entry per box, indented with one tab (vis_pose.py:111-126)."""
+    parent = os.path.dirname(path)
+    if parent:
+        os.makedirs(parent, exist_ok=True)
+    info = [{"keypoints": np.asarray(kp).tolist(), "keypoint_scores": np.asarray(sc).tolist()} for kp, sc in zip(keypoints, scores)]
+    tmp = f"{path}.tmp{threading.get_ident()}"
+    with open(tmp, "w") as f:
+        json.dump({"instance_info": info}, f, indent="\t")
+    os.replace(tmp, path)  # a reader (or skip_exists) never sees half a file
+
+
+def predict_keypoints(images_dir: str, out_kp2d_dir: str, fmasks_dir: Optional[str] = None, sapiens_ckpt_path: Optional[str] = None,
+                      detector_ckpt_path: Optional[str] = None, gpu_ids: Optional[Sequence[int]] = None, num_workers: int = 4, *,
+                      pose_model: Optional[Callable] = None, shape: Tuple[int, int] = (1024, 768), heatmap_scale: int = 4,
+                      batch_size: int = 4, skip_exists: bool = True, bbox_source: str = "image") -> dict:
+    """Predict the 2-D keypoints of every image under `images_dir` and write ``out_kp2d_dir/{camera}/{frame}.json``.
+
+    pose_model: any callable taking fp32 [n, 3, H, W] on the device and returning [n, K, H / heatmap_scale, W / heatmap_scale] on the
+    device; by default ``load_pose_model(sapiens_ckpt_path)``, once per GPU (which must then accept fp32 input; see there).  It is the
+    caller's network: its output never visits the host.  A ``detector_ckpt_path`` is refused (the reference's RTMDet detector needs mmdet, which this package does not carry): the box
+    is the whole image, or the box of the foreground mask with ``bbox_source="fmask"``.  The reference's ``flip`` is not taken (it
+    averages the flipped pass without flipping it back).  One worker thread per GPU id; decoding and the
+    JSON files go through a pool of `num_workers` threads.  Returns counts."""
+    if detector_ckpt_path:
+        raise NotImplementedError("detector_ckpt_path: the person detector is mmdet's RTMDet, which diffuman4d_amd does not carry; "
+                                  'the box is the whole image, or bbox_source="fmask"')
+    if bbox_source not in ("image", "fmask"):
+        raise ValueError(f'bbox_source must be "image" or "fmask", got {bbox_source!r}')
+    if bbox_source == "fmask" and (fmasks_dir is None or fmasks_dir == "None"):
+        raise ValueError('bbox_source="fmask" needs fmasks_dir')
+    if pose_model is None and not sapiens_ckpt_path:
+        raise ValueError("name the pose network: sapiens_ckpt_path (a local checkpoint file) or pose_model (a callable)")
+    H, W = int(shape[0]), int(shape[1])
+    if batch_size < 1 or heatmap_scale < 1:
+        raise ValueError("batch_size and heatmap_scale must be at least 1")
+    images, fmasks = list_inputs(images_dir, fmasks_dir)
+    outs = [output_path(out_kp2d_dir, p) for p in images]
+    todo = [k for k in range(len(images)) if not (skip_exists and os.path.exists(outs[k]) and _parses(outs[k]))]
+    result = {"images": len(images), "written": 0, "skipped": len(images) - len(todo)}
+    if not todo:
+        return result
+    if gpu_ids is None:
+        gpu_ids = list(range(torch.cuda.device_count()))
+    devices = [_l.hip_device(f"cuda:{int(g)}", "predict_keypoints") for g in gpu_ids]
+    if not devices:
+        raise _l.Dm4dError("predict_keypoints: no HIP device is available (no CPU fallback in diffuman4d_amd)")
+    batches = [todo[i: i + batch_size] for i in range(0, len(todo), batch_size)]
+    hm_size = (int(W / heatmap_scale), int(H / heatmap_scale))
+    pool = ThreadPoolExecutor(max_workers=max(1, min(int(num_workers), MAX_HOST_THREADS)), thread_name_prefix="dm4d-pose")
+
+    def worker(g: int) -> List:
+        dev = devices[g]
+        writes = []
+        with torch.cuda.device(dev), torch.cuda.stream(torch.cuda.Stream(device=dev)), torch.no_grad():
+            model = pose_model if pose_model is not None else load_pose_model(sapiens_ckpt_path, dev)
+            for batch in batches[g::len(devices)]:
+                x, centers, scales = pose_inputs([images[k] for k in batch], None if fmasks is None else [fmasks[k] for k in batch], None,
+                                                 (H, W), dev, bbox_source=bbox_source, pool=pool)
+                heat = model(x)
+                if not isinstance(heat, torch.Tensor) or heat.device.type != "cuda" or heat.dim() != 4 or heat.shape[0] != x.shape[0]:
+                    raise _l.Dm4dError("pose_model: expected a [n, K, Hh, Wh] tensor on the device")
+                if (heat.shape[3], heat.shape[2]) != hm_size:
+                    raise _l.Dm4dError(f"pose_model: heatmaps of {heat.shape[3]} x {heat.shape[2]}, expected {hm_size[0]} x {hm_size[1]} "
+                                       f"(input {W} x {H}, heatmap_scale {heatmap_scale})")
+                kp, sc = decode_heatmaps(heat, (W, H), centers, scales)
+                for r, k in enumerate(batch):  # one box per image here
+                    writes.append(pool.submit(write_instances, outs[k], kp[r: r + 1], sc[r: r + 1]))
+        return writes
+
+    try:
+        with ThreadPoolExecutor(max_workers=len(devices), thread_name_prefix="dm4d-pose-gpu") as gpus:
+            for fut in [gpus.submit(worker, g) for g in range(len(devices))]:
+                for w in fut.result():
+                    w.result()
+                    result["written"] += 1
+    finally:
+        pool.shutdown(wait=True)
+    return result

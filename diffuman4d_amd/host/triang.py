@@ -31,13 +31,7 @@ MAX_HOST_THREADS = 16
 LAUNCH_BYTES = 1 << 28    # the frame axis is cut so that one launch's kp2d + score stay below this
 
 
-def _hip_device(device, what: str) -> torch.device:
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _l.Dm4dError(f"{what}: device {device!r} is not a HIP device (no CPU fallback in diffuman4d_amd)")
-    if not torch.cuda.is_available():
-        raise _l.Dm4dError(f"{what}: no HIP device is available (no CPU fallback in diffuman4d_amd)")
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
+_hip_device = _l.hip_device
 
 
 # -- the two operations ---------------------------------------------------------------------------------------------------------------

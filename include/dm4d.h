@@ -435,6 +435,50 @@ int dm4d_jpeg_encode_rgb_u8(void* stream, const void* pixels, int64_t pixels_byt
                             const int64_t* desc_host, const int64_t* desc_dev, int n, const uint16_t* qtab_host, const uint16_t* qtab_dev,
                             void* workspace, int64_t workspace_bytes, void* blob, int64_t blob_bytes, int64_t* out);
 
+/* 2-D keypoint prediction around a caller-named pose network (pose.hip, diffuman4d_amd/host/pose.py::predict_keypoints; the reference's
+ *   predict_keypoints stage, scripts/preprocess/sapiens/lite/demo/vis_pose.py:45-63 and :92-109 with pose_utils.py:13-179 and :182-279).
+ *   The network itself is the caller's; these are the steps on either side of it.
+ *
+ * dm4d_pose_input_u8_f32 (vis_pose.py preprocess_pose with sapiens_utils' Image.composite(image, black, fmask) before it): the network's
+ *   input for `rows` (image, box) pairs in one launch -> out [rows, 3, H, W] fp32, planes R, G, B.
+ *   staging: device bytes holding uint8 RGB images (HWC, rows tight) and uint8 L masks.  desc: rows x DM4D_POSE_FIELDS int64 = {image byte
+ *   offset | mask byte offset or -1 | image h, w (1..DM4D_POSE_MAX_SIDE) | offset of the row's warp table in tab, in int32 elements | 0, 0, 0};
+ *   rows may differ in size and may share an image.  A row's warp table = {adelta[W] | bdelta[W] | X0[H] | Y0[H]} int32 with 10 fractional
+ *   bits, made by the host from the inverse A of get_udp_warp_matrix(center, scale, 0, (W, H)) in fp64: adelta[x] = rint(1024 A00 x),
+ *   bdelta[x] = rint(1024 A10 x), X0[y] = rint(1024 (A01 y + A02)) + 16, Y0[y] = rint(1024 (A11 y + A12)) + 16, each within +-DM4D_POSE_TAB_LIMIT.
+ *   Output pixel (x, y): X = (X0[y] + adelta[x]) >> 5, Y = (Y0[y] + bdelta[x]) >> 5 (1/32 pixel); source pixel (X >> 5, Y >> 5), fractions
+ *   fx = X & 31, fy = Y & 31; weights 32 (32 - fx)(32 - fy), 32 fx (32 - fy), 32 (32 - fx) fy, 32 fx fy (they sum to 32768) on the taps
+ *   (0,0), (1,0), (0,1), (1,1); v = (sum w t + 2^14) >> 15.  A tap is the composited pixel MULDIV255(p, m) = (((p m + 128) >> 8) + p m + 128) >> 8
+ *   of the image byte p and the mask byte m (p itself without a mask), 0 outside the image.  Integers only up to here: a rule modelled on
+ *   OpenCV's bilinear warpAffine, not a copy of its code paths.  out = (float(v) - mean[c]) / std[c], each operation rounded to fp32 on its
+ *   own (bit-equal to torch-CPU `(v.float() - mean) / std`); norm_host = {mean R, G, B | std R, G, B} fp32 on the host.
+ *   desc_host / tab_host are host copies of the bytes at desc_dev / tab_dev: offsets, sizes and table entries are validated on them before
+ *   the launch.  A row's result is a function of its own descriptor, table and planes: independent of the batch, bitwise repeatable.
+ * dm4d_pose_mask_box_u8: boxes [n, 4] int32 = {x1, y1, x2, y2} = {first column, first row, last column + 1, last row + 1} of the pixels >= 128
+ *   of each row's mask (descriptor fields 1-3; field 0 is not read), {0, 0, w, h} for a mask without one.  One workgroup per mask, one pass
+ *   of 16-byte loads, shuffles and LDS; no atomics.
+ * dm4d_pose_udp_decode_f32 (pose_utils.py udp_decode up to its division by the heatmap size: get_heatmap_maximum, gaussian_blur with an
+ *   11 x 11 kernel, refine_keypoints_dark_udp): heatmaps [n, K, Hh, Wh] fp32 contiguous -> scores [n, K] = each map's maximum, bit for bit;
+ *   locs [n, K, 2] fp32 = the refined (x, y) in heatmap pixels.  One workgroup per map.  The location starts at the first maximum in
+ *   row-major order (np.argmax).  The map is blurred with the separable 11-tap Gaussian of sigma 2 (taps exp(-x^2 / 8) / sum in fp64, rounded
+ *   to fp32; zeros outside the map, which is what the reference's pad-by-5 + reflecting blur + crop computes), rows first, in bands of at
+ *   most 32 rows with a 5-row halo either side held in LDS, each tap sum an fmaf chain in ascending tap order; scaled by maximum /
+ *   blurred maximum, clipped to [1e-3, 50], log; dx, dy, dxx, dyy, dxy from the 3 x 3 neighbourhood (replicated at the map's edge) in fp32
+ *   as the reference writes them; the 2 x 2 Hessian + FLT_EPSILON I is inverted in fp64 (adjugate / determinant) and location - H^-1 d is
+ *   rounded to fp32 once.  A map whose maximum is <= 0 keeps location (-1, -1) and is not refined (the reference reads wrapped-around
+ *   memory there).  Non-finite heatmaps are unspecified.  No atomics; a map's result does not depend on the batch.                   */
+#define DM4D_POSE_FIELDS 8
+#define DM4D_POSE_MAX_SIDE 16384
+#define DM4D_POSE_MAX_HEATMAP_H 4096
+#define DM4D_POSE_MAX_HEATMAP_W 1024
+#define DM4D_POSE_TAB_LIMIT (1 << 29) /* |warp table entry|: the sum of two stays inside int32 */
+int dm4d_pose_input_u8_f32(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host, const int64_t* desc_dev,
+                           int rows, const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len, const float* norm_host, float* out,
+                           int H, int W);
+int dm4d_pose_mask_box_u8(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
+                          int32_t* boxes);
+int dm4d_pose_udp_decode_f32(void* stream, const float* heatmaps, int n, int K, int Hh, int Wh, float* scores, float* locs);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

@@ -6,7 +6,8 @@
 // Pillow's separable filter (libImaging/Resample.c): int32 coefficients with 22 fractional bits, a horizontal pass whose result is
 // rounded to uint8, then a vertical pass over it; every output value is clip8((2^21 + sum u * k) >> 22).  Crop pixels outside the
 // image are zeros that take part in the sums (Pillow's crop padding).  The coefficient tables are computed on the host
-// (diffuman4d_amd/host/capture.py) in float64 exactly as Pillow computes them; this file only applies them.
+// (diffuman4d_amd/host/resample.py) in float64 exactly as Pillow computes them; this file only applies them, with clip8 and the
+// constants of image_common.h (the 7-channel, 4-columns-per-lane register layout of its two loops is its own).
 //
 // This translation unit is compiled with -ffp-contract=off (build.py EXTRA_FLAGS): the epilogue rounds every fp32 operation on its
 // own, as PyTorch's CPU kernels do, and a contracted multiply-add would change the last bit.
@@ -15,22 +16,16 @@
 #include "common.h"
 #include "dm4d.h"
 #include "errors.h"
+#include "image_common.h"
 
 namespace {
 
-constexpr int kPrecisionBits = 22;
 constexpr int kThreads = 64;
 
 // descriptor fields (int64 each, DM4D_CAPTURE_FIELDS per frame), see dm4d.h
 enum {
   F_IMG = 0, F_MASK, F_SKEL, F_SRC_H, F_SRC_W, F_TOP, F_LEFT, F_CROP_H, F_CROP_W, F_HTAB, F_HK, F_VTAB, F_VK, F_SCRATCH, F_YFIRST, F_NROWS
 };
-
-__device__ __forceinline__ uint32_t clip8(int32_t v) {
-  if (v >= (1 << kPrecisionBits << 8)) return 255u;
-  if (v <= 0) return 0u;
-  return (uint32_t)(v >> kPrecisionBits);
-}
 
 // Horizontal pass: one lane = 4 consecutive output columns of one scratch row, all 7 channels (image RGB, mask, skeleton RGB);
 // scratch pixel = 8 bytes {i0 i1 i2 m s0 s1 s2 0}, a lane stores 32 contiguous bytes.
@@ -56,7 +51,7 @@ __global__ void __launch_bounds__(kThreads) capture_hpass_kernel(const uint8_t* 
     const int ox = x0 + j;
     int32_t acc[7];
 #pragma unroll
-    for (int c = 0; c < 7; ++c) acc[c] = 1 << (kPrecisionBits - 1);
+    for (int c = 0; c < 7; ++c) acc[c] = kPillowHalf;
     if (row_ok) {
       const int xmin = bounds[2 * ox], cnt = bounds[2 * ox + 1];
       const int32_t* k = coefs + (int64_t)ox * ksize;
@@ -103,7 +98,7 @@ __global__ void __launch_bounds__(kThreads) capture_vpass_kernel(const int64_t* 
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
-    for (int c = 0; c < 7; ++c) acc[j][c] = 1 << (kPrecisionBits - 1);
+    for (int c = 0; c < 7; ++c) acc[j][c] = kPillowHalf;
   for (int t = 0; t < cnt; ++t) {
     const U4* row = reinterpret_cast<const U4*>(col + (int64_t)(ymin + t) * W * 8);
     const U4 a = row[0], b = row[1];
@@ -136,16 +131,6 @@ __global__ void __launch_bounds__(kThreads) capture_vpass_kernel(const int64_t* 
   }
 }
 
-// host-side check of one coefficient table: `n` windows [xmin, xmin + cnt) inside [0, in_size), each at most ksize long
-bool table_ok(const int32_t* tab, int64_t tab_len, int64_t off, int64_t ksize, int n, int64_t in_size) {
-  if (off < 0 || ksize < 1 || ksize > (1 << 16) || off + (int64_t)n * (2 + ksize) > tab_len) return false;
-  for (int i = 0; i < n; ++i) {
-    const int64_t xmin = tab[off + 2 * i], cnt = tab[off + 2 * i + 1];
-    if (xmin < 0 || cnt < 1 || cnt > ksize || xmin + cnt > in_size) return false;
-  }
-  return true;
-}
-
 }  // namespace
 
 extern "C" int dm4d_capture_crop_resize_f32(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host,
@@ -170,7 +155,8 @@ extern "C" int dm4d_capture_crop_resize_f32(void* stream, const void* staging, i
     if (d[F_IMG] < 0 || d[F_IMG] + sh * sw * 3 > staging_bytes || d[F_MASK] < 0 || d[F_MASK] + sh * sw > staging_bytes ||
         d[F_SKEL] < 0 || d[F_SKEL] + sh * sw * 3 > staging_bytes)
       return dm4d_set_error(DM4D_ERR_ARG, "capture_crop_resize: a source plane lies outside the staging buffer");
-    if (!table_ok(tab_host, tab_len, d[F_HTAB], d[F_HK], W, cw) || !table_ok(tab_host, tab_len, d[F_VTAB], d[F_VK], H, ch))
+    if (!pillow_table_ok(tab_host, tab_len, d[F_HTAB], d[F_HK], 1 << 16, W, cw, false) ||
+        !pillow_table_ok(tab_host, tab_len, d[F_VTAB], d[F_VK], 1 << 16, H, ch, false))
       return dm4d_set_error(DM4D_ERR_ARG, "capture_crop_resize: a coefficient table is out of range or its windows leave the crop");
     const int64_t y_first = d[F_YFIRST], n_rows = d[F_NROWS];
     if (y_first < 0 || n_rows < 1 || n_rows > 65535 || y_first + n_rows > ch)

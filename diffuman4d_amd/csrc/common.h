@@ -27,6 +27,15 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
 
 __device__ __forceinline__ u16 f2bf(float f) { return (u16)(pack_bf2(f, 0.f) & 0xffffu); }
 
+// x as two bf16 terms: hi = bf16(x), lo = bf16(x - hi)
+__device__ __forceinline__ void split2(float x, u16& hi, u16& lo) {
+  hi = f2bf(x);
+  lo = f2bf(x - bf2f(hi));
+}
+
+// launch grid of ceil(n / block) blocks along x
+inline dim3 grid1d(int64_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
+
 __device__ __forceinline__ void unpack8(const U4& v, float* f) {
   f[0] = __uint_as_float(v.x << 16);
   f[1] = __uint_as_float(v.x & 0xffff0000u);

@@ -397,8 +397,6 @@ __global__ void resize_aa_kernel(const float* X, float* Y, int64_t planes, int H
   Y[i] = acc;
 }
 
-inline dim3 grid1d(int64_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
-
 }  // namespace
 
 // One implementation per operator, instantiated for bf16 tensors (the fast path) and fp32 tensors (parity precision).

@@ -19,20 +19,20 @@
 //   stuff   FF -> FF 00 into the blob
 // Every position comes from a scan; the only atomics are LDS-local ORs inside one wave's buffer.
 //
-// Crop restore = Pillow's two-pass bicubic resize exactly as capture.hip applies it (coefficient tables from host/capture.py), pasted
-// onto a white canvas.
+// Crop restore = Pillow's two-pass bicubic resize by the one definition of its rule in image_common.h (coefficient tables from
+// host/resample.py), pasted onto a white canvas.
 #include <stdint.h>
 
 #include "common.h"
 #include "dm4d.h"
 #include "errors.h"
+#include "image_common.h"
 
 namespace {
 
 constexpr int kWave = 64;
 constexpr int kScanThreads = 1024;
 constexpr int kStuffThreads = DM4D_JPEG_CHUNK / 16;  // one lane per 16 bytes
-constexpr int kPrecisionBits = 22;                   // Pillow's resize coefficients (libImaging/Resample.c)
 constexpr int kMcuWords = 320;                       // LDS words of one MCU's bit stream: 7 + 9948 bits and two words of slack
 constexpr int64_t kMcuBits = 9948;                   // see dm4d.h
 
@@ -258,13 +258,8 @@ __device__ __forceinline__ int32_t dc_pred(const int16_t* __restrict__ mcu, int 
 }
 
 // exclusive prefix sum of `len` over the wave; total = the wave's sum
-__device__ __forceinline__ int wave_excl(int lane, int len, int& total) {
-  int s = len;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int o = __shfl_up(s, off);
-    if (lane >= off) s += o;
-  }
+__device__ __forceinline__ int wave_excl(int len, int& total) {
+  const int s = wave_incl_scan(len);
   total = __shfl(s, 63);
   return s - len;
 }
@@ -282,7 +277,7 @@ __global__ void __launch_bounds__(kWave) jpeg_size_kernel(const int64_t* __restr
     uint64_t sym;
     int len, total;
     block_symbol(lane, mcu[b * 64 + lane], dc_pred(mcu, m, b), b >= 4, sym, len);
-    const int at = pos + wave_excl(lane, len, total);
+    const int at = pos + wave_excl(len, total);
     if (pos < 8) {  // the same for every lane
       uint32_t c = (len && at < 8) ? (uint32_t)(sym >> 56) >> at : 0u;
 #pragma unroll
@@ -297,40 +292,11 @@ __global__ void __launch_bounds__(kWave) jpeg_size_kernel(const int64_t* __restr
   }
 }
 
-// One block: a[0 .. cnt) -> exclusive prefix sums in place; returns the total to every thread.
-template <typename T>
-__device__ T block_scan_inplace(T* __restrict__ a, int64_t cnt) {
-  __shared__ T wave_sum[kScanThreads / 64];
-  __shared__ T carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t t0 = 0; t0 < cnt; t0 += kScanThreads) {
-    const int64_t i = t0 + threadIdx.x;
-    const T c = i < cnt ? a[i] : (T)0;
-    T s = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const T o = __shfl_up(s, off);
-      if (lane >= off) s += o;
-    }
-    if (lane == 63) wave_sum[wave] = s;
-    __syncthreads();
-    T before = carry_s;
-    for (int w = 0; w < wave; ++w) before += wave_sum[w];
-    if (i < cnt) a[i] = before + s - c;
-    __syncthreads();
-    if (threadIdx.x == kScanThreads - 1) carry_s = before + s;
-    __syncthreads();
-  }
-  return carry_s;
-}
-
 // bit lengths of an image's MCUs -> bit positions; nbytes[i] = bytes of its unstuffed scan (the last one padded)
 __global__ void __launch_bounds__(kScanThreads) jpeg_scan_bits_kernel(const int64_t* __restrict__ desc, uint32_t* __restrict__ bits,
                                                                       int64_t* __restrict__ nbytes) {
   const Image im = image_of(desc, blockIdx.x, nullptr, nullptr);
-  const uint32_t total = block_scan_inplace<uint32_t>(bits + im.mcu0, im.mcus);
+  const uint32_t total = block_excl_scan_inplace<uint32_t, kScanThreads>(bits + im.mcu0, im.mcus);
   if (threadIdx.x == 0) nbytes[blockIdx.x] = ((int64_t)total + 7) >> 3;
 }
 
@@ -351,7 +317,7 @@ __global__ void __launch_bounds__(kWave) jpeg_emit_kernel(const int64_t* __restr
     uint64_t sym;
     int len, total;
     block_symbol(lane, mcu[b * 64 + lane], dc_pred(mcu, m, b), b >= 4, sym, len);
-    const int at = pos + wave_excl(lane, len, total);
+    const int at = pos + wave_excl(len, total);
     const int w = at >> 5, sh = at & 31;
     if (len && w + 2 < kMcuWords) {
       const uint32_t hi = (uint32_t)(sym >> 32), lo = (uint32_t)sym;
@@ -416,7 +382,7 @@ __global__ void __launch_bounds__(kScanThreads) jpeg_scan_ff_kernel(const int64_
                                                                     const int64_t* __restrict__ nbytes, int64_t* __restrict__ lens) {
   const Image im = image_of(desc, blockIdx.x, nullptr, nullptr);
   const int64_t nb = nbytes[blockIdx.x];
-  const uint32_t total = block_scan_inplace<uint32_t>(counts + im.chunk0, (nb + DM4D_JPEG_CHUNK - 1) / DM4D_JPEG_CHUNK);
+  const uint32_t total = block_excl_scan_inplace<uint32_t, kScanThreads>(counts + im.chunk0, (nb + DM4D_JPEG_CHUNK - 1) / DM4D_JPEG_CHUNK);
   if (threadIdx.x == 0) lens[blockIdx.x] = nb + (int64_t)total;
 }
 
@@ -424,7 +390,7 @@ __global__ void __launch_bounds__(kScanThreads) jpeg_scan_ff_kernel(const int64_
 __global__ void __launch_bounds__(kScanThreads) jpeg_offsets_kernel(const int64_t* __restrict__ lens, int64_t* __restrict__ offs, int n) {
   for (int i = threadIdx.x; i < n; i += kScanThreads) offs[i] = lens[i];
   __syncthreads();
-  block_scan_inplace<int64_t>(offs, n);
+  block_excl_scan_inplace<int64_t, kScanThreads>(offs, n);
 }
 
 __global__ void __launch_bounds__(kStuffThreads) jpeg_stuff_kernel(const int64_t* __restrict__ desc, const uint8_t* __restrict__ raw,
@@ -438,12 +404,7 @@ __global__ void __launch_bounds__(kStuffThreads) jpeg_stuff_kernel(const int64_t
   uint8_t v[16];
   const int n = load16(raw + im.mcu0 * DM4D_JPEG_MCU_UNSTUFFED, off, nb, v);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int s = n;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(s, o);
-    if (lane >= o) s += t;
-  }
+  const int s = wave_incl_scan(n);
   if (lane == 63) wave_n[wave] = s;
   __syncthreads();
   int64_t at = offs[blockIdx.y] + off + (int64_t)before[im.chunk0 + blockIdx.x] + (s - n);
@@ -458,12 +419,6 @@ __global__ void __launch_bounds__(kStuffThreads) jpeg_stuff_kernel(const int64_t
 }
 
 // -- crop restore ------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t clip8(int32_t v) {
-  if (v >= (1 << kPrecisionBits << 8)) return 255u;
-  if (v <= 0) return 0u;
-  return (uint32_t)(v >> kPrecisionBits);
-}
-
 // Horizontal pass: one lane = one pixel of scratch [H][cw][3]
 __global__ void __launch_bounds__(kWave) restore_hpass_kernel(const uint8_t* __restrict__ pixels, const int64_t* __restrict__ desc,
                                                               const int32_t* __restrict__ tab, uint8_t* __restrict__ scratch) {
@@ -475,16 +430,10 @@ __global__ void __launch_bounds__(kWave) restore_hpass_kernel(const uint8_t* __r
   const int32_t* bounds = tab + d[R_HTAB];
   const int32_t* k = bounds + 2 * cw + (int64_t)ox * ksize;
   const int xmin = bounds[2 * ox], cnt = bounds[2 * ox + 1];
-  const uint8_t* src = pixels + d[R_SRC] + ((int64_t)r * W + xmin) * 3;
-  int32_t acc[3] = {1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1)};
-  for (int t = 0; t < cnt; ++t) {
-    const int32_t wt = k[t];
-    acc[0] += (int32_t)src[3 * t] * wt;
-    acc[1] += (int32_t)src[3 * t + 1] * wt;
-    acc[2] += (int32_t)src[3 * t + 2] * wt;
-  }
+  uint32_t o[3];
+  pillow_rgb(ByteRgb{pixels + d[R_SRC] + ((int64_t)r * W + xmin) * 3, 3}, k, cnt, o);
   uint8_t* dst = scratch + d[R_SCRATCH] + ((int64_t)r * cw + ox) * 3;
-  dst[0] = (uint8_t)clip8(acc[0]), dst[1] = (uint8_t)clip8(acc[1]), dst[2] = (uint8_t)clip8(acc[2]);
+  dst[0] = (uint8_t)o[0], dst[1] = (uint8_t)o[1], dst[2] = (uint8_t)o[2];
 }
 
 // Vertical pass + paste: one lane = one canvas pixel; white where the patch does not cover it
@@ -502,29 +451,10 @@ __global__ void __launch_bounds__(kWave) restore_vpass_kernel(const int64_t* __r
     const int32_t* bounds = tab + d[R_VTAB];
     const int32_t* k = bounds + 2 * ch + (int64_t)py * ksize;
     const int ymin = bounds[2 * py], cnt = bounds[2 * py + 1];
-    const uint8_t* col = scratch + d[R_SCRATCH] + ((int64_t)ymin * cw + px) * 3;
-    int32_t acc[3] = {1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1), 1 << (kPrecisionBits - 1)};
-    for (int t = 0; t < cnt; ++t) {
-      const int32_t wt = k[t];
-      const uint8_t* p = col + (int64_t)t * cw * 3;
-      acc[0] += (int32_t)p[0] * wt;
-      acc[1] += (int32_t)p[1] * wt;
-      acc[2] += (int32_t)p[2] * wt;
-    }
-    o[0] = clip8(acc[0]), o[1] = clip8(acc[1]), o[2] = clip8(acc[2]);
+    pillow_rgb(ByteRgb{scratch + d[R_SCRATCH] + ((int64_t)ymin * cw + px) * 3, (int64_t)cw * 3}, k, cnt, o);
   }
   uint8_t* dst = canvases + d[R_DST] + ((int64_t)y * w + x) * 3;
   dst[0] = (uint8_t)o[0], dst[1] = (uint8_t)o[1], dst[2] = (uint8_t)o[2];
-}
-
-// host-side check of one coefficient table: `n` windows [xmin, xmin + cnt) inside [0, in_size), each at most ksize long
-bool table_ok(const int32_t* tab, int64_t tab_len, int64_t off, int64_t ksize, int64_t n, int64_t in_size) {
-  if (off < 0 || ksize < 1 || ksize > (1 << 18) || off > tab_len || n * (2 + ksize) > tab_len - off) return false;
-  for (int64_t i = 0; i < n; ++i) {
-    const int64_t xmin = tab[off + 2 * i], cnt = tab[off + 2 * i + 1];
-    if (xmin < 0 || cnt < 1 || cnt > ksize || xmin + cnt > in_size) return false;
-  }
-  return true;
 }
 
 bool size_ok(int64_t v) { return v >= 1 && v <= 65535; }
@@ -569,7 +499,8 @@ extern "C" int dm4d_restore_crop_u8(void* stream, const void* pixels, int64_t pi
       return dm4d_set_error(DM4D_ERR_ARG, "restore_crop: crop offset out of range in a descriptor");
     if (d[R_SRC] < 0 || d[R_SRC] > pixels_bytes || H * W * 3 > pixels_bytes - d[R_SRC])
       return dm4d_set_error(DM4D_ERR_ARG, "restore_crop: a source image lies outside the pixel buffer");
-    if (!table_ok(tab_host, tab_len, d[R_HTAB], d[R_HK], cw, W) || !table_ok(tab_host, tab_len, d[R_VTAB], d[R_VK], ch, H))
+    if (!pillow_table_ok(tab_host, tab_len, d[R_HTAB], d[R_HK], 1 << 18, cw, W, false) ||
+        !pillow_table_ok(tab_host, tab_len, d[R_VTAB], d[R_VK], 1 << 18, ch, H, false))
       return dm4d_set_error(DM4D_ERR_ARG, "restore_crop: a coefficient table is out of range or its windows leave the image");
     if (d[R_SCRATCH] < 0 || d[R_SCRATCH] > scratch_bytes || H * cw * 3 > scratch_bytes - d[R_SCRATCH])
       return dm4d_set_error(DM4D_ERR_ARG, "restore_crop: a scratch region lies outside the scratch buffer");

@@ -39,13 +39,6 @@ __constant__ float kScale[3] = {0.458f, 0.448f, 0.450f};
 // torchmetrics' _normalize_tensor(in_feat, eps=1e-8): in_feat / sqrt(eps + sum_c in_feat^2) -- the epsilon is INSIDE the square root
 constexpr double kNormEps = 1e-8;
 
-inline dim3 grid1d(int64_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
-
-__device__ __forceinline__ void split2(float x, u16& hi, u16& lo) {
-  hi = f2bf(x);
-  lo = f2bf(x - bf2f(hi));
-}
-
 // ---- (a) composites -> scaled first-layer operand ------------------------------------------------------------------------------
 __global__ void __launch_bounds__(kThreads) lpips_input_kernel(const float* __restrict__ gt, const float* __restrict__ pred,
                                                                int64_t cs, int64_t rs, int h, int w, u16* __restrict__ Y) {

@@ -22,13 +22,6 @@
 
 namespace {
 
-__device__ __forceinline__ void split2(float x, u16& hi, u16& lo) {
-  hi = f2bf(x);
-  lo = f2bf(x - bf2f(hi));
-}
-
-inline dim3 grid1d(int64_t n, int block) { return dim3((unsigned)((n + block - 1) / block)); }
-
 // ------------------------------------------------------------------------------------------------
 // fp32 -> two-term operand
 // ------------------------------------------------------------------------------------------------

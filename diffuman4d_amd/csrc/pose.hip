@@ -18,6 +18,7 @@
 #include "common.h"
 #include "dm4d.h"
 #include "errors.h"
+#include "image_common.h"
 
 namespace {
 
@@ -75,67 +76,16 @@ __global__ void __launch_bounds__(kInThreads) pose_input_kernel(const uint8_t* _
 // ------------------------------------------------------------------------------------------------------------------------ mask box
 constexpr int kBoxThreads = 1024;
 
-struct Box {
-  int fc, fr, lc, lr;
-};
-
-__device__ __forceinline__ void box_merge(Box& b, const Box& o) {
-  b.fc = min(b.fc, o.fc);
-  b.fr = min(b.fr, o.fr);
-  b.lc = max(b.lc, o.lc);
-  b.lr = max(b.lr, o.lr);
-}
-
-// the bytes >= 128 among the `count` bytes of `word` (little endian) that start at pixel `at` of the mask
-__device__ __forceinline__ void box_scan_word(Box& b, uint32_t word, int count, int64_t at, int w) {
-  if ((word & 0x80808080u) == 0) return;
-  int row = (int)(at / w), col = (int)(at - (int64_t)row * w);
-  for (int j = 0; j < count; ++j) {
-    if ((word >> (8 * j)) & 0x80u) box_merge(b, Box{col, row, col, row});
-    if (++col == w) {
-      col = 0;
-      ++row;
-    }
-  }
-}
-
 // one workgroup per mask: 16-byte loads between a scalar head and tail, shuffles reduce a wave, LDS the workgroup
 __global__ void __launch_bounds__(kBoxThreads) pose_mask_box_kernel(const uint8_t* __restrict__ staging, const int64_t* __restrict__ desc,
                                                                     int32_t* __restrict__ boxes) {
-  __shared__ int s_box[kBoxThreads / 64][4];
   const int tid = threadIdx.x, f = blockIdx.x;
   const int64_t* d = desc + (int64_t)f * DM4D_POSE_FIELDS;
-  const uint8_t* src = staging + d[1];
   const int h = (int)d[2], w = (int)d[3];
-  const int64_t total = (int64_t)h * w;
-  int64_t head = (16 - (int64_t)((uintptr_t)src & 15)) & 15;
-  if (head > total) head = total;
-  const int64_t nvec = (total - head) / 16;
-  const int64_t tail0 = head + nvec * 16;
   Box b{w, h, -1, -1};
-  for (int64_t v = tid; v < nvec; v += kBoxThreads) {
-    const int64_t at = head + v * 16;
-    const U4 q = ldg16(src + at);
-    if (((q.x | q.y | q.z | q.w) & 0x80808080u) == 0) continue;
-    box_scan_word(b, q.x, 4, at, w);
-    box_scan_word(b, q.y, 4, at + 4, w);
-    box_scan_word(b, q.z, 4, at + 8, w);
-    box_scan_word(b, q.w, 4, at + 12, w);
-  }
-  if (tid < head) box_scan_word(b, src[tid], 1, tid, w);
-  if (tail0 + tid < total) box_scan_word(b, src[tail0 + tid], 1, tail0 + tid, w);  // fewer than 16 bytes
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const Box o{__shfl_xor(b.fc, off), __shfl_xor(b.fr, off), __shfl_xor(b.lc, off), __shfl_xor(b.lr, off)};
-    box_merge(b, o);
-  }
-  if ((tid & 63) == 0) {
-    int* s = s_box[tid >> 6];
-    s[0] = b.fc, s[1] = b.fr, s[2] = b.lc, s[3] = b.lr;
-  }
-  __syncthreads();
+  box_scan_plane<1, 0x80808080u>(staging + d[1], (int64_t)h * w, w, tid, kBoxThreads, true, b);
+  box_block_reduce<kBoxThreads>(b);
   if (tid == 0) {
-    for (int k = 1; k < kBoxThreads / 64; ++k) box_merge(b, Box{s_box[k][0], s_box[k][1], s_box[k][2], s_box[k][3]});
     int32_t* dst = boxes + (int64_t)f * 4;
     if (b.lc < 0) {
       dst[0] = 0, dst[1] = 0, dst[2] = w, dst[3] = h;  // an empty mask: the whole image

@@ -9,7 +9,7 @@
 //   rasterise   one lane per footprint pixel: the list is walked from the back, the first primitive that covers the pixel gives its
 //               colour (= the last one painted wins), an uncovered pixel is black.  Coverage is the integer rule of dm4d.h, evaluated
 //               in int64: with coordinates in [-8192, 8191] and pixels in [0, 4096) the largest term, 4 (v x d)^2, stays below 2^61.
-//   horizontal  Pillow's pass along x over the footprint rows, rounded and clipped to uint8 (Resample.c), into LDS
+//   horizontal  Pillow's pass along x over the footprint rows, rounded and clipped to uint8 (pillow_rgb, image_common.h), into LDS
 //   vertical    the pass along y over those bytes; the tile's RGB bytes are staged in LDS and stored row by row
 //
 // A tile with an empty list stores zeros and skips the passes (most of a map is black).  The result is a function of the frame's own
@@ -19,10 +19,10 @@
 #include "common.h"
 #include "dm4d.h"
 #include "errors.h"
+#include "image_common.h"
 
 namespace {
 
-constexpr int kPrecisionBits = 22;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kLdsLimit = 64 * 1024;  // per workgroup: what a launch gets without asking for more; two or more tiles per CU
@@ -30,12 +30,6 @@ constexpr int kMaxCanvas = 4096;
 constexpr int kMaxTaps = 4096;
 
 enum { P_KIND = 0, P_X1, P_Y1, P_X2, P_Y2, P_SIZE, P_COLOR };
-
-__device__ __forceinline__ uint32_t clip8(int32_t v) {
-  if (v >= (1 << kPrecisionBits << 8)) return 255u;
-  if (v <= 0) return 0u;
-  return (uint32_t)(v >> kPrecisionBits);
-}
 
 struct Prim {
   int kind, x1, y1, x2, y2, size;
@@ -156,16 +150,9 @@ __global__ void __launch_bounds__(kThreads) skeleton_draw_kernel(const int32_t* 
     const int ox = ox0 + j;
     const int xmin = htab[2 * ox] - fx0, cnt = htab[2 * ox + 1];
     const int32_t* k = hcoef + (int64_t)ox * hk;
-    const uint32_t* src = s_canvas + r * fw + xmin;
-    int32_t a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
-    for (int t = 0; t < cnt; ++t) {
-      const uint32_t c = src[t];
-      const int32_t wt = k[t];
-      a0 += (int32_t)(c & 0xffu) * wt;
-      a1 += (int32_t)((c >> 8) & 0xffu) * wt;
-      a2 += (int32_t)((c >> 16) & 0xffu) * wt;
-    }
-    s_rows[r * T + j] = clip8(a0) | (clip8(a1) << 8) | (clip8(a2) << 16);
+    uint32_t o[3];
+    pillow_rgb(PackedRgb{s_canvas + r * fw + xmin, 1}, k, cnt, o);
+    s_rows[r * T + j] = o[0] | (o[1] << 8) | (o[2] << 16);
   }
   __syncthreads();
 
@@ -176,37 +163,18 @@ __global__ void __launch_bounds__(kThreads) skeleton_draw_kernel(const int32_t* 
     const int oy = oy0 + r;
     const int ymin = vtab[2 * oy] - fy0, cnt = vtab[2 * oy + 1];
     const int32_t* k = vcoef + (int64_t)oy * vk;
-    int32_t a0 = 1 << (kPrecisionBits - 1), a1 = a0, a2 = a0;
-    for (int t = 0; t < cnt; ++t) {
-      const uint32_t c = s_rows[(ymin + t) * T + j];
-      const int32_t wt = k[t];
-      a0 += (int32_t)(c & 0xffu) * wt;
-      a1 += (int32_t)((c >> 8) & 0xffu) * wt;
-      a2 += (int32_t)((c >> 16) & 0xffu) * wt;
-    }
+    uint32_t o[3];
+    pillow_rgb(PackedRgb{s_rows + ymin * T + j, T}, k, cnt, o);
     uint8_t* dst = s_tile + (r * T + j) * 3;
-    dst[0] = (uint8_t)clip8(a0);
-    dst[1] = (uint8_t)clip8(a1);
-    dst[2] = (uint8_t)clip8(a2);
+    dst[0] = (uint8_t)o[0];
+    dst[1] = (uint8_t)o[1];
+    dst[2] = (uint8_t)o[2];
   }
   __syncthreads();
   for (int i = tid; i < nrows * row_bytes; i += kThreads) {
     const int r = i / row_bytes, c = i % row_bytes;
     tile_out[(int64_t)r * w * 3 + c] = s_tile[r * T * 3 + c];
   }
-}
-
-// host-side check of one coefficient table (n windows {start, length} then n x ksize weights): windows inside [0, in_size), at most
-// ksize long, starts and ends non-decreasing
-bool table_ok(const int32_t* tab, int n, int ksize, int in_size) {
-  int64_t prev_start = 0, prev_end = 0;
-  for (int i = 0; i < n; ++i) {
-    const int64_t start = tab[2 * i], cnt = tab[2 * i + 1];
-    if (start < 0 || cnt < 1 || cnt > ksize || start + cnt > in_size || start < prev_start || start + cnt < prev_end) return false;
-    prev_start = start;
-    prev_end = start + cnt;
-  }
-  return true;
 }
 
 // the largest footprint extent along one axis over tiles of T outputs
@@ -259,7 +227,8 @@ extern "C" int dm4d_skeleton_draw_u8(void* stream, const int32_t* prims_host, co
       return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a thickness below 1, a negative radius, or a size above DM4D_SKEL_MAX_SIZE");
     if ((uint32_t)p[P_COLOR] >> 24) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a colour has bits above r | g << 8 | b << 16");
   }
-  if (!table_ok(htab_host, w, hk, W) || !table_ok(vtab_host, h, vk, H))
+  if (!pillow_table_ok(htab_host, (int64_t)w * (2 + hk), 0, hk, kMaxTaps, w, W, true) ||
+      !pillow_table_ok(vtab_host, (int64_t)h * (2 + vk), 0, vk, kMaxTaps, h, H, true))
     return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a coefficient table's windows leave the canvas, exceed ksize or are not ordered");
   const hipStream_t s = (hipStream_t)stream;
   for (int T : {32, 16, 8}) {
@@ -295,74 +264,14 @@ __host__ __device__ inline int box_blocks(int64_t frame_bytes) {
   return (int)(n < 1 ? 1 : n > kBoxMaxBlocks ? kBoxMaxBlocks : n);
 }
 
-struct Box {
-  int fc, fr, lc, lr;
-};
-
-__device__ __forceinline__ void box_add(Box& b, int col, int row) {
-  b.fc = min(b.fc, col);
-  b.fr = min(b.fr, row);
-  b.lc = max(b.lc, col);
-  b.lr = max(b.lr, row);
-}
-
-__device__ __forceinline__ void box_merge(Box& b, const Box& o) {
-  b.fc = min(b.fc, o.fc);
-  b.fr = min(b.fr, o.fr);
-  b.lc = max(b.lc, o.lc);
-  b.lr = max(b.lr, o.lr);
-}
-
-// the non-zero bytes among the `count` bytes of `word` (little endian) that start at byte `at` of the frame
-__device__ __forceinline__ void box_scan_word(Box& b, uint32_t word, int count, int64_t at, int row_bytes) {
-  if (word == 0) return;
-  int row = (int)(at / row_bytes), cb = (int)(at % row_bytes);
-  for (int j = 0; j < count; ++j) {
-    if ((word >> (8 * j)) & 0xffu) box_add(b, cb / 3, row);
-    if (++cb == row_bytes) {
-      cb = 0;
-      ++row;
-    }
-  }
-}
-
 __global__ void __launch_bounds__(kBoxThreads) skeleton_box_partial_kernel(const uint8_t* __restrict__ maps, int64_t frame_bytes, int h, int w,
                                                                            int32_t* __restrict__ partials) {
-  __shared__ int s_box[kBoxThreads / 64][4];
   const int tid = threadIdx.x, f = blockIdx.y, nblocks = gridDim.x;
-  const uint8_t* src = maps + (int64_t)f * frame_bytes;
-  const int row_bytes = w * 3;
-  int64_t head = (16 - (int64_t)((uintptr_t)src & 15)) & 15;
-  if (head > frame_bytes) head = frame_bytes;
-  const int64_t nvec = (frame_bytes - head) / 16;
-  const int64_t tail0 = head + nvec * 16;
   Box b{w, h, -1, -1};
-  for (int64_t v = (int64_t)blockIdx.x * kBoxThreads + tid; v < nvec; v += (int64_t)nblocks * kBoxThreads) {
-    const int64_t at = head + v * 16;
-    const U4 q = ldg16(src + at);
-    if ((q.x | q.y | q.z | q.w) == 0) continue;
-    box_scan_word(b, q.x, 4, at, row_bytes);
-    box_scan_word(b, q.y, 4, at + 4, row_bytes);
-    box_scan_word(b, q.z, 4, at + 8, row_bytes);
-    box_scan_word(b, q.w, 4, at + 12, row_bytes);
-  }
-  if (blockIdx.x == 0) {  // head and tail, a byte per thread
-    if (tid < head) box_scan_word(b, src[tid], 1, tid, row_bytes);
-    const int64_t t = tail0 + tid;
-    if (t < frame_bytes) box_scan_word(b, src[t], 1, t, row_bytes);
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const Box o{__shfl_xor(b.fc, off), __shfl_xor(b.fr, off), __shfl_xor(b.lc, off), __shfl_xor(b.lr, off)};
-    box_merge(b, o);
-  }
-  if ((tid & 63) == 0) {
-    int* s = s_box[tid >> 6];
-    s[0] = b.fc, s[1] = b.fr, s[2] = b.lc, s[3] = b.lr;
-  }
-  __syncthreads();
+  box_scan_plane<3, 0xffffffffu>(maps + (int64_t)f * frame_bytes, frame_bytes, w * 3, (int64_t)blockIdx.x * kBoxThreads + tid,
+                                 (int64_t)nblocks * kBoxThreads, blockIdx.x == 0, b);
+  box_block_reduce<kBoxThreads>(b);
   if (tid == 0) {
-    for (int k = 1; k < kBoxThreads / 64; ++k) box_merge(b, Box{s_box[k][0], s_box[k][1], s_box[k][2], s_box[k][3]});
     int32_t* dst = partials + ((int64_t)f * nblocks + blockIdx.x) * 4;
     dst[0] = b.fc, dst[1] = b.fr, dst[2] = b.lc, dst[3] = b.lr;
   }
@@ -374,11 +283,7 @@ __global__ void __launch_bounds__(64) skeleton_box_reduce_kernel(const int32_t* 
   Box b{w, h, -1, -1};
   const int32_t* p = partials + (int64_t)f * nblocks * 4;
   for (int k = lane; k < nblocks; k += 64) box_merge(b, Box{p[4 * k], p[4 * k + 1], p[4 * k + 2], p[4 * k + 3]});
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    const Box o{__shfl_xor(b.fc, off), __shfl_xor(b.fr, off), __shfl_xor(b.lc, off), __shfl_xor(b.lr, off)};
-    box_merge(b, o);
-  }
+  box_wave_reduce(b);
   if (lane == 0) {
     int32_t* dst = boxes + (int64_t)f * 4;
     dst[0] = b.fc, dst[1] = b.fr, dst[2] = b.lc, dst[3] = b.lr;

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "dm4d.h"
 #include "errors.h"
+#include "image_common.h"
 
 namespace {
 
@@ -129,33 +130,11 @@ __global__ void __launch_bounds__(kThreads) vhull_flags_kernel(Grid g, const dou
 // ONE block: counts[i] -> sum of counts[0 .. i) in place; header[0] = points of the frame before this chunk, *total += the chunk's.
 __global__ void __launch_bounds__(kScanThreads) vhull_scan_kernel(uint32_t* __restrict__ counts, int64_t nblocks, int64_t* __restrict__ header,
                                                                   int64_t* __restrict__ total) {
-  __shared__ uint32_t wave_sum[kScanThreads / 64];
-  __shared__ uint32_t carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int64_t t0 = 0; t0 < nblocks; t0 += kScanThreads) {
-    const int64_t i = t0 + threadIdx.x;
-    const uint32_t c = i < nblocks ? counts[i] : 0u;
-    uint32_t s = c;  // inclusive scan inside the wave
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-      const uint32_t o = __shfl_up(s, off);
-      if (lane >= off) s += o;
-    }
-    if (lane == 63) wave_sum[wave] = s;
-    __syncthreads();
-    uint32_t before = carry_s;
-    for (int w = 0; w < wave; ++w) before += wave_sum[w];
-    if (i < nblocks) counts[i] = before + s - c;
-    __syncthreads();
-    if (threadIdx.x == kScanThreads - 1) carry_s = before + s;
-    __syncthreads();
-  }
+  const uint32_t sum = block_excl_scan_inplace<uint32_t, kScanThreads>(counts, nblocks);
   if (threadIdx.x == 0) {
     const int64_t base = *total;
     header[0] = base;
-    *total = base + (int64_t)carry_s;
+    *total = base + (int64_t)sum;
   }
 }
 

@@ -32,44 +32,12 @@ from PIL import Image
 
 from . import ops
 from .dataset import plucker_maps, relative_poses
+from .lib import align16
+from .resample import PRECISION_BITS, TableSet, bicubic_table  # noqa: F401  (tests and tools import the first and the last from here)
 
 log = logging.getLogger(__name__)
 
 FIELDS = ops.CAPTURE_FIELDS  # int64 fields of one frame descriptor: an alias of the one mirror in host/lib.py, not a second copy
-PRECISION_BITS = 22  # Pillow's fixed-point coefficients for 8-bit images (libImaging/Resample.c)
-_ALIGN = 16
-
-
-def _bicubic(x: np.ndarray) -> np.ndarray:
-    """Pillow's bicubic kernel, a = -0.5, in its own order of operations."""
-    x = np.abs(x)
-    near = ((1.5 * x - 2.5) * x) * x + 1.0
-    far = (((x - 5.0) * x + 8.0) * x - 4.0) * -0.5
-    return np.where(x < 1.0, near, np.where(x < 2.0, far, 0.0))
-
-
-def bicubic_table(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
-    """Pillow's coefficients for resizing an axis of `in_size` pixels (the crop) to `out_size`: ([out, 2] int32 window
-    {start, length}, [out, ksize] int32 weights with 22 fractional bits).  float64 throughout, the weights of a window summed left
-    to right (a pairwise sum can move a coefficient by one unit), each scaled by 1 / filterscale as a product."""
-    scale = in_size / out_size
-    fs = max(scale, 1.0)
-    support = 2.0 * fs
-    ksize = int(math.ceil(support)) * 2 + 1
-    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
-    lo = np.maximum(np.trunc(center - support + 0.5), 0).astype(np.int64)  # C's (int) truncates
-    hi = np.minimum(np.trunc(center + support + 0.5), in_size).astype(np.int64)
-    n = hi - lo
-    t = np.arange(ksize)
-    w = _bicubic(((t[None, :] + lo[:, None]) - center[:, None] + 0.5) * (1.0 / fs))
-    w = np.where(t[None, :] < n[:, None], w, 0.0)
-    total = np.zeros(out_size)
-    for j in range(ksize):  # sequential sum; the zero tail adds nothing
-        total = total + w[:, j]
-    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
-    scaled = w * float(1 << PRECISION_BITS)
-    k = np.trunc(np.where(w < 0, -0.5 + scaled, 0.5 + scaled)).astype(np.int32)
-    return np.stack([lo, n], axis=1).astype(np.int32), k
 
 
 # -- cameras ----------------------------------------------------------------------------------------------------------------------
@@ -190,10 +158,6 @@ def _intrinsic(K: torch.Tensor, crop: List[int], height: int) -> torch.Tensor:
     return K
 
 
-def _up(n: int) -> int:
-    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
-
-
 SKELETON_SOURCES = ("files", "kp2d")
 KP2D_PATH_PAT = "{data_dir}/{scene_label}/poses_2d/{spa_label}/{tem_label}.json"
 
@@ -228,7 +192,7 @@ class SpaTemDataset:
         self.kp2d_canvas_shape = None if kp2d_canvas_shape is None else tuple(int(v) for v in kp2d_canvas_shape)
         self.palette = None
         if skeleton_source == "kp2d":
-            from . import skeleton as _sk  # here, not at the top: host/skeleton.py imports this module's bicubic_table
+            from . import skeleton as _sk  # here, not at the top: host/skeleton.py imports host/triang.py, which imports this module
             if palette is None:
                 raise ValueError("skeleton_source='kp2d' needs palette=: a path or a Palette, as skeleton.load_palette takes it (no colour "
                                  f"or link table is part of this package); {_sk.PALETTE_HELP}")
@@ -315,18 +279,11 @@ class SpaTemDataset:
     def _tables(self, frames: List[Dict]) -> Tuple[Dict[Tuple[int, int], Tuple[int, int]], np.ndarray]:
         """Pillow's coefficient tables of every distinct (crop size, output size) pair -> ({pair: (offset in int32 units, ksize)},
         the int32 array that holds them)."""
-        H, W = self.height, self.width
-        tables: Dict[Tuple[int, int], Tuple[int, int]] = {}
-        chunks: List[np.ndarray] = []
-        n_tab = 0
+        ts = TableSet()
         for fr in frames:
-            for key in ((fr["crop"][3], W), (fr["crop"][2], H)):
-                if key not in tables:
-                    b, k = bicubic_table(*key)
-                    tables[key] = (n_tab, k.shape[1])
-                    chunks += [b.reshape(-1), k.reshape(-1)]
-                    n_tab += b.size + k.size
-        return tables, np.concatenate(chunks).astype(np.int32)
+            ts.add(fr["crop"][3], self.width)
+            ts.add(fr["crop"][2], self.height)
+        return ts.tables, ts.array()
 
     def _descriptors(self, frames: List[Dict], plane_offs, shapes, tables, tab: np.ndarray) -> np.ndarray:
         """int64 [n, FIELDS] frame descriptors (include/dm4d.h): plane_offs = (image, mask, skeleton) byte offsets per frame, image None
@@ -342,7 +299,7 @@ class SpaTemDataset:
             y_first, y_last = int(vb[0, 0]), int(vb[-1, 0] + vb[-1, 1])  # crop rows the vertical windows read
             desc[i] = [os_ if oi is None else oi, om, os_, sh, sw, top, left, ch, cw, htab, hk, vtab, vk, scratch, y_first,
                        y_last - y_first]
-            scratch = _up(scratch + (y_last - y_first) * W * 8)
+            scratch = align16(scratch + (y_last - y_first) * W * 8)
         return desc
 
     def _resize_on_device_kp2d(self, frames: List[Dict], device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -374,14 +331,14 @@ class SpaTemDataset:
                 for k, i in enumerate(idx[:n_targets]):
                     mask_offs[i] = cur + k * h * w
                 cur += n_targets * h * w
-        file_off = off = _up(cur)  # where the planes that come from files start
+        file_off = off = align16(cur)  # where the planes that come from files start
         file_offs = []
         for fr in frames:
             o = []
             for name in ("img", "mask"):
                 a = fr[name]
                 o.append(None if a is None else off)
-                off = off if a is None else _up(off + a.size)
+                off = off if a is None else align16(off + a.size)
             file_offs.append(o)
         total = off
 
@@ -413,7 +370,7 @@ class SpaTemDataset:
             shapes = [(fr["plan"].out_size[1], fr["plan"].out_size[0]) for fr in frames]
             plane_offs = [(oi, mask_offs[i] if om is None else om, skel_offs[i]) for i, (oi, om) in enumerate(file_offs)]
             desc = self._descriptors(frames, plane_offs, shapes, tables, tab)
-            desc_off = _up(tab.nbytes)
+            desc_off = align16(tab.nbytes)
             meta = torch.empty(desc_off + desc.nbytes, dtype=torch.uint8, pin_memory=on_gpu)
             meta.numpy()[:tab.nbytes] = tab.view(np.uint8)
             meta.numpy()[desc_off:] = desc.reshape(-1).view(np.uint8)
@@ -449,10 +406,10 @@ class SpaTemDataset:
                     o.append(None)
                     continue
                 o.append(off)
-                off = _up(off + a.size)
+                off = align16(off + a.size)
             plane_offs.append(o)
         tab_off = off
-        desc_off = _up(tab_off + tab.nbytes)
+        desc_off = align16(tab_off + tab.nbytes)
         total = desc_off + len(frames) * FIELDS * 8
         desc = self._descriptors(frames, plane_offs, [fr["skel"].shape[:2] for fr in frames], tables, tab)
         on_gpu = device.type == "cuda"

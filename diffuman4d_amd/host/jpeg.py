@@ -18,6 +18,7 @@ import torch
 
 from . import lib as _l
 from .ops import _p, _req, _stream
+from .resample import TableSet
 
 # -- Annex K ------------------------------------------------------------------------------------------------------------------------
 QUANT_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
@@ -94,45 +95,30 @@ def _mcus(h: int, w: int) -> int:
     return ((h + 15) // 16) * ((w + 15) // 16)
 
 
-def _pad16(n: int) -> int:
-    return (n + 15) // 16 * 16
-
-
 def _image_bytes(img, crop, hw) -> int:
     """Device bytes one image of a batch needs: canvas + resize scratch + encoder workspace + its share of the blob."""
     m = _mcus(*hw)
     n = m * (768 + 8 + _l.JPEG_MCU_UNSTUFFED + _l.JPEG_MCU_BOUND) + 64
     if crop is not None:
-        n += _pad16(hw[0] * hw[1] * 3) + _pad16(img.shape[0] * int(crop[3]) * 3)
+        n += _l.align16(hw[0] * hw[1] * 3) + _l.align16(img.shape[0] * int(crop[3]) * 3)
     return n
 
 
 def restore_crops(pixels: torch.Tensor, items, device) -> Tuple[torch.Tensor, list]:
     """``imgwrite.restore_cropped_image`` of a batch on the device (dm4d_restore_crop_u8, two launches): items = [(byte offset of the
     uint8 [H, W, 3] image in `pixels`, H, W, (ct, cl, ch, cw), (canvas h, canvas w))] -> (uint8 buffer of the canvases, their byte
-    offsets in it).  The coefficient tables are Pillow's (host/capture.py bicubic_table)."""
-    from .capture import bicubic_table
+    offsets in it).  The coefficient tables are Pillow's (host/resample.py)."""
     _req(pixels, "pixels", torch.uint8)
     desc = torch.zeros((len(items), _l.RESTORE_FIELDS), dtype=torch.int64)
-    tabs, tab_at, tab_len, scratch_len, canvas_len, places = [], {}, 0, 0, 0, []
-
-    def table(n_in: int, n_out: int) -> Tuple[int, int]:
-        nonlocal tab_len
-        if (n_in, n_out) not in tab_at:
-            bounds, k = bicubic_table(n_in, n_out)
-            tab_at[(n_in, n_out)] = (tab_len, k.shape[1])
-            tabs.extend([torch.from_numpy(bounds.reshape(-1).copy()), torch.from_numpy(k.reshape(-1).copy())])
-            tab_len += bounds.size + k.size
-        return tab_at[(n_in, n_out)]
-
+    tables, scratch_len, canvas_len, places = TableSet(), 0, 0, []
     for i, (src, H, W, (ct, cl, ch, cw), (h, w)) in enumerate(items):
-        htab, hk = table(W, cw)
-        vtab, vk = table(H, ch)
+        htab, hk = tables.add(W, cw)
+        vtab, vk = tables.add(H, ch)
         desc[i, :15] = torch.tensor([src, H, W, ct, cl, ch, cw, h, w, htab, hk, vtab, vk, scratch_len, canvas_len])
         places.append(canvas_len)
-        scratch_len += (H * cw * 3 + 15) // 16 * 16
-        canvas_len += (h * w * 3 + 15) // 16 * 16
-    tab = torch.cat(tabs).to(torch.int32).contiguous()
+        scratch_len += _l.align16(H * cw * 3)
+        canvas_len += _l.align16(h * w * 3)
+    tab = torch.from_numpy(tables.array())
     scratch = torch.empty(scratch_len, dtype=torch.uint8, device=device)
     canvases = torch.empty(canvas_len, dtype=torch.uint8, device=device)
     desc_dev, tab_dev = desc.to(device), tab.to(device)

@@ -179,6 +179,11 @@ def lib_path() -> Path:
     return _LIB_PATH
 
 
+def align16(n: int) -> int:
+    """n rounded up to a multiple of 16: where the next region of a staging buffer or a workspace starts."""
+    return (n + 15) // 16 * 16
+
+
 def load():
     """Load libdm4d.so and attach prototypes.  Raises if it is missing -- never falls back."""
     global _lib

@@ -34,13 +34,12 @@ from PIL import Image
 
 from . import lpips as _lpips
 from . import ops
-from .lib import Dm4dError
+from .lib import Dm4dError, align16
 
 log = logging.getLogger(__name__)
 
 BACKGROUNDS = {"black": 0, "white": 1, "grey": 2}
 MIN_EDGE = 11  # the 11 x 11 SSIM window has to fit into the crop
-_ALIGN = 16
 
 ImageLike = Union[torch.Tensor, str, np.ndarray]
 
@@ -53,10 +52,6 @@ def resized_size(h: int, w: int, canvas_size: int) -> Tuple[int, int]:
     short, long = (w, h) if w <= h else (h, w)
     new_short, new_long = canvas_size, int(canvas_size * long / short)
     return (new_long, new_short) if w <= h else (new_short, new_long)
-
-
-def _up(n: int) -> int:
-    return (n + _ALIGN - 1) // _ALIGN * _ALIGN
 
 
 def _load(x: ImageLike, channels: int):
@@ -164,7 +159,7 @@ class ImageEvaluator:
                 else:
                     offs[name] = off
                     jobs.append((off, a))
-                    off = _up(off + a.nbytes)
+                    off = align16(off + a.nbytes)
             mask = it["pmask"] if it["pmask"] is not None else it["gmask"]
             flags = ((ops.EVAL_IMAGE_F32 if it["pred"].dtype != np.uint8 else 0)
                      | (ops.EVAL_MASK_F32 if mask is not None and mask.dtype != np.uint8 else 0)

@@ -36,10 +36,6 @@ MAX_HOST_THREADS = 16
 FIELDS = _l.POSE_FIELDS
 
 
-def _up(n: int) -> int:
-    return (n + 15) & ~15
-
-
 # -- boxes -> centre, scale, warp tables (host, numpy) -------------------------------------------------------------------------------
 def box_center_scale(bbox, shape: Tuple[int, int], padding: float = PADDING) -> Tuple[np.ndarray, np.ndarray]:
     """[x1, y1, x2, y2] -> (center (2,), scale (2,)) float64 as top_down_affine_transform forms them (pose_utils.py:248-269): the box
@@ -132,12 +128,12 @@ class _Staged:
         for k, (h, w) in enumerate(self.sizes):
             if ims is not None:
                 self.image_off.append(off)
-                off = _up(off + h * w * 3)
+                off = _l.align16(off + h * w * 3)
             else:
                 self.image_off.append(-1)
             if mks is not None and mks[k] is not None:
                 self.mask_off.append(off)
-                off = _up(off + h * w)
+                off = _l.align16(off + h * w)
             else:
                 self.mask_off.append(-1)
         host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
@@ -159,7 +155,7 @@ class _Staged:
     def meta(self, rows: Sequence[Tuple[int, int]], tab: Optional[np.ndarray]) -> Tuple[torch.Tensor, torch.Tensor, int, int]:
         """rows: (image index, table offset in int32 elements) -> (meta on the device, its pinned host copy, tab_off, desc_off)."""
         tab_bytes = 0 if tab is None else tab.nbytes
-        desc_off = _up(tab_bytes)
+        desc_off = _l.align16(tab_bytes)
         desc = np.zeros((len(rows), FIELDS), dtype=np.int64)
         for r, (k, toff) in enumerate(rows):
             desc[r, :5] = [self.image_off[k], self.mask_off[k], self.sizes[k][0], self.sizes[k][1], toff]

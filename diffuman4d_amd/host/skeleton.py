@@ -31,7 +31,7 @@ import torch
 
 from . import lib as _l
 from . import ops
-from .capture import bicubic_table
+from .resample import TableSet
 from .triang import _hip_device
 
 log = logging.getLogger(__name__)
@@ -234,21 +234,21 @@ def _draw_chunks(plans: Sequence[DrawPlan], dev: torch.device, out: Optional[tor
     (H, W), (w, h) = plans[0].canvas_shape, plans[0].out_size
     if any(p.canvas_shape != (H, W) or p.out_size != (w, h) for p in plans):
         raise ValueError("draw_plans: the frames of one batch must share the canvas shape and the output size")
-    hb, hk = bicubic_table(W, w)
-    vb, vk = bicubic_table(H, h)
-    htab = np.concatenate([hb.reshape(-1), hk.reshape(-1)]).astype(np.int32)
-    vtab = np.concatenate([vb.reshape(-1), vk.reshape(-1)]).astype(np.int32)
+    tables = TableSet()
+    (ho, hk), (vo, vk) = tables.add(W, w), tables.add(H, h)
     step = max(1, LAUNCH_BYTES // (h * w * 3))
     with torch.cuda.device(dev) if dev.type == "cuda" else contextlib.nullcontext():
-        htab_h, vtab_h = torch.from_numpy(htab), torch.from_numpy(vtab)
-        htab_d, vtab_d = htab_h.to(dev), vtab_h.to(dev)
+        tab_h = torch.from_numpy(tables.array())
+        tab_d = tab_h.to(dev)  # dm4d_skeleton_draw_u8 takes each axis' table by pointer: views of the one array
+        htab_h, htab_d = (t[ho:ho + w * (2 + hk)] for t in (tab_h, tab_d))
+        vtab_h, vtab_d = (t[vo:vo + h * (2 + vk)] for t in (tab_h, tab_d))
         for b0 in range(0, len(plans), step):
             chunk = plans[b0:b0 + step]
             recs = [pack_calls(p.calls) for p in chunk]
             offsets = torch.from_numpy(np.concatenate([[0], np.cumsum([len(r) for r in recs])]).astype(np.int32))
             prims = torch.from_numpy(np.concatenate(recs + [np.zeros((1, ops.SKEL_FIELDS), dtype=np.int32)]))  # never empty
-            yield b0, ops.skeleton_draw(prims, prims.to(dev), offsets, offsets.to(dev), htab_h, htab_d, hk.shape[1], vtab_h, vtab_d,
-                                        vk.shape[1], H, W, h, w, out=None if out is None else out[b0:b0 + len(chunk)])
+            yield b0, ops.skeleton_draw(prims, prims.to(dev), offsets, offsets.to(dev), htab_h, htab_d, hk, vtab_h, vtab_d,
+                                        vk, H, W, h, w, out=None if out is None else out[b0:b0 + len(chunk)])
 
 
 def draw_plans_into(plans: Sequence[DrawPlan], out: torch.Tensor) -> torch.Tensor:

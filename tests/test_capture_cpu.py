@@ -231,6 +231,13 @@ def test_capture_entry_rejects_bad_arguments():
     bad_tab = tab.copy()
     bad_tab[2 * 3] = 8  # a window [8, 9) outside a crop of 8 columns
     assert f(*args(t=bad_tab)) == -1 and "coefficient table" in last()
+    # ksize one above this entry's limit of 1 << 16, everything else in order: a horizontal table of 8 windows [0, 1) with room
+    # for its 8 x 65537 weights, then the vertical table as before
+    k = (1 << 16) + 1
+    wide_tab = np.concatenate([bounds, np.zeros(W * k, np.int32), tab])
+    wide = desc.copy()
+    wide[0, 10], wide[0, 11] = k, 2 * W + W * k
+    assert f(*args(d=wide, t=wide_tab)) == -1 and "coefficient table" in last()
     assert f(*args(scratch=16)) == -1 and "scratch region" in last()
     bad = desc.copy()
     bad[0, 15] = 9  # more scratch rows than the crop has

@@ -39,6 +39,7 @@ def cases(quality):
         out.append(("block_checkerboard_48x64", np.repeat(((((x >> 3) + (y >> 3)) & 1) * 255).astype(np.uint8)[..., None], 3, axis=2)))
     else:
         out.append(("smooth_plus_noise_320x576", _smooth_plus_noise(320, 576)))
+        out.append(("noise_16x16400", _noise(200, 16, 16400)))  # 1025 MCUs: the scan of their bit lengths takes a second round of 1024
     for _, a in out:
         a.setflags(write=False)
     return tuple(out)
@@ -107,6 +108,16 @@ def test_chunked_batch_equals_one_chunk(hip_device):
     """A workspace budget that forces several chunks (one image each at the smallest budget) changes no byte."""
     imgs = [torch.from_numpy(a.copy()).to(hip_device) for _, a in cases(90)]
     assert list(jpeg.encode_jpeg_batch(imgs, quality=90, workspace_bytes=1)) == list(device_batch(90))
+
+
+def test_a_batch_longer_than_one_scan_round(hip_device):
+    """1025 images: the one-block scan of the files' lengths (their places in the blob) carries over from its first 1024 to the last."""
+    batch = np.random.default_rng(300).integers(0, 256, (1025, 8, 8, 3), dtype=np.uint8)
+    got = jpeg.encode_jpeg_batch(list(torch.from_numpy(batch).to(hip_device)), quality=90)
+    assert len(got) == 1025
+    for k, g in enumerate(got):
+        p = pillow_bytes(batch[k], 90)
+        assert g == p, f"image {k} of 1025: device != Pillow ({first_difference(g, p)})"
 
 
 CROPS = [(-5, 7, 50, 30),              # clipped at a negative row offset, up-scaled

@@ -226,6 +226,11 @@ def test_the_entry_validates_its_host_copies_before_launching():
     bad[2 * 1023 + 1] += 1  # the last window now ends one pixel past the canvas
     rc, msg = _call([line], [0, 1], htab=bad)
     assert rc == -1 and "coefficient table" in msg
+    bad = np.concatenate([hb.reshape(-1), hk.reshape(-1)]).astype(np.int32)
+    bad[2 * 500] = bad[2 * 499] - 1  # window 500 starts (and ends) before window 499, still inside the canvas and no longer than ksize
+    assert 0 <= bad[2 * 500] and bad[2 * 500 + 1] <= hk.shape[1]
+    rc, msg = _call([line], [0, 1], htab=bad)
+    assert rc == -1 and "not ordered" in msg
     rc, msg = _call([line], [0, 1], h=100, w=100)  # a ratio of 20: no tile's footprint fits
     assert rc == -1 and "does not fit in LDS" in msg
     rc, msg = _call([line], [0, 1], H=5000)

@@ -8,12 +8,11 @@
 // and  x W^T = [hi | lo] [W | W]^T  is one more pass of the SAME kernels over a K axis twice as long (dm4d_gemm_bf16 /
 // dm4d_conv3x3_nhwc_bf16_flags with DM4D_EPI_F32OUT / F32SIDE / SPLITOUT).  This file holds what sits between those launches:
 //   * split_kernel            fp32 [M, C] (one or two sources = the up-block channel concat) -> operand [M, hi(Cp) | lo(Cp)]
-//   * gn32_*                  GroupNorm(+SiLU) fp32 in, statistics in fp64, operand out
-//   * ln32_kernel             LayerNorm fp32 in, operand out
-//   * softmax32_split_kernel  row softmax of fp32 logits -> three-plane operand [p_hi | p_lo | p_hi] (VAE mid block: both factors
-//                             of q k^T and of p v are activations, so each product takes three terms hi hi + lo hi + hi lo)
+//   * to_f16_vec8_kernel      the same tensor as ONE fp16 plane, eight channels per thread (precision "fp16")
 //   * attn_split_kernel       the d = 64 flash attention with three MFMAs per product (Kh Qh + Kh Ql + Kl Qh; Vh Ph + Vl Ph + Vh Pl),
 //                             exact running-max softmax in fp32, operand out
+// The normalisations and the row softmax of this precision (gn32_*, ln32_kernel, softmax32_split_kernel) live in norm.hip with the
+// fast ones.
 // None of these is tuned: the parity mode exists to PROVE the arithmetic of the path (tests/modelcheck.py --precision parity), its
 // cost is reported beside the fast mode's (bench.py `parity`).
 #include "common.h"
@@ -94,341 +93,6 @@ __global__ __launch_bounds__(256) void to_f16_vec8_kernel(SplitParams p) {
     v[e] = x * p.scale;
   }
   stg16(p.Y + m * p.ldy + c, pack8h_sat(v));
-}
-
-// ------------------------------------------------------------------------------------------------
-// GroupNorm (+SiLU), fp32 NHWC in (two sources = channel concat), operand out.  Sums in fp64: no shift trick needed.
-// ------------------------------------------------------------------------------------------------
-constexpr int GN_THREADS = 256;
-constexpr int GN_MAXC = 4096;
-
-__host__ __device__ inline int gn32_nchunk(int B, int HW) {
-  int n = (2048 + B - 1) / B;
-  int cap = (HW + 15) / 16;
-  if (n > cap) n = cap;
-  if (n < 1) n = 1;
-  return n;
-}
-
-struct GN32Params {
-  const float* X1;
-  const float* X2;
-  int C1, C2, B, HW, groups, nchunk;
-  float eps;
-  const u16* gamma;
-  const u16* beta;
-  u16* Y;  // [B*HW, 2 C]
-  int silu;
-  double* ws;  // [B][nchunk][groups][2]
-};
-
-__global__ __launch_bounds__(GN_THREADS) void gn32_stats_kernel(GN32Params p) {
-  extern __shared__ __attribute__((aligned(16))) double smd[];  // [PPB][C][2]
-  const int C = p.C1 + p.C2;
-  const int b = blockIdx.x / p.nchunk, chunk = blockIdx.x % p.nchunk;
-  const int per = (p.HW + p.nchunk - 1) / p.nchunk;
-  const int p0 = chunk * per, p1 = min(p0 + per, p.HW);
-  const int PPB = C >= GN_THREADS ? 1 : GN_THREADS / C;
-  const int tid = threadIdx.x;
-  for (int slot = tid; slot < C * PPB; slot += GN_THREADS) {
-    const int c = slot % C, prow = slot / C;
-    const float* src;
-    int ld;
-    if (c < p.C1) {
-      src = p.X1 + (int64_t)b * p.HW * p.C1 + c;
-      ld = p.C1;
-    } else {
-      src = p.X2 + (int64_t)b * p.HW * p.C2 + (c - p.C1);
-      ld = p.C2;
-    }
-    double s = 0.0, q = 0.0;
-    for (int px = p0 + prow; px < p1; px += PPB) {
-      const double v = (double)src[(int64_t)px * ld];
-      s += v;
-      q += v * v;
-    }
-    smd[(prow * C + c) * 2 + 0] = s;
-    smd[(prow * C + c) * 2 + 1] = q;
-  }
-  __syncthreads();
-  const int gs = C / p.groups;
-  for (int g = tid; g < p.groups; g += GN_THREADS) {
-    double s = 0.0, q = 0.0;
-    for (int r = 0; r < PPB; ++r)
-      for (int c = g * gs; c < (g + 1) * gs; ++c) {
-        s += smd[(r * C + c) * 2 + 0];
-        q += smd[(r * C + c) * 2 + 1];
-      }
-    double* w = p.ws + (((int64_t)b * p.nchunk + chunk) * p.groups + g) * 2;
-    w[0] = s;
-    w[1] = q;
-  }
-}
-
-// H16 (precision "fp16"): gamma / beta are fp16 and the result is ONE fp16 plane, Y [B*HW, C].
-template <bool H16>
-__global__ __launch_bounds__(GN_THREADS) void gn32_apply_kernel(GN32Params p) {
-  extern __shared__ __attribute__((aligned(16))) float smf[];  // mean[groups], rstd[groups]
-  const int C = p.C1 + p.C2;
-  float* mean = smf;
-  float* rstd = smf + p.groups;
-  const int b = blockIdx.x / p.nchunk, chunk = blockIdx.x % p.nchunk;
-  const int per = (p.HW + p.nchunk - 1) / p.nchunk;
-  const int p0 = chunk * per, p1 = min(p0 + per, p.HW);
-  const int tid = threadIdx.x;
-  const int gs = C / p.groups;
-  for (int g = tid; g < p.groups; g += GN_THREADS) {
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < p.nchunk; ++k) {
-      const double* w = p.ws + (((int64_t)b * p.nchunk + k) * p.groups + g) * 2;
-      s += w[0];
-      q += w[1];
-    }
-    const double n = (double)gs * (double)p.HW;
-    const double mu = s / n;
-    double var = q / n - mu * mu;
-    var = var < 0.0 ? 0.0 : var;
-    mean[g] = (float)mu;
-    rstd[g] = (float)(1.0 / sqrt(var + (double)p.eps));
-  }
-  __syncthreads();
-  const int PPB = C >= GN_THREADS ? 1 : GN_THREADS / C;
-  for (int slot = tid; slot < C * PPB; slot += GN_THREADS) {
-    const int c = slot % C, prow = slot / C;
-    const int g = c / gs;
-    const float mu = mean[g], a = rstd[g] * (H16 ? h2f(p.gamma[c]) : bf2f(p.gamma[c])), bt = H16 ? h2f(p.beta[c]) : bf2f(p.beta[c]);
-    const float* src;
-    int ld;
-    if (c < p.C1) {
-      src = p.X1 + (int64_t)b * p.HW * p.C1 + c;
-      ld = p.C1;
-    } else {
-      src = p.X2 + (int64_t)b * p.HW * p.C2 + (c - p.C1);
-      ld = p.C2;
-    }
-    constexpr int PL = H16 ? 1 : 2;
-    u16* dst = p.Y + (int64_t)b * p.HW * (PL * C) + c;
-    for (int px = p0 + prow; px < p1; px += PPB) {
-      float y = (src[(int64_t)px * ld] - mu) * a + bt;
-      if (p.silu) y = silu_f(y);
-      if constexpr (H16) {
-        dst[(int64_t)px * C] = f2h_sat(y);
-      } else {
-        u16 hi, lo;
-        split2(y, hi, lo);
-        dst[(int64_t)px * (2 * C)] = hi;
-        dst[(int64_t)px * (2 * C) + C] = lo;
-      }
-    }
-  }
-}
-
-// The same two passes with FOUR channels per thread (16-byte loads, 8-byte stores of each plane): what every layer of the UNet and the VAE
-// runs (C1, C2 multiples of 4).  With one channel per thread a C = 320 layer kept a quarter of the block idle in its second sweep and moved
-// 2 bytes per store instruction: 1.15 TB/s over a step (round 4 bench); the sums are still fp64, so the statistics differ from the
-// one-channel form by fp64 rounding only.
-__global__ __launch_bounds__(GN_THREADS) void gn32_stats4_kernel(GN32Params p) {
-  extern __shared__ __attribute__((aligned(16))) double smd[];  // [PPB][C][2]
-  const int C = p.C1 + p.C2, Q = C / 4;
-  const int b = blockIdx.x / p.nchunk, chunk = blockIdx.x % p.nchunk;
-  const int per = (p.HW + p.nchunk - 1) / p.nchunk;
-  const int p0 = chunk * per, p1 = min(p0 + per, p.HW);
-  const int PPB = Q >= GN_THREADS ? 1 : GN_THREADS / Q;
-  const int tid = threadIdx.x;
-  for (int slot = tid; slot < Q * PPB; slot += GN_THREADS) {
-    const int c = (slot % Q) * 4, prow = slot / Q;
-    const float* src;
-    int ld;
-    if (c < p.C1) {
-      src = p.X1 + (int64_t)b * p.HW * p.C1 + c;
-      ld = p.C1;
-    } else {
-      src = p.X2 + (int64_t)b * p.HW * p.C2 + (c - p.C1);
-      ld = p.C2;
-    }
-    double s[4] = {0.0, 0.0, 0.0, 0.0}, q[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int px = p0 + prow; px < p1; px += PPB) {
-      const f32x4_t v = *reinterpret_cast<const f32x4_t*>(src + (int64_t)px * ld);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const double d = (double)v[e];
-        s[e] += d;
-        q[e] += d * d;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      smd[(prow * C + c + e) * 2 + 0] = s[e];
-      smd[(prow * C + c + e) * 2 + 1] = q[e];
-    }
-  }
-  __syncthreads();
-  const int gs = C / p.groups;
-  for (int g = tid; g < p.groups; g += GN_THREADS) {
-    double s = 0.0, q = 0.0;
-    for (int r = 0; r < PPB; ++r)
-      for (int c = g * gs; c < (g + 1) * gs; ++c) {
-        s += smd[(r * C + c) * 2 + 0];
-        q += smd[(r * C + c) * 2 + 1];
-      }
-    double* w = p.ws + (((int64_t)b * p.nchunk + chunk) * p.groups + g) * 2;
-    w[0] = s;
-    w[1] = q;
-  }
-}
-
-template <bool H16>
-__global__ __launch_bounds__(GN_THREADS) void gn32_apply4_kernel(GN32Params p) {
-  extern __shared__ __attribute__((aligned(16))) float smf[];  // mean[groups], rstd[groups]
-  const int C = p.C1 + p.C2, Q = C / 4;
-  float* mean = smf;
-  float* rstd = smf + p.groups;
-  const int b = blockIdx.x / p.nchunk, chunk = blockIdx.x % p.nchunk;
-  const int per = (p.HW + p.nchunk - 1) / p.nchunk;
-  const int p0 = chunk * per, p1 = min(p0 + per, p.HW);
-  const int tid = threadIdx.x;
-  const int gs = C / p.groups;
-  for (int g = tid; g < p.groups; g += GN_THREADS) {
-    double s = 0.0, q = 0.0;
-    for (int k = 0; k < p.nchunk; ++k) {
-      const double* w = p.ws + (((int64_t)b * p.nchunk + k) * p.groups + g) * 2;
-      s += w[0];
-      q += w[1];
-    }
-    const double n = (double)gs * (double)p.HW;
-    const double mu = s / n;
-    double var = q / n - mu * mu;
-    var = var < 0.0 ? 0.0 : var;
-    mean[g] = (float)mu;
-    rstd[g] = (float)(1.0 / sqrt(var + (double)p.eps));
-  }
-  __syncthreads();
-  const int PPB = Q >= GN_THREADS ? 1 : GN_THREADS / Q;
-  for (int slot = tid; slot < Q * PPB; slot += GN_THREADS) {
-    const int c = (slot % Q) * 4, prow = slot / Q;
-    float mu[4], a[4], bt[4];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int g = (c + e) / gs;
-      mu[e] = mean[g];
-      a[e] = rstd[g] * (H16 ? h2f(p.gamma[c + e]) : bf2f(p.gamma[c + e]));
-      bt[e] = H16 ? h2f(p.beta[c + e]) : bf2f(p.beta[c + e]);
-    }
-    const float* src;
-    int ld;
-    if (c < p.C1) {
-      src = p.X1 + (int64_t)b * p.HW * p.C1 + c;
-      ld = p.C1;
-    } else {
-      src = p.X2 + (int64_t)b * p.HW * p.C2 + (c - p.C1);
-      ld = p.C2;
-    }
-    constexpr int PL = H16 ? 1 : 2;
-    u16* dst = p.Y + (int64_t)b * p.HW * (PL * C) + c;
-    for (int px = p0 + prow; px < p1; px += PPB) {
-      const f32x4_t v = *reinterpret_cast<const f32x4_t*>(src + (int64_t)px * ld);
-      if constexpr (H16) {
-        float y[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          y[e] = (v[e] - mu[e]) * a[e] + bt[e];
-          if (p.silu) y[e] = silu_f(y[e]);
-        }
-        uint2 ph;
-        ph.x = pack_h2(sat_h(y[0]), sat_h(y[1])), ph.y = pack_h2(sat_h(y[2]), sat_h(y[3]));
-        *reinterpret_cast<uint2*>(dst + (int64_t)px * C) = ph;
-        continue;
-      }
-      u16 hi[4], lo[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float y = (v[e] - mu[e]) * a[e] + bt[e];
-        if (p.silu) y = silu_f(y);
-        split2(y, hi[e], lo[e]);
-      }
-      uint2 ph, pl;
-      ph.x = (uint32_t)hi[0] | ((uint32_t)hi[1] << 16), ph.y = (uint32_t)hi[2] | ((uint32_t)hi[3] << 16);
-      pl.x = (uint32_t)lo[0] | ((uint32_t)lo[1] << 16), pl.y = (uint32_t)lo[2] | ((uint32_t)lo[3] << 16);
-      *reinterpret_cast<uint2*>(dst + (int64_t)px * (2 * C)) = ph;
-      *reinterpret_cast<uint2*>(dst + (int64_t)px * (2 * C) + C) = pl;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// LayerNorm, fp32 in, operand out: one wave per row, two-pass statistics in fp32
-// ------------------------------------------------------------------------------------------------
-template <bool H16>
-__global__ __launch_bounds__(256) void ln32_kernel(const float* X, int64_t ldx, const u16* gamma, const u16* beta, u16* Y, int64_t ldy,
-                                                   int M, int C, float eps) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= M) return;
-  const float* x = X + (int64_t)row * ldx;
-  float s = 0.f;
-  for (int c = lane; c < C; c += 64) s += x[c];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  const float mu = s / (float)C;
-  float q = 0.f;
-  for (int c = lane; c < C; c += 64) {
-    const float d = x[c] - mu;
-    q += d * d;
-  }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
-  const float rs = rsqrtf(q / (float)C + eps);
-  u16* y = Y + (int64_t)row * ldy;
-  for (int c = lane; c < C; c += 64) {
-    if constexpr (H16) {
-      y[c] = f2h_sat((x[c] - mu) * rs * h2f(gamma[c]) + h2f(beta[c]));
-    } else {
-      const float v = (x[c] - mu) * rs * bf2f(gamma[c]) + bf2f(beta[c]);
-      u16 hi, lo;
-      split2(v, hi, lo);
-      y[c] = hi;
-      y[C + c] = lo;
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// P = softmax(S * scale) per row of fp32 logits -> [p_hi | p_lo | p_hi], each plane Np wide (columns N..Np-1 zero)
-// ------------------------------------------------------------------------------------------------
-template <bool H16>
-__global__ __launch_bounds__(256) void softmax32_split_kernel(const float* S, int64_t lds, u16* P, int64_t ldp, int M, int N, int Np,
-                                                              float scale) {
-  __shared__ float red[4];
-  const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const float* s = S + (int64_t)row * lds;
-  float mx = -3.0e38f;
-  for (int c = tid; c < N; c += 256) mx = fmaxf(mx, s[c]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
-  if (lane == 0) red[wave] = mx;
-  __syncthreads();
-  mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-  __syncthreads();
-  float sum = 0.f;
-  for (int c = tid; c < N; c += 256) sum += expf((s[c] - mx) * scale);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off);
-  if (lane == 0) red[wave] = sum;
-  __syncthreads();
-  sum = (red[0] + red[1]) + (red[2] + red[3]);
-  const float inv = 1.0f / sum;
-  u16* y = P + (int64_t)row * ldp;
-  for (int c = tid; c < Np; c += 256) {
-    if constexpr (H16) {  // one fp16 plane [M, Np]
-      y[c] = c < N ? f2h(expf((s[c] - mx) * scale) * inv) : (u16)0;
-    } else {
-      u16 hi = 0, lo = 0;
-      if (c < N) split2(expf((s[c] - mx) * scale) * inv, hi, lo);
-      y[c] = hi;
-      y[Np + c] = lo;
-      y[2 * Np + c] = hi;
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -680,85 +344,6 @@ extern "C" int dm4d_to_f16_f32(void* stream, const float* X1, int64_t row_stride
   }
   hipLaunchKernelGGL(split_kernel, grid1d(M * Cp, 256), dim3(256), 0, (hipStream_t)stream, p);
   return dm4d_check_launch("split_kernel");
-}
-
-extern "C" size_t dm4d_groupnorm_f32_ws_bytes(int B, int HW, int groups) {
-  return (size_t)B * gn32_nchunk(B, HW) * groups * 2 * sizeof(double);
-}
-
-template <bool H16>
-static int groupnorm_f32_impl(void* stream, const float* X1, int C1, const float* X2, int C2, int B, int HW, int groups, float eps,
-                              const void* gamma, const void* beta, void* Y, int apply_silu, void* ws) {
-  if (!X1 || !gamma || !beta || !Y || !ws || B <= 0 || HW <= 0 || groups <= 0 || C1 <= 0 || C2 < 0 || (C2 > 0 && !X2))
-    return dm4d_set_error(DM4D_ERR_ARG, "groupnorm_f32: bad arguments");
-  const int C = C1 + C2;
-  if (C % groups != 0 || C > GN_MAXC) return dm4d_set_error(DM4D_ERR_ARG, "groupnorm_f32: channels must divide into groups and be <= 4096");
-  GN32Params p{X1, X2, C1, C2, B, HW, groups, gn32_nchunk(B, HW), eps, (const u16*)gamma, (const u16*)beta, (u16*)Y, apply_silu,
-               (double*)ws};
-  const bool vec4 = C1 % 4 == 0 && C2 % 4 == 0 && ((uintptr_t)X1 & 15) == 0 && (C2 == 0 || ((uintptr_t)X2 & 15) == 0) && ((uintptr_t)Y & 7) == 0;
-  if (vec4) {
-    const int Q = C / 4, PPB = Q >= GN_THREADS ? 1 : GN_THREADS / Q;
-    const size_t sm1 = (size_t)PPB * C * 2 * sizeof(double);
-    if (sm1 <= 64 * 1024) {
-      hipLaunchKernelGGL(gn32_stats4_kernel, dim3(B * p.nchunk), dim3(GN_THREADS), sm1, (hipStream_t)stream, p);
-      int rc = dm4d_check_launch("gn32_stats4_kernel");
-      if (rc) return rc;
-      hipLaunchKernelGGL((gn32_apply4_kernel<H16>), dim3(B * p.nchunk), dim3(GN_THREADS), 2 * groups * sizeof(float), (hipStream_t)stream, p);
-      return dm4d_check_launch("gn32_apply4_kernel");
-    }
-  }
-  const int PPB = C >= GN_THREADS ? 1 : GN_THREADS / C;
-  const size_t sm1 = (size_t)PPB * C * 2 * sizeof(double);
-  hipLaunchKernelGGL(gn32_stats_kernel, dim3(B * p.nchunk), dim3(GN_THREADS), sm1, (hipStream_t)stream, p);
-  int rc = dm4d_check_launch("gn32_stats_kernel");
-  if (rc) return rc;
-  hipLaunchKernelGGL((gn32_apply_kernel<H16>), dim3(B * p.nchunk), dim3(GN_THREADS), 2 * groups * sizeof(float), (hipStream_t)stream, p);
-  return dm4d_check_launch("gn32_apply_kernel");
-}
-
-extern "C" int dm4d_groupnorm_nhwc_f32_split(void* stream, const float* X1, int C1, const float* X2, int C2, int B, int HW,
-                                             int groups, float eps, const void* gamma, const void* beta, void* Y, int apply_silu,
-                                             void* ws) {
-  return groupnorm_f32_impl<false>(stream, X1, C1, X2, C2, B, HW, groups, eps, gamma, beta, Y, apply_silu, ws);
-}
-
-extern "C" int dm4d_groupnorm_f32_f16_general(void* stream, const float* X1, int C1, const float* X2, int C2, int B, int HW, int groups,
-                                           float eps, const void* gamma, const void* beta, void* Y, int apply_silu, void* ws) {
-  return groupnorm_f32_impl<true>(stream, X1, C1, X2, C2, B, HW, groups, eps, gamma, beta, Y, apply_silu, ws);
-}
-
-extern "C" int dm4d_layernorm_f32_split(void* stream, const float* X, int64_t ldx, const void* gamma, const void* beta, void* Y,
-                                        int64_t ldy, int M, int C, float eps) {
-  if (!X || !gamma || !beta || !Y || M <= 0 || C <= 0 || ldx < C || ldy < 2 * (int64_t)C)
-    return dm4d_set_error(DM4D_ERR_ARG, "layernorm_f32: bad arguments");
-  hipLaunchKernelGGL(ln32_kernel<false>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, X, ldx, (const u16*)gamma, (const u16*)beta,
-                     (u16*)Y, ldy, M, C, eps);
-  return dm4d_check_launch("ln32_kernel");
-}
-
-extern "C" int dm4d_layernorm_f32_f16_general(void* stream, const float* X, int64_t ldx, const void* gamma, const void* beta, void* Y,
-                                      int64_t ldy, int M, int C, float eps) {
-  if (!X || !gamma || !beta || !Y || M <= 0 || C <= 0 || ldx < C || ldy < (int64_t)C)
-    return dm4d_set_error(DM4D_ERR_ARG, "layernorm_f32_f16: bad arguments");
-  hipLaunchKernelGGL(ln32_kernel<true>, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream, X, ldx, (const u16*)gamma, (const u16*)beta,
-                     (u16*)Y, ldy, M, C, eps);
-  return dm4d_check_launch("ln32_kernel");
-}
-
-extern "C" int dm4d_softmax_rows_f32_f16(void* stream, const float* S, int64_t lds, void* P, int64_t ldp, int M, int N, int Np,
-                                         float scale) {
-  if (!S || !P || M <= 0 || N <= 0 || Np < N || lds < N || ldp < (int64_t)Np)
-    return dm4d_set_error(DM4D_ERR_ARG, "softmax_rows_f32_f16: bad arguments");
-  hipLaunchKernelGGL(softmax32_split_kernel<true>, dim3(M), dim3(256), 0, (hipStream_t)stream, S, lds, (u16*)P, ldp, M, N, Np, scale);
-  return dm4d_check_launch("softmax32_split_kernel");
-}
-
-extern "C" int dm4d_softmax_rows_f32_split(void* stream, const float* S, int64_t lds, void* P, int64_t ldp, int M, int N, int Np,
-                                           float scale) {
-  if (!S || !P || M <= 0 || N <= 0 || Np < N || lds < N || ldp < 3 * (int64_t)Np)
-    return dm4d_set_error(DM4D_ERR_ARG, "softmax_rows_f32_split: bad arguments");
-  hipLaunchKernelGGL(softmax32_split_kernel<false>, dim3(M), dim3(256), 0, (hipStream_t)stream, S, lds, (u16*)P, ldp, M, N, Np, scale);
-  return dm4d_check_launch("softmax32_split_kernel");
 }
 
 extern "C" int dm4d_attention_split_bf16(void* stream, const void* Q, const void* K, const void* V, void* O, int64_t ldq, int64_t ldk,

@@ -1312,7 +1312,10 @@ CASES = {
     "par_gn_vae_128ch_eps6": (case_par_groupnorm, dict(B=2, HW=4096, C1=128, eps=1e-6)),
     "par_gn_mean_200sigma": (case_par_groupnorm, dict(B=2, HW=512, C1=64, groups=8, silu=False, mean_shift=400.0)),
     "par_gn_nosilu_small": (case_par_groupnorm, dict(B=1, HW=45, C1=1280, silu=False, eps=1e-6)),
+    "par_gn_odd_channels": (case_par_groupnorm, dict(B=2, HW=77, C1=66, groups=6)),  # channel counts off the 4-wide path: one channel per thread
+    "par_gn_odd_two_sources": (case_par_groupnorm, dict(B=2, HW=77, C1=66, C2=30, groups=6, silu=False)),
     "par_ln": (case_par_layernorm, dict(M=1000, C=320)),
+    "par_ln_odd": (case_par_layernorm, dict(M=37, C=100)),
     "par_ln_1280": (case_par_layernorm, dict(M=333, C=1280)),
     "par_softmax": (case_par_softmax, dict(M=96, N=2880, Np=2880)),
     "par_softmax_padded": (case_par_softmax, dict(M=33, N=1353, Np=1376)),
@@ -1384,6 +1387,7 @@ CASES = {
     "h16_ln_1280": (case_h16_layernorm, dict(M=333, C=1280)),
     "h16_ln_320_tall_odd_rows": (case_h16_layernorm, dict(M=9001, C=320, seed=3)),
     "h16_ln_640_tall": (case_h16_layernorm, dict(M=8200, C=640, seed=4)),
+    "h16_ln_odd": (case_h16_layernorm, dict(M=37, C=100)),  # C % 8 != 0: the general kernel (ln32_kernel, one fp16 plane)
     "h16_softmax": (case_h16_softmax, dict(M=96, N=2880, Np=2880)),
     "h16_softmax_padded": (case_h16_softmax, dict(M=33, N=1353, Np=1376)),
     "h16_attn_small": (case_h16_attention, dict(batch=2, heads=2, L=128)),

@@ -131,6 +131,10 @@ SIGNATURES = {
     "dm4d_pose_input_u8_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i, _i]),
     "dm4d_pose_mask_box_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp]),
     "dm4d_pose_udp_decode_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    # foreground masks around a caller-named matting network: rotate + bilinear resize + normalise, and logits -> bytes + bicubic
+    # resize + rotate back (host/matting.py)
+    "dm4d_matting_input_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i]),
+    "dm4d_matting_mask_f16_u8": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _i, _i]),
 }
 
 # The constants of include/dm4d.h that the host uses, under the header's names without the DM4D_ prefix.  This block is their ONLY
@@ -169,6 +173,8 @@ POSE_MAX_SIDE = 16384
 POSE_MAX_HEATMAP_H = 4096
 POSE_MAX_HEATMAP_W = 1024
 POSE_TAB_LIMIT = 1 << 29
+MATTING_FIELDS = 8
+MATTING_MAX_SIDE = 16384
 
 
 class Dm4dError(RuntimeError):

@@ -1,0 +1,338 @@
+"""Foreground-mask prediction around a caller-named matting network: the ``remove_background`` action of the reference's preprocess.sh
+(scripts/preprocess/remove_background.py), which writes ``fmasks/{camera}/{frame}.png``, the files that ``host/vhull.py``,
+``host/pose.py`` (``bbox_source="fmask"``), ``host/capture.py`` (``SpaTemDataset``) and ``host/metrics.py`` (``evaluate_results``) read.
+
+The network (BiRefNet / RMBG-2.0 in the reference) is not part of this package and is never downloaded: the caller names a local
+directory (``load_matting_model``) or hands over any callable (``matting_model``).  Everything around it runs on the device
+(csrc/matting.hip):
+
+  * ``matting_inputs``: images are decoded with Pillow in a thread pool into pinned staging and uploaded once as bytes; at most two
+    launches rotate them (an index map), resize them with Pillow's antialiased bilinear filter to the network's size and normalise them
+    through a 3 x 256 table that torch CPU itself fills with the reference's arithmetic;
+  * ``matting_masks``: the logits, which never visit the host, become bytes through the 65536-entry table of ``quantiser_table`` (the
+    reference's ``.sigmoid()`` + ``to_pil_image`` in fp16, DESIGN.md "Foreground masks"), are resized with Pillow's bicubic filter to
+    each image's size and turned back; one packed blob of mask planes comes back in one copy.
+
+Both are byte-exact to the reference's Pillow + torch CPU route.  There is no CPU path: a ``device`` that is not a HIP device is an
+error.
+"""
+from __future__ import annotations
+
+import os
+import threading
+from concurrent.futures import ThreadPoolExecutor
+from glob import glob
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+from PIL import Image
+
+from . import lib as _l
+from . import ops
+from .pose import _open  # a path, a PIL image or an array -> a PIL image
+from .resample import TableSet
+
+MEAN = (0.485, 0.456, 0.406)   # remove_background.py:20, the ImageNet constants
+STD = (0.229, 0.224, 0.225)
+IMAGE_SIZE = (1024, 1024)      # remove_background.py:15
+MAX_HOST_THREADS = 16
+FIELDS = _l.MATTING_FIELDS
+ROTATIONS = (0, 90, 180, 270)
+
+
+# -- the two tables (host) -------------------------------------------------------------------------------------------------------------
+def normalisation_table(dtype: torch.dtype = torch.float16) -> torch.Tensor:
+    """[3, 256] of `dtype` (fp16 or fp32) on the host: what ``ToTensor`` + ``Normalize(MEAN, STD)`` (+ ``.half()``) make of every byte
+    of every channel, computed by torch CPU with the reference's own operations, so that a lookup is bit-equal to them."""
+    if dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"dtype must be torch.float16 or torch.float32, got {dtype}")
+    rows = [torch.arange(256).float().div(255).sub(m).div(s) for m, s in zip(MEAN, STD)]
+    return torch.stack(rows).to(dtype).contiguous()
+
+
+def quantiser_table() -> np.ndarray:
+    """uint8 [65536]: fp16 bit pattern of a logit -> mask byte, by definition ``s = fp16(1 / (1 + exp(-x)))`` evaluated in fp64 and
+    rounded once, ``m = fp16(fp32(s) * 255)``, byte = trunc(m); NaN -> 0.  The reference's ``.sigmoid()`` then ``to_pil_image``
+    (``.mul(255).byte()``) in fp16, made independent of any device's exp: the device only looks values up."""
+    x = np.arange(65536, dtype=np.uint32).astype(np.uint16).view(np.float16).astype(np.float64)
+    with np.errstate(over="ignore", invalid="ignore"):
+        s = (1.0 / (1.0 + np.exp(-x))).astype(np.float16)
+        m = (s.astype(np.float32) * np.float32(255.0)).astype(np.float16)
+        return np.where(np.isnan(x), 0, np.trunc(m.astype(np.float32))).astype(np.uint8)
+
+
+_tables_lock = threading.Lock()
+_device_tables: Dict[Tuple, torch.Tensor] = {}
+
+
+def _on_device(kind, device: torch.device) -> torch.Tensor:
+    """The normalisation table of a dtype (kind = the dtype) or the quantiser table (kind = "q") on `device`, uploaded once."""
+    key = (kind, device)
+    with _tables_lock:
+        if key not in _device_tables:
+            host = torch.from_numpy(quantiser_table()) if kind == "q" else normalisation_table(kind)
+            _device_tables[key] = host.to(device)
+        return _device_tables[key]
+
+
+# -- staging ---------------------------------------------------------------------------------------------------------------------------
+def _quarter_turns(rotate_clockwise: int) -> int:
+    if rotate_clockwise not in ROTATIONS or isinstance(rotate_clockwise, bool):
+        raise ValueError(f"rotate_clockwise must be one of 0, 90, 180, 270, got {rotate_clockwise!r}")
+    return int(rotate_clockwise) // 90
+
+
+def _run(pool: Optional[ThreadPoolExecutor], fn, xs) -> List:
+    return list(pool.map(fn, xs)) if pool is not None else [fn(x) for x in xs]
+
+
+def _open_all(images, pool: Optional[ThreadPoolExecutor]) -> Tuple[List, List[Tuple[int, int]]]:
+    """Open (not yet decode) and check the images -> (PIL images, sizes [(h, w)]).  Needs no device."""
+    images = list(images)
+    if len(images) < 1:
+        raise ValueError("images: at least one image")
+    ims = _run(pool, _open, images)
+    sizes = [(im.size[1], im.size[0]) for im in ims]
+    for k, (h, w) in enumerate(sizes):
+        if not (1 <= h <= _l.MATTING_MAX_SIDE and 1 <= w <= _l.MATTING_MAX_SIDE):
+            raise ValueError(f"images[{k}]: size {w} x {h} is outside 1..{_l.MATTING_MAX_SIDE}")
+    return ims, sizes
+
+
+def _check_sizes(sizes) -> List[Tuple[int, int]]:
+    sizes = [(int(h), int(w)) for h, w in sizes]
+    for k, (h, w) in enumerate(sizes):
+        if not (1 <= h <= _l.MATTING_MAX_SIDE and 1 <= w <= _l.MATTING_MAX_SIDE):
+            raise ValueError(f"sizes[{k}]: {w} x {h} is outside 1..{_l.MATTING_MAX_SIDE}")
+    return sizes
+
+
+def _plan(sizes: Sequence[Tuple[int, int]], net: Tuple[int, int], rot: int, to_net: bool):
+    """Descriptors and tables of one launch for images of `sizes` = [(h, w)] as stored -> (desc int64 [n, FIELDS] with the plane offsets
+    filled in, tab int32, plane bytes, scratch bytes).  to_net: images -> the network's size `net` = (S_h, S_w), bilinear, planes of 3
+    bytes per pixel, scratch rh x S_w words; else: `net` -> the images' sizes, bicubic, planes of 1 byte, scratch S_h x rw bytes."""
+    S_h, S_w = net
+    ts = TableSet()
+    desc = np.zeros((len(sizes), FIELDS), dtype=np.int64)
+    plane_off = scratch_off = 0
+    for k, (h, w) in enumerate(sizes):
+        rh, rw = (w, h) if rot & 1 else (h, w)
+        row = desc[k]
+        row[0], row[1], row[2] = plane_off, h, w
+        plane_off = _l.align16(plane_off + h * w * (3 if to_net else 1))
+        pairs = ((rw, S_w), (rh, S_h)) if to_net else ((S_w, rw), (S_h, rh))
+        for field, (n_in, n_out) in zip((3, 5), pairs):
+            row[field], row[field + 1] = (-1, 0) if n_in == n_out else ts.add(n_in, n_out, "bilinear" if to_net else "bicubic")
+        if row[3] >= 0:
+            row[7] = scratch_off
+            scratch_off = _l.align16(scratch_off + (rh * S_w * 4 if to_net else S_h * rw))
+    tab = ts.array() if ts.tables else np.zeros(1, dtype=np.int32)  # the library wants a table even where no axis changes its size
+    return desc, tab, plane_off, max(scratch_off, 16)
+
+
+def _meta(desc: np.ndarray, tab: np.ndarray, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """{tab | desc} in one pinned buffer and its copy on the device -> (meta, meta_host, desc_off); the tables start at byte 0."""
+    desc_off = _l.align16(tab.nbytes)
+    host = torch.zeros(desc_off + desc.nbytes, dtype=torch.uint8, pin_memory=True)
+    view = host.numpy()
+    view[:tab.nbytes] = tab.view(np.uint8)
+    view[desc_off:] = desc.reshape(-1).view(np.uint8)
+    return host.to(device, non_blocking=True), host, desc_off
+
+
+def _inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: int, dtype: torch.dtype, pool: Optional[ThreadPoolExecutor]) -> torch.Tensor:
+    S_h, S_w = int(size[0]), int(size[1])
+    if not (1 <= S_h <= _l.MATTING_MAX_SIDE and 1 <= S_w <= _l.MATTING_MAX_SIDE):
+        raise ValueError(f"size {S_h} x {S_w} is outside 1..{_l.MATTING_MAX_SIDE}")
+    desc, tab, plane_bytes, scratch_bytes = _plan(sizes, (S_h, S_w), rot, True)
+    host = torch.empty(plane_bytes, dtype=torch.uint8, pin_memory=True)
+    view = host.numpy()
+
+    def decode(k):
+        h, w = sizes[k]
+        o = int(desc[k, 0])
+        np.copyto(view[o: o + h * w * 3].reshape(h, w, 3), np.asarray(ims[k].convert("RGB")))
+    _run(pool, decode, range(len(ims)))
+    blob = host.to(dev, non_blocking=True)
+    meta, meta_host, desc_off = _meta(desc, tab, dev)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+    out = ops.matting_input(blob, meta, meta_host, len(ims), desc_off, 0, tab.size, _on_device(dtype, dev), scratch, S_h, S_w, rot)
+    torch.cuda.current_stream().synchronize()  # the pinned buffers may go; the tensor is complete when it is handed over
+    return out
+
+
+def matting_inputs(images, size: Tuple[int, int] = IMAGE_SIZE, device="cuda", *, rotate_clockwise: int = 0, dtype: torch.dtype = torch.float16,
+                   pool: Optional[ThreadPoolExecutor] = None) -> torch.Tensor:
+    """The matting network's input for a batch of images -> `dtype` (fp16 or fp32) [n, 3, S_h, S_w] on `device`, bit-equal to the
+    reference's ``transform_image(image.rotate(-rotate_clockwise, expand=True))`` (+ ``.half()`` for fp16).
+
+    images: paths, PIL images or uint8 [h, w, 3] arrays, of any sizes from 1 to MATTING_MAX_SIDE (anything else is converted to RGB).
+    size: the network's input (S_h, S_w); the aspect ratio is not kept, as in the reference.  rotate_clockwise: 0, 90, 180 or 270."""
+    rot = _quarter_turns(rotate_clockwise)
+    if dtype not in (torch.float16, torch.float32):
+        raise ValueError(f"dtype must be torch.float16 or torch.float32, got {dtype}")
+    ims, sizes = _open_all(images, pool)
+    dev = _l.hip_device(device, "matting_inputs")
+    with torch.cuda.device(dev):
+        return _inputs(ims, sizes, size, dev, rot, dtype, pool)
+
+
+def matting_masks(logits: torch.Tensor, sizes: Sequence[Tuple[int, int]], *, rotate_clockwise: int = 0) -> List[np.ndarray]:
+    """The network's logits [n, 1, S_h, S_w] on the device (fp16; bf16 and fp32 are converted to fp16 there first), sizes = the images'
+    [(h, w)] -> a list of uint8 [h, w] arrays, byte-equal to the reference's ``to_pil_image(logits.sigmoid()).resize((w', h'))``
+    turned back by `rotate_clockwise` (w', h': the rotated image's size).  The planes are packed 16-byte aligned in one device blob and
+    copied back once; the arrays are views of that one host buffer."""
+    rot = _quarter_turns(rotate_clockwise)
+    if not isinstance(logits, torch.Tensor) or logits.device.type != "cuda":
+        raise _l.Dm4dError("logits: expected a tensor on a HIP device (no CPU fallback in diffuman4d_amd)")
+    if logits.dim() != 4 or logits.shape[1] != 1 or logits.numel() == 0:
+        raise ValueError(f"logits: expected [n, 1, S_h, S_w], got {tuple(logits.shape)}")
+    if logits.dtype not in (torch.float16, torch.bfloat16, torch.float32):
+        raise ValueError(f"logits: expected fp16, bf16 or fp32, got {logits.dtype}")
+    sizes = _check_sizes(sizes)
+    n, _, S_h, S_w = logits.shape
+    if len(sizes) != n:
+        raise ValueError(f"sizes: expected one (h, w) per logit plane ({n}), got {len(sizes)}")
+    if not (S_h <= _l.MATTING_MAX_SIDE and S_w <= _l.MATTING_MAX_SIDE):
+        raise ValueError(f"logits: {S_h} x {S_w} is outside 1..{_l.MATTING_MAX_SIDE}")
+    dev = logits.device
+    with torch.cuda.device(dev):
+        desc, tab, blob_bytes, scratch_bytes = _plan(sizes, (S_h, S_w), rot, False)
+        meta, meta_host, desc_off = _meta(desc, tab, dev)
+        scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
+        blob = ops.matting_mask(logits.to(torch.float16).contiguous(), meta, meta_host, n, desc_off, 0, tab.size, _on_device("q", dev), scratch,
+                                blob_bytes, rot)
+        host = blob.cpu().numpy()  # synchronises: meta_host may go
+    return [host[int(desc[k, 0]): int(desc[k, 0]) + h * w].reshape(h, w) for k, (h, w) in enumerate(sizes)]
+
+
+# -- the stage -------------------------------------------------------------------------------------------------------------------------
+def load_matting_model(model_name: str, device) -> Callable:
+    """The caller's matting network from a local directory in the Hugging Face layout (a downloaded ``ZhengPeng7/BiRefNet`` or
+    ``briaai/RMBG-2.0``), as the reference loads it (remove_background.py:25-33) but strictly offline:
+    ``AutoModelForImageSegmentation.from_pretrained(dir, trust_remote_code=True, local_files_only=True)``, then ``.eval().half()``.
+    A `model_name` that is not an existing directory (a hub name, for instance) raises FileNotFoundError before ``transformers`` is
+    even imported: nothing is ever downloaded.
+
+    This path has not been run: no checkpoint is at hand, and the tests go through ``matting_model``."""
+    if not isinstance(model_name, (str, os.PathLike)) or not os.path.isdir(model_name):
+        raise FileNotFoundError(f"matting network {model_name!r} is not a local directory (it is never downloaded: name a directory that "
+                                "holds the checkpoint)")
+    from transformers import AutoModelForImageSegmentation
+    model = AutoModelForImageSegmentation.from_pretrained(os.fspath(model_name), trust_remote_code=True, local_files_only=True)
+    return model.to(device).eval().half()
+
+
+def list_inputs(images_dir: str, out_fmasks_dir: str, out_images_alpha_dir: Optional[str] = None, image_ext: str = ".webp",
+                mask_ext: str = ".png") -> Tuple[List[str], List[str], List[Optional[str]]]:
+    """``**/*{image_ext}`` under images_dir, sorted, and each one's mask and RGBA path: the image path with `image_ext` replaced by
+    `mask_ext` (``.png`` for the RGBA image) and `images_dir` by the output directory, in that order (remove_background.py:124-131)."""
+    images = sorted(glob(f"{images_dir}/**/*{image_ext}", recursive=True))
+    fmasks = [p.replace(image_ext, mask_ext).replace(images_dir, out_fmasks_dir) for p in images]
+    if out_images_alpha_dir is not None:
+        alphas: List[Optional[str]] = [p.replace(image_ext, ".png").replace(images_dir, out_images_alpha_dir) for p in images]
+    else:
+        alphas = [None] * len(images)
+    return images, fmasks, alphas
+
+
+def _verifies(path: str) -> bool:
+    try:
+        with Image.open(path) as im:
+            im.verify()
+        return True
+    except Exception:
+        return False
+
+
+def pending_batches(fmask_paths: Sequence[str], batch_size: int, skip_exists: bool) -> Tuple[List[List[int]], int]:
+    """The batches of indices that have to be predicted, in order, and the number of images skipped.  The reference's rule
+    (remove_background.py:56-70): batches are cut before anything is skipped, and with `skip_exists` a batch is skipped only if every
+    mask of it exists and ``Image.open(...).verify()`` accepts it; one missing or damaged mask reruns its whole batch."""
+    batches = [list(range(i, min(i + batch_size, len(fmask_paths)))) for i in range(0, len(fmask_paths), batch_size)]
+    if not skip_exists:
+        return batches, 0
+    todo = [b for b in batches if not all(os.path.exists(fmask_paths[k]) and _verifies(fmask_paths[k]) for k in b)]
+    return todo, len(fmask_paths) - sum(len(b) for b in todo)
+
+
+def _save(image: Image.Image, path: str) -> None:
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    root, ext = os.path.splitext(path)
+    tmp = f"{root}.tmp{threading.get_ident()}{ext}"  # keeps the extension: Pillow picks the format by it
+    image.save(tmp)
+    os.replace(tmp, path)  # a reader (or skip_exists) never sees half a file
+
+
+def write_mask(mask: np.ndarray, fmask_path: str, image_src=None, image_alpha_path: Optional[str] = None) -> None:
+    """``Image.fromarray(mask).save(fmask_path)`` and, with `image_alpha_path`, the image (in its stored orientation) with the mask as
+    its alpha channel (``putalpha``, remove_background.py:89-93).  Both appear atomically."""
+    fmask = Image.fromarray(mask)
+    _save(fmask, fmask_path)
+    if image_alpha_path is not None:
+        image = _open(image_src).copy()
+        image.putalpha(fmask)
+        _save(image, image_alpha_path)
+
+
+def remove_background(images_dir: str, out_fmasks_dir: str, out_images_alpha_dir: Optional[str] = None, model_name: Optional[str] = None,
+                      image_ext: str = ".webp", mask_ext: str = ".png", rotate_clockwise: int = 0, batch_size: int = 8, num_workers: int = 4,
+                      skip_exists: bool = False, gpu_ids: Optional[Sequence[int]] = None, *, matting_model: Optional[Callable] = None,
+                      image_size: Tuple[int, int] = IMAGE_SIZE) -> dict:
+    """Predict the foreground mask of every ``**/*{image_ext}`` under `images_dir` and write ``out_fmasks_dir/{camera}/{frame}{mask_ext}``
+    (and the RGBA images under `out_images_alpha_dir`), with the reference's arguments in its names and order.
+
+    matting_model: any callable taking fp16 [n, 3, S_h, S_w] on the device and returning a tensor [n, 1, S_h, S_w] of logits on the
+    device, or a list / tuple of tensors of which the last is taken (BiRefNet's side outputs); by default
+    ``load_matting_model(model_name)``, once per GPU.  It is the caller's network: its output never visits the host.  One worker thread
+    per GPU id; decoding and the PNG files go through a pool of `num_workers` threads.  Returns counts."""
+    rot = _quarter_turns(rotate_clockwise)
+    if matting_model is None:
+        if not model_name:
+            raise ValueError("name the matting network: model_name (a local directory) or matting_model (a callable)")
+        if not os.path.isdir(model_name):
+            load_matting_model(model_name, "cpu")  # raises: a hub name is refused before anything runs
+    if batch_size < 1:
+        raise ValueError("batch_size must be at least 1")
+    size = (int(image_size[0]), int(image_size[1]))
+    images, fmasks, alphas = list_inputs(images_dir, out_fmasks_dir, out_images_alpha_dir, image_ext, mask_ext)
+    batches, skipped = pending_batches(fmasks, batch_size, skip_exists)
+    result = {"images": len(images), "written": 0, "skipped": skipped}
+    if not batches:
+        return result
+    if gpu_ids is None:
+        gpu_ids = list(range(torch.cuda.device_count()))
+    devices = [_l.hip_device(f"cuda:{int(g)}", "remove_background") for g in gpu_ids]
+    if not devices:
+        raise _l.Dm4dError("remove_background: no HIP device is available (no CPU fallback in diffuman4d_amd)")
+    pool = ThreadPoolExecutor(max_workers=max(1, min(int(num_workers), MAX_HOST_THREADS)), thread_name_prefix="dm4d-matting")
+
+    def worker(g: int) -> List:
+        dev = devices[g]
+        writes = []
+        with torch.cuda.device(dev), torch.cuda.stream(torch.cuda.Stream(device=dev)), torch.no_grad():
+            model = matting_model if matting_model is not None else load_matting_model(model_name, dev)
+            for batch in batches[g::len(devices)]:
+                ims, sizes = _open_all([images[k] for k in batch], pool)
+                x = _inputs(ims, sizes, size, dev, rot, torch.float16, pool)
+                out = model(x)
+                if isinstance(out, (list, tuple)) and len(out) > 0:
+                    out = out[-1]
+                if not isinstance(out, torch.Tensor) or out.device.type != "cuda" or tuple(out.shape) != (len(batch), 1) + size:
+                    raise _l.Dm4dError(f"matting_model: expected a [{len(batch)}, 1, {size[0]}, {size[1]}] tensor on the device (or a list "
+                                       "of tensors that ends in one)")
+                masks = matting_masks(out, sizes, rotate_clockwise=rotate_clockwise)
+                for r, k in enumerate(batch):
+                    writes.append(pool.submit(write_mask, masks[r], fmasks[k], images[k], alphas[k]))
+        return writes
+
+    try:
+        with ThreadPoolExecutor(max_workers=len(devices), thread_name_prefix="dm4d-matting-gpu") as gpus:
+            for fut in [gpus.submit(worker, g) for g in range(len(devices))]:
+                for w in fut.result():
+                    w.result()
+                    result["written"] += 1
+    finally:
+        pool.shutdown(wait=True)
+    return result

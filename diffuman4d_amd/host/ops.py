@@ -1182,3 +1182,55 @@ def pose_udp_decode(heatmaps: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]
     scores = torch.empty((n, K), dtype=F32, device=heatmaps.device)
     _l.call("dm4d_pose_udp_decode_f32", _stream(), _p(heatmaps), n, K, Hh, Wh, _p(scores), _p(locs))
     return locs, scores
+
+
+def _matting_meta(meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int) -> None:
+    _req(meta, "meta", torch.uint8)
+    if not meta.is_contiguous() or meta_host.device.type != "cpu" or meta_host.dtype != torch.uint8 or meta_host.numel() != meta.numel() or \
+            not meta_host.is_contiguous():
+        raise _l.Dm4dError("meta / meta_host: expected contiguous uint8 tensors, one the host copy of the other")
+    if n < 1 or desc_off < 0 or desc_off % 8 or desc_off + n * _l.MATTING_FIELDS * 8 > meta.numel():
+        raise _l.Dm4dError("desc_off: the descriptors lie outside meta, or are not aligned")
+    if tab_off < 0 or tab_off % 4 or tab_len < 1 or tab_off + tab_len * 4 > meta.numel():
+        raise _l.Dm4dError("tab_off: the tables lie outside meta, or are not aligned")
+
+
+def matting_input(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int,
+                  lut: torch.Tensor, scratch: torch.Tensor, S_h: int, S_w: int, rot: int) -> torch.Tensor:
+    """The matting network's input for `n` staged images (host/matting.py) -> lut's dtype (fp16 or fp32) [n, 3, S_h, S_w] on blob's
+    device, at most two launches on the current stream.  `blob`: device uint8 holding the RGB planes; `meta`: device uint8 holding
+    int32 coefficient tables at byte `tab_off` and int64 MATTING_FIELDS descriptors at byte `desc_off`, `meta_host` its host copy, on
+    which the library checks every descriptor and table before it launches.  lut: device [3, 256], the normalisation of every byte;
+    scratch: device uint8 for the horizontal pass; rot: quarter turns clockwise."""
+    _req(blob, "blob", torch.uint8), _req(scratch, "scratch", torch.uint8)
+    _matting_meta(meta, meta_host, n, desc_off, tab_off, tab_len)
+    if lut.dtype not in (F16, F32):
+        raise _l.Dm4dError(f"lut: expected fp16 or fp32, got {lut.dtype}")
+    _req(lut, "lut", lut.dtype)
+    if tuple(lut.shape) != (3, 256) or not lut.is_contiguous() or not blob.is_contiguous() or blob.numel() == 0 or scratch.numel() == 0 or \
+            len({blob.device, meta.device, lut.device, scratch.device}) != 1:
+        raise _l.Dm4dError("blob / meta / lut / scratch: expected contiguous non-empty tensors on one device, lut [3, 256]")
+    out = torch.empty((n, 3, S_h, S_w), dtype=lut.dtype, device=blob.device)
+    host, dev = meta_host.data_ptr(), meta.data_ptr()
+    _l.call("dm4d_matting_input_u8", _stream(), _p(blob), blob.numel(), host + desc_off, dev + desc_off, n, host + tab_off, dev + tab_off,
+            tab_len, _p(lut), _p(scratch), scratch.numel(), _p(out), S_h, S_w, rot, int(lut.dtype == F32))
+    return out
+
+
+def matting_mask(logits: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int,
+                 qtab: torch.Tensor, scratch: torch.Tensor, blob_bytes: int, rot: int) -> torch.Tensor:
+    """fp16 logits [n, 1, S_h, S_w] (contiguous) -> the packed uint8 masks of `n` images, `blob_bytes` bytes on the logits' device, at
+    most two launches on the current stream.  meta / meta_host as for matting_input (a descriptor's first field: the mask's 16-byte
+    aligned offset in the result).  qtab: device uint8 [65536], fp16 bit pattern -> byte; scratch: device uint8 for the horizontal pass."""
+    _req(logits, "logits", F16), _req(qtab, "qtab", torch.uint8), _req(scratch, "scratch", torch.uint8)
+    _matting_meta(meta, meta_host, n, desc_off, tab_off, tab_len)
+    if logits.dim() != 4 or logits.shape[0] != n or logits.shape[1] != 1 or not logits.is_contiguous() or logits.numel() == 0:
+        raise _l.Dm4dError(f"logits: expected a contiguous [{n}, 1, S_h, S_w] tensor, got {tuple(logits.shape)}")
+    if qtab.numel() != 65536 or not qtab.is_contiguous() or scratch.numel() == 0 or blob_bytes < 1 or \
+            len({logits.device, meta.device, qtab.device, scratch.device}) != 1:
+        raise _l.Dm4dError("qtab / scratch / meta: expected contiguous tensors on the logits' device, qtab of 65536 bytes")
+    blob = torch.empty(blob_bytes, dtype=torch.uint8, device=logits.device)
+    host, dev = meta_host.data_ptr(), meta.data_ptr()
+    _l.call("dm4d_matting_mask_f16_u8", _stream(), _p(logits), host + desc_off, dev + desc_off, n, host + tab_off, dev + tab_off, tab_len,
+            _p(qtab), _p(scratch), scratch.numel(), _p(blob), blob_bytes, int(logits.shape[2]), int(logits.shape[3]), rot)
+    return blob

@@ -479,6 +479,37 @@ int dm4d_pose_mask_box_u8(void* stream, const void* staging, int64_t staging_byt
                           int32_t* boxes);
 int dm4d_pose_udp_decode_f32(void* stream, const float* heatmaps, int n, int K, int Hh, int Wh, float* scores, float* locs);
 
+/* Foreground-mask prediction around a caller-named matting network (matting.hip, diffuman4d_amd/host/matting.py::remove_background; the
+ *   reference's remove_background stage, scripts/preprocess/remove_background.py:15-22 and :36-93).  The network itself is the caller's;
+ *   these are the steps on either side of it.  Integer arithmetic apart from the table lookups; no atomics, no workgroup waits on
+ *   another; an image's result is a function of its own descriptor, tables and plane: independent of the batch, bitwise repeatable.
+ *
+ * Both entries take n x DM4D_MATTING_FIELDS int64 descriptors = {byte offset of the image's plane | h, w of the image as stored
+ *   (1..DM4D_MATTING_MAX_SIDE) | offset of the horizontal coefficient table in tab (int32 elements), or -1 | its ksize | offset of the
+ *   vertical table, or -1 | its ksize | byte offset of the image's scratch region (16-byte aligned)}.  rot = quarter turns clockwise
+ *   (0..3) of Image.rotate(-90 rot, expand=True), applied as an index map: the rotated image is rh x rw = h x w (rot even) or w x h (odd).
+ *   tab as for dm4d_capture_crop_resize_f32: per table, `out` windows {start, length} then out x ksize weights with 22 fractional bits,
+ *   applied by Pillow's rule (horizontal pass rounded to uint8, then the vertical pass; clip8((2^21 + sum u k) >> 22)).  An axis whose
+ *   size does not change has no table (-1) and is not filtered, as in Pillow; any other axis must have one.  desc_host / tab_host are
+ *   host copies of the bytes at desc_dev / tab_dev: sizes, offsets, windows and regions are validated on them before anything is launched.
+ *
+ * dm4d_matting_input_u8 (transforms.Resize + ToTensor + Normalize + .half()): staging holds uint8 RGB images (HWC, rows tight).  Each is
+ *   rotated, resized rw -> S_w (scratch: rh x S_w packed words r | g << 8 | b << 16) and rh -> S_h, and every byte b of channel c becomes
+ *   lut[c * 256 + b] -> out [n, 3, S_h, S_w] of fp16 (out_f32 = 0) or fp32 (1); lut_dev: 3 x 256 values of that type on the device, made
+ *   by the host with the reference's own arithmetic.  At most two launches.
+ * dm4d_matting_mask_f16_u8 (.sigmoid() + to_pil_image + resize(image.size) + the rotation back): logits [n, S_h, S_w] fp16; a value with
+ *   bit pattern p is the byte qtab_dev[p] (65536 bytes on the device: the kernels contain no exp).  The byte plane is resized S_w -> rw
+ *   (the lookup is part of this pass; scratch: S_h x rw bytes) and S_h -> rh, turned back by the same index map and written as h x w bytes
+ *   (rows tight) at the image's offset in blob, which must be 16-byte aligned.  At most two launches.                                  */
+#define DM4D_MATTING_FIELDS 8
+#define DM4D_MATTING_MAX_SIDE 16384
+int dm4d_matting_input_u8(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
+                          const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len, const void* lut_dev, void* scratch,
+                          int64_t scratch_bytes, void* out, int S_h, int S_w, int rot, int out_f32);
+int dm4d_matting_mask_f16_u8(void* stream, const void* logits, const int64_t* desc_host, const int64_t* desc_dev, int n,
+                             const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len, const void* qtab_dev, void* scratch,
+                             int64_t scratch_bytes, void* blob, int64_t blob_bytes, int S_h, int S_w, int rot);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

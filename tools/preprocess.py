@@ -1,0 +1,116 @@
+#!/usr/bin/env python
+"""Preprocess one captured scene: the five actions of the reference's scripts/preprocess/preprocess.sh, in process, each by this
+package's native stage, with the reference's action names, default order and default sub-directories of ``--data_dir``.
+
+  python tools/preprocess.py --data_dir DATA/SCENE [--actions remove_background,carve_vhull,...] \\
+      --matting_model_dir CKPT/BiRefNet --sapiens_ckpt_path CKPT/sapiens_..._torchscript.pt2 --palette palette.json
+
+  remove_background      images/ -> fmasks/                                   (tools/remove_background.py; needs --matting_model_dir)
+  carve_vhull            fmasks/ + transforms.json -> surfs/, and surfs/000000.ply is copied to sparse_pcd.ply (tools/carve_visual_hull.py)
+  predict_keypoints      images/ + fmasks/ -> poses_sapiens/                  (tools/predict_keypoints.py; needs --sapiens_ckpt_path)
+  triangulate_skeleton   transforms.json + poses_sapiens/ -> poses_3d/, poses_pcd/, poses_2d/      (tools/triangulate_skeleton.py)
+  draw_skeleton          poses_2d/ -> skeletons/                              (tools/draw_skeleton.py; needs --palette)
+
+The two networks and the palette are the caller's files; nothing is downloaded.  An unknown action is an error before anything runs.
+Prints one JSON line per action with the stage's counts.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import shutil
+import sys
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parent.parent))
+
+ALL_ACTIONS = ("remove_background", "carve_vhull", "predict_keypoints", "triangulate_skeleton", "draw_skeleton")  # preprocess.sh:6
+
+
+def _remove_background(*args, **kw):
+    from diffuman4d_amd.host import matting
+    return matting.remove_background(*args, **kw)
+
+
+def _carve_vhull(*args, **kw):
+    from diffuman4d_amd.host import vhull
+    return vhull.carve_scene(*args, **kw)
+
+
+def _predict_keypoints(*args, **kw):
+    from diffuman4d_amd.host import pose
+    return pose.predict_keypoints(*args, **kw)
+
+
+def _triangulate_skeleton(*args, **kw):
+    from diffuman4d_amd.host import triang
+    return triang.triangulate_skeleton(*args, **kw)
+
+
+def _draw_skeleton(*args, **kw):
+    from diffuman4d_amd.host import skeleton
+    return skeleton.draw_skeleton(*args, **kw)
+
+
+# action -> the stage function it calls; every call goes through this dict (a test substitutes recorders)
+STAGES = {"remove_background": _remove_background, "carve_vhull": _carve_vhull, "predict_keypoints": _predict_keypoints,
+          "triangulate_skeleton": _triangulate_skeleton, "draw_skeleton": _draw_skeleton}
+
+
+def parse_actions(text) -> list:
+    """'a,b,c' -> ['a', 'b', 'c'] in the given order; nothing given: all five in the reference's order.  An unknown name: ValueError."""
+    actions = [a.strip() for a in (text or "").split(",") if a.strip()] or list(ALL_ACTIONS)
+    for act in actions:
+        if act not in ALL_ACTIONS:
+            raise ValueError(f"Invalid action: {act} (known: {', '.join(ALL_ACTIONS)})")
+    return actions
+
+
+def run(data_dir: str, actions, *, matting_model_dir=None, sapiens_ckpt_path=None, palette=None, batch_size: int = 8) -> list:
+    """Run `actions` on the scene under `data_dir` (preprocess.sh:31-77) -> [(action, what its stage returned)]."""
+    d = str(data_dir)
+    out = []
+    for act in actions:
+        if act == "remove_background":
+            res = STAGES[act](f"{d}/images", f"{d}/fmasks", model_name=matting_model_dir, batch_size=batch_size)
+        elif act == "carve_vhull":
+            res = STAGES[act](f"{d}/fmasks", f"{d}/transforms.json", f"{d}/surfs")
+            shutil.copyfile(f"{d}/surfs/000000.ply", f"{d}/sparse_pcd.ply")
+        elif act == "predict_keypoints":
+            res = STAGES[act](f"{d}/images", f"{d}/poses_sapiens", f"{d}/fmasks", sapiens_ckpt_path)
+        elif act == "triangulate_skeleton":
+            res = STAGES[act](f"{d}/transforms.json", f"{d}/poses_sapiens", f"{d}/poses_3d", out_pcd_dir=f"{d}/poses_pcd",
+                              out_kp2d_proj_dir=f"{d}/poses_2d")
+        else:
+            res = STAGES[act](f"{d}/poses_2d", f"{d}/skeletons", palette=palette)
+        out.append((act, res))
+    return out
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--data_dir", required=True, help="the scene: images/ and transforms.json, and what the earlier actions wrote")
+    ap.add_argument("--actions", default=None, help=f"comma-separated, run in the given order (default: {','.join(ALL_ACTIONS)})")
+    ap.add_argument("--matting_model_dir", default=None, help="remove_background: the matting network, a local directory")
+    ap.add_argument("--sapiens_ckpt_path", default=None, help="predict_keypoints: the pose checkpoint, a local file")
+    ap.add_argument("--palette", default=None, help="draw_skeleton: JSON file with keypoint_colors, links and x_link_color")
+    ap.add_argument("--batch_size", type=int, default=8, help="remove_background: images per batch (decrease it if memory runs out)")
+    args = ap.parse_args(argv)
+    try:
+        actions = parse_actions(args.actions)
+    except ValueError as e:
+        ap.error(str(e))
+    for act, flag in (("remove_background", "matting_model_dir"), ("predict_keypoints", "sapiens_ckpt_path"), ("draw_skeleton", "palette")):
+        if act in actions and not getattr(args, flag):
+            ap.error(f"{act} needs --{flag}")
+    if not os.path.isdir(args.data_dir):
+        ap.error(f"--data_dir {args.data_dir!r} is not a directory")
+    for act, res in run(args.data_dir, actions, matting_model_dir=args.matting_model_dir, sapiens_ckpt_path=args.sapiens_ckpt_path,
+                        palette=args.palette, batch_size=args.batch_size):
+        print(json.dumps({"action": act, "result": res}, default=str))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -11,6 +11,8 @@ skeleton, ``to_tensor``, ``* 2 - 1`` and the white-background blend -- is split 
 Every task's uint8 planes, tables and frame descriptors go into one pinned staging buffer and up in one copy.  ``pixel_values``
 and ``skeletons`` come back as fp32 NCHW tensors on ``device``; cameras, Pluecker maps and masks stay on the host.
 
+Offsets, the pinned buffer, its filling and the table / descriptor pack are host/staging.py's.
+
 ``skeleton_source="kp2d"`` (opt-in) reads no skeleton image: every frame's map is drawn on the device from its ``poses_2d`` keypoint
 file (host/skeleton.py, ``dm4d_skeleton_draw_u8``) straight into the device staging buffer, and for ``has_gt_target=False`` targets
 ``dm4d_skeleton_box_mask_u8`` derives the box mask and the bounding box there as well; only the boxes (16 bytes per frame) come back.
@@ -32,7 +34,7 @@ from PIL import Image
 
 from . import ops
 from .dataset import plucker_maps, relative_poses
-from .lib import align16
+from .staging import Layout, fill, pack_meta, pinned, write_meta
 from .resample import PRECISION_BITS, TableSet, bicubic_table  # noqa: F401  (tests and tools import the first and the last from here)
 
 log = logging.getLogger(__name__)
@@ -290,16 +292,15 @@ class SpaTemDataset:
         where the skeleton serves as image; shapes = the (h, w) of each frame's planes."""
         H, W = self.height, self.width
         desc = np.zeros((len(frames), FIELDS), dtype=np.int64)
-        scratch = 0
+        scratch = Layout()  # the device scratch of the horizontal pass: one region per frame
         for i, (fr, (oi, om, os_), (sh, sw)) in enumerate(zip(frames, plane_offs, shapes)):
             top, left, ch, cw = fr["crop"][:4]
             htab, hk = tables[(cw, W)]
             vtab, vk = tables[(ch, H)]
             vb = tab[vtab: vtab + 2 * H].reshape(H, 2)
             y_first, y_last = int(vb[0, 0]), int(vb[-1, 0] + vb[-1, 1])  # crop rows the vertical windows read
-            desc[i] = [os_ if oi is None else oi, om, os_, sh, sw, top, left, ch, cw, htab, hk, vtab, vk, scratch, y_first,
-                       y_last - y_first]
-            scratch = align16(scratch + (y_last - y_first) * W * 8)
+            desc[i] = [os_ if oi is None else oi, om, os_, sh, sw, top, left, ch, cw, htab, hk, vtab, vk,
+                       scratch.add((y_last - y_first) * W * 8), y_first, y_last - y_first]
         return desc
 
     def _resize_on_device_kp2d(self, frames: List[Dict], device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -331,20 +332,13 @@ class SpaTemDataset:
                 for k, i in enumerate(idx[:n_targets]):
                     mask_offs[i] = cur + k * h * w
                 cur += n_targets * h * w
-        file_off = off = align16(cur)  # where the planes that come from files start
-        file_offs = []
-        for fr in frames:
-            o = []
-            for name in ("img", "mask"):
-                a = fr[name]
-                o.append(None if a is None else off)
-                off = off if a is None else align16(off + a.size)
-            file_offs.append(o)
-        total = off
+        lay = Layout(cur)
+        file_off = lay.total  # where the planes that come from files start
+        file_offs = [[None if fr[name] is None else lay.add(fr[name].size) for name in ("img", "mask")] for fr in frames]
+        total = lay.total
 
         on_gpu = device.type == "cuda"
-        blob = torch.empty(total - file_off, dtype=torch.uint8, pin_memory=on_gpu)
-        host = blob.numpy()
+        blob = pinned(total - file_off, device)
         st = self._stream(device) if on_gpu else None
         with (torch.cuda.device(device) if on_gpu else contextlib.nullcontext()), (torch.cuda.stream(st) if on_gpu else contextlib.nullcontext()):
             dev_blob = torch.empty(total, dtype=torch.uint8, device=device)
@@ -357,7 +351,7 @@ class SpaTemDataset:
                     boxes.append((idx[:nt], h, w, ops.skeleton_box_mask(maps[:nt], skeleton_mask_pads(h, w), masks=masks)[0]))
             # the image planes go into the pinned buffer, and up, while the device draws
             jobs = [(o - file_off, fr[name]) for fr, offs in zip(frames, file_offs) for o, name in zip(offs, ("img", "mask")) if o is not None]
-            list(self._pool.map(lambda j: np.copyto(host[j[0]: j[0] + j[1].size], j[1].reshape(-1)), jobs))
+            fill(blob.numpy(), jobs, self._pool)
             if total > file_off:
                 dev_blob[file_off:].copy_(blob, non_blocking=True)
             for idx, h, w, b in boxes:  # 16 bytes per target; .cpu() waits for the stream
@@ -370,12 +364,8 @@ class SpaTemDataset:
             shapes = [(fr["plan"].out_size[1], fr["plan"].out_size[0]) for fr in frames]
             plane_offs = [(oi, mask_offs[i] if om is None else om, skel_offs[i]) for i, (oi, om) in enumerate(file_offs)]
             desc = self._descriptors(frames, plane_offs, shapes, tables, tab)
-            desc_off = align16(tab.nbytes)
-            meta = torch.empty(desc_off + desc.nbytes, dtype=torch.uint8, pin_memory=on_gpu)
-            meta.numpy()[:tab.nbytes] = tab.view(np.uint8)
-            meta.numpy()[desc_off:] = desc.reshape(-1).view(np.uint8)
-            meta_dev = meta.to(device, non_blocking=True)
-            pix, skel = ops.capture_crop_resize(dev_blob, meta, n, desc_off, 0, tab.size, H, W, meta=meta_dev)
+            meta_dev, meta, tab_off, tab_len, desc_off = pack_meta(tab, desc, device)
+            pix, skel = ops.capture_crop_resize(dev_blob, meta, n, desc_off, tab_off, tab_len, H, W, meta=meta_dev)
         if on_gpu:
             st.synchronize()  # as _resize_on_device: the tensors are complete when handed over, the pinned buffers may be released
         return pix, skel
@@ -397,29 +387,16 @@ class SpaTemDataset:
         H, W = self.height, self.width
         tables, tab = self._tables(frames)
         # layout: [frame planes | tables | descriptors], every region 16-byte aligned
-        off, plane_offs = 0, []
-        for fr in frames:
-            o = []
-            for name in ("img", "mask", "skel"):
-                a = fr[name]
-                if a is None:  # has_gt_target=False target: the image IS the skeleton
-                    o.append(None)
-                    continue
-                o.append(off)
-                off = align16(off + a.size)
-            plane_offs.append(o)
-        tab_off = off
-        desc_off = align16(tab_off + tab.nbytes)
-        total = desc_off + len(frames) * FIELDS * 8
+        lay = Layout()  # None: a has_gt_target=False target, whose image IS the skeleton
+        plane_offs = [[None if fr[name] is None else lay.add(fr[name].size) for name in ("img", "mask", "skel")] for fr in frames]
+        tab_off = lay.add(tab.nbytes)
+        desc_off = lay.add(len(frames) * FIELDS * 8)
         desc = self._descriptors(frames, plane_offs, [fr["skel"].shape[:2] for fr in frames], tables, tab)
-        on_gpu = device.type == "cuda"
-        blob = torch.empty(total, dtype=torch.uint8, pin_memory=on_gpu)
-        host = blob.numpy()
+        blob = pinned(lay.total, device)
         jobs = [(o, fr[n]) for fr, offs in zip(frames, plane_offs) for o, n in zip(offs, ("img", "mask", "skel")) if o is not None]
-        list(self._pool.map(lambda j: np.copyto(host[j[0]: j[0] + j[1].size], j[1].reshape(-1)), jobs))
-        host[tab_off: tab_off + tab.nbytes] = tab.view(np.uint8)
-        host[desc_off: total] = desc.reshape(-1).view(np.uint8)
-        if not on_gpu:  # no device: the ops call decides (it refuses host tensors -- there is no CPU fallback)
+        fill(blob.numpy(), jobs, self._pool)
+        write_meta(blob.numpy(), tab, tab_off, desc, desc_off)
+        if device.type != "cuda":  # no device: the ops call decides (it refuses host tensors -- there is no CPU fallback)
             return ops.capture_crop_resize(blob, blob, len(frames), desc_off, tab_off, tab.size, H, W)
         st = self._stream(device)
         with torch.cuda.device(device), torch.cuda.stream(st):

@@ -6,7 +6,8 @@ The network (BiRefNet / RMBG-2.0 in the reference) is not part of this package a
 directory (``load_matting_model``) or hands over any callable (``matting_model``).  Everything around it runs on the device
 (csrc/matting.hip):
 
-  * ``matting_inputs``: images are decoded with Pillow in a thread pool into pinned staging and uploaded once as bytes; at most two
+  * ``matting_inputs``: images are decoded with Pillow in a thread pool into pinned staging and uploaded once as bytes (the buffer,
+    its filling and the {tables | descriptors} pack are host/staging.py's; ``_plan`` says where every plane lies); at most two
     launches rotate them (an index map), resize them with Pillow's antialiased bilinear filter to the network's size and normalise them
     through a 3 x 256 table that torch CPU itself fills with the reference's arithmetic;
   * ``matting_masks``: the logits, which never visit the host, become bytes through the 65536-entry table of ``quantiser_table`` (the
@@ -30,13 +31,13 @@ from PIL import Image
 
 from . import lib as _l
 from . import ops
-from .pose import _open  # a path, a PIL image or an array -> a PIL image
+from . import staging as _st
 from .resample import TableSet
+from .staging import MAX_HOST_THREADS  # noqa: F401  (importable from here as before)
 
 MEAN = (0.485, 0.456, 0.406)   # remove_background.py:20, the ImageNet constants
 STD = (0.229, 0.224, 0.225)
 IMAGE_SIZE = (1024, 1024)      # remove_background.py:15
-MAX_HOST_THREADS = 16
 FIELDS = _l.MATTING_FIELDS
 ROTATIONS = (0, 90, 180, 270)
 
@@ -83,29 +84,13 @@ def _quarter_turns(rotate_clockwise: int) -> int:
     return int(rotate_clockwise) // 90
 
 
-def _run(pool: Optional[ThreadPoolExecutor], fn, xs) -> List:
-    return list(pool.map(fn, xs)) if pool is not None else [fn(x) for x in xs]
-
-
 def _open_all(images, pool: Optional[ThreadPoolExecutor]) -> Tuple[List, List[Tuple[int, int]]]:
     """Open (not yet decode) and check the images -> (PIL images, sizes [(h, w)]).  Needs no device."""
     images = list(images)
     if len(images) < 1:
         raise ValueError("images: at least one image")
-    ims = _run(pool, _open, images)
-    sizes = [(im.size[1], im.size[0]) for im in ims]
-    for k, (h, w) in enumerate(sizes):
-        if not (1 <= h <= _l.MATTING_MAX_SIDE and 1 <= w <= _l.MATTING_MAX_SIDE):
-            raise ValueError(f"images[{k}]: size {w} x {h} is outside 1..{_l.MATTING_MAX_SIDE}")
-    return ims, sizes
-
-
-def _check_sizes(sizes) -> List[Tuple[int, int]]:
-    sizes = [(int(h), int(w)) for h, w in sizes]
-    for k, (h, w) in enumerate(sizes):
-        if not (1 <= h <= _l.MATTING_MAX_SIDE and 1 <= w <= _l.MATTING_MAX_SIDE):
-            raise ValueError(f"sizes[{k}]: {w} x {h} is outside 1..{_l.MATTING_MAX_SIDE}")
-    return sizes
+    ims = _st.pool_map(pool, _st.open_image, images)
+    return ims, _st.check_sizes([im.size[::-1] for im in ims], _l.MATTING_MAX_SIDE, "images")
 
 
 def _plan(sizes: Sequence[Tuple[int, int]], net: Tuple[int, int], rot: int, to_net: bool):
@@ -115,30 +100,18 @@ def _plan(sizes: Sequence[Tuple[int, int]], net: Tuple[int, int], rot: int, to_n
     S_h, S_w = net
     ts = TableSet()
     desc = np.zeros((len(sizes), FIELDS), dtype=np.int64)
-    plane_off = scratch_off = 0
+    planes, scratch = _st.Layout(), _st.Layout()
     for k, (h, w) in enumerate(sizes):
         rh, rw = (w, h) if rot & 1 else (h, w)
         row = desc[k]
-        row[0], row[1], row[2] = plane_off, h, w
-        plane_off = _l.align16(plane_off + h * w * (3 if to_net else 1))
+        row[0], row[1], row[2] = planes.add(h * w * (3 if to_net else 1)), h, w
         pairs = ((rw, S_w), (rh, S_h)) if to_net else ((S_w, rw), (S_h, rh))
         for field, (n_in, n_out) in zip((3, 5), pairs):
             row[field], row[field + 1] = (-1, 0) if n_in == n_out else ts.add(n_in, n_out, "bilinear" if to_net else "bicubic")
         if row[3] >= 0:
-            row[7] = scratch_off
-            scratch_off = _l.align16(scratch_off + (rh * S_w * 4 if to_net else S_h * rw))
+            row[7] = scratch.add(rh * S_w * 4 if to_net else S_h * rw)
     tab = ts.array() if ts.tables else np.zeros(1, dtype=np.int32)  # the library wants a table even where no axis changes its size
-    return desc, tab, plane_off, max(scratch_off, 16)
-
-
-def _meta(desc: np.ndarray, tab: np.ndarray, device: torch.device) -> Tuple[torch.Tensor, torch.Tensor, int]:
-    """{tab | desc} in one pinned buffer and its copy on the device -> (meta, meta_host, desc_off); the tables start at byte 0."""
-    desc_off = _l.align16(tab.nbytes)
-    host = torch.zeros(desc_off + desc.nbytes, dtype=torch.uint8, pin_memory=True)
-    view = host.numpy()
-    view[:tab.nbytes] = tab.view(np.uint8)
-    view[desc_off:] = desc.reshape(-1).view(np.uint8)
-    return host.to(device, non_blocking=True), host, desc_off
+    return desc, tab, planes.total, max(scratch.total, 16)
 
 
 def _inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: int, dtype: torch.dtype, pool: Optional[ThreadPoolExecutor]) -> torch.Tensor:
@@ -146,18 +119,12 @@ def _inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: int, dtyp
     if not (1 <= S_h <= _l.MATTING_MAX_SIDE and 1 <= S_w <= _l.MATTING_MAX_SIDE):
         raise ValueError(f"size {S_h} x {S_w} is outside 1..{_l.MATTING_MAX_SIDE}")
     desc, tab, plane_bytes, scratch_bytes = _plan(sizes, (S_h, S_w), rot, True)
-    host = torch.empty(plane_bytes, dtype=torch.uint8, pin_memory=True)
-    view = host.numpy()
-
-    def decode(k):
-        h, w = sizes[k]
-        o = int(desc[k, 0])
-        np.copyto(view[o: o + h * w * 3].reshape(h, w, 3), np.asarray(ims[k].convert("RGB")))
-    _run(pool, decode, range(len(ims)))
+    host = _st.pinned(plane_bytes, dev)
+    _st.fill(host.numpy(), [(int(desc[k, 0]), (im, "RGB")) for k, im in enumerate(ims)], pool)
     blob = host.to(dev, non_blocking=True)
-    meta, meta_host, desc_off = _meta(desc, tab, dev)
+    meta, meta_host, tab_off, tab_len, desc_off = _st.pack_meta(tab, desc, dev)
     scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
-    out = ops.matting_input(blob, meta, meta_host, len(ims), desc_off, 0, tab.size, _on_device(dtype, dev), scratch, S_h, S_w, rot)
+    out = ops.matting_input(blob, meta, meta_host, len(ims), desc_off, tab_off, tab_len, _on_device(dtype, dev), scratch, S_h, S_w, rot)
     torch.cuda.current_stream().synchronize()  # the pinned buffers may go; the tensor is complete when it is handed over
     return out
 
@@ -190,7 +157,7 @@ def matting_masks(logits: torch.Tensor, sizes: Sequence[Tuple[int, int]], *, rot
         raise ValueError(f"logits: expected [n, 1, S_h, S_w], got {tuple(logits.shape)}")
     if logits.dtype not in (torch.float16, torch.bfloat16, torch.float32):
         raise ValueError(f"logits: expected fp16, bf16 or fp32, got {logits.dtype}")
-    sizes = _check_sizes(sizes)
+    sizes = _st.check_sizes(sizes, _l.MATTING_MAX_SIDE, "sizes")
     n, _, S_h, S_w = logits.shape
     if len(sizes) != n:
         raise ValueError(f"sizes: expected one (h, w) per logit plane ({n}), got {len(sizes)}")
@@ -199,10 +166,10 @@ def matting_masks(logits: torch.Tensor, sizes: Sequence[Tuple[int, int]], *, rot
     dev = logits.device
     with torch.cuda.device(dev):
         desc, tab, blob_bytes, scratch_bytes = _plan(sizes, (S_h, S_w), rot, False)
-        meta, meta_host, desc_off = _meta(desc, tab, dev)
+        meta, meta_host, tab_off, tab_len, desc_off = _st.pack_meta(tab, desc, dev)
         scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
-        blob = ops.matting_mask(logits.to(torch.float16).contiguous(), meta, meta_host, n, desc_off, 0, tab.size, _on_device("q", dev), scratch,
-                                blob_bytes, rot)
+        blob = ops.matting_mask(logits.to(torch.float16).contiguous(), meta, meta_host, n, desc_off, tab_off, tab_len, _on_device("q", dev),
+                                scratch, blob_bytes, rot)
         host = blob.cpu().numpy()  # synchronises: meta_host may go
     return [host[int(desc[k, 0]): int(desc[k, 0]) + h * w].reshape(h, w) for k, (h, w) in enumerate(sizes)]
 
@@ -257,23 +224,15 @@ def pending_batches(fmask_paths: Sequence[str], batch_size: int, skip_exists: bo
     return todo, len(fmask_paths) - sum(len(b) for b in todo)
 
 
-def _save(image: Image.Image, path: str) -> None:
-    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
-    root, ext = os.path.splitext(path)
-    tmp = f"{root}.tmp{threading.get_ident()}{ext}"  # keeps the extension: Pillow picks the format by it
-    image.save(tmp)
-    os.replace(tmp, path)  # a reader (or skip_exists) never sees half a file
-
-
 def write_mask(mask: np.ndarray, fmask_path: str, image_src=None, image_alpha_path: Optional[str] = None) -> None:
     """``Image.fromarray(mask).save(fmask_path)`` and, with `image_alpha_path`, the image (in its stored orientation) with the mask as
     its alpha channel (``putalpha``, remove_background.py:89-93).  Both appear atomically."""
     fmask = Image.fromarray(mask)
-    _save(fmask, fmask_path)
+    _st.atomic_write(fmask_path, fmask.save)
     if image_alpha_path is not None:
-        image = _open(image_src).copy()
+        image = _st.open_image(image_src).copy()
         image.putalpha(fmask)
-        _save(image, image_alpha_path)
+        _st.atomic_write(image_alpha_path, image.save)
 
 
 def remove_background(images_dir: str, out_fmasks_dir: str, out_images_alpha_dir: Optional[str] = None, model_name: Optional[str] = None,
@@ -301,38 +260,18 @@ def remove_background(images_dir: str, out_fmasks_dir: str, out_images_alpha_dir
     result = {"images": len(images), "written": 0, "skipped": skipped}
     if not batches:
         return result
-    if gpu_ids is None:
-        gpu_ids = list(range(torch.cuda.device_count()))
-    devices = [_l.hip_device(f"cuda:{int(g)}", "remove_background") for g in gpu_ids]
-    if not devices:
-        raise _l.Dm4dError("remove_background: no HIP device is available (no CPU fallback in diffuman4d_amd)")
-    pool = ThreadPoolExecutor(max_workers=max(1, min(int(num_workers), MAX_HOST_THREADS)), thread_name_prefix="dm4d-matting")
 
-    def worker(g: int) -> List:
-        dev = devices[g]
-        writes = []
-        with torch.cuda.device(dev), torch.cuda.stream(torch.cuda.Stream(device=dev)), torch.no_grad():
-            model = matting_model if matting_model is not None else load_matting_model(model_name, dev)
-            for batch in batches[g::len(devices)]:
-                ims, sizes = _open_all([images[k] for k in batch], pool)
-                x = _inputs(ims, sizes, size, dev, rot, torch.float16, pool)
-                out = model(x)
-                if isinstance(out, (list, tuple)) and len(out) > 0:
-                    out = out[-1]
-                if not isinstance(out, torch.Tensor) or out.device.type != "cuda" or tuple(out.shape) != (len(batch), 1) + size:
-                    raise _l.Dm4dError(f"matting_model: expected a [{len(batch)}, 1, {size[0]}, {size[1]}] tensor on the device (or a list "
-                                       "of tensors that ends in one)")
-                masks = matting_masks(out, sizes, rotate_clockwise=rotate_clockwise)
-                for r, k in enumerate(batch):
-                    writes.append(pool.submit(write_mask, masks[r], fmasks[k], images[k], alphas[k]))
-        return writes
+    def process_batch(model: Callable, batch: List[int], dev: torch.device, pool: ThreadPoolExecutor) -> List:
+        ims, sizes = _open_all([images[k] for k in batch], pool)
+        out = model(_inputs(ims, sizes, size, dev, rot, torch.float16, pool))
+        if isinstance(out, (list, tuple)) and len(out) > 0:
+            out = out[-1]
+        if not isinstance(out, torch.Tensor) or out.device.type != "cuda" or tuple(out.shape) != (len(batch), 1) + size:
+            raise _l.Dm4dError(f"matting_model: expected a [{len(batch)}, 1, {size[0]}, {size[1]}] tensor on the device (or a list "
+                               "of tensors that ends in one)")
+        masks = matting_masks(out, sizes, rotate_clockwise=rotate_clockwise)
+        return [pool.submit(write_mask, masks[r], fmasks[k], images[k], alphas[k]) for r, k in enumerate(batch)]
 
-    try:
-        with ThreadPoolExecutor(max_workers=len(devices), thread_name_prefix="dm4d-matting-gpu") as gpus:
-            for fut in [gpus.submit(worker, g) for g in range(len(devices))]:
-                for w in fut.result():
-                    w.result()
-                    result["written"] += 1
-    finally:
-        pool.shutdown(wait=True)
+    load_model = lambda dev: matting_model if matting_model is not None else load_matting_model(model_name, dev)
+    result["written"] = _st.run_stage("remove_background", gpu_ids, num_workers, "dm4d-matting", batches, load_model, process_batch)
     return result

@@ -9,7 +9,7 @@ to the canvas, the padded bounding box of the masks, the crop, torchmetrics' PSN
   * device (``dm4d_eval_psnr_ssim_f64``, csrc/metrics.hip): everything else, for a whole batch of pairs at once.  The reference cannot
     batch "because the croppings are different"; per-pair descriptors remove that limit.
 
-Every batch's planes and descriptors go into one pinned staging buffer and up in one copy; uint8 planes stay uint8 on the way
+Every batch's planes and descriptors go into one pinned staging buffer (host/staging.py) and up in one copy; uint8 planes stay uint8 on the way
 (4 x fewer bytes than ``to_tensor``'s floats).  There is no CPU path: a host tensor is uploaded, a missing library raises.
 
 LPIPS-VGG is built (``host/lpips.py::LpipsVGG``, csrc/lpips.hip: VGG-16 on the MFMA convolution with three-term bf16 products, fp64
@@ -34,7 +34,8 @@ from PIL import Image
 
 from . import lpips as _lpips
 from . import ops
-from .lib import Dm4dError, align16
+from .lib import Dm4dError
+from .staging import Layout, fill, pinned, write_meta
 
 log = logging.getLogger(__name__)
 
@@ -146,7 +147,7 @@ class ImageEvaluator:
     def _run(self, items: List[Dict], debug: bool):
         """Pack planes and descriptors into one staging buffer, upload it, launch -> (out [n, 8] fp64, boxes [n, 4], debug) on the host
         (debug stays on the device)."""
-        off, jobs = 0, []
+        lay, jobs = Layout(), []
         desc = np.zeros((len(items), ops.EVAL_FIELDS), dtype=np.int64)
         for i, it in enumerate(items):
             offs = {}
@@ -157,25 +158,20 @@ class ImageEvaluator:
                 elif name == "gmask" and a is it["pmask"]:
                     offs[name] = offs["pmask"]  # evaluate_results passes ONE mask file for both: it is decoded and uploaded once
                 else:
-                    offs[name] = off
-                    jobs.append((off, a))
-                    off = align16(off + a.nbytes)
+                    offs[name] = lay.add(a.nbytes)
+                    jobs.append((offs[name], a))
             mask = it["pmask"] if it["pmask"] is not None else it["gmask"]
             flags = ((ops.EVAL_IMAGE_F32 if it["pred"].dtype != np.uint8 else 0)
                      | (ops.EVAL_MASK_F32 if mask is not None and mask.dtype != np.uint8 else 0)
                      | (ops.EVAL_CROP_MASKS if it["crop"] else 0) | (it["bg"] << ops.EVAL_BG_SHIFT))
             desc[i, :13] = [offs["pred"], offs["gt"], offs["pmask"], offs["gmask"], it["h"], it["w"], it["oh"], it["ow"], flags,
                             0, 0, it["ow"], it["oh"]]
-        desc_off = off
-        total = desc_off + desc.nbytes
-        on_gpu = self.device.type == "cuda"
-        blob = torch.empty(total, dtype=torch.uint8, pin_memory=on_gpu)
-        host = blob.numpy()
-        list(self._pool.map(lambda j: np.copyto(host[j[0]: j[0] + j[1].nbytes], np.ascontiguousarray(j[1]).reshape(-1).view(np.uint8)),
-                            jobs))
-        host[desc_off: total] = desc.reshape(-1).view(np.uint8)
+        desc_off = lay.add(desc.nbytes)
+        blob = pinned(lay.total, self.device)
+        fill(blob.numpy(), jobs, self._pool)
+        write_meta(blob.numpy(), None, 0, desc, desc_off)
         desc_t = torch.from_numpy(desc)
-        if not on_gpu:  # no device: the ops call decides (it refuses host tensors -- there is no CPU fallback)
+        if self.device.type != "cuda":  # no device: the ops call decides (it refuses host tensors -- there is no CPU fallback)
             res = ops.eval_psnr_ssim(blob, desc_t, desc_off, debug=debug)
             return res[0], res[1], (res[2] if debug else None)
         st = self._stream()

@@ -60,6 +60,19 @@ def _p(t: Optional[torch.Tensor]):
     return None if t is None else t.data_ptr()
 
 
+def _check_meta(meta: torch.Tensor, meta_host: torch.Tensor, fields: int, rows: int, desc_off: int, tab_off: Optional[int] = None,
+                tab_len: Optional[int] = None, what: str = "meta") -> None:
+    """`meta_host` is the host copy of the device bytes `meta` (named `what` in the refusals), and the `rows` int64 descriptors of
+    `fields` fields at byte `desc_off` -- with `tab_off`, also the `tab_len` int32 table entries at that byte -- lie inside it, aligned."""
+    if meta_host.device.type != "cpu" or meta_host.dtype != torch.uint8 or meta_host.numel() != meta.numel() or \
+            not meta_host.is_contiguous() or not meta.is_contiguous():
+        raise _l.Dm4dError(f"{what}: expected a contiguous uint8 tensor and its contiguous host copy")
+    if rows < 1 or desc_off < 0 or desc_off % 8 or desc_off + rows * fields * 8 > meta.numel():
+        raise _l.Dm4dError(f"desc_off: the descriptors lie outside {what}, or are not aligned")
+    if tab_off is not None and (tab_off < 0 or tab_off % 4 or tab_len < 1 or tab_off + tab_len * 4 > meta.numel()):
+        raise _l.Dm4dError(f"tab_off: the tables lie outside {what}, or are not aligned")
+
+
 def gemm(a: torch.Tensor, w: torch.Tensor, *, a2: Optional[torch.Tensor] = None, bias=None, rowbias=None,
          rows_per_rowbias: int = 1, residual=None, geglu: bool = False, silu: bool = False, out_scale: float = 1.0,
          out: Optional[torch.Tensor] = None, out_f32: bool = False, split_out: bool = False, scale_cols: int = 0,
@@ -897,11 +910,8 @@ def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: i
     planes only, some of which may never have been on the host."""
     _req(blob, "blob", torch.uint8)
     where = blob if meta is None else _req(meta, "meta", torch.uint8)
-    if blob_host.device.type != "cpu" or blob_host.dtype != torch.uint8 or blob_host.numel() != where.numel():
-        raise _l.Dm4dError("blob_host: expected the host copy of " + ("blob" if meta is None else "meta"))
-    if min(desc_off, tab_off) < 0 or desc_off % 8 or tab_off % 4 or max(desc_off + n_frames * CAPTURE_FIELDS * 8, tab_off + tab_len * 4) > where.numel():
-        raise _l.Dm4dError("desc_off / tab_off: the tables or the descriptors lie outside the buffer, or are not aligned")
-    if where.device != blob.device or not where.is_contiguous() or not blob.is_contiguous():
+    _check_meta(where, blob_host, CAPTURE_FIELDS, n_frames, desc_off, tab_off, tab_len, what="blob" if meta is None else "meta")
+    if where.device != blob.device or not blob.is_contiguous():
         raise _l.Dm4dError("meta: expected a contiguous tensor on blob's device")
     desc = blob_host[desc_off: desc_off + n_frames * CAPTURE_FIELDS * 8].view(torch.int64).reshape(n_frames, CAPTURE_FIELDS)
     tab = blob_host[tab_off: tab_off + tab_len * 4].view(torch.int32)
@@ -1134,14 +1144,10 @@ def skeleton_box_mask(maps: torch.Tensor, pads: Tuple[int, int, int], masks: Opt
     return boxes, masks
 
 
-def _pose_meta(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, rows: int, desc_off: int) -> None:
+def _pose_blob(blob: torch.Tensor, meta: torch.Tensor) -> None:
     _req(blob, "blob", torch.uint8), _req(meta, "meta", torch.uint8)
-    if meta.device != blob.device or not blob.is_contiguous() or not meta.is_contiguous() or blob.numel() == 0:
+    if meta.device != blob.device or not blob.is_contiguous() or blob.numel() == 0:
         raise _l.Dm4dError("blob / meta: expected contiguous non-empty tensors on one device")
-    if meta_host.device.type != "cpu" or meta_host.dtype != torch.uint8 or meta_host.numel() != meta.numel() or not meta_host.is_contiguous():
-        raise _l.Dm4dError("meta_host: expected the host copy of meta")
-    if rows < 1 or desc_off < 0 or desc_off % 8 or desc_off + rows * _l.POSE_FIELDS * 8 > meta.numel():
-        raise _l.Dm4dError("desc_off: the descriptors lie outside meta, or are not aligned")
 
 
 def pose_input(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, rows: int, desc_off: int, tab_off: int, tab_len: int,
@@ -1150,9 +1156,8 @@ def pose_input(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, 
     current stream.  `blob`: device uint8 holding the image and mask planes; `meta`: device uint8 holding int32 warp tables at byte
     `tab_off` and int64 POSE_FIELDS descriptors at byte `desc_off`, `meta_host` its host copy, on which the library checks every
     descriptor and table before it launches.  norm: host fp32 [6] = mean R, G, B | std R, G, B."""
-    _pose_meta(blob, meta, meta_host, rows, desc_off)
-    if tab_off < 0 or tab_off % 4 or tab_len < 1 or tab_off + tab_len * 4 > meta.numel():
-        raise _l.Dm4dError("tab_off: the tables lie outside meta, or are not aligned")
+    _pose_blob(blob, meta)
+    _check_meta(meta, meta_host, _l.POSE_FIELDS, rows, desc_off, tab_off, tab_len)
     if norm.device.type != "cpu" or norm.dtype != F32 or norm.numel() != 6 or not norm.is_contiguous():
         raise _l.Dm4dError("norm: expected a contiguous host fp32 tensor of 6 values")
     out = torch.empty((rows, 3, H, W), dtype=F32, device=blob.device)
@@ -1165,7 +1170,8 @@ def pose_input(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, 
 def pose_mask_box(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int) -> torch.Tensor:
     """[x1, y1, x2, y2] of the pixels >= 128 of the masks that `n` POSE_FIELDS descriptors at byte `desc_off` of meta name ({0, 0, w, h}
     for a mask without one) -> int32 [n, 4] on blob's device; blob / meta / meta_host as for pose_input.  One launch on the current stream."""
-    _pose_meta(blob, meta, meta_host, n, desc_off)
+    _pose_blob(blob, meta)
+    _check_meta(meta, meta_host, _l.POSE_FIELDS, n, desc_off)
     boxes = torch.empty((n, 4), dtype=torch.int32, device=blob.device)
     _l.call("dm4d_pose_mask_box_u8", _stream(), _p(blob), blob.numel(), meta_host.data_ptr() + desc_off, meta.data_ptr() + desc_off, n, _p(boxes))
     return boxes
@@ -1184,17 +1190,6 @@ def pose_udp_decode(heatmaps: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]
     return locs, scores
 
 
-def _matting_meta(meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int) -> None:
-    _req(meta, "meta", torch.uint8)
-    if not meta.is_contiguous() or meta_host.device.type != "cpu" or meta_host.dtype != torch.uint8 or meta_host.numel() != meta.numel() or \
-            not meta_host.is_contiguous():
-        raise _l.Dm4dError("meta / meta_host: expected contiguous uint8 tensors, one the host copy of the other")
-    if n < 1 or desc_off < 0 or desc_off % 8 or desc_off + n * _l.MATTING_FIELDS * 8 > meta.numel():
-        raise _l.Dm4dError("desc_off: the descriptors lie outside meta, or are not aligned")
-    if tab_off < 0 or tab_off % 4 or tab_len < 1 or tab_off + tab_len * 4 > meta.numel():
-        raise _l.Dm4dError("tab_off: the tables lie outside meta, or are not aligned")
-
-
 def matting_input(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int,
                   lut: torch.Tensor, scratch: torch.Tensor, S_h: int, S_w: int, rot: int) -> torch.Tensor:
     """The matting network's input for `n` staged images (host/matting.py) -> lut's dtype (fp16 or fp32) [n, 3, S_h, S_w] on blob's
@@ -1202,8 +1197,8 @@ def matting_input(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tenso
     int32 coefficient tables at byte `tab_off` and int64 MATTING_FIELDS descriptors at byte `desc_off`, `meta_host` its host copy, on
     which the library checks every descriptor and table before it launches.  lut: device [3, 256], the normalisation of every byte;
     scratch: device uint8 for the horizontal pass; rot: quarter turns clockwise."""
-    _req(blob, "blob", torch.uint8), _req(scratch, "scratch", torch.uint8)
-    _matting_meta(meta, meta_host, n, desc_off, tab_off, tab_len)
+    _req(blob, "blob", torch.uint8), _req(scratch, "scratch", torch.uint8), _req(meta, "meta", torch.uint8)
+    _check_meta(meta, meta_host, _l.MATTING_FIELDS, n, desc_off, tab_off, tab_len)
     if lut.dtype not in (F16, F32):
         raise _l.Dm4dError(f"lut: expected fp16 or fp32, got {lut.dtype}")
     _req(lut, "lut", lut.dtype)
@@ -1222,8 +1217,8 @@ def matting_mask(logits: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tens
     """fp16 logits [n, 1, S_h, S_w] (contiguous) -> the packed uint8 masks of `n` images, `blob_bytes` bytes on the logits' device, at
     most two launches on the current stream.  meta / meta_host as for matting_input (a descriptor's first field: the mask's 16-byte
     aligned offset in the result).  qtab: device uint8 [65536], fp16 bit pattern -> byte; scratch: device uint8 for the horizontal pass."""
-    _req(logits, "logits", F16), _req(qtab, "qtab", torch.uint8), _req(scratch, "scratch", torch.uint8)
-    _matting_meta(meta, meta_host, n, desc_off, tab_off, tab_len)
+    _req(logits, "logits", F16), _req(qtab, "qtab", torch.uint8), _req(scratch, "scratch", torch.uint8), _req(meta, "meta", torch.uint8)
+    _check_meta(meta, meta_host, _l.MATTING_FIELDS, n, desc_off, tab_off, tab_len)
     if logits.dim() != 4 or logits.shape[0] != n or logits.shape[1] != 1 or not logits.is_contiguous() or logits.numel() == 0:
         raise _l.Dm4dError(f"logits: expected a contiguous [{n}, 1, S_h, S_w] tensor, got {tuple(logits.shape)}")
     if qtab.numel() != 65536 or not qtab.is_contiguous() or scratch.numel() == 0 or blob_bytes < 1 or \

@@ -5,7 +5,8 @@
 The network is not part of this package and is never downloaded: the caller names a checkpoint file (``load_pose_model``) or hands over
 any callable (``pose_model``).  Everything around it runs on the device (csrc/pose.hip):
 
-  * ``pose_inputs``: images (and foreground masks) are decoded with Pillow in a thread pool into pinned staging and uploaded once;
+  * ``pose_inputs``: images (and foreground masks) are decoded with Pillow in a thread pool into pinned staging and uploaded once
+    (host/staging.py lays the planes out, fills them and packs {tables | descriptors}; ``plane_layout`` and ``descriptors`` say where);
     one launch composites each image over black through its mask, warps every person box to the network's input and normalises it.
     The warp is an integer rule of this package (DESIGN.md, "Keypoint prediction"), modelled on OpenCV's bilinear warpAffine;
   * ``decode_heatmaps``: one launch takes the heatmaps, which never visit the host, to refined keypoints (UDP / DARK decoding); the
@@ -17,22 +18,21 @@ from __future__ import annotations
 
 import json
 import os
-import threading
 from concurrent.futures import ThreadPoolExecutor
 from glob import glob
 from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
-from PIL import Image
 
 from . import lib as _l
 from . import ops
+from . import staging as _st
+from .staging import MAX_HOST_THREADS  # noqa: F401  (importable from here as before)
 
 MEAN = (123.5, 116.5, 103.5)   # vis_pose.py:451-452, RGB order (preprocess_pose's two BGR swaps cancel)
 STD = (58.5, 57.0, 57.5)
 PADDING = 1.25                 # top_down_affine_transform's default
-MAX_HOST_THREADS = 16
 FIELDS = _l.POSE_FIELDS
 
 
@@ -84,103 +84,70 @@ def warp_tables(mat: np.ndarray, shape: Tuple[int, int]) -> np.ndarray:
 
 
 # -- staging ---------------------------------------------------------------------------------------------------------------------------
-def _open(src):
-    """A path, a PIL image or an array -> a PIL image (not yet decoded for a path)."""
-    if isinstance(src, Image.Image):
-        return src
-    if isinstance(src, np.ndarray):
-        return Image.fromarray(src)
-    return Image.open(os.fspath(src))
-
-
 def _open_all(images, fmasks, pool: Optional[ThreadPoolExecutor]):
-    """Open (not yet decode) the images and masks and check them -> (PIL images or None, PIL masks with None entries or None).
-    `images` None: masks alone (``fmask_boxes``).  Needs no device."""
+    """Open (not yet decode) the images and masks and check them -> (PIL images or None, PIL masks with None for an image without one,
+    sizes [(h, w)]).  `images` None: masks alone (``fmask_boxes``).  Needs no device."""
     n = len(fmasks) if images is None else len(images)
     if n < 1:
         raise ValueError("images: at least one image")
     if images is not None and fmasks is not None and len(fmasks) != n:
         raise ValueError("fmask_paths and image_paths must have the same length")
-    run = (lambda fn, xs: list(pool.map(fn, xs))) if pool is not None else (lambda fn, xs: [fn(x) for x in xs])
-    ims = run(_open, images) if images is not None else None
-    mks = run(lambda m: None if m is None else _open(m), fmasks) if fmasks is not None else None
-    for k in range(n):
-        size = ims[k].size if ims is not None else mks[k].size
-        if not (1 <= size[1] <= _l.POSE_MAX_SIDE and 1 <= size[0] <= _l.POSE_MAX_SIDE):
-            raise ValueError(f"images[{k}]: size {size[0]} x {size[1]} is outside 1..{_l.POSE_MAX_SIDE}")
-        if mks is not None and mks[k] is not None:
-            if mks[k].mode not in ("L", "1"):
-                raise ValueError(f"fmasks[{k}]: mode {mks[k].mode!r}, expected 'L' or '1'")
-            if mks[k].size != size:
+    ims = _st.pool_map(pool, _st.open_image, images) if images is not None else None
+    mks = _st.pool_map(pool, lambda m: None if m is None else _st.open_image(m), fmasks) if fmasks is not None else [None] * n
+    sizes = _st.check_sizes([im.size[::-1] for im in (ims if ims is not None else mks)], _l.POSE_MAX_SIDE, "images")
+    for k, m in enumerate(mks):
+        if m is not None:
+            if m.mode not in ("L", "1"):
+                raise ValueError(f"fmasks[{k}]: mode {m.mode!r}, expected 'L' or '1'")
+            if m.size != sizes[k][::-1]:
                 raise ValueError("images do not match")  # Pillow's text for Image.composite
-    return ims, mks
+    return ims, mks, sizes
 
 
-class _Staged:
-    """Opened images and masks of one batch, decoded into pinned staging and uploaded: `blob` uint8 on the device (planes, 16-byte
-    aligned), sizes [(h, w)], image / mask byte offsets (-1: absent)."""
-
-    def __init__(self, ims, mks, device: torch.device, pool: Optional[ThreadPoolExecutor]):
-        n = len(ims) if ims is not None else len(mks)
-        run = (lambda fn, xs: list(pool.map(fn, xs))) if pool is not None else (lambda fn, xs: [fn(x) for x in xs])
-        self.sizes = [((ims if ims is not None else mks)[k].size[1], (ims if ims is not None else mks)[k].size[0]) for k in range(n)]
-        off, self.image_off, self.mask_off = 0, [], []
-        for k, (h, w) in enumerate(self.sizes):
-            if ims is not None:
-                self.image_off.append(off)
-                off = _l.align16(off + h * w * 3)
-            else:
-                self.image_off.append(-1)
-            if mks is not None and mks[k] is not None:
-                self.mask_off.append(off)
-                off = _l.align16(off + h * w)
-            else:
-                self.mask_off.append(-1)
-        host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
-        view = host.numpy()
-
-        def decode(k):
-            h, w = self.sizes[k]
-            o = self.image_off[k]
-            if o >= 0:
-                np.copyto(view[o: o + h * w * 3].reshape(h, w, 3), np.asarray(ims[k].convert("RGB")))
-            o = self.mask_off[k]
-            if o >= 0:
-                np.copyto(view[o: o + h * w].reshape(h, w), np.asarray(mks[k].convert("L")))
-        run(decode, range(n))
-        self.device = device
-        self.host = host  # pinned: alive until the consumer has synchronised
-        self.blob = host.to(device, non_blocking=True)
-
-    def meta(self, rows: Sequence[Tuple[int, int]], tab: Optional[np.ndarray]) -> Tuple[torch.Tensor, torch.Tensor, int, int]:
-        """rows: (image index, table offset in int32 elements) -> (meta on the device, its pinned host copy, tab_off, desc_off)."""
-        tab_bytes = 0 if tab is None else tab.nbytes
-        desc_off = _l.align16(tab_bytes)
-        desc = np.zeros((len(rows), FIELDS), dtype=np.int64)
-        for r, (k, toff) in enumerate(rows):
-            desc[r, :5] = [self.image_off[k], self.mask_off[k], self.sizes[k][0], self.sizes[k][1], toff]
-        host = torch.empty(desc_off + desc.nbytes, dtype=torch.uint8, pin_memory=True)
-        view = host.numpy()
-        view[:] = 0
-        if tab is not None:
-            view[:tab_bytes] = tab.view(np.uint8)
-        view[desc_off:] = desc.reshape(-1).view(np.uint8)
-        return host.to(self.device, non_blocking=True), host, 0, desc_off
+def plane_layout(sizes: Sequence[Tuple[int, int]], with_images: bool, has_mask: Sequence[bool]) -> Tuple[List[int], List[int], int]:
+    """Where the planes of a batch of `sizes` = [(h, w)] lie in its blob: each image (3 bytes per pixel), then its mask (1), every
+    plane 16-byte aligned -> (image offsets, mask offsets, bytes of the blob); -1: an absent plane."""
+    lay = _st.Layout()
+    image_off, mask_off = [], []
+    for (h, w), masked in zip(sizes, has_mask):
+        image_off.append(lay.add(h * w * 3) if with_images else -1)
+        mask_off.append(lay.add(h * w) if masked else -1)
+    return image_off, mask_off, lay.total
 
 
-def _mask_boxes(staged: _Staged) -> np.ndarray:
-    n = len(staged.sizes)
-    meta, meta_host, _, desc_off = staged.meta([(k, 0) for k in range(n)], None)
-    return ops.pose_mask_box(staged.blob, meta, meta_host, n, desc_off).cpu().numpy()
+def descriptors(rows: Sequence[Tuple[int, int]], sizes, image_off, mask_off) -> np.ndarray:
+    """rows: (image index, table offset in int32 elements) -> int64 [len(rows), FIELDS] = {image offset, mask offset, h, w, table
+    offset, 0, 0, 0} (include/dm4d.h)."""
+    desc = np.zeros((len(rows), FIELDS), dtype=np.int64)
+    for r, (k, toff) in enumerate(rows):
+        desc[r, :5] = [image_off[k], mask_off[k], sizes[k][0], sizes[k][1], toff]
+    return desc
+
+
+def _stage(ims, mks, sizes, device: torch.device, pool: Optional[ThreadPoolExecutor]):
+    """Decode one batch into pinned staging and queue its upload -> (blob uint8 on the device, the pinned buffer, image offsets, mask
+    offsets).  The pinned buffer has to stay alive until the consumer has synchronised."""
+    image_off, mask_off, total = plane_layout(sizes, ims is not None, [m is not None for m in mks])
+    jobs = [(o, (ims[k], "RGB")) for k, o in enumerate(image_off) if o >= 0] + [(o, (mks[k], "L")) for k, o in enumerate(mask_off) if o >= 0]
+    host = _st.pinned(total, device)
+    _st.fill(host.numpy(), jobs, pool)
+    return host.to(device, non_blocking=True), host, image_off, mask_off
+
+
+def _mask_boxes(blob: torch.Tensor, sizes, image_off, mask_off) -> np.ndarray:
+    n = len(sizes)
+    meta, meta_host, _, _, desc_off = _st.pack_meta(None, descriptors([(k, 0) for k in range(n)], sizes, image_off, mask_off), blob.device)
+    return ops.pose_mask_box(blob, meta, meta_host, n, desc_off).cpu().numpy()  # .cpu() synchronises: meta_host may go
 
 
 def fmask_boxes(fmasks, device="cuda") -> np.ndarray:
     """[n, 4] int32: per mask (path, PIL image or uint8 array; mode ``L`` or ``1``) the box [x1, y1, x2, y2] of its pixels >= 128, x2 and
     y2 exclusive; the whole image for a mask without one.  One launch (dm4d_pose_mask_box_u8)."""
-    _, mks = _open_all(None, list(fmasks), None)
+    _, mks, sizes = _open_all(None, list(fmasks), None)
     dev = _l.hip_device(device, "fmask_boxes")
     with torch.cuda.device(dev):
-        return _mask_boxes(_Staged(None, mks, dev, None))
+        blob, _host, image_off, mask_off = _stage(None, mks, sizes, dev, None)
+        return _mask_boxes(blob, sizes, image_off, mask_off)
 
 
 def _boxes_of(b, h: int, w: int) -> List:
@@ -207,19 +174,19 @@ def pose_inputs(images, fmasks=None, bboxes=None, shape: Tuple[int, int] = (1024
     if bbox_source not in ("image", "fmask"):
         raise ValueError(f'bbox_source must be "image" or "fmask", got {bbox_source!r}')
     H, W = int(shape[0]), int(shape[1])
-    ims, mks = _open_all(list(images), None if fmasks is None else list(fmasks), pool)
+    ims, mks, sizes = _open_all(list(images), None if fmasks is None else list(fmasks), pool)
     n = len(ims)
     if bboxes is not None and len(bboxes) != n:
         raise ValueError(f"bboxes: expected one entry per image ({n}), got {len(bboxes)}")
-    if bboxes is None and bbox_source == "fmask" and (mks is None or any(m is None for m in mks)):
+    if bboxes is None and bbox_source == "fmask" and any(m is None for m in mks):
         raise ValueError('bbox_source="fmask" needs a mask for every image')
     dev = _l.hip_device(device, "pose_inputs")
     with torch.cuda.device(dev):
-        staged = _Staged(ims, mks, dev, pool)
+        blob, _host, image_off, mask_off = _stage(ims, mks, sizes, dev, pool)
         if bboxes is None:
-            boxes = _mask_boxes(staged)[:, None, :] if bbox_source == "fmask" else [[[0, 0, w, h]] for h, w in staged.sizes]
+            boxes = _mask_boxes(blob, sizes, image_off, mask_off)[:, None, :] if bbox_source == "fmask" else [[[0, 0, w, h]] for h, w in sizes]
         else:
-            boxes = [_boxes_of(b, *staged.sizes[k]) for k, b in enumerate(bboxes)]
+            boxes = [_boxes_of(b, *sizes[k]) for k, b in enumerate(bboxes)]
         rows, tabs, centers, scales = [], [], [], []
         per_row = 2 * (W + H)
         for k in range(n):
@@ -231,8 +198,8 @@ def pose_inputs(images, fmasks=None, bboxes=None, shape: Tuple[int, int] = (1024
         if not rows:
             raise ValueError("bboxes: no box at all")
         tab = np.concatenate(tabs)
-        meta, meta_host, tab_off, desc_off = staged.meta(rows, tab)
-        out = ops.pose_input(staged.blob, meta, meta_host, len(rows), desc_off, tab_off, tab.size, H, W, torch.tensor(MEAN + STD, dtype=torch.float32))
+        meta, meta_host, tab_off, tab_len, desc_off = _st.pack_meta(tab, descriptors(rows, sizes, image_off, mask_off), dev)
+        out = ops.pose_input(blob, meta, meta_host, len(rows), desc_off, tab_off, tab_len, H, W, torch.tensor(MEAN + STD, dtype=torch.float32))
         torch.cuda.current_stream().synchronize()  # the pinned buffers may go; the tensor is complete when it is handed over
     return out, np.stack(centers), np.stack(scales)
 
@@ -303,14 +270,12 @@ def _parses(path: str) -> bool:
 
 def write_instances(path: str, keypoints: np.ndarray, scores: np.ndarray) -> None:
     """``{"instance_info": [{"keypoints", "keypoint_scores"}, ...]}``, one entry per box, indented with one tab (vis_pose.py:111-126)."""
-    parent = os.path.dirname(path)
-    if parent:
-        os.makedirs(parent, exist_ok=True)
     info = [{"keypoints": np.asarray(kp).tolist(), "keypoint_scores": np.asarray(sc).tolist()} for kp, sc in zip(keypoints, scores)]
-    tmp = f"{path}.tmp{threading.get_ident()}"
-    with open(tmp, "w") as f:
-        json.dump({"instance_info": info}, f, indent="\t")
-    os.replace(tmp, path)  # a reader (or skip_exists) never sees half a file
+
+    def write(tmp: str) -> None:
+        with open(tmp, "w") as f:
+            json.dump({"instance_info": info}, f, indent="\t")
+    _st.atomic_write(path, write)
 
 
 def predict_keypoints(images_dir: str, out_kp2d_dir: str, fmasks_dir: Optional[str] = None, sapiens_ckpt_path: Optional[str] = None,
@@ -343,40 +308,21 @@ def predict_keypoints(images_dir: str, out_kp2d_dir: str, fmasks_dir: Optional[s
     result = {"images": len(images), "written": 0, "skipped": len(images) - len(todo)}
     if not todo:
         return result
-    if gpu_ids is None:
-        gpu_ids = list(range(torch.cuda.device_count()))
-    devices = [_l.hip_device(f"cuda:{int(g)}", "predict_keypoints") for g in gpu_ids]
-    if not devices:
-        raise _l.Dm4dError("predict_keypoints: no HIP device is available (no CPU fallback in diffuman4d_amd)")
     batches = [todo[i: i + batch_size] for i in range(0, len(todo), batch_size)]
     hm_size = (int(W / heatmap_scale), int(H / heatmap_scale))
-    pool = ThreadPoolExecutor(max_workers=max(1, min(int(num_workers), MAX_HOST_THREADS)), thread_name_prefix="dm4d-pose")
 
-    def worker(g: int) -> List:
-        dev = devices[g]
-        writes = []
-        with torch.cuda.device(dev), torch.cuda.stream(torch.cuda.Stream(device=dev)), torch.no_grad():
-            model = pose_model if pose_model is not None else load_pose_model(sapiens_ckpt_path, dev)
-            for batch in batches[g::len(devices)]:
-                x, centers, scales = pose_inputs([images[k] for k in batch], None if fmasks is None else [fmasks[k] for k in batch], None,
-                                                 (H, W), dev, bbox_source=bbox_source, pool=pool)
-                heat = model(x)
-                if not isinstance(heat, torch.Tensor) or heat.device.type != "cuda" or heat.dim() != 4 or heat.shape[0] != x.shape[0]:
-                    raise _l.Dm4dError("pose_model: expected a [n, K, Hh, Wh] tensor on the device")
-                if (heat.shape[3], heat.shape[2]) != hm_size:
-                    raise _l.Dm4dError(f"pose_model: heatmaps of {heat.shape[3]} x {heat.shape[2]}, expected {hm_size[0]} x {hm_size[1]} "
-                                       f"(input {W} x {H}, heatmap_scale {heatmap_scale})")
-                kp, sc = decode_heatmaps(heat, (W, H), centers, scales)
-                for r, k in enumerate(batch):  # one box per image here
-                    writes.append(pool.submit(write_instances, outs[k], kp[r: r + 1], sc[r: r + 1]))
-        return writes
+    def process_batch(model: Callable, batch: List[int], dev: torch.device, pool: ThreadPoolExecutor) -> List:
+        x, centers, scales = pose_inputs([images[k] for k in batch], None if fmasks is None else [fmasks[k] for k in batch], None,
+                                         (H, W), dev, bbox_source=bbox_source, pool=pool)
+        heat = model(x)
+        if not isinstance(heat, torch.Tensor) or heat.device.type != "cuda" or heat.dim() != 4 or heat.shape[0] != x.shape[0]:
+            raise _l.Dm4dError("pose_model: expected a [n, K, Hh, Wh] tensor on the device")
+        if (heat.shape[3], heat.shape[2]) != hm_size:
+            raise _l.Dm4dError(f"pose_model: heatmaps of {heat.shape[3]} x {heat.shape[2]}, expected {hm_size[0]} x {hm_size[1]} "
+                               f"(input {W} x {H}, heatmap_scale {heatmap_scale})")
+        kp, sc = decode_heatmaps(heat, (W, H), centers, scales)
+        return [pool.submit(write_instances, outs[k], kp[r: r + 1], sc[r: r + 1]) for r, k in enumerate(batch)]  # one box per image here
 
-    try:
-        with ThreadPoolExecutor(max_workers=len(devices), thread_name_prefix="dm4d-pose-gpu") as gpus:
-            for fut in [gpus.submit(worker, g) for g in range(len(devices))]:
-                for w in fut.result():
-                    w.result()
-                    result["written"] += 1
-    finally:
-        pool.shutdown(wait=True)
+    load_model = lambda dev: pose_model if pose_model is not None else load_pose_model(sapiens_ckpt_path, dev)
+    result["written"] = _st.run_stage("predict_keypoints", gpu_ids, num_workers, "dm4d-pose", batches, load_model, process_batch)
     return result

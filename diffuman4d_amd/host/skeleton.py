@@ -32,7 +32,7 @@ import torch
 from . import lib as _l
 from . import ops
 from .resample import TableSet
-from .triang import _hip_device
+from .staging import MAX_HOST_THREADS  # noqa: F401  (importable from here as before)
 
 log = logging.getLogger(__name__)
 
@@ -41,7 +41,6 @@ X_LINKS = ((65, (5, 12)), (66, (6, 11)))  # "add x links for the body": left sho
 MAJOR_LINKS = 25           # link ids below this are painted at twice the radius and thickness
 COORD_MIN, COORD_MAX = ops.SKEL_COORD_MIN, ops.SKEL_COORD_MAX
 MIN_OUT, MAX_OUT = 256, 8192   # supported max(out_kpmap_shape): below, a tile's canvas footprint no longer fits in LDS
-MAX_HOST_THREADS = 16
 LAUNCH_BYTES = 1 << 28     # the frame axis is cut so that one launch's maps stay below this
 
 PALETTE_HELP = ("a palette is a JSON file {\"keypoint_colors\": [[r, g, b] | null, ...], \"links\": [{\"id\": 0, \"link\": [i1, i2], "
@@ -266,7 +265,7 @@ def draw_plans(plans: Sequence[DrawPlan], device="cuda") -> np.ndarray:
     """Plans of one canvas shape and output size -> uint8 [B, h, w, 3], one launch (cut along B where the maps pass 256 MiB)."""
     if not plans:
         raise ValueError("draw_plans: no frames")
-    dev = _hip_device(device, "draw_skeleton_maps")
+    dev = _l.hip_device(device, "draw_skeleton_maps")
     out = [maps.cpu().numpy() for _, maps in _draw_chunks(plans, dev)]
     return out[0] if len(out) == 1 else np.concatenate(out)
 
@@ -344,7 +343,7 @@ def draw_skeleton(kp2d_dir: str, out_kpmap_dir: str, kp2d_score_dir: Optional[st
     per phase (read, plan, launch, and write = the time the run waited for the encoder)."""
     palette = load_palette(palette)
     _check_out_shape(out_kpmap_shape)
-    dev = _hip_device(device, "draw_skeleton")
+    dev = _l.hip_device(device, "draw_skeleton")
     if spa_labels is None:
         spa_labels = sorted(os.listdir(kp2d_dir))
     else:

@@ -23,11 +23,11 @@ import torch
 from . import lib as _l
 from . import ops
 from .capture import read_cameras
+from .staging import MAX_HOST_THREADS  # noqa: F401  (importable from here as before)
 from .vhull import save_pcd_ply
 
 INVALID = -1e6
 MAX_VIEWS = 24            # triangulate_one_point's max_views default, which triangulate_points never overrides
-MAX_HOST_THREADS = 16
 LAUNCH_BYTES = 1 << 28    # the frame axis is cut so that one launch's kp2d + score stay below this
 
 

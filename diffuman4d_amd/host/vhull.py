@@ -21,8 +21,8 @@ from PIL import Image
 
 from . import lib as _l
 from . import ops
+from .staging import MAX_HOST_THREADS  # noqa: F401  (importable from here as before)
 
-MAX_HOST_THREADS = 16
 PLY_HEADER = ("ply\n"
               "format binary_little_endian 1.0\n"
               "element vertex {n}\n"
@@ -123,15 +123,6 @@ def build_voxel_grid_linspaces(bounds, voxel_size) -> Tuple[torch.Tensor, torch.
     return torch.arange(xmin, xmax, voxel_size), torch.arange(ymin, ymax, voxel_size), torch.arange(zmin, zmax, voxel_size)
 
 
-def _hip_device(device) -> torch.device:
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _l.Dm4dError(f"carve_visual_hull: device {device!r} is not a HIP device (no CPU fallback in diffuman4d_amd)")
-    if not torch.cuda.is_available():
-        raise _l.Dm4dError("carve_visual_hull: no HIP device is available (no CPU fallback in diffuman4d_amd)")
-    return torch.device("cuda", torch.cuda.current_device()) if dev.index is None else dev
-
-
 def _check_args(fmasks, Ps, voxel_size, min_views) -> torch.Tensor:
     if not torch.is_tensor(fmasks) or fmasks.dim() != 3 or fmasks.dtype != torch.bool:
         raise ValueError(f"fmasks: expected a [B, H, W] torch.bool tensor, got {getattr(fmasks, 'dtype', type(fmasks))} "
@@ -206,7 +197,7 @@ def carve_visual_hull(fmasks, Ps, bounds, voxel_size=0.02, batch_size=1e6, min_v
     for a, name in zip(axes, "xyz"):
         if a.numel() == 0:
             raise ValueError(f"bounds: the {name} axis is empty ({name}min >= {name}max for voxel_size {voxel_size})")
-    dev = _hip_device(device)
+    dev = _l.hip_device(device, "carve_visual_hull")
     with torch.cuda.device(dev):
         bits = ops.vhull_pack_masks(fmasks.contiguous().to(dev))  # a pageable copy on the carving stream: not overlapped
         axes = tuple(a.to(torch.float32).to(dev) for a in axes)
@@ -238,7 +229,7 @@ def carve_scene(fmasks_dir: str, cameras_path: str, out_vhull_dir: str, camera_r
     inside ndarray.min).  Returns {"frames": {label: number of points}, "bounds": [min, max]}."""
     cam_labels, frm_labels = _list_labels(fmasks_dir, camera_range, frame_range)
     P = read_projections(cameras_path, cam_labels)
-    dev = _hip_device(device)
+    dev = _l.hip_device(device, "carve_visual_hull")
     threads = max(1, min(int(host_threads), MAX_HOST_THREADS))
 
     def paths(frm: str) -> List[str]:

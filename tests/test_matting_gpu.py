@@ -2,6 +2,7 @@
 CPU arithmetic).  Every comparison is for equality: the network input bit for bit, the masks byte for byte."""
 import functools
 import os
+import threading
 
 import numpy as np
 import pytest
@@ -211,6 +212,39 @@ def test_remove_background_end_to_end(hip_device, tmp_path, rot):
         matting.remove_background(images_dir, out, matting_model=lambda x: x[:, :1].cpu(), image_size=(16, 16), gpu_ids=[0])
     with pytest.raises(L.Dm4dError, match="on the device"):
         matting.remove_background(images_dir, out, matting_model=lambda x: x, image_size=(16, 16), gpu_ids=[0])  # three channels
+
+
+def test_remove_background_with_two_workers_equals_one(hip_device, tmp_path):
+    """The stage driver (host/staging.py run_stage) with two worker threads on one device, one image per batch: the same files byte for
+    byte as with one worker; skip_exists then writes nothing; a network that fails in one worker reaches the caller and leaves no thread."""
+    from diffuman4d_amd.host import matting
+    rng = np.random.default_rng(17)
+    for k, (h, w) in enumerate([(5, 7), (16, 16), (33, 20)]):
+        path = tmp_path / "images" / "00" / f"{k:06d}.webp"
+        path.parent.mkdir(parents=True, exist_ok=True)
+        Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).save(path, lossless=True, exact=True)
+
+    def run(out, gpu_ids, skip_exists, model=lambda x: [x, x[:, :1] * 4]):
+        return matting.remove_background(str(tmp_path / "images"), str(tmp_path / out), str(tmp_path / (out + "_rgba")), batch_size=1,
+                                         num_workers=2, skip_exists=skip_exists, gpu_ids=gpu_ids, matting_model=model, image_size=(16, 24))
+    assert run("one", [0], False) == {"images": 3, "written": 3, "skipped": 0}
+    assert run("two", [0, 0], False) == {"images": 3, "written": 3, "skipped": 0}
+    for d in ("one", "one_rgba"):
+        files = sorted(p.relative_to(tmp_path / d) for p in (tmp_path / d).rglob("*") if p.is_file())
+        other = tmp_path / d.replace("one", "two")
+        assert len(files) == 3 and files == sorted(p.relative_to(other) for p in other.rglob("*") if p.is_file())
+        for f in files:
+            assert (tmp_path / d / f).read_bytes() == (other / f).read_bytes(), f
+    assert run("two", [0, 0], True) == {"images": 3, "written": 0, "skipped": 3}
+
+    def fails_in_the_second_worker(x):
+        if threading.current_thread().name.endswith("gpu_1"):
+            raise RuntimeError("the network fails")
+        return x[:, :1]
+    with pytest.raises(RuntimeError, match="the network fails"):
+        run("three", [0, 0], False, fails_in_the_second_worker)
+    assert len([p for p in (tmp_path / "three").rglob("*.png")]) == 2  # the first worker's batches, 0 and 2, were written
+    assert not [t.name for t in threading.enumerate() if t.name.startswith("dm4d-matting")]
 
 
 def test_there_is_no_cpu_path(hip_device):

@@ -6,6 +6,7 @@ the float64 model was at most 1.81e-6 heatmap pixel on the maps up to 64 x 48, t
 import functools
 import json
 import os
+import threading
 
 import numpy as np
 import pytest
@@ -215,3 +216,38 @@ def test_predict_keypoints_end_to_end(hip_device, tmp_path):
                                  gpu_ids=[hip_device.index or 0])
     assert res == {"images": 3, "written": 0, "skipped": 3}
     assert all(os.stat(p).st_mtime_ns == t for p, t in stamps.items())
+
+
+def test_predict_keypoints_with_two_workers_equals_one(hip_device, tmp_path):
+    """The stage driver (host/staging.py run_stage) with two worker threads on one device, one image per batch: the same files byte for
+    byte as with one worker; skip_exists then writes nothing; a batch that fails in one worker reaches the caller and leaves no thread."""
+    from diffuman4d_amd.host import pose, staging
+    rng = np.random.default_rng(5)
+    for k, (h, w) in enumerate([(5, 7), (16, 16), (33, 20)]):
+        path = tmp_path / "images" / "00" / f"{k:06d}.webp"
+        path.parent.mkdir(parents=True, exist_ok=True)
+        Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).save(path, lossless=True)
+    g = hip_device.index or 0
+
+    def run(out, gpu_ids, skip_exists):
+        return pose.predict_keypoints(str(tmp_path / "images"), str(tmp_path / out), pose_model=stub_model, shape=(64, 48), batch_size=1,
+                                      gpu_ids=gpu_ids, num_workers=2, skip_exists=skip_exists)
+    assert run("one", [g], False) == {"images": 3, "written": 3, "skipped": 0}
+    assert run("two", [g, g], False) == {"images": 3, "written": 3, "skipped": 0}
+    files = sorted(p.relative_to(tmp_path / "one") for p in (tmp_path / "one").rglob("*") if p.is_file())
+    assert len(files) == 3 and files == sorted(p.relative_to(tmp_path / "two") for p in (tmp_path / "two").rglob("*") if p.is_file())
+    for f in files:
+        assert (tmp_path / "one" / f).read_bytes() == (tmp_path / "two" / f).read_bytes(), f
+    assert run("two", [g, g], True) == {"images": 3, "written": 0, "skipped": 3}
+
+    seen = []
+
+    def process_batch(model, batch, dev, pool):
+        seen.append((batch, dev, torch.cuda.current_stream(dev) != torch.cuda.default_stream(dev), torch.is_grad_enabled()))
+        if batch == [1]:
+            raise RuntimeError("batch 1 fails")
+        return [pool.submit(len, batch)]
+    with pytest.raises(RuntimeError, match="batch 1 fails"):
+        staging.run_stage("a_stage", [g, g], 2, "dm4d-test-stage", [[0], [1], [2]], lambda dev: None, process_batch)
+    assert sorted(s[0] for s in seen) == [[0], [1], [2]] and all(s[1:] == (torch.device("cuda", g), True, False) for s in seen)
+    assert not [t.name for t in threading.enumerate() if t.name.startswith("dm4d-test-stage")]

@@ -36,7 +36,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
-from diffuman4d_amd.host import matting, ops  # noqa: E402
+from diffuman4d_amd.host import matting, ops, staging  # noqa: E402
 
 NET = (1024, 1024)
 
@@ -57,18 +57,14 @@ class Batch:
         self.sizes = [a.shape[:2] for a in arrays]
         self.n = len(arrays)
         desc, tab, plane_bytes, scratch_bytes = matting._plan(self.sizes, NET, 0, True)
-        host = torch.empty(plane_bytes, dtype=torch.uint8, pin_memory=True)
-        for k, a in enumerate(arrays):
-            o = int(desc[k, 0])
-            host.numpy()[o: o + a.size] = a.reshape(-1)
+        host = staging.pinned(plane_bytes, dev)
+        staging.fill(host.numpy(), [(int(desc[k, 0]), a) for k, a in enumerate(arrays)], None)
         self.blob = host.to(dev)
-        self.in_meta, self.in_meta_host, self.in_desc_off = matting._meta(desc, tab, dev)
-        self.in_tab_len = tab.size
+        self.in_meta, self.in_meta_host, _, self.in_tab_len, self.in_desc_off = staging.pack_meta(tab, desc, dev)
         self.in_scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
         desc, tab, self.blob_bytes, scratch_bytes = matting._plan(self.sizes, NET, 0, False)
         self.out_desc = desc
-        self.out_meta, self.out_meta_host, self.out_desc_off = matting._meta(desc, tab, dev)
-        self.out_tab_len = tab.size
+        self.out_meta, self.out_meta_host, _, self.out_tab_len, self.out_desc_off = staging.pack_meta(tab, desc, dev)
         self.out_scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
         self.lut, self.qtab = matting._on_device(torch.float16, dev), matting._on_device("q", dev)
         torch.cuda.synchronize()

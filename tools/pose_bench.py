@@ -35,7 +35,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
-from diffuman4d_amd.host import ops, pose  # noqa: E402
+from diffuman4d_amd.host import ops, pose, staging  # noqa: E402
 
 K, HH, WH = 133, 256, 192
 SHAPE = (1024, 768)
@@ -125,19 +125,23 @@ def main(argv=None):
     images = [rng.integers(0, 256, SRC + (3,), dtype=np.uint8) for _ in range(args.batch)]
     ys, xs = np.mgrid[0:SRC[0], 0:SRC[1]]
     masks = [(255 * (((xs - 512) / (200 + 20 * i)) ** 2 + ((ys - 540) / 430) ** 2 < 1)).astype(np.uint8) for i in range(args.batch)]
-    ims, mks = pose._open_all(images, masks, None)
-    staged = pose._Staged(ims, mks, dev, None)
+    sizes = [SRC] * args.batch
+    image_off, mask_off, total = pose.plane_layout(sizes, True, [True] * args.batch)
+    host = staging.pinned(total, dev)
+    staging.fill(host.numpy(), list(zip(image_off + mask_off, images + masks)), None)
+    blob = host.to(dev)
     tab = np.concatenate([pose.warp_tables(pose.udp_warp_matrix(*pose.box_center_scale([0, 0, SRC[1], SRC[0]], SHAPE), SHAPE), SHAPE)] * args.batch)
     per_row = 2 * (SHAPE[0] + SHAPE[1])
-    meta, meta_host, tab_off, desc_off = staged.meta([(k, k * per_row) for k in range(args.batch)], tab)
+    desc = pose.descriptors([(k, k * per_row) for k in range(args.batch)], sizes, image_off, mask_off)
+    meta, meta_host, tab_off, tab_len, desc_off = staging.pack_meta(tab, desc, dev)
     norm = torch.tensor(pose.MEAN + pose.STD, dtype=torch.float32)
-    t, count = device_time(lambda: ops.pose_input(staged.blob, meta, meta_host, args.batch, desc_off, tab_off, tab.size, SHAPE[0], SHAPE[1], norm),
+    t, count = device_time(lambda: ops.pose_input(blob, meta, meta_host, args.batch, desc_off, tab_off, tab_len, SHAPE[0], SHAPE[1], norm),
                            args.reps, args.inner, args.window)
     out_bytes = 3 * SHAPE[0] * SHAPE[1] * 4
     lines.append({"what": "input", "seconds_per_image": t / args.batch, "images_per_second": args.batch / t,
                   "output_bytes_per_second": out_bytes * args.batch / t, "launches_per_window": count,
                   "note": "the sources (16 MB) stay in the Infinity Cache between launches"})
-    t, count = device_time(lambda: ops.pose_mask_box(staged.blob, meta, meta_host, args.batch, desc_off), args.reps, args.inner, args.window)
+    t, count = device_time(lambda: ops.pose_mask_box(blob, meta, meta_host, args.batch, desc_off), args.reps, args.inner, args.window)
     lines.append({"what": "maskbox", "seconds_per_mask": t / args.batch, "mask_bytes_per_second": SRC[0] * SRC[1] * args.batch / t,
                   "launches_per_window": count})
 

@@ -135,6 +135,10 @@ SIGNATURES = {
     # resize + rotate back (host/matting.py)
     "dm4d_matting_input_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i]),
     "dm4d_matting_mask_f16_u8": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _i, _i, _i]),
+    # complete PNG files (L and RGBA) of a batch of images, deflate and checksums included (host/png.py)
+    "dm4d_png_bound": (C.c_size_t, [_i, _i, _i]),
+    "dm4d_png_ws_bytes": (C.c_size_t, [_i64, _i64, _i]),
+    "dm4d_png_encode_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp]),
 }
 
 # The constants of include/dm4d.h that the host uses, under the header's names without the DM4D_ prefix.  This block is their ONLY
@@ -175,6 +179,11 @@ POSE_MAX_HEATMAP_W = 1024
 POSE_TAB_LIMIT = 1 << 29
 MATTING_FIELDS = 8
 MATTING_MAX_SIDE = 16384
+PNG_FIELDS = 16
+PNG_L = 0
+PNG_RGBA = 1
+PNG_STRIPE_BYTES = 32768
+PNG_STRIPE_REC = 1712
 
 
 class Dm4dError(RuntimeError):

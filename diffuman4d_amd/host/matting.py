@@ -16,6 +16,10 @@ directory (``load_matting_model``) or hands over any callable (``matting_model``
 
 Both are byte-exact to the reference's Pillow + torch CPU route.  There is no CPU path: a ``device`` that is not a HIP device is an
 error.
+
+``remove_background(device_png=True)`` also keeps the mask planes and the staged source bytes on the device and lets host/png.py
+encode the mask and RGBA PNG files there; only file bytes come down.  Those files decode to the same pixels as the default route's
+and differ from them in bytes (DESIGN.md "Device PNG").
 """
 from __future__ import annotations
 
@@ -115,6 +119,11 @@ def _plan(sizes: Sequence[Tuple[int, int]], net: Tuple[int, int], rot: int, to_n
 
 
 def _inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: int, dtype: torch.dtype, pool: Optional[ThreadPoolExecutor]) -> torch.Tensor:
+    return _staged_inputs(ims, sizes, size, dev, rot, dtype, pool)[0]
+
+
+def _staged_inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: int, dtype: torch.dtype, pool: Optional[ThreadPoolExecutor]):
+    """-> (the network's input, the staged RGB bytes on the device: every image as stored, HWC with tight rows, its byte offsets)."""
     S_h, S_w = int(size[0]), int(size[1])
     if not (1 <= S_h <= _l.MATTING_MAX_SIDE and 1 <= S_w <= _l.MATTING_MAX_SIDE):
         raise ValueError(f"size {S_h} x {S_w} is outside 1..{_l.MATTING_MAX_SIDE}")
@@ -126,7 +135,7 @@ def _inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: int, dtyp
     scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
     out = ops.matting_input(blob, meta, meta_host, len(ims), desc_off, tab_off, tab_len, _on_device(dtype, dev), scratch, S_h, S_w, rot)
     torch.cuda.current_stream().synchronize()  # the pinned buffers may go; the tensor is complete when it is handed over
-    return out
+    return out, blob, [int(v) for v in desc[:, 0]]
 
 
 def matting_inputs(images, size: Tuple[int, int] = IMAGE_SIZE, device="cuda", *, rotate_clockwise: int = 0, dtype: torch.dtype = torch.float16,
@@ -150,6 +159,14 @@ def matting_masks(logits: torch.Tensor, sizes: Sequence[Tuple[int, int]], *, rot
     [(h, w)] -> a list of uint8 [h, w] arrays, byte-equal to the reference's ``to_pil_image(logits.sigmoid()).resize((w', h'))``
     turned back by `rotate_clockwise` (w', h': the rotated image's size).  The planes are packed 16-byte aligned in one device blob and
     copied back once; the arrays are views of that one host buffer."""
+    blob, offsets, sizes, _ = _mask_blob(logits, sizes, rotate_clockwise)
+    host = blob.cpu().numpy()  # synchronises: the descriptors' host copy may go
+    return [host[off: off + h * w].reshape(h, w) for off, (h, w) in zip(offsets, sizes)]
+
+
+def _mask_blob(logits: torch.Tensor, sizes: Sequence[Tuple[int, int]], rotate_clockwise: int):
+    """``matting_masks`` up to the copy: -> (the packed mask planes on the device, their byte offsets, the checked sizes, the host
+    copy of the descriptors, which the caller keeps until it has synchronised the stream)."""
     rot = _quarter_turns(rotate_clockwise)
     if not isinstance(logits, torch.Tensor) or logits.device.type != "cuda":
         raise _l.Dm4dError("logits: expected a tensor on a HIP device (no CPU fallback in diffuman4d_amd)")
@@ -170,8 +187,7 @@ def matting_masks(logits: torch.Tensor, sizes: Sequence[Tuple[int, int]], *, rot
         scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
         blob = ops.matting_mask(logits.to(torch.float16).contiguous(), meta, meta_host, n, desc_off, tab_off, tab_len, _on_device("q", dev),
                                 scratch, blob_bytes, rot)
-        host = blob.cpu().numpy()  # synchronises: meta_host may go
-    return [host[int(desc[k, 0]): int(desc[k, 0]) + h * w].reshape(h, w) for k, (h, w) in enumerate(sizes)]
+    return blob, [int(v) for v in desc[:, 0]], sizes, meta_host
 
 
 # -- the stage -------------------------------------------------------------------------------------------------------------------------
@@ -227,26 +243,55 @@ def pending_batches(fmask_paths: Sequence[str], batch_size: int, skip_exists: bo
 def write_mask(mask: np.ndarray, fmask_path: str, image_src=None, image_alpha_path: Optional[str] = None) -> None:
     """``Image.fromarray(mask).save(fmask_path)`` and, with `image_alpha_path`, the image (in its stored orientation) with the mask as
     its alpha channel (``putalpha``, remove_background.py:89-93).  Both appear atomically."""
-    fmask = Image.fromarray(mask)
-    _st.atomic_write(fmask_path, fmask.save)
+    _st.atomic_write(fmask_path, Image.fromarray(mask).save)
     if image_alpha_path is not None:
-        image = _st.open_image(image_src).copy()
-        image.putalpha(fmask)
-        _st.atomic_write(image_alpha_path, image.save)
+        write_image_alpha(mask, image_src, image_alpha_path)
+
+
+def write_image_alpha(mask: np.ndarray, image_src, image_alpha_path: str) -> None:
+    """The image (in its stored orientation) with `mask` as its alpha channel (``putalpha``), written atomically."""
+    image = _st.open_image(image_src).copy()
+    image.putalpha(Image.fromarray(mask))
+    _st.atomic_write(image_alpha_path, image.save)
+
+
+def _store_bytes(path: str, data: bytes) -> None:
+    def write(tmp):
+        with open(tmp, "wb") as f:
+            f.write(data)
+    _st.atomic_write(path, write)
+
+
+def _store_device_files(fmask_path: str, fmask_file: bytes, image_alpha_path: Optional[str], alpha_file: Optional[bytes], mask, image_src) -> None:
+    """One image of the `device_png` route: the files the device encoded are stored verbatim; an RGBA file the device did not encode
+    (the stored image is not RGB) is written by ``write_image_alpha`` from the mask plane `mask`."""
+    _store_bytes(fmask_path, fmask_file)
+    if image_alpha_path is not None:
+        if alpha_file is not None:
+            _store_bytes(image_alpha_path, alpha_file)
+        else:
+            write_image_alpha(mask, image_src, image_alpha_path)
 
 
 def remove_background(images_dir: str, out_fmasks_dir: str, out_images_alpha_dir: Optional[str] = None, model_name: Optional[str] = None,
                       image_ext: str = ".webp", mask_ext: str = ".png", rotate_clockwise: int = 0, batch_size: int = 8, num_workers: int = 4,
                       skip_exists: bool = False, gpu_ids: Optional[Sequence[int]] = None, *, matting_model: Optional[Callable] = None,
-                      image_size: Tuple[int, int] = IMAGE_SIZE) -> dict:
+                      image_size: Tuple[int, int] = IMAGE_SIZE, device_png: bool = False) -> dict:
     """Predict the foreground mask of every ``**/*{image_ext}`` under `images_dir` and write ``out_fmasks_dir/{camera}/{frame}{mask_ext}``
     (and the RGBA images under `out_images_alpha_dir`), with the reference's arguments in its names and order.
 
     matting_model: any callable taking fp16 [n, 3, S_h, S_w] on the device and returning a tensor [n, 1, S_h, S_w] of logits on the
     device, or a list / tuple of tensors of which the last is taken (BiRefNet's side outputs); by default
     ``load_matting_model(model_name)``, once per GPU.  It is the caller's network: its output never visits the host.  One worker thread
-    per GPU id; decoding and the PNG files go through a pool of `num_workers` threads.  Returns counts."""
+    per GPU id; decoding and the PNG files go through a pool of `num_workers` threads.  Returns counts.
+
+    device_png: the mask planes and the staged source bytes stay on the device and host/png.py encodes ``fmasks/*.png`` (L) and, with
+    `out_images_alpha_dir`, ``images_alpha/*.png`` (RGBA = staged RGB + mask) there; only file bytes come down and the pool's threads
+    store them.  The files decode to the same pixels as the default route's and differ from them in bytes (DESIGN.md "Device PNG").
+    `mask_ext` must be ``.png``.  An image whose stored mode is not RGB gets its RGBA file from the default route's ``putalpha``."""
     rot = _quarter_turns(rotate_clockwise)
+    if device_png and mask_ext != ".png":
+        raise ValueError(f"device_png writes PNG files: mask_ext must be '.png', got {mask_ext!r}")
     if matting_model is None:
         if not model_name:
             raise ValueError("name the matting network: model_name (a local directory) or matting_model (a callable)")
@@ -263,14 +308,33 @@ def remove_background(images_dir: str, out_fmasks_dir: str, out_images_alpha_dir
 
     def process_batch(model: Callable, batch: List[int], dev: torch.device, pool: ThreadPoolExecutor) -> List:
         ims, sizes = _open_all([images[k] for k in batch], pool)
-        out = model(_inputs(ims, sizes, size, dev, rot, torch.float16, pool))
+        net_in, staged, src_at = _staged_inputs(ims, sizes, size, dev, rot, torch.float16, pool)
+        out = model(net_in)
         if isinstance(out, (list, tuple)) and len(out) > 0:
             out = out[-1]
         if not isinstance(out, torch.Tensor) or out.device.type != "cuda" or tuple(out.shape) != (len(batch), 1) + size:
             raise _l.Dm4dError(f"matting_model: expected a [{len(batch)}, 1, {size[0]}, {size[1]}] tensor on the device (or a list "
                                "of tensors that ends in one)")
-        masks = matting_masks(out, sizes, rotate_clockwise=rotate_clockwise)
-        return [pool.submit(write_mask, masks[r], fmasks[k], images[k], alphas[k]) for r, k in enumerate(batch)]
+        if not device_png:
+            del staged
+            masks = matting_masks(out, sizes, rotate_clockwise=rotate_clockwise)
+            return [pool.submit(write_mask, masks[r], fmasks[k], images[k], alphas[k]) for r, k in enumerate(batch)]
+        from . import png
+        blob, mask_at, _, keep = _mask_blob(out, sizes, rotate_clockwise)
+        items = [(png.L, h, w, mask_at[r], w) for r, (h, w) in enumerate(sizes)]
+        rgba = [r for r, k in enumerate(batch) if alphas[k] is not None and ims[r].mode == "RGB"]
+        items += [(png.RGBA, sizes[r][0], sizes[r][1], src_at[r], 3 * sizes[r][1], mask_at[r], sizes[r][1]) for r in rgba]
+        files = png.png_encode_planes(blob, staged if rgba else None, items)  # synchronises
+        del keep
+        alpha_file = {r: files[len(batch) + j] for j, r in enumerate(rgba)}
+        writes = []
+        for r, k in enumerate(batch):
+            h, w = sizes[r]
+            host_mask = None
+            if alphas[k] is not None and r not in alpha_file:
+                host_mask = blob[mask_at[r]: mask_at[r] + h * w].cpu().numpy().reshape(h, w)
+            writes.append(pool.submit(_store_device_files, fmasks[k], files[r], alphas[k], alpha_file.get(r), host_mask, images[k]))
+        return writes
 
     load_model = lambda dev: matting_model if matting_model is not None else load_matting_model(model_name, dev)
     result["written"] = _st.run_stage("remove_background", gpu_ids, num_workers, "dm4d-matting", batches, load_model, process_batch)

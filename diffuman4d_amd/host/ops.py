@@ -1229,3 +1229,26 @@ def matting_mask(logits: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tens
     _l.call("dm4d_matting_mask_f16_u8", _stream(), _p(logits), host + desc_off, dev + desc_off, n, host + tab_off, dev + tab_off, tab_len,
             _p(qtab), _p(scratch), scratch.numel(), _p(blob), blob_bytes, int(logits.shape[2]), int(logits.shape[3]), rot)
     return blob
+
+
+def png_encode(planes: torch.Tensor, rgb: Optional[torch.Tensor], desc: torch.Tensor, blob_bytes: int, ws_bytes: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Complete PNG files of the images that `desc` (host int64 [n, PNG_FIELDS], include/dm4d.h) names in the device uint8 buffers
+    `planes` (L planes and alpha planes) and `rgb` (packed RGB images; None when there is no RGBA image) -> (blob of `blob_bytes` on the
+    device, device int64 [2 n]: the files' offsets in it, then their lengths).  Five launches on the current stream; nothing is
+    synchronised.  The library checks every descriptor against the buffers before it launches."""
+    _req(planes, "planes", torch.uint8)
+    if rgb is not None:
+        _req(rgb, "rgb", torch.uint8)
+    if desc.device.type != "cpu" or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != _l.PNG_FIELDS or not desc.is_contiguous() \
+            or desc.shape[0] < 1:
+        raise _l.Dm4dError(f"desc: expected a contiguous host int64 [n, {_l.PNG_FIELDS}] tensor")
+    if not planes.is_contiguous() or planes.numel() == 0 or (rgb is not None and (not rgb.is_contiguous() or rgb.device != planes.device)):
+        raise _l.Dm4dError("planes / rgb: expected contiguous non-empty tensors on one device")
+    n, dev = int(desc.shape[0]), planes.device
+    ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+    blob = torch.empty(blob_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(2 * n, dtype=torch.int64, device=dev)
+    desc_dev = desc.to(dev)
+    _l.call("dm4d_png_encode_u8", _stream(), _p(planes), planes.numel(), _p(rgb), 0 if rgb is None else rgb.numel(), desc.data_ptr(),
+            _p(desc_dev), n, _p(ws), ws.numel() * 8, _p(blob), blob.numel(), _p(out))
+    return blob, out

@@ -256,6 +256,13 @@ class SamplingRunner:
             gpu_ids = sorted({d.index for d in devices if isinstance(d, torch.device) and d.type == "cuda" and d.index is not None}) or None
         return evaluate_results(gpu_ids=gpu_ids, **_evaluation_arguments(self.sampler), **extra)
 
+    def to_nerfstudio(self, **kw) -> dict:
+        """The nerfstudio export of the result directory (the reference's ``to_nerfstudio``, sampling_runner.py:79-84: the scene
+        directory, the output directory and the input cameras come from the sampler; host/nerfstudio.py).  `kw`: the keyword-only
+        arguments of ``diffuman4d_to_nerfstudio`` (``matting_model_dir`` or ``matting_model``, ``device_png``, ``batch_size`` ...)."""
+        from .nerfstudio import diffuman4d_to_nerfstudio
+        return diffuman4d_to_nerfstudio(**_nerfstudio_arguments(self.sampler), **kw)
+
 
 def _evaluation_arguments(s: SlidingIterativeSampler) -> dict:
     """The reference's evaluate_results call (sampling_runner.py:65-77): predicted .jpg, captured .webp, mask .png, the target
@@ -264,6 +271,11 @@ def _evaluation_arguments(s: SlidingIterativeSampler) -> dict:
     return dict(pred_images_dir=f"{s.output_dir}/images", gt_images_dir=f"{scene}/images", fmasks_dir=f"{scene}/fmasks",
                 pred_image_ext=".jpg", gt_image_ext=".webp", fmask_ext=".png", spa_labels=s.target_spa_labels, tem_labels=s.tem_labels,
                 out_metrics_path=f"{s.output_dir}/metrics.json", crop_with_fmask=True, background_color="white")
+
+
+def _nerfstudio_arguments(s: SlidingIterativeSampler) -> dict:
+    """The reference's diffuman4d_to_nerfstudio call (sampling_runner.py:79-84)."""
+    return dict(data_dir=f"{s.dataset.data_dir}/{s.dataset.scene_label}", result_dir=s.output_dir, input_cameras=s.input_spa_labels)
 
 
 class DistributedSamplingRunner:
@@ -592,3 +604,13 @@ class DistributedSamplingRunner:
         if self.rank != 0:
             return None
         return aggregate_metrics([v for part in gathered for v in part], out_path)
+
+    def to_nerfstudio(self, **kw):
+        """``SamplingRunner.to_nerfstudio`` on rank 0 alone, behind a barrier (every image is on disk); the other ranks wait at a
+        second barrier until the export is written.  -> the counts on rank 0, None elsewhere."""
+        from .nerfstudio import diffuman4d_to_nerfstudio
+        self.dist.barrier(self.group)
+        try:
+            return diffuman4d_to_nerfstudio(**_nerfstudio_arguments(self.sampler), **kw) if self.rank == 0 else None
+        finally:
+            self.dist.barrier(self.group)

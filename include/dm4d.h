@@ -510,6 +510,34 @@ int dm4d_matting_mask_f16_u8(void* stream, const void* logits, const int64_t* de
                              const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len, const void* qtab_dev, void* scratch,
                              int64_t scratch_bytes, void* blob, int64_t blob_bytes, int S_h, int S_w, int rot);
 
+/* PNG files on the device (png.hip; diffuman4d_amd/host/png.py, the `device_png` route of host/matting.py::remove_background): n 8-bit
+ *   images of different sizes -> n complete files back to back in blob, every byte made on the device (signature, IHDR, one IDAT chunk
+ *   per stripe, IEND, the chunk CRC-32s, the zlib header and the Adler-32).  tests/png_model.py is the definition in numpy and DESIGN.md
+ *   "Device PNG" its text: Paeth filter (type 4) on every row; the filtered stream (R = 1 + w * channels bytes a row) in stripes of
+ *   max(1, DM4D_PNG_STRIPE_BYTES / R) whole rows; in a stripe a maximal run of n equal bytes = a literal, (n - 1) / 258 matches of length
+ *   258 at distance 1, and the rest r as one match (r >= 3) or r literals; one dynamic-Huffman block per stripe from a canonical code
+ *   built on the device (lengths at most 15, and 7 for the code-length alphabet), then an empty stored block to the byte boundary.
+ *   Integer only; five launches whatever n is; no workgroup waits on another; LDS integer atomics only; a file depends on its image
+ *   alone and is the same in every call.
+ * desc: n x DM4D_PNG_FIELDS int64 = {kind: DM4D_PNG_L or DM4D_PNG_RGBA | h, w in 1..DM4D_MATTING_MAX_SIDE | L: byte offset of the plane
+ *   in `planes`; RGBA: of the packed 3-byte RGB image in `rgb` | its row stride in bytes (>= w, >= 3 w) | RGBA: byte offset of the alpha
+ *   plane in `planes`, and its row stride; L: 0, 0 | byte offset of the image's filtered stream = the sum of h * R before it | index of
+ *   its first stripe = the stripes before it | 0 ...}.  desc_host is the host copy of desc_dev, validated before anything is launched.
+ * dm4d_png_bound(h, w, channels 1 or 4) = 64 + 576 stripes + 2 h R (0 out of range): a token costs at most 15 bits per byte it covers,
+ *   a block header at most 17 + 57 + 288 x 14 bits.  blob_bytes >= the sum of the images' bounds, or the call is an error.
+ * out: device int64 [2 n] = n byte offsets into blob, then n lengths; the host copies blob[: offset[n - 1] + length[n - 1]].
+ * workspace: dm4d_png_ws_bytes(sum of h * R, total stripes, n) bytes, 16-byte aligned (0 for counts out of range).                    */
+#define DM4D_PNG_FIELDS 16
+#define DM4D_PNG_L 0
+#define DM4D_PNG_RGBA 1
+#define DM4D_PNG_STRIPE_BYTES 32768
+#define DM4D_PNG_STRIPE_REC 1712
+size_t dm4d_png_bound(int h, int w, int channels);
+size_t dm4d_png_ws_bytes(int64_t filtered_bytes, int64_t stripes, int n);
+int dm4d_png_encode_u8(void* stream, const void* planes, int64_t planes_bytes, const void* rgb, int64_t rgb_bytes, const int64_t* desc_host,
+                       const int64_t* desc_dev, int n, void* workspace, int64_t workspace_bytes, void* blob, int64_t blob_bytes,
+                       int64_t* out);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

@@ -72,7 +72,22 @@ def inference(cfg: dict):
         if metrics is not None:  # every rank evaluates, rank 0 holds the result
             log.info("Metrics: %s (per view: %s/metrics.json)", metrics["mean"], sampler.output_dir)
     if cfg.get("to_nerfstudio"):
-        log.warning("to_nerfstudio is a post-processing step of the reference that is out of scope here")
+        # nerfstudio.matting_model_dir=PATH: the matting network (a local directory in the Hugging Face layout; never fetched here) that
+        # the export's masks need.  nerfstudio.device_png=true: encode the mask / RGBA PNG files on the GPU; nerfstudio.batch_size=N
+        ns = cfg.get("nerfstudio") or {}
+        if ns.get("matting_model_dir"):
+            kw = {"matting_model_dir": str(ns["matting_model_dir"]), "device_png": _as_bool(ns.get("device_png", False))}
+            if ns.get("batch_size") is not None:
+                kw["batch_size"] = int(ns["batch_size"])
+            runner.to_nerfstudio(**kw)
+        else:
+            log.warning("to_nerfstudio is a post-processing step of the reference whose matting network is out of scope here: name a "
+                        "local copy of it with nerfstudio.matting_model_dir=PATH (optionally nerfstudio.device_png=true "
+                        "nerfstudio.batch_size=N) to run the export, or pass to_nerfstudio=false")
+
+
+def _as_bool(v) -> bool:
+    return v.strip().lower() in ("1", "true", "yes", "on") if isinstance(v, str) else bool(v)
 
 
 def main(argv=None):

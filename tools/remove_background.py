@@ -38,6 +38,8 @@ def main(argv=None) -> int:
     ap.add_argument("--skip_exists", action="store_true", help="skip a batch whose masks all exist and verify")
     ap.add_argument("--gpu_ids", type=_ints, default=None, help="e.g. 0,1 (default: every device)")
     ap.add_argument("--image_size", type=_ints, default=[1024, 1024], help="network input height,width")
+    ap.add_argument("--device_png", action="store_true",
+                    help="encode the mask and RGBA PNG files on the GPU (host/png.py): same pixels as the default route, other bytes")
     args = ap.parse_args(argv)
     if len(args.image_size) != 2:
         ap.error("--image_size takes height,width")
@@ -47,7 +49,7 @@ def main(argv=None) -> int:
     from diffuman4d_amd.host import matting
     res = matting.remove_background(args.images_dir, args.out_fmasks_dir, args.out_images_alpha_dir, model, args.image_ext, args.mask_ext,
                                     args.rotate_clockwise, args.batch_size, args.num_workers, args.skip_exists, args.gpu_ids,
-                                    image_size=tuple(args.image_size))
+                                    image_size=tuple(args.image_size), device_png=args.device_png)
     print(json.dumps(res))
     return 0
 

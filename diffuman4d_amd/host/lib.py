@@ -139,6 +139,9 @@ SIGNATURES = {
     "dm4d_png_bound": (C.c_size_t, [_i, _i, _i]),
     "dm4d_png_ws_bytes": (C.c_size_t, [_i64, _i64, _i]),
     "dm4d_png_encode_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp]),
+    # baseline JPEG files decoded into a caller's buffer: speculative Huffman decoding, IDCT, up-sampling, colour (host/jpegdec.py)
+    "dm4d_jpeg_decode_ws_bytes": (C.c_size_t, [_i64, _i]),
+    "dm4d_jpeg_decode_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
 }
 
 # The constants of include/dm4d.h that the host uses, under the header's names without the DM4D_ prefix.  This block is their ONLY
@@ -184,6 +187,15 @@ PNG_L = 0
 PNG_RGBA = 1
 PNG_STRIPE_BYTES = 32768
 PNG_STRIPE_REC = 1712
+JPEGDEC_FIELDS = 16
+JPEGDEC_TABLE_BYTES = 1104
+JPEGDEC_SUB_BITS = 1024
+JPEGDEC_TILE_LANES = 256
+JPEGDEC_MAX_SCAN_BYTES = 1 << 28
+JPEGDEC_ST_BAD_CODE = 1
+JPEGDEC_ST_ZIGZAG = 2
+JPEGDEC_ST_END = 4
+JPEGDEC_ST_RANGE = 8
 
 
 class Dm4dError(RuntimeError):

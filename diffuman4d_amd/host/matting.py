@@ -122,15 +122,43 @@ def _inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: int, dtyp
     return _staged_inputs(ims, sizes, size, dev, rot, dtype, pool)[0]
 
 
-def _staged_inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: int, dtype: torch.dtype, pool: Optional[ThreadPoolExecutor]):
-    """-> (the network's input, the staged RGB bytes on the device: every image as stored, HWC with tight rows, its byte offsets)."""
+def _device_files(ims, sizes) -> dict:
+    """{index: (plan, file bytes)} of the images that were opened from baseline JPEG files of the set csrc/jpegdec.hip decodes."""
+    from . import jpegdec
+    out = {}
+    for k, im in enumerate(ims):
+        name = getattr(im, "filename", "")
+        if im.format == "JPEG" and name and im.mode in ("RGB", "L"):
+            data = jpegdec.read_file(name)
+            plan = jpegdec.probe(data)
+            if plan is not None and (plan.h, plan.w) == tuple(sizes[k]) and plan.mode == im.mode:
+                out[k] = (plan, data)
+    return out
+
+
+def _staged_inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: int, dtype: torch.dtype, pool: Optional[ThreadPoolExecutor],
+                   device_decode: bool = False):
+    """-> (the network's input, the staged RGB bytes on the device: every image as stored, HWC with tight rows, its byte offsets).
+    device_decode: images opened from supported JPEG files upload their file bytes and are decoded into their regions on the device
+    (host/jpegdec.py; a grayscale file replicated, as convert("RGB") does); the others, and files the decoder refuses, keep the
+    Pillow fill."""
     S_h, S_w = int(size[0]), int(size[1])
     if not (1 <= S_h <= _l.MATTING_MAX_SIDE and 1 <= S_w <= _l.MATTING_MAX_SIDE):
         raise ValueError(f"size {S_h} x {S_w} is outside 1..{_l.MATTING_MAX_SIDE}")
     desc, tab, plane_bytes, scratch_bytes = _plan(sizes, (S_h, S_w), rot, True)
     host = _st.pinned(plane_bytes, dev)
-    _st.fill(host.numpy(), [(int(desc[k, 0]), (im, "RGB")) for k, im in enumerate(ims)], pool)
+    on_device = _device_files(ims, sizes) if device_decode else {}
+    _st.fill(host.numpy(), [(int(desc[k, 0]), (im, "RGB")) for k, im in enumerate(ims) if k not in on_device], pool)
     blob = host.to(dev, non_blocking=True)
+    if on_device:
+        from . import jpegdec
+        ks = sorted(on_device)
+        status = jpegdec.decode_plans([on_device[k][0] for k in ks], [on_device[k][1] for k in ks], blob, [int(desc[k, 0]) for k in ks],
+                                      [3] * len(ks))
+        for k, st in zip(ks, status):
+            if st:  # the decoder refused the scan: Pillow's pixels (or Pillow's exception)
+                a = np.array(ims[k].convert("RGB")).reshape(-1)
+                blob[int(desc[k, 0]): int(desc[k, 0]) + a.size].copy_(torch.from_numpy(a))
     meta, meta_host, tab_off, tab_len, desc_off = _st.pack_meta(tab, desc, dev)
     scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
     out = ops.matting_input(blob, meta, meta_host, len(ims), desc_off, tab_off, tab_len, _on_device(dtype, dev), scratch, S_h, S_w, rot)
@@ -276,7 +304,7 @@ def _store_device_files(fmask_path: str, fmask_file: bytes, image_alpha_path: Op
 def remove_background(images_dir: str, out_fmasks_dir: str, out_images_alpha_dir: Optional[str] = None, model_name: Optional[str] = None,
                       image_ext: str = ".webp", mask_ext: str = ".png", rotate_clockwise: int = 0, batch_size: int = 8, num_workers: int = 4,
                       skip_exists: bool = False, gpu_ids: Optional[Sequence[int]] = None, *, matting_model: Optional[Callable] = None,
-                      image_size: Tuple[int, int] = IMAGE_SIZE, device_png: bool = False) -> dict:
+                      image_size: Tuple[int, int] = IMAGE_SIZE, device_png: bool = False, device_decode: bool = False) -> dict:
     """Predict the foreground mask of every ``**/*{image_ext}`` under `images_dir` and write ``out_fmasks_dir/{camera}/{frame}{mask_ext}``
     (and the RGBA images under `out_images_alpha_dir`), with the reference's arguments in its names and order.
 
@@ -288,7 +316,11 @@ def remove_background(images_dir: str, out_fmasks_dir: str, out_images_alpha_dir
     device_png: the mask planes and the staged source bytes stay on the device and host/png.py encodes ``fmasks/*.png`` (L) and, with
     `out_images_alpha_dir`, ``images_alpha/*.png`` (RGBA = staged RGB + mask) there; only file bytes come down and the pool's threads
     store them.  The files decode to the same pixels as the default route's and differ from them in bytes (DESIGN.md "Device PNG").
-    `mask_ext` must be ``.png``.  An image whose stored mode is not RGB gets its RGBA file from the default route's ``putalpha``."""
+    `mask_ext` must be ``.png``.  An image whose stored mode is not RGB gets its RGBA file from the default route's ``putalpha``.
+
+    device_decode: inputs that are baseline JPEG files of the supported set (host/jpegdec.py::probe) are not decoded by Pillow: their
+    file bytes go up and csrc/jpegdec.hip decodes them into the staged RGB regions, byte for byte Pillow's pixels, so every file
+    written is the same as without it.  Other inputs keep the Pillow route."""
     rot = _quarter_turns(rotate_clockwise)
     if device_png and mask_ext != ".png":
         raise ValueError(f"device_png writes PNG files: mask_ext must be '.png', got {mask_ext!r}")
@@ -308,7 +340,7 @@ def remove_background(images_dir: str, out_fmasks_dir: str, out_images_alpha_dir
 
     def process_batch(model: Callable, batch: List[int], dev: torch.device, pool: ThreadPoolExecutor) -> List:
         ims, sizes = _open_all([images[k] for k in batch], pool)
-        net_in, staged, src_at = _staged_inputs(ims, sizes, size, dev, rot, torch.float16, pool)
+        net_in, staged, src_at = _staged_inputs(ims, sizes, size, dev, rot, torch.float16, pool, device_decode)
         out = model(net_in)
         if isinstance(out, (list, tuple)) and len(out) > 0:
             out = out[-1]

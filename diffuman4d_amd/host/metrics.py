@@ -55,14 +55,39 @@ def resized_size(h: int, w: int, canvas_size: int) -> Tuple[int, int]:
     return (new_long, new_short) if w <= h else (new_short, new_long)
 
 
-def _load(x: ImageLike, channels: int):
+class _DeviceJpeg:
+    """An RGB file the device will decode into its region of the staging blob (host/jpegdec.py): it stands where the decoded uint8
+    [h, w, 3] array would, with its shape, dtype and size, and holds the file's bytes and plan instead of pixels."""
+    dtype = np.dtype(np.uint8)
+
+    def __init__(self, path, plan, data: bytes):
+        self.path, self.plan, self.data = path, plan, data
+        self.shape = (plan.h, plan.w, 3)
+        self.nbytes = plan.h * plan.w * 3
+
+    def pixels(self) -> np.ndarray:
+        """The Pillow route of the same file."""
+        with Image.open(self.path) as im:
+            return np.asarray(im)
+
+
+def _load(x: ImageLike, channels: int, device_decode: bool = False):
     """A path -> uint8 [h, w, 3] / [h, w] (what TF.to_tensor would divide by 255); a tensor -> fp32 [3, h, w] / [h, w] on the host.
-    A uint8 numpy array is taken as an already decoded file (np.asarray(Image.open(path)))."""
+    A uint8 numpy array is taken as an already decoded file (np.asarray(Image.open(path))).  device_decode: the path of a baseline
+    JPEG file the device decodes (host/jpegdec.py::probe) is not decoded here -> a _DeviceJpeg; the mode check is made on its header."""
     if isinstance(x, np.ndarray):
         if x.dtype != np.uint8 or x.ndim != (3 if channels == 3 else 2) or (channels == 3 and x.shape[2] != 3):
             raise ValueError(f"expected a decoded uint8 [h, w{', 3' if channels == 3 else ''}] array, got {x.dtype} {x.shape}")
         return np.ascontiguousarray(x)
     if isinstance(x, (str, os.PathLike)):
+        if device_decode and channels == 3:
+            from . import jpegdec
+            data = jpegdec.read_file(x)
+            plan = jpegdec.probe(data)
+            if plan is not None:
+                if plan.mode != "RGB":
+                    raise ValueError(f"{x}: image mode {plan.mode!r}, expected 'RGB' (no conversion is made: it would change values)")
+                return _DeviceJpeg(x, plan, data)
         with Image.open(x) as im:
             want = "RGB" if channels == 3 else "L"
             if im.mode != want:
@@ -98,8 +123,13 @@ class ImageEvaluator:
     background_color) -> (psnr, ssim, lpips)``; ``evaluate_batch`` takes many such argument sets and spends one upload and one
     library call on them.  Results are Python floats (fp64 of the device's fp64 means)."""
 
-    def __init__(self, device, lpips: Optional[Callable] = None, decode_threads: int = 8):
+    def __init__(self, device, lpips: Optional[Callable] = None, decode_threads: int = 8, device_decode: bool = False):
+        """device_decode: predictions and ground truths that are baseline JPEG files of the supported set are decoded on the device,
+        into their regions of the staging blob (host/jpegdec.py), instead of by Pillow in the decode threads: the same bytes."""
         self.device = torch.device(device)
+        self.device_decode = bool(device_decode)
+        if self.device_decode and self.device.type != "cuda":
+            raise Dm4dError(f"device_decode: device {device!r} is not a HIP device (no CPU fallback in diffuman4d_amd)")
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.lpips = lpips
@@ -109,9 +139,9 @@ class ImageEvaluator:
     # -- host half of one pair ----------------------------------------------------------------------------------------------------
     @staticmethod
     def _prepare(pred: ImageLike, gt: ImageLike, pred_fmask: Optional[ImageLike] = None, gt_fmask: Optional[ImageLike] = None,
-                 canvas_size: int = 1024, crop_with_fmask: bool = True, background_color: str = "black") -> Dict:
+                 canvas_size: int = 1024, crop_with_fmask: bool = True, background_color: str = "black", device_decode: bool = False) -> Dict:
         same_mask = pred_fmask is not None and pred_fmask is gt_fmask or (isinstance(pred_fmask, str) and pred_fmask == gt_fmask)
-        p, g = _load(pred, 3), _load(gt, 3)
+        p, g = _load(pred, 3, device_decode), _load(gt, 3, device_decode)
         pm = None if pred_fmask is None else _load(pred_fmask, 1)
         gm = pm if same_mask else (None if gt_fmask is None else _load(gt_fmask, 1))
         ps, gs = _chw_shape(p, 3), _chw_shape(g, 3)
@@ -127,6 +157,7 @@ class ImageEvaluator:
         if crop_with_fmask and (pm is None and gm is None):
             raise ValueError("Either pred_fmask or gt_fmask should be provided to crop with fmask.")
         if p.dtype != g.dtype:  # one decoded file, one tensor: both travel as fp32
+            p, g = (a.pixels() if isinstance(a, _DeviceJpeg) else a for a in (p, g))
             p, g = _as_f32(p, 3), _as_f32(g, 3)
         if pm is not None and gm is not None and pm.dtype != gm.dtype:
             pm, gm = _as_f32(pm, 1), _as_f32(gm, 1)
@@ -147,7 +178,7 @@ class ImageEvaluator:
     def _run(self, items: List[Dict], debug: bool):
         """Pack planes and descriptors into one staging buffer, upload it, launch -> (out [n, 8] fp64, boxes [n, 4], debug) on the host
         (debug stays on the device)."""
-        lay, jobs = Layout(), []
+        lay, jobs, files = Layout(), [], []
         desc = np.zeros((len(items), ops.EVAL_FIELDS), dtype=np.int64)
         for i, it in enumerate(items):
             offs = {}
@@ -159,7 +190,7 @@ class ImageEvaluator:
                     offs[name] = offs["pmask"]  # evaluate_results passes ONE mask file for both: it is decoded and uploaded once
                 else:
                     offs[name] = lay.add(a.nbytes)
-                    jobs.append((offs[name], a))
+                    (files if isinstance(a, _DeviceJpeg) else jobs).append((offs[name], a))
             mask = it["pmask"] if it["pmask"] is not None else it["gmask"]
             flags = ((ops.EVAL_IMAGE_F32 if it["pred"].dtype != np.uint8 else 0)
                      | (ops.EVAL_MASK_F32 if mask is not None and mask.dtype != np.uint8 else 0)
@@ -177,6 +208,14 @@ class ImageEvaluator:
         st = self._stream()
         with torch.cuda.device(self.device), torch.cuda.stream(st):
             dev_blob = blob.to(self.device, non_blocking=True)
+            if files:  # their regions of the blob went up unfilled: the device decodes into them
+                from . import jpegdec
+                status = jpegdec.decode_plans([a.plan for _, a in files], [a.data for _, a in files], dev_blob, [off for off, _ in files],
+                                              [3] * len(files))
+                for (off, a), s in zip(files, status):
+                    if s:  # the decoder refused the scan: Pillow's pixels (or Pillow's exception)
+                        px = np.array(a.pixels()).reshape(-1)
+                        dev_blob[off: off + px.size].copy_(torch.from_numpy(px))
             res = ops.eval_psnr_ssim(dev_blob, desc_t, desc_off, debug=debug)
             out, boxes = res[0].cpu(), res[1].cpu()
         st.synchronize()
@@ -186,7 +225,7 @@ class ImageEvaluator:
         """`pairs`: keyword sets of ``__call__``.  -> [(psnr, ssim, lpips)] in the same order; the first failing pair raises."""
         if not pairs:
             return []
-        items = list(self._pool.map(lambda kw: self._prepare(**kw), pairs))
+        items = list(self._pool.map(lambda kw: self._prepare(**kw, device_decode=self.device_decode), pairs))
         out, boxes, dbg = self._run(items, debug=self.lpips is not None)
         out, boxes = out.numpy(), boxes.numpy()
         res = []
@@ -232,14 +271,14 @@ def evaluation_keys(pred_images_dir: str, spa_labels: Optional[List[str]] = None
 def evaluate_keys(keys: List[str], device, pred_images_dir: str, gt_images_dir: str, fmasks_dir: Optional[str] = None,
                   pred_image_ext: str = ".jpg", gt_image_ext: str = ".jpg", fmask_ext: str = ".png", crop_with_fmask: bool = True,
                   background_color: str = "black", canvas_size: int = 1024, lpips: Optional[Callable] = None, batch_size: int = 16,
-                  decode_threads: int = 8, *, lpips_weights: Optional[Tuple[str, str]] = None) -> List[Dict]:
+                  decode_threads: int = 8, *, lpips_weights: Optional[Tuple[str, str]] = None, device_decode: bool = False) -> List[Dict]:
     """The reference's evaluate_on_single_gpu: [{key, psnr, ssim, lpips}] of `keys` on one device, `batch_size` pairs per launch.
     `lpips_weights` = (vgg16_path, lin_path): this worker builds its own ``LpipsVGG`` on `device` (instead of a `lpips` callable)."""
     if lpips_weights is not None:
         if lpips is not None:
             raise ValueError("pass either lpips= (a callable) or lpips_weights= (the two weight files), not both")
         lpips = _lpips.LpipsVGG(device, *lpips_weights)
-    ev = ImageEvaluator(device, lpips=lpips, decode_threads=decode_threads)
+    ev = ImageEvaluator(device, lpips=lpips, decode_threads=decode_threads, **({"device_decode": True} if device_decode else {}))
     res = []
     try:
         for i in range(0, len(keys), max(1, int(batch_size))):
@@ -280,11 +319,12 @@ def evaluate_results(pred_images_dir: str, gt_images_dir: str, fmasks_dir: Optio
                      tem_labels: Optional[List[str]] = None, out_metrics_path: Optional[str] = None, crop_with_fmask: bool = True,
                      background_color: str = "black", gpu_ids: Optional[List[int]] = None, *, canvas_size: int = 1024,
                      lpips: Optional[Callable] = None, batch_size: int = 16, decode_threads: int = 8,
-                     lpips_weights: Optional[Tuple[str, str]] = None) -> Dict:
+                     lpips_weights: Optional[Tuple[str, str]] = None, device_decode: bool = False) -> Dict:
     """The reference's ``evaluate_results`` (its keyword list, its key enumeration, its JSON): one thread per entry of `gpu_ids`
     (default: every visible device) over ``keys[i::n]``.  Keyword-only extensions: `canvas_size` (the reference always uses the
     evaluator's default, 1024), `lpips` (a callable, see the module docstring) or `lpips_weights` = (vgg16_path, lin_path) (every worker
-    thread builds its own ``LpipsVGG`` on its device), `batch_size` (pairs per launch), `decode_threads`."""
+    thread builds its own ``LpipsVGG`` on its device), `batch_size` (pairs per launch), `decode_threads`, `device_decode` (baseline
+    JPEG predictions and ground truths are decoded on the device, host/jpegdec.py: the same metrics.json)."""
     if lpips is not None and lpips_weights is not None:
         raise ValueError("pass either lpips= (a callable) or lpips_weights= (the two weight files), not both")
     keys = evaluation_keys(pred_images_dir, spa_labels, tem_labels)
@@ -300,6 +340,8 @@ def evaluate_results(pred_images_dir: str, gt_images_dir: str, fmasks_dir: Optio
               canvas_size=canvas_size, lpips=lpips, batch_size=batch_size, decode_threads=decode_threads)
     if lpips_weights is not None:
         kw["lpips_weights"] = tuple(lpips_weights)
+    if device_decode:
+        kw["device_decode"] = True
     with ThreadPoolExecutor(max_workers=n, thread_name_prefix="dm4d-eval") as ex:
         futures = [ex.submit(evaluate_keys, keys[i::n], _device_of(g), **kw) for i, g in enumerate(gpu_ids)]
         values = [v for f in futures for v in f.result()]

@@ -24,7 +24,8 @@ log = logging.getLogger(__name__)
 
 def diffuman4d_to_nerfstudio(data_dir: str, result_dir: str, input_cameras: Optional[Sequence[str]] = None, *,
                              matting_model_dir: Optional[str] = None, matting_model: Optional[Callable] = None, batch_size: int = 4,
-                             device_png: bool = False, gpu_ids: Optional[Sequence[int]] = None, skip_exists: bool = False) -> dict:
+                             device_png: bool = False, gpu_ids: Optional[Sequence[int]] = None, skip_exists: bool = False,
+                             device_decode: bool = False) -> dict:
     """`data_dir` (the scene: ``transforms.json``, ``sparse_pcd.ply``) + `result_dir` (``images/{camera}/{frame}.jpg``) -> the camera
     files, the point cloud, the foreground masks and the RGBA images in `result_dir`; the reference's arguments in its names and order.
 
@@ -34,6 +35,8 @@ def diffuman4d_to_nerfstudio(data_dir: str, result_dir: str, input_cameras: Opti
         not a local directory raises FileNotFoundError before anything is written;
       * it raises NameError when `input_cameras` is None; here ``transforms_input.json`` is simply not written in that case.
     device_png: encode the mask and RGBA PNG files on the device (``remove_background(device_png=True)``): same pixels, other bytes.
+    device_decode: decode the result JPEG files on the device instead of in Pillow (``remove_background(device_decode=True)``): the
+    same files are written.
     -> the counts of ``remove_background``."""
     if matting_model is None:
         if not matting_model_dir:
@@ -47,6 +50,6 @@ def diffuman4d_to_nerfstudio(data_dir: str, result_dir: str, input_cameras: Opti
     counts = remove_background(images_dir=f"{result_dir}/images", out_fmasks_dir=f"{result_dir}/fmasks",
                                out_images_alpha_dir=f"{result_dir}/images_alpha", model_name=matting_model_dir, image_ext=".jpg",
                                mask_ext=".png", rotate_clockwise=0, batch_size=batch_size, skip_exists=skip_exists, gpu_ids=gpu_ids,
-                               matting_model=matting_model, device_png=device_png)
+                               matting_model=matting_model, device_png=device_png, **({"device_decode": True} if device_decode else {}))
     log.info("Saved foreground masks to %s/fmasks", result_dir)
     return counts

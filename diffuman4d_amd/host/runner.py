@@ -259,7 +259,7 @@ class SamplingRunner:
     def to_nerfstudio(self, **kw) -> dict:
         """The nerfstudio export of the result directory (the reference's ``to_nerfstudio``, sampling_runner.py:79-84: the scene
         directory, the output directory and the input cameras come from the sampler; host/nerfstudio.py).  `kw`: the keyword-only
-        arguments of ``diffuman4d_to_nerfstudio`` (``matting_model_dir`` or ``matting_model``, ``device_png``, ``batch_size`` ...)."""
+        arguments of ``diffuman4d_to_nerfstudio`` (``matting_model_dir`` or ``matting_model``, ``device_png``, ``device_decode``, ``batch_size`` ...)."""
         from .nerfstudio import diffuman4d_to_nerfstudio
         return diffuman4d_to_nerfstudio(**_nerfstudio_arguments(self.sampler), **kw)
 

@@ -538,6 +538,39 @@ int dm4d_png_encode_u8(void* stream, const void* planes, int64_t planes_bytes, c
                        const int64_t* desc_dev, int n, void* workspace, int64_t workspace_bytes, void* blob, int64_t blob_bytes,
                        int64_t* out);
 
+/* Baseline JPEG files decoded on the device (jpegdec.hip; diffuman4d_amd/host/jpegdec.py): n files of the supported set (SOF0, 8 bits,
+ *   one interleaved Huffman scan without restart markers, grayscale or YCbCr at 4:4:4 / 4:2:2 / 4:2:0 -- host/jpegdec.py::probe) ->
+ *   their pixels, byte for byte libjpeg's default decompression (Huffman decoding, jidctint "islow", "fancy" up-sampling, the 16-bit
+ *   YCbCr -> RGB tables).  tests/jpegdec_model.py is the definition in numpy and DESIGN.md "Device JPEG decode" its text.  Integer only;
+ *   a fill and two launches whatever n is; no workgroup waits on another; no atomics; an image depends on its file alone and is the
+ *   same in every call.
+ * scans: the files' entropy-coded segments with the FF 00 stuffing removed, each starting on a multiple of 4 bytes.
+ * desc: n x DM4D_JPEGDEC_FIELDS int64 = {byte offset of the scan in `scans` | its bytes (1 .. DM4D_JPEGDEC_MAX_SCAN_BYTES - 1) | h, w in
+ *   1..65535 | components 1 or 3 | luma sampling factors h, v: 1 1, 2 1 or 2 2 (1 1 for one component) | byte offset of the image in
+ *   `out` | bytes per pixel there: 3 (grayscale replicated), or 1 for one component; rows tight | index of its first coefficient block =
+ *   the blocks before it, an image having MCUs x (1 or h v + 2) | 0 ...}.  desc_host is the host copy of desc_dev, validated before
+ *   anything is launched.
+ * tab: n x DM4D_JPEGDEC_TABLE_BYTES uint8 = per component (three; a grayscale file repeats its one) {DC BITS [16], DC HUFFVAL [16], AC
+ *   BITS [16], AC HUFFVAL [256]}, then per component the 64 quantisers (8-bit) in natural order.  The lookup tables are built on the
+ *   device.  tab_host is validated like libjpeg validates a DHT.
+ * The scan is decoded speculatively in subsequences of DM4D_JPEGDEC_SUB_BITS bits, DM4D_JPEGDEC_TILE_LANES of them per tile.
+ * status: device int32 [n]; nonzero (DM4D_JPEGDEC_ST_* bits) = the image's pixels are unspecified: a window no Huffman code starts, a
+ *   zig-zag index past 63, a scan that ends early or has data left over, a dequantised coefficient outside [-8192, 8191].
+ * workspace: dm4d_jpeg_decode_ws_bytes(total blocks, n) bytes (int16 [64] per block), 16-byte aligned (0 for counts out of range).  */
+#define DM4D_JPEGDEC_FIELDS 16
+#define DM4D_JPEGDEC_TABLE_BYTES 1104
+#define DM4D_JPEGDEC_SUB_BITS 1024
+#define DM4D_JPEGDEC_TILE_LANES 256
+#define DM4D_JPEGDEC_MAX_SCAN_BYTES (1 << 28)
+#define DM4D_JPEGDEC_ST_BAD_CODE 1
+#define DM4D_JPEGDEC_ST_ZIGZAG 2
+#define DM4D_JPEGDEC_ST_END 4
+#define DM4D_JPEGDEC_ST_RANGE 8
+size_t dm4d_jpeg_decode_ws_bytes(int64_t total_blocks, int n);
+int dm4d_jpeg_decode_u8(void* stream, const void* scans, int64_t scans_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
+                        const uint8_t* tab_host, const uint8_t* tab_dev, void* workspace, int64_t workspace_bytes, void* out,
+                        int64_t out_bytes, int32_t* status);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

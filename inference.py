@@ -68,17 +68,22 @@ def inference(cfg: dict):
         missing = [k for k, v in paths.items() if not v]
         if len(missing) == 1:
             raise ValueError(f"evaluation.{missing[0]} is missing: LPIPS needs both evaluation.lpips_vgg16 and evaluation.lpips_lin")
-        metrics = runner.evaluate() if missing else runner.evaluate(lpips_weights=(str(paths["lpips_vgg16"]), str(paths["lpips_lin"])))
+        # evaluation.device_decode=true: decode the result JPEG files on the GPU (host/jpegdec.py) instead of in Pillow
+        extra = {"device_decode": True} if _as_bool(ev.get("device_decode", False)) else {}
+        metrics = runner.evaluate(**extra) if missing else runner.evaluate(lpips_weights=(str(paths["lpips_vgg16"]), str(paths["lpips_lin"])), **extra)
         if metrics is not None:  # every rank evaluates, rank 0 holds the result
             log.info("Metrics: %s (per view: %s/metrics.json)", metrics["mean"], sampler.output_dir)
     if cfg.get("to_nerfstudio"):
         # nerfstudio.matting_model_dir=PATH: the matting network (a local directory in the Hugging Face layout; never fetched here) that
-        # the export's masks need.  nerfstudio.device_png=true: encode the mask / RGBA PNG files on the GPU; nerfstudio.batch_size=N
+        # the export's masks need.  nerfstudio.device_png=true: encode the mask / RGBA PNG files on the GPU; nerfstudio.batch_size=N;
+        # nerfstudio.device_decode=true: decode the result JPEG files on the GPU
         ns = cfg.get("nerfstudio") or {}
         if ns.get("matting_model_dir"):
             kw = {"matting_model_dir": str(ns["matting_model_dir"]), "device_png": _as_bool(ns.get("device_png", False))}
             if ns.get("batch_size") is not None:
                 kw["batch_size"] = int(ns["batch_size"])
+            if _as_bool(ns.get("device_decode", False)):
+                kw["device_decode"] = True
             runner.to_nerfstudio(**kw)
         else:
             log.warning("to_nerfstudio is a post-processing step of the reference whose matting network is out of scope here: name a "

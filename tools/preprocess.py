@@ -68,13 +68,15 @@ def parse_actions(text) -> list:
 
 
 def run(data_dir: str, actions, *, matting_model_dir=None, sapiens_ckpt_path=None, palette=None, batch_size: int = 8,
-        device_png: bool = False) -> list:
+        device_png: bool = False, device_decode: bool = False) -> list:
     """Run `actions` on the scene under `data_dir` (preprocess.sh:31-77) -> [(action, what its stage returned)]."""
     d = str(data_dir)
     out = []
     for act in actions:
         if act == "remove_background":
             extra = {"device_png": True} if device_png else {}
+            if device_decode:
+                extra["device_decode"] = True
             res = STAGES[act](f"{d}/images", f"{d}/fmasks", model_name=matting_model_dir, batch_size=batch_size, **extra)
         elif act == "carve_vhull":
             res = STAGES[act](f"{d}/fmasks", f"{d}/transforms.json", f"{d}/surfs")
@@ -99,6 +101,7 @@ def main(argv=None) -> int:
     ap.add_argument("--palette", default=None, help="draw_skeleton: JSON file with keypoint_colors, links and x_link_color")
     ap.add_argument("--batch_size", type=int, default=8, help="remove_background: images per batch (decrease it if memory runs out)")
     ap.add_argument("--device_png", action="store_true", help="remove_background: encode the mask PNG files on the GPU (same pixels, other bytes)")
+    ap.add_argument("--device_decode", action="store_true", help="remove_background: decode baseline JPEG inputs on the GPU (same files written)")
     args = ap.parse_args(argv)
     try:
         actions = parse_actions(args.actions)
@@ -110,7 +113,7 @@ def main(argv=None) -> int:
     if not os.path.isdir(args.data_dir):
         ap.error(f"--data_dir {args.data_dir!r} is not a directory")
     for act, res in run(args.data_dir, actions, matting_model_dir=args.matting_model_dir, sapiens_ckpt_path=args.sapiens_ckpt_path,
-                        palette=args.palette, batch_size=args.batch_size, device_png=args.device_png):
+                        palette=args.palette, batch_size=args.batch_size, device_png=args.device_png, device_decode=args.device_decode):
         print(json.dumps({"action": act, "result": res}, default=str))
     return 0
 

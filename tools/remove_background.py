@@ -40,6 +40,8 @@ def main(argv=None) -> int:
     ap.add_argument("--image_size", type=_ints, default=[1024, 1024], help="network input height,width")
     ap.add_argument("--device_png", action="store_true",
                     help="encode the mask and RGBA PNG files on the GPU (host/png.py): same pixels as the default route, other bytes")
+    ap.add_argument("--device_decode", action="store_true",
+                    help="decode baseline JPEG inputs on the GPU (host/jpegdec.py): the same files are written")
     args = ap.parse_args(argv)
     if len(args.image_size) != 2:
         ap.error("--image_size takes height,width")
@@ -49,7 +51,8 @@ def main(argv=None) -> int:
     from diffuman4d_amd.host import matting
     res = matting.remove_background(args.images_dir, args.out_fmasks_dir, args.out_images_alpha_dir, model, args.image_ext, args.mask_ext,
                                     args.rotate_clockwise, args.batch_size, args.num_workers, args.skip_exists, args.gpu_ids,
-                                    image_size=tuple(args.image_size), device_png=args.device_png)
+                                    image_size=tuple(args.image_size), device_png=args.device_png,
+                                    **({"device_decode": True} if args.device_decode else {}))
     print(json.dumps(res))
     return 0
 

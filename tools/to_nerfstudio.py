@@ -34,13 +34,15 @@ def main(argv=None) -> int:
     ap.add_argument("--input_cameras", type=_labels, default=None, help="camera labels of the input views, e.g. 01,13,25,37")
     ap.add_argument("--matting_model_dir", required=True, help="the matting network, a local directory (nothing is downloaded)")
     ap.add_argument("--device_png", action="store_true", help="encode the mask and RGBA PNG files on the GPU")
+    ap.add_argument("--device_decode", action="store_true", help="decode the result JPEG files on the GPU (the same files are written)")
     ap.add_argument("--batch_size", type=int, default=4)
     ap.add_argument("--gpu_ids", type=_ints, default=None, help="e.g. 0,1 (default: every device)")
     ap.add_argument("--skip_exists", action="store_true", help="skip a batch whose masks all exist and verify")
     args = ap.parse_args(argv)
     from diffuman4d_amd.host.nerfstudio import diffuman4d_to_nerfstudio
     res = diffuman4d_to_nerfstudio(args.data_dir, args.result_dir, args.input_cameras, matting_model_dir=args.matting_model_dir,
-                                   batch_size=args.batch_size, device_png=args.device_png, gpu_ids=args.gpu_ids, skip_exists=args.skip_exists)
+                                   batch_size=args.batch_size, device_png=args.device_png, gpu_ids=args.gpu_ids, skip_exists=args.skip_exists,
+                                   **({"device_decode": True} if args.device_decode else {}))
     print(json.dumps(res))
     return 0
 

@@ -51,9 +51,9 @@ __device__ __forceinline__ double project_row(const double* p, double X0, double
   return __dadd_rn(__dadd_rn(__dadd_rn(__dmul_rn(p[0], X0), __dmul_rn(p[1], X1)), __dmul_rn(p[2], X2)), p[3]);
 }
 
-// bits[b][y][w]: bit (x & 31) of word x >> 5 = masks[b][y][x] != 0; the tail bits of a row's last word are 0
+// bits[b][y][w]: bit (x & 31) of word x >> 5 = masks[b][y][x] >= thr (1: nonzero); the tail bits of a row's last word are 0
 __global__ void __launch_bounds__(kThreads) vhull_pack_kernel(const uint8_t* __restrict__ masks, uint32_t* __restrict__ bits, int64_t rows,
-                                                              int W, int words) {
+                                                              int W, int words, uint32_t thr) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= rows * words) return;
   const int64_t line = i / words;  // which (view, image row)
@@ -67,11 +67,11 @@ __global__ void __launch_bounds__(kThreads) vhull_pack_kernel(const uint8_t* __r
       const uint32_t four = src4[q];
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if ((four >> (8 * j)) & 0xffu) v |= 1u << (4 * q + j);
+        if (((four >> (8 * j)) & 0xffu) >= thr) v |= 1u << (4 * q + j);
     }
   } else {
     for (int j = 0; j < 32 && x0 + j < W; ++j)
-      if (src[j]) v |= 1u << j;
+      if (src[j] >= thr) v |= 1u << j;
   }
   bits[i] = v;
 }
@@ -159,7 +159,8 @@ int64_t blocks_of(int64_t n) { return (n + kThreads - 1) / kThreads; }
 
 }  // namespace
 
-extern "C" int dm4d_vhull_pack_masks(void* stream, const void* masks, void* bits, int B, int H, int W) {
+extern "C" int dm4d_vhull_pack_masks_u8(void* stream, const void* masks, void* bits, int B, int H, int W, int threshold) {
+  if (threshold < 1 || threshold > 255) return dm4d_set_error(DM4D_ERR_ARG, "vhull_pack_masks: threshold outside 1..255");
   if (!masks || !bits) return dm4d_set_error(DM4D_ERR_ARG, "vhull_pack_masks: null pointer");
   if (B <= 0 || H <= 0 || W <= 0 || B > 65535 || H > (1 << 16) || W > (1 << 16))
     return dm4d_set_error(DM4D_ERR_ARG, "vhull_pack_masks: empty or oversized shape");
@@ -169,8 +170,12 @@ extern "C" int dm4d_vhull_pack_masks(void* stream, const void* masks, void* bits
   const int64_t grid = (rows * words + kThreads - 1) / kThreads;
   if (grid > 0x7fffffffll) return dm4d_set_error(DM4D_ERR_ARG, "vhull_pack_masks: too many mask words for one launch");
   hipLaunchKernelGGL(vhull_pack_kernel, dim3((unsigned)grid), dim3(kThreads), 0, (hipStream_t)stream, (const uint8_t*)masks, (uint32_t*)bits,
-                     rows, W, words);
+                     rows, W, words, (uint32_t)threshold);
   return dm4d_check_launch("vhull_pack_kernel");
+}
+
+extern "C" int dm4d_vhull_pack_masks(void* stream, const void* masks, void* bits, int B, int H, int W) {
+  return dm4d_vhull_pack_masks_u8(stream, masks, bits, B, H, W, 1);
 }
 
 extern "C" size_t dm4d_vhull_ws_bytes(int64_t n_voxels) {

@@ -112,6 +112,7 @@ SIGNATURES = {
     "dm4d_lpips_tap_distance_f64": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _i64, _vp]),
     # visual-hull carving: masks to bits, then flags + scan + gather per chunk of the voxel grid (host/vhull.py)
     "dm4d_vhull_pack_masks": (_i, [_vp, _vp, _vp, _i, _i, _i]),
+    "dm4d_vhull_pack_masks_u8": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     "dm4d_vhull_ws_bytes": (C.c_size_t, [_i64]),
     "dm4d_vhull_carve_chunk": (_i, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i, _i, _i, _i, _i64, _i64, _vp, _i64, _vp, _vp, _i64]),
     # skeleton triangulation: one wave per (frame, keypoint), and the projection of the points into cameras (host/triang.py)
@@ -142,6 +143,9 @@ SIGNATURES = {
     # baseline JPEG files decoded into a caller's buffer: speculative Huffman decoding, IDCT, up-sampling, colour (host/jpegdec.py)
     "dm4d_jpeg_decode_ws_bytes": (C.c_size_t, [_i64, _i]),
     "dm4d_jpeg_decode_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    # 8-bit PNG files decoded into a caller's buffer: inflate through an LDS window, then the unfilter wavefront (host/pngdec.py)
+    "dm4d_png_decode_ws_bytes": (C.c_size_t, [_i64, _i]),
+    "dm4d_png_decode_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp]),
 }
 
 # The constants of include/dm4d.h that the host uses, under the header's names without the DM4D_ prefix.  This block is their ONLY
@@ -196,6 +200,17 @@ JPEGDEC_ST_BAD_CODE = 1
 JPEGDEC_ST_ZIGZAG = 2
 JPEGDEC_ST_END = 4
 JPEGDEC_ST_RANGE = 8
+PNGDEC_FIELDS = 8
+PNGDEC_RING_BYTES = 65536
+PNGDEC_MAX_ROW_BYTES = 32768
+PNGDEC_MAX_STREAM_BYTES = 1 << 28
+PNGDEC_ST_HEADER = 1
+PNGDEC_ST_BLOCK = 2
+PNGDEC_ST_CODE = 4
+PNGDEC_ST_DISTANCE = 8
+PNGDEC_ST_END = 16
+PNGDEC_ST_ADLER = 32
+PNGDEC_ST_FILTER = 64
 
 
 class Dm4dError(RuntimeError):

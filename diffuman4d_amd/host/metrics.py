@@ -71,23 +71,35 @@ class _DeviceJpeg:
             return np.asarray(im)
 
 
+class _DevicePng(_DeviceJpeg):
+    """The same for an 8-bit PNG file of host/pngdec.py's supported set: an RGB image [h, w, 3] or a mode-L mask [h, w]."""
+
+    def __init__(self, path, plan, data: bytes):
+        self.path, self.plan, self.data = path, plan, data
+        self.shape = (plan.h, plan.w, 3) if plan.channels == 3 else (plan.h, plan.w)
+        self.nbytes = plan.h * plan.w * plan.channels
+
+
 def _load(x: ImageLike, channels: int, device_decode: bool = False):
     """A path -> uint8 [h, w, 3] / [h, w] (what TF.to_tensor would divide by 255); a tensor -> fp32 [3, h, w] / [h, w] on the host.
     A uint8 numpy array is taken as an already decoded file (np.asarray(Image.open(path))).  device_decode: the path of a baseline
-    JPEG file the device decodes (host/jpegdec.py::probe) is not decoded here -> a _DeviceJpeg; the mode check is made on its header."""
+    JPEG file the device decodes (host/jpegdec.py::probe) is not decoded here -> a _DeviceJpeg; the mode check is made on its header.
+    The same for an 8-bit PNG file (host/pngdec.py::probe), image or mask -> a _DevicePng."""
     if isinstance(x, np.ndarray):
         if x.dtype != np.uint8 or x.ndim != (3 if channels == 3 else 2) or (channels == 3 and x.shape[2] != 3):
             raise ValueError(f"expected a decoded uint8 [h, w{', 3' if channels == 3 else ''}] array, got {x.dtype} {x.shape}")
         return np.ascontiguousarray(x)
     if isinstance(x, (str, os.PathLike)):
-        if device_decode and channels == 3:
-            from . import jpegdec
+        if device_decode:
+            from . import jpegdec, pngdec
+            want = "RGB" if channels == 3 else "L"
             data = jpegdec.read_file(x)
-            plan = jpegdec.probe(data)
-            if plan is not None:
-                if plan.mode != "RGB":
-                    raise ValueError(f"{x}: image mode {plan.mode!r}, expected 'RGB' (no conversion is made: it would change values)")
-                return _DeviceJpeg(x, plan, data)
+            for probe, holder in ((jpegdec.probe, _DeviceJpeg), (pngdec.probe, _DevicePng)):
+                plan = probe(data) if channels == 3 or holder is _DevicePng else None
+                if plan is not None:
+                    if plan.mode != want:
+                        raise ValueError(f"{x}: image mode {plan.mode!r}, expected {want!r} (no conversion is made: it would change values)")
+                    return holder(x, plan, data)
         with Image.open(x) as im:
             want = "RGB" if channels == 3 else "L"
             if im.mode != want:
@@ -124,8 +136,9 @@ class ImageEvaluator:
     library call on them.  Results are Python floats (fp64 of the device's fp64 means)."""
 
     def __init__(self, device, lpips: Optional[Callable] = None, decode_threads: int = 8, device_decode: bool = False):
-        """device_decode: predictions and ground truths that are baseline JPEG files of the supported set are decoded on the device,
-        into their regions of the staging blob (host/jpegdec.py), instead of by Pillow in the decode threads: the same bytes."""
+        """device_decode: predictions and ground truths that are baseline JPEG files of the supported set, and images and masks that
+        are 8-bit PNG files of theirs, are decoded on the device, into their regions of the staging blob (host/jpegdec.py,
+        host/pngdec.py), instead of by Pillow in the decode threads: the same bytes."""
         self.device = torch.device(device)
         self.device_decode = bool(device_decode)
         if self.device_decode and self.device.type != "cuda":
@@ -142,8 +155,8 @@ class ImageEvaluator:
                  canvas_size: int = 1024, crop_with_fmask: bool = True, background_color: str = "black", device_decode: bool = False) -> Dict:
         same_mask = pred_fmask is not None and pred_fmask is gt_fmask or (isinstance(pred_fmask, str) and pred_fmask == gt_fmask)
         p, g = _load(pred, 3, device_decode), _load(gt, 3, device_decode)
-        pm = None if pred_fmask is None else _load(pred_fmask, 1)
-        gm = pm if same_mask else (None if gt_fmask is None else _load(gt_fmask, 1))
+        pm = None if pred_fmask is None else _load(pred_fmask, 1, device_decode)
+        gm = pm if same_mask else (None if gt_fmask is None else _load(gt_fmask, 1, device_decode))
         ps, gs = _chw_shape(p, 3), _chw_shape(g, 3)
         # the reference's sanity checks, in its order and with its texts (metric_utils.py:86-96)
         if gs != ps:
@@ -160,6 +173,7 @@ class ImageEvaluator:
             p, g = (a.pixels() if isinstance(a, _DeviceJpeg) else a for a in (p, g))
             p, g = _as_f32(p, 3), _as_f32(g, 3)
         if pm is not None and gm is not None and pm.dtype != gm.dtype:
+            pm, gm = (a.pixels() if isinstance(a, _DeviceJpeg) else a for a in (pm, gm))
             pm, gm = _as_f32(pm, 1), _as_f32(gm, 1)
         h, w = ps[-2:]
         oh, ow = resized_size(h, w, int(canvas_size))
@@ -209,13 +223,17 @@ class ImageEvaluator:
         with torch.cuda.device(self.device), torch.cuda.stream(st):
             dev_blob = blob.to(self.device, non_blocking=True)
             if files:  # their regions of the blob went up unfilled: the device decodes into them
-                from . import jpegdec
-                status = jpegdec.decode_plans([a.plan for _, a in files], [a.data for _, a in files], dev_blob, [off for off, _ in files],
-                                              [3] * len(files))
-                for (off, a), s in zip(files, status):
-                    if s:  # the decoder refused the scan: Pillow's pixels (or Pillow's exception)
-                        px = np.array(a.pixels()).reshape(-1)
-                        dev_blob[off: off + px.size].copy_(torch.from_numpy(px))
+                from . import jpegdec, pngdec
+                for codec, kind in ((pngdec, _DevicePng), (jpegdec, _DeviceJpeg)):
+                    part = [(off, a) for off, a in files if type(a) is kind]
+                    if not part:
+                        continue
+                    status = codec.decode_plans([a.plan for _, a in part], [a.data for _, a in part], dev_blob, [off for off, _ in part],
+                                                [a.nbytes // (a.plan.h * a.plan.w) for _, a in part])
+                    for (off, a), s in zip(part, status):
+                        if s:  # the decoder refused the file: Pillow's pixels (or Pillow's exception)
+                            px = np.array(a.pixels()).reshape(-1)
+                            dev_blob[off: off + px.size].copy_(torch.from_numpy(px))
             res = ops.eval_psnr_ssim(dev_blob, desc_t, desc_off, debug=debug)
             out, boxes = res[0].cpu(), res[1].cpu()
         st.synchronize()
@@ -324,7 +342,8 @@ def evaluate_results(pred_images_dir: str, gt_images_dir: str, fmasks_dir: Optio
     (default: every visible device) over ``keys[i::n]``.  Keyword-only extensions: `canvas_size` (the reference always uses the
     evaluator's default, 1024), `lpips` (a callable, see the module docstring) or `lpips_weights` = (vgg16_path, lin_path) (every worker
     thread builds its own ``LpipsVGG`` on its device), `batch_size` (pairs per launch), `decode_threads`, `device_decode` (baseline
-    JPEG predictions and ground truths are decoded on the device, host/jpegdec.py: the same metrics.json)."""
+    JPEG predictions and ground truths, and 8-bit PNG images and masks, are decoded on the device, host/jpegdec.py and
+    host/pngdec.py: the same metrics.json)."""
     if lpips is not None and lpips_weights is not None:
         raise ValueError("pass either lpips= (a callable) or lpips_weights= (the two weight files), not both")
     keys = evaluation_keys(pred_images_dir, spa_labels, tem_labels)

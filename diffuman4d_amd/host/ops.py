@@ -1009,6 +1009,17 @@ def vhull_pack_masks(masks: torch.Tensor) -> torch.Tensor:
     return bits
 
 
+def vhull_pack_masks_u8(masks: torch.Tensor, threshold: int = 128) -> torch.Tensor:
+    """Gray masks uint8 [B, H, W] (decoded mode-L files) -> the bits of vhull_pack_masks(masks >= threshold), without the bool tensor."""
+    _req(masks, "masks", torch.uint8)
+    if masks.dim() != 3 or not masks.is_contiguous():
+        raise _l.Dm4dError(f"masks: expected a contiguous [B, H, W] tensor, got {tuple(masks.shape)}")
+    B, H, W = masks.shape
+    bits = torch.empty((B, H, (W + 31) // 32), dtype=torch.int32, device=masks.device)
+    _l.call("dm4d_vhull_pack_masks_u8", _stream(), _p(masks), _p(bits), B, H, W, int(threshold))
+    return bits
+
+
 def vhull_ws(n_voxels: int, device) -> torch.Tensor:
     """The workspace of vhull_carve_chunk for chunks of up to n_voxels voxels (reused from chunk to chunk)."""
     nbytes = int(_l.load().dm4d_vhull_ws_bytes(n_voxels))

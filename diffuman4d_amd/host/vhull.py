@@ -6,7 +6,9 @@ names and arguments, built from its behaviour.  What it does per batch of voxels
 centres, project them into every view in fp64, round, test the image range, gather the masks, count, compact -- runs here in three
 launches per chunk of the grid (``dm4d_vhull_carve_chunk``: flags, a one-block scan, gather) on masks packed to bits.  The host
 makes the grid axes, builds the cameras, decodes the PNG masks (frame ``t + 1`` in a thread pool while frame ``t`` carves) and
-writes the PLY files.  There is no CPU path: a ``device`` that is not a HIP device is an error.
+writes the PLY files.  With ``carve_scene(device_decode=True)`` the pool only reads the files and the device decodes the PNG masks
+(``host/pngdec.py``) and packs them to bits, with the same files written.  There is no CPU path: a ``device`` that is not a HIP
+device is an error.
 """
 from __future__ import annotations
 
@@ -204,6 +206,40 @@ def carve_visual_hull(fmasks, Ps, bounds, voxel_size=0.02, batch_size=1e6, min_v
         return _carve(bits, tuple(fmasks.shape[1:]), P.contiguous().to(dev), axes, batch_size, min_views)
 
 
+def _frame_bits(paths: Sequence[str], datas: Sequence[bytes], frm: str, dev) -> Tuple[torch.Tensor, Tuple[int, int]]:
+    """The packed masks of one frame from its files' bytes, decoded on the device (host/pngdec.py): every supported mode-L file goes
+    into its plane of one [B, H, W] uint8 buffer in one call, and ``dm4d_vhull_pack_masks_u8`` turns value >= 128 (load_binary_mask's
+    rule) into the bits.  A file the decoder does not take (mode ``1`` files among them) or flags is decoded by load_binary_mask and its
+    plane uploaded; a supported file of another mode raises load_binary_mask's ValueError from the header."""
+    from . import pngdec
+    plans = [pngdec.probe(d) for d in datas]
+    host: Dict[int, torch.Tensor] = {}
+    shapes = []
+    for k, (path, plan) in enumerate(zip(paths, plans)):
+        if plan is None:
+            host[k] = load_binary_mask(path)
+            shapes.append(tuple(host[k].shape))
+        elif plan.mode != "L":
+            raise ValueError(f"{path}: image mode {plan.mode!r}, expected 'L' or '1'")
+        else:
+            shapes.append((plan.h, plan.w))
+    if len(set(shapes)) != 1:
+        raise ValueError(f"fmasks_dir: the masks of frame {frm} differ in size: {sorted(set(shapes))}")
+    H, W = shapes[0]
+    with torch.cuda.device(dev):
+        planes = torch.empty((len(paths), H, W), dtype=torch.uint8, device=dev)
+        ours = [k for k, p in enumerate(plans) if p is not None]
+        if ours:
+            status = pngdec.decode_plans([plans[k] for k in ours], [datas[k] for k in ours], planes.view(-1), [k * H * W for k in ours],
+                                         [1] * len(ours))
+            for k, s in zip(ours, status):
+                if s:  # the decoder refused the stream: Pillow's pixels (or Pillow's exception)
+                    host[k] = load_binary_mask(paths[k])
+        for k, m in host.items():
+            planes[k].copy_(m.to(torch.uint8) * 255)
+        return ops.vhull_pack_masks_u8(planes, 128), (H, W)
+
+
 def _list_labels(fmasks_dir: str, camera_range, frame_range) -> Tuple[List[str], List[str]]:
     cam_labels = sorted(os.listdir(fmasks_dir))
     if not cam_labels:
@@ -218,7 +254,7 @@ def _list_labels(fmasks_dir: str, camera_range, frame_range) -> Tuple[List[str],
 
 def carve_scene(fmasks_dir: str, cameras_path: str, out_vhull_dir: str, camera_range=(0, None, 1), frame_range=(0, None, 1),
                 bounds=(-3.0, 3.0, -3.0, 3.0, -3.0, 3.0), voxel_size: float = 0.025, batch_size=1e6, min_views: Optional[int] = None,
-                device="cuda", sparse_pcd_path: Optional[str] = None, host_threads: int = 8) -> Dict:
+                device="cuda", sparse_pcd_path: Optional[str] = None, host_threads: int = 8, device_decode: bool = False) -> Dict:
     """Carve every selected frame of a scene (the reference's main, carve_visual_hull.py:154-231): writes
     ``out_vhull_dir/{frame}.ply`` and ``{out_vhull_dir}_bounds.json`` ([min, max] over all frames) and, with `sparse_pcd_path`, the
     first frame's cloud there as well (the ``cp`` of preprocess.sh:47).  Camera and frame labels come from the sorted listings of
@@ -226,7 +262,11 @@ def carve_scene(fmasks_dir: str, cameras_path: str, out_vhull_dir: str, camera_r
 
     Frames are streamed: the masks of frame t + 1 decode in a pool of `host_threads` threads (at most 16) while frame t carves, so
     the host holds two frames of masks, not the scene's.  A frame whose hull is empty raises ValueError (the reference fails there
-    inside ndarray.min).  Returns {"frames": {label: number of points}, "bounds": [min, max]}."""
+    inside ndarray.min).  Returns {"frames": {label: number of points}, "bounds": [min, max]}.
+
+    device_decode: the pool prefetches the next frame's file BYTES instead of decoded masks; a frame's 8-bit PNG files are decoded on
+    the device in one call and packed to bits there (_frame_bits), so no bool tensor exists and no decoded plane crosses PCIe.  The
+    same files are written."""
     cam_labels, frm_labels = _list_labels(fmasks_dir, camera_range, frame_range)
     P = read_projections(cameras_path, cam_labels)
     dev = _l.hip_device(device, "carve_visual_hull")
@@ -235,19 +275,39 @@ def carve_scene(fmasks_dir: str, cameras_path: str, out_vhull_dir: str, camera_r
     def paths(frm: str) -> List[str]:
         return [os.path.join(fmasks_dir, cam, f"{frm}.png") for cam in cam_labels]
 
+    if device_decode:
+        from .jpegdec import read_file as fetch
+    else:
+        fetch = load_binary_mask
+
+    def carve_bits(frm: str, datas) -> torch.Tensor:
+        """carve_visual_hull from the frame's file bytes: the same checks, grid and launches, the bits made on the device"""
+        Pd = _check_args(torch.zeros((P.shape[0], 1, 1), dtype=torch.bool), P, voxel_size, min_views)
+        axes = build_voxel_grid_linspaces(bounds, voxel_size)
+        for a, name in zip(axes, "xyz"):
+            if a.numel() == 0:
+                raise ValueError(f"bounds: the {name} axis is empty ({name}min >= {name}max for voxel_size {voxel_size})")
+        bits, hw = _frame_bits(paths(frm), datas, frm, dev)
+        with torch.cuda.device(dev):
+            axes = tuple(a.to(torch.float32).to(dev) for a in axes)
+            return _carve(bits, hw, Pd.contiguous().to(dev), axes, batch_size, min_views)
+
     lows, highs = [], []  # per frame: the corners of its cloud's box
     counts: Dict[str, int] = {}
     with ThreadPoolExecutor(max_workers=threads, thread_name_prefix="dm4d-vhull") as pool:
-        pending = [pool.submit(load_binary_mask, p) for p in paths(frm_labels[0])]
+        pending = [pool.submit(fetch, p) for p in paths(frm_labels[0])]
         for i, frm in enumerate(frm_labels):
             masks = [f.result() for f in pending]
             if i + 1 < len(frm_labels):
-                pending = [pool.submit(load_binary_mask, p) for p in paths(frm_labels[i + 1])]
-            shapes = {tuple(m.shape) for m in masks}
-            if len(shapes) != 1:
-                raise ValueError(f"fmasks_dir: the masks of frame {frm} differ in size: {sorted(shapes)}")
-            pts = carve_visual_hull(torch.stack(masks), P, bounds, voxel_size=voxel_size, batch_size=batch_size, min_views=min_views,
-                                    device=dev).cpu().numpy()
+                pending = [pool.submit(fetch, p) for p in paths(frm_labels[i + 1])]
+            if device_decode:
+                pts = carve_bits(frm, masks).cpu().numpy()
+            else:
+                shapes = {tuple(m.shape) for m in masks}
+                if len(shapes) != 1:
+                    raise ValueError(f"fmasks_dir: the masks of frame {frm} differ in size: {sorted(shapes)}")
+                pts = carve_visual_hull(torch.stack(masks), P, bounds, voxel_size=voxel_size, batch_size=batch_size, min_views=min_views,
+                                        device=dev).cpu().numpy()
             if len(pts) == 0:
                 raise ValueError(f"frame {frm}: the visual hull is empty; enlarge bounds or lower min_views")
             save_pcd_ply(os.path.join(out_vhull_dir, f"{frm}.ply"), pts)

@@ -317,6 +317,8 @@ int dm4d_lpips_tap_distance_f64(void* stream, const float* F, const float* lin, 
 #define DM4D_VHULL_BLOCK 256
 #define DM4D_VHULL_MAX_CHUNK (1ll << 26)
 int dm4d_vhull_pack_masks(void* stream, const void* masks, void* bits, int B, int H, int W);
+/* the same bits from gray values (decoded mode-L mask files, host/pngdec.py): a pixel is foreground where its value >= threshold (1 .. 255) */
+int dm4d_vhull_pack_masks_u8(void* stream, const void* masks, void* bits, int B, int H, int W, int threshold);
 size_t dm4d_vhull_ws_bytes(int64_t n_voxels);
 int dm4d_vhull_carve_chunk(void* stream, const float* xs, const float* ys, const float* zs, int64_t nx, int64_t ny, int64_t nz,
                            const double* P, const void* bits, int B, int H, int W, int min_views, int64_t first, int64_t n_voxels,
@@ -570,6 +572,43 @@ size_t dm4d_jpeg_decode_ws_bytes(int64_t total_blocks, int n);
 int dm4d_jpeg_decode_u8(void* stream, const void* scans, int64_t scans_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
                         const uint8_t* tab_host, const uint8_t* tab_dev, void* workspace, int64_t workspace_bytes, void* out,
                         int64_t out_bytes, int32_t* status);
+
+/* 8-bit PNG files decoded on the device (pngdec.hip; diffuman4d_amd/host/pngdec.py): n files of the supported set (bit depth 8, colour
+ *   type 0, 2 or 6, not interlaced -- host/pngdec.py::probe) -> their pixels, byte for byte ``np.asarray(Image.open(file))``.
+ *   tests/pngdec_model.py is the definition in numpy and DESIGN.md "Device PNG decode" its text.  Integer only; two launches whatever n
+ *   is; no workgroup waits on another; no atomics; an image depends on its file alone and is the same in every call.
+ *   inflate   one workgroup (one wave) per image: zlib header, stored / fixed / dynamic blocks (RFC 1950 / 1951, table validity as
+ *             zlib's inflate_table), lookup tables built in LDS, literal runs and match copies by all lanes; the last
+ *             DM4D_PNGDEC_RING_BYTES / 2 bytes of output live in an LDS ring whose halves are flushed to the workspace with 16-byte
+ *             stores and summed into the Adler-32.  Output: the filtered scanlines, h * (1 + w * channels) bytes.
+ *   unfilter  one wave per image, a skewed wavefront over bands of 64 rows (lane j = row 64 b + j, one pixel behind lane j - 1); the
+ *             five predictors are selected by the row's filter byte; a band's last row stays in LDS (DM4D_PNGDEC_MAX_ROW_BYTES).
+ * streams: the files' concatenated IDAT payloads, each starting on a multiple of 4 bytes (and padded to one).
+ * desc: n x DM4D_PNGDEC_FIELDS int64 = {byte offset of the stream in `streams` | its bytes (2 .. DM4D_PNGDEC_MAX_STREAM_BYTES - 1) | h, w
+ *   >= 1 with w * channels <= DM4D_PNGDEC_MAX_ROW_BYTES and h * (1 + w * channels) < 2^31 | the file's channels: 1, 3 or 4 | byte offset
+ *   of the image in `out` | bytes per pixel there: the file's channels; rows tight | byte offset of its filtered stream in the workspace
+ *   = the sum of h * (1 + w * channels), each rounded up to 16, before it}.  desc_host is the host copy of desc_dev, validated before
+ *   anything is launched.
+ * status: device int32 [n]; nonzero (DM4D_PNGDEC_ST_* bits) = the image's pixels are unspecified: HEADER the zlib header; BLOCK a block
+ *   header, a stored length, a code-length rule or an invalid set of code lengths; CODE an undefined or reserved code; DISTANCE a
+ *   distance before the start of the output; END the stream exhausted before the final block ends, or an output length other than
+ *   h * (1 + w * channels); ADLER the Adler-32; FILTER a filter byte other than 0 .. 4.  The unfilter launch skips an image whose
+ *   inflate status is nonzero.
+ * workspace: dm4d_png_decode_ws_bytes(sum of the rounded filtered sizes, n) bytes, 16-byte aligned (0 for counts out of range).        */
+#define DM4D_PNGDEC_FIELDS 8
+#define DM4D_PNGDEC_RING_BYTES 65536
+#define DM4D_PNGDEC_MAX_ROW_BYTES 32768
+#define DM4D_PNGDEC_MAX_STREAM_BYTES (1 << 28)
+#define DM4D_PNGDEC_ST_HEADER 1
+#define DM4D_PNGDEC_ST_BLOCK 2
+#define DM4D_PNGDEC_ST_CODE 4
+#define DM4D_PNGDEC_ST_DISTANCE 8
+#define DM4D_PNGDEC_ST_END 16
+#define DM4D_PNGDEC_ST_ADLER 32
+#define DM4D_PNGDEC_ST_FILTER 64
+size_t dm4d_png_decode_ws_bytes(int64_t total_filtered_bytes, int n);
+int dm4d_png_decode_u8(void* stream, const void* streams, int64_t streams_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
+                       void* workspace, int64_t workspace_bytes, void* out, int64_t out_bytes, int32_t* status);
 
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);

@@ -68,7 +68,7 @@ def inference(cfg: dict):
         missing = [k for k, v in paths.items() if not v]
         if len(missing) == 1:
             raise ValueError(f"evaluation.{missing[0]} is missing: LPIPS needs both evaluation.lpips_vgg16 and evaluation.lpips_lin")
-        # evaluation.device_decode=true: decode the result JPEG files on the GPU (host/jpegdec.py) instead of in Pillow
+        # evaluation.device_decode=true: decode the result JPEG files and the PNG images and masks on the GPU (host/jpegdec.py, host/pngdec.py) instead of in Pillow
         extra = {"device_decode": True} if _as_bool(ev.get("device_decode", False)) else {}
         metrics = runner.evaluate(**extra) if missing else runner.evaluate(lpips_weights=(str(paths["lpips_vgg16"]), str(paths["lpips_lin"])), **extra)
         if metrics is not None:  # every rank evaluates, rank 0 holds the result

@@ -46,11 +46,13 @@ def main(argv=None) -> int:
     ap.add_argument("--sparse_pcd", default=None, help="also write the first frame's cloud here")
     ap.add_argument("--device", default="cuda")
     ap.add_argument("--host_threads", type=int, default=8, help="mask decode threads (at most 16)")
+    ap.add_argument("--device_decode", action="store_true", help="decode the PNG masks on the GPU (host/pngdec.py): the same files are written")
     args = ap.parse_args(argv)
     from diffuman4d_amd.host import vhull
     res = vhull.carve_scene(args.fmasks_dir, args.cameras_path, args.out_vhull_dir, camera_range=args.camera_range,
                             frame_range=args.frame_range, bounds=args.bounds, voxel_size=args.voxel_size, batch_size=args.batch_size,
-                            min_views=args.min_views, device=args.device, sparse_pcd_path=args.sparse_pcd, host_threads=args.host_threads)
+                            min_views=args.min_views, device=args.device, sparse_pcd_path=args.sparse_pcd, host_threads=args.host_threads,
+                            **({"device_decode": True} if args.device_decode else {}))
     print(json.dumps(res))
     return 0
 

@@ -16,6 +16,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
+from . import codec as _c
 from . import lib as _l
 from .ops import _p, _req, _stream
 from .resample import TableSet
@@ -167,7 +168,7 @@ def jpeg_encode_chunk(images, crops, sizes, qtab) -> list:
         nbytes = int(lib.dm4d_jpeg_ws_bytes(mcu0, n))
         if nbytes == 0:
             raise _l.Dm4dError(f"jpeg_encode_chunk: {n} images with {mcu0} MCUs are out of range for one call")
-        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+        ws = _c.workspace(nbytes, dev)
         blob = torch.empty(bound, dtype=torch.uint8, device=dev)
         out = torch.empty(2 * n, dtype=torch.int64, device=dev)
         q = torch.tensor([int(v) for v in qtab], dtype=torch.int16)  # values 1..255: the same bytes as uint16
@@ -175,12 +176,7 @@ def jpeg_encode_chunk(images, crops, sizes, qtab) -> list:
         _l.call("dm4d_jpeg_encode_rgb_u8", _stream(), _p(pixels) if pixels.numel() else None, pixels.numel(), _p(canvases),
                 0 if canvases is None else canvases.numel(), desc.data_ptr(), _p(desc_dev), n, q.data_ptr(), _p(q_dev), _p(ws),
                 ws.numel() * 8, _p(blob), blob.numel(), _p(out))
-        where = out.cpu().tolist()  # the one synchronisation: n offsets, then n lengths
-        total = where[n - 1] + where[2 * n - 1]
-        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        host.copy_(blob[:total])
-        data = host.numpy().tobytes()
-    return [data[where[k]:where[k] + where[n + k]] for k in range(n)]
+        return _c.read_back(blob, out)
 
 
 def encode_jpeg_batch(images, quality: int = 90, crops: Optional[Sequence] = None, workspace_bytes: int = DEFAULT_WORKSPACE) -> List[bytes]:
@@ -208,16 +204,7 @@ def encode_jpeg_batch(images, quality: int = 90, crops: Optional[Sequence] = Non
         sizes.append(hw)
     files: List[bytes] = []
     qtab = [v for tab in quant_tables(q) for v in tab]
-    first = 0
-    while first < len(images):
-        last, used = first, 0
-        while last < len(images):
-            need = _image_bytes(images[last], crops[last], sizes[last])
-            if last > first and used + need > workspace_bytes:
-                break
-            used += need
-            last += 1
+    for first, last in _c.chunks([_image_bytes(*it) for it in zip(images, crops, sizes)], workspace_bytes):
         scans = jpeg_encode_chunk(images[first:last], crops[first:last], sizes[first:last], qtab)
         files += [jpeg_header(hw[0], hw[1], q) + s + b"\xff\xd9" for hw, s in zip(sizes[first:last], scans)]
-        first = last
     return files

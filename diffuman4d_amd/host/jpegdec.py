@@ -6,20 +6,24 @@ entropy-coded segments (their ``FF 00`` stuffing removed with one ``bytes.replac
 has csrc/jpegdec.hip decode the batch into a caller-given device buffer at caller-given offsets (``dm4d_jpeg_decode_u8``): one workgroup
 per image finds the symbol boundaries of the scan by speculative decoding and writes int16 coefficients, a second launch dequantises,
 inverts the DCT (jidctint "islow"), up-samples the chroma ("fancy" triangle filter) and converts to RGB.  ``decode_jpeg_batch`` is the
-list-in, tensors-out form.  DESIGN.md "Device JPEG decode" has the definition; tests/jpegdec_model.py is the same in numpy.  There is
-no CPU path: a non-HIP device is an error.
+list-in, tensors-out form.  What is specific to JPEG is here (``probe``, ``Plan``, ``stage_chunk``, ``launch_chunk``); the chunked
+driver behind ``decode_plans``, the body of ``decode_jpeg_batch`` and the Pillow route are host/codec.py's, shared with host/pngdec.py.
+DESIGN.md "Device JPEG decode" has the definition; tests/jpegdec_model.py is the same in numpy.  There is no CPU path: a non-HIP
+device is an error.
 """
 from __future__ import annotations
 
-import io
 import re
 import struct
+import sys
 from dataclasses import dataclass
-from pathlib import Path
 from typing import List, Optional, Sequence, Tuple
 
+from . import codec as _c
 from . import lib as _l
 from .jpeg import ZIGZAG
+
+_this = sys.modules[__name__]  # the codec of host/codec.py's bodies: its attributes are looked up when they are called
 
 DEFAULT_WORKSPACE = 1 << 30
 MAX_SCAN_BYTES = 1 << 28  # bit positions of a scan are 32-bit on the device
@@ -51,6 +55,21 @@ class Plan:
     def blocks(self) -> int:
         """int16 [64] coefficient blocks of the whole scan, dummy blocks of edge MCUs included"""
         return self.mcus * (1 if self.ncomp == 1 else self.hs * self.vs + 2)
+
+    # what host/codec.py asks of a plan
+    @property
+    def bytes_per_pixel(self) -> int:
+        return self.ncomp
+
+    @property
+    def workspace_need(self) -> int:
+        """bytes of the coefficient workspace"""
+        return self.blocks * 128
+
+    @property
+    def payload_len(self) -> int:
+        """bytes of the file that go up: the scan as it lies in the file"""
+        return self.scan[1] - self.scan[0]
 
     def scan_bytes(self, data: bytes) -> bytes:
         """The entropy-coded segment without its byte stuffing."""
@@ -192,49 +211,13 @@ def probe(data) -> Optional[Plan]:
     return Plan(h, w, nc, hs, vs, bytes(rec + qrec), (pos, end.start()))
 
 
-def read_file(f) -> bytes:
-    """A file's bytes: `f` is a path, or the bytes themselves."""
-    if isinstance(f, (bytes, bytearray, memoryview)):
-        return bytes(f)
-    return Path(f).read_bytes()
-
-
-def pillow_pixels(data: bytes):
-    """The Pillow route: ``np.asarray(Image.open(file))``.  Raises what Pillow raises."""
-    import numpy as np
-    from PIL import Image
-    with Image.open(io.BytesIO(data)) as im:
-        return np.asarray(im)
-
-
 def decode_plans(plans: Sequence[Plan], files: Sequence[bytes], out, offsets: Sequence[int], channels: Sequence[int],
                  workspace_bytes: int = DEFAULT_WORKSPACE) -> List[int]:
     """Decode files[k] (whose plan is plans[k]) into the uint8 device tensor `out` at byte offsets[k], rows tight, channels[k] bytes a
     pixel (3, or 1 for a grayscale file).  -> the status words: nonzero = the decoder refused the file and its region of `out` holds
     nothing of use (the caller decodes it with Pillow).  The batch goes in chunks whose coefficient workspace stays below
     `workspace_bytes` (a chunk holds at least one file); one synchronisation, at the end."""
-    import torch
-    from .ops import _req
-    _req(out, "out", torch.uint8)
-    if not out.is_contiguous():
-        raise _l.Dm4dError("out: expected a contiguous uint8 tensor")
-    if not (len(plans) == len(files) == len(offsets) == len(channels)):
-        raise ValueError("decode_plans: plans, files, offsets and channels differ in length")
-    statuses = []
-    first = 0
-    with torch.cuda.device(out.device):
-        while first < len(plans):
-            last, used = first, 0
-            while last < len(plans) and last - first < 65535:
-                need = plans[last].blocks * 128
-                if last > first and used + need > workspace_bytes:
-                    break
-                used += need
-                last += 1
-            staged = stage_chunk(plans[first:last], files[first:last], offsets[first:last], channels[first:last], out.device)
-            statuses.append(launch_chunk(staged, out))
-            first = last
-        return torch.cat(statuses).cpu().tolist() if statuses else []
+    return _c.decode_plans(_this, plans, files, out, offsets, channels, workspace_bytes)
 
 
 def stage_chunk(plans, files, offsets, channels, dev) -> dict:
@@ -257,7 +240,7 @@ def stage_chunk(plans, files, offsets, channels, dev) -> dict:
     tab = torch.frombuffer(bytearray(b"".join(p.tables for p in plans)), dtype=torch.uint8)
     scans_dev = torch.frombuffer(scans, dtype=torch.uint8).to(dev)
     desc_dev, tab_dev = desc.to(dev), tab.to(dev)
-    ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+    ws = _c.workspace(nbytes, dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
     return {"n": n, "scans": scans_dev, "desc": desc, "desc_dev": desc_dev, "tab": tab, "tab_dev": tab_dev, "ws": ws, "status": status,
             "bytes_up": len(scans) + desc.numel() * 8 + tab.numel()}
@@ -277,35 +260,4 @@ def decode_jpeg_batch(files, device="cuda", *, workspace_bytes: int = DEFAULT_WO
     ``np.asarray(Image.open(f))`` gives.  Baseline JPEG files of the supported set are decoded on the device; a file ``probe`` refuses,
     or one the decoder reports a nonzero status for, is decoded by Pillow and uploaded (and raises what Pillow raises).
     stats: if given, receives "device" and "pillow" = how many files took each route, "bytes_uploaded"."""
-    import torch
-    dev = _l.hip_device(device, "decode_jpeg_batch")
-    datas = [read_file(f) for f in files]
-    plans = [probe(d) for d in datas]
-    ours = [k for k, p in enumerate(plans) if p is not None]
-    offsets, total = [], 0
-    for k in ours:
-        offsets.append(total)
-        total += _l.align16(plans[k].h * plans[k].w * plans[k].ncomp)
-    out = [None] * len(datas)
-    uploaded = 0
-    if ours:
-        buf = torch.empty(total, dtype=torch.uint8, device=dev)
-        st = decode_plans([plans[k] for k in ours], [datas[k] for k in ours], buf, offsets, [plans[k].ncomp for k in ours], workspace_bytes)
-        for k, at, s in zip(ours, offsets, st):
-            p = plans[k]
-            uploaded += p.scan[1] - p.scan[0]
-            if s == 0:
-                shape = (p.h, p.w, 3) if p.ncomp == 3 else (p.h, p.w)
-                out[k] = buf[at:at + p.h * p.w * p.ncomp].view(shape)
-    routed = 0
-    for k in range(len(datas)):
-        if out[k] is None:
-            a = pillow_pixels(datas[k])
-            out[k] = torch.from_numpy(a.copy()).to(dev)
-            uploaded += a.nbytes
-            routed += 1
-    if stats is not None:
-        stats["device"] = stats.get("device", 0) + len(datas) - routed
-        stats["pillow"] = stats.get("pillow", 0) + routed
-        stats["bytes_uploaded"] = stats.get("bytes_uploaded", 0) + uploaded
-    return out
+    return _c.decode_batch(_this, "decode_jpeg_batch", files, device, workspace_bytes, stats)

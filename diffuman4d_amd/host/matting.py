@@ -36,6 +36,7 @@ from PIL import Image
 from . import lib as _l
 from . import ops
 from . import staging as _st
+from .codec import decode_or_fallback, read_file
 from .resample import TableSet
 from .staging import MAX_HOST_THREADS  # noqa: F401  (importable from here as before)
 
@@ -129,7 +130,7 @@ def _device_files(ims, sizes) -> dict:
     for k, im in enumerate(ims):
         name = getattr(im, "filename", "")
         if im.format == "JPEG" and name and im.mode in ("RGB", "L"):
-            data = jpegdec.read_file(name)
+            data = read_file(name)
             plan = jpegdec.probe(data)
             if plan is not None and (plan.h, plan.w) == tuple(sizes[k]) and plan.mode == im.mode:
                 out[k] = (plan, data)
@@ -152,13 +153,8 @@ def _staged_inputs(ims, sizes, size: Tuple[int, int], dev: torch.device, rot: in
     blob = host.to(dev, non_blocking=True)
     if on_device:
         from . import jpegdec
-        ks = sorted(on_device)
-        status = jpegdec.decode_plans([on_device[k][0] for k in ks], [on_device[k][1] for k in ks], blob, [int(desc[k, 0]) for k in ks],
-                                      [3] * len(ks))
-        for k, st in zip(ks, status):
-            if st:  # the decoder refused the scan: Pillow's pixels (or Pillow's exception)
-                a = np.array(ims[k].convert("RGB")).reshape(-1)
-                blob[int(desc[k, 0]): int(desc[k, 0]) + a.size].copy_(torch.from_numpy(a))
+        ks = sorted(on_device)  # a scan the decoder refuses: Pillow's pixels (or Pillow's exception)
+        decode_or_fallback(jpegdec, [(*on_device[k], int(desc[k, 0]), 3) for k in ks], blob, lambda j: np.asarray(ims[ks[j]].convert("RGB")))
     meta, meta_host, tab_off, tab_len, desc_off = _st.pack_meta(tab, desc, dev)
     scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=dev)
     out = ops.matting_input(blob, meta, meta_host, len(ims), desc_off, tab_off, tab_len, _on_device(dtype, dev), scratch, S_h, S_w, rot)

@@ -34,6 +34,7 @@ from PIL import Image
 
 from . import lpips as _lpips
 from . import ops
+from .codec import decode_or_fallback, read_file
 from .lib import Dm4dError
 from .staging import Layout, fill, pinned, write_meta
 
@@ -55,15 +56,17 @@ def resized_size(h: int, w: int, canvas_size: int) -> Tuple[int, int]:
     return (new_long, new_short) if w <= h else (new_short, new_long)
 
 
-class _DeviceJpeg:
-    """An RGB file the device will decode into its region of the staging blob (host/jpegdec.py): it stands where the decoded uint8
-    [h, w, 3] array would, with its shape, dtype and size, and holds the file's bytes and plan instead of pixels."""
+class _DeviceFile:
+    """A file the device will decode into its region of the staging blob (`codec`: host/jpegdec.py or host/pngdec.py): an RGB image
+    [h, w, 3] or a mode-L mask [h, w].  It stands where the decoded uint8 array would, with its shape, dtype and size, and holds the
+    file's bytes and plan instead of pixels."""
     dtype = np.dtype(np.uint8)
 
-    def __init__(self, path, plan, data: bytes):
-        self.path, self.plan, self.data = path, plan, data
-        self.shape = (plan.h, plan.w, 3)
-        self.nbytes = plan.h * plan.w * 3
+    def __init__(self, path, codec, plan, data: bytes):
+        self.path, self.codec, self.plan, self.data = path, codec, plan, data
+        bpp = plan.bytes_per_pixel
+        self.shape = (plan.h, plan.w) if bpp == 1 else (plan.h, plan.w, bpp)
+        self.nbytes = plan.h * plan.w * bpp
 
     def pixels(self) -> np.ndarray:
         """The Pillow route of the same file."""
@@ -71,20 +74,11 @@ class _DeviceJpeg:
             return np.asarray(im)
 
 
-class _DevicePng(_DeviceJpeg):
-    """The same for an 8-bit PNG file of host/pngdec.py's supported set: an RGB image [h, w, 3] or a mode-L mask [h, w]."""
-
-    def __init__(self, path, plan, data: bytes):
-        self.path, self.plan, self.data = path, plan, data
-        self.shape = (plan.h, plan.w, 3) if plan.channels == 3 else (plan.h, plan.w)
-        self.nbytes = plan.h * plan.w * plan.channels
-
-
 def _load(x: ImageLike, channels: int, device_decode: bool = False):
     """A path -> uint8 [h, w, 3] / [h, w] (what TF.to_tensor would divide by 255); a tensor -> fp32 [3, h, w] / [h, w] on the host.
     A uint8 numpy array is taken as an already decoded file (np.asarray(Image.open(path))).  device_decode: the path of a baseline
-    JPEG file the device decodes (host/jpegdec.py::probe) is not decoded here -> a _DeviceJpeg; the mode check is made on its header.
-    The same for an 8-bit PNG file (host/pngdec.py::probe), image or mask -> a _DevicePng."""
+    JPEG file the device decodes (host/jpegdec.py::probe; images only) or of an 8-bit PNG file it decodes (host/pngdec.py::probe; images
+    and masks) is not decoded here -> a _DeviceFile; the mode check is made on its header."""
     if isinstance(x, np.ndarray):
         if x.dtype != np.uint8 or x.ndim != (3 if channels == 3 else 2) or (channels == 3 and x.shape[2] != 3):
             raise ValueError(f"expected a decoded uint8 [h, w{', 3' if channels == 3 else ''}] array, got {x.dtype} {x.shape}")
@@ -93,13 +87,13 @@ def _load(x: ImageLike, channels: int, device_decode: bool = False):
         if device_decode:
             from . import jpegdec, pngdec
             want = "RGB" if channels == 3 else "L"
-            data = jpegdec.read_file(x)
-            for probe, holder in ((jpegdec.probe, _DeviceJpeg), (pngdec.probe, _DevicePng)):
-                plan = probe(data) if channels == 3 or holder is _DevicePng else None
+            data = read_file(x)
+            for codec in (jpegdec, pngdec) if channels == 3 else (pngdec,):
+                plan = codec.probe(data)
                 if plan is not None:
                     if plan.mode != want:
                         raise ValueError(f"{x}: image mode {plan.mode!r}, expected {want!r} (no conversion is made: it would change values)")
-                    return holder(x, plan, data)
+                    return _DeviceFile(x, codec, plan, data)
         with Image.open(x) as im:
             want = "RGB" if channels == 3 else "L"
             if im.mode != want:
@@ -170,10 +164,10 @@ class ImageEvaluator:
         if crop_with_fmask and (pm is None and gm is None):
             raise ValueError("Either pred_fmask or gt_fmask should be provided to crop with fmask.")
         if p.dtype != g.dtype:  # one decoded file, one tensor: both travel as fp32
-            p, g = (a.pixels() if isinstance(a, _DeviceJpeg) else a for a in (p, g))
+            p, g = (a.pixels() if isinstance(a, _DeviceFile) else a for a in (p, g))
             p, g = _as_f32(p, 3), _as_f32(g, 3)
         if pm is not None and gm is not None and pm.dtype != gm.dtype:
-            pm, gm = (a.pixels() if isinstance(a, _DeviceJpeg) else a for a in (pm, gm))
+            pm, gm = (a.pixels() if isinstance(a, _DeviceFile) else a for a in (pm, gm))
             pm, gm = _as_f32(pm, 1), _as_f32(gm, 1)
         h, w = ps[-2:]
         oh, ow = resized_size(h, w, int(canvas_size))
@@ -204,7 +198,7 @@ class ImageEvaluator:
                     offs[name] = offs["pmask"]  # evaluate_results passes ONE mask file for both: it is decoded and uploaded once
                 else:
                     offs[name] = lay.add(a.nbytes)
-                    (files if isinstance(a, _DeviceJpeg) else jobs).append((offs[name], a))
+                    (files if isinstance(a, _DeviceFile) else jobs).append((offs[name], a))
             mask = it["pmask"] if it["pmask"] is not None else it["gmask"]
             flags = ((ops.EVAL_IMAGE_F32 if it["pred"].dtype != np.uint8 else 0)
                      | (ops.EVAL_MASK_F32 if mask is not None and mask.dtype != np.uint8 else 0)
@@ -224,16 +218,11 @@ class ImageEvaluator:
             dev_blob = blob.to(self.device, non_blocking=True)
             if files:  # their regions of the blob went up unfilled: the device decodes into them
                 from . import jpegdec, pngdec
-                for codec, kind in ((pngdec, _DevicePng), (jpegdec, _DeviceJpeg)):
-                    part = [(off, a) for off, a in files if type(a) is kind]
-                    if not part:
-                        continue
-                    status = codec.decode_plans([a.plan for _, a in part], [a.data for _, a in part], dev_blob, [off for off, _ in part],
-                                                [a.nbytes // (a.plan.h * a.plan.w) for _, a in part])
-                    for (off, a), s in zip(part, status):
-                        if s:  # the decoder refused the file: Pillow's pixels (or Pillow's exception)
-                            px = np.array(a.pixels()).reshape(-1)
-                            dev_blob[off: off + px.size].copy_(torch.from_numpy(px))
+                for codec in (pngdec, jpegdec):  # one call per codec; a file the decoder refuses: Pillow's pixels (or Pillow's exception)
+                    part = [(off, a) for off, a in files if a.codec is codec]
+                    if part:
+                        decode_or_fallback(codec, [(a.plan, a.data, off, a.plan.bytes_per_pixel) for off, a in part], dev_blob,
+                                           lambda k: part[k][1].pixels())
             res = ops.eval_psnr_ssim(dev_blob, desc_t, desc_off, debug=debug)
             out, boxes = res[0].cpu(), res[1].cpu()
         st.synchronize()

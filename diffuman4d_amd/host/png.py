@@ -12,6 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import torch
 
+from . import codec as _c
 from . import lib as _l
 from . import ops
 
@@ -62,13 +63,7 @@ def png_encode_planes(planes: torch.Tensor, rgb: Optional[torch.Tensor], items: 
     if ws_bytes == 0:
         raise _l.Dm4dError(f"png_encode_planes: {n} images with {filt0} filtered bytes are out of range for one call")
     with torch.cuda.device(planes.device):
-        blob, out = ops.png_encode(planes, rgb, desc, bound, ws_bytes)
-        where = out.cpu().tolist()  # the one synchronisation: n offsets, then n lengths
-        total = where[n - 1] + where[2 * n - 1]
-        host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
-        host.copy_(blob[:total])
-        data = host.numpy().tobytes()
-    return [data[where[k]:where[k] + where[n + k]] for k in range(n)]
+        return _c.read_back(*ops.png_encode(planes, rgb, desc, bound, ws_bytes))
 
 
 def encode_png_batch(planes, alphas: Optional[Sequence] = None, workspace_bytes: int = DEFAULT_WORKSPACE) -> List[bytes]:
@@ -100,15 +95,7 @@ def encode_png_batch(planes, alphas: Optional[Sequence] = None, workspace_bytes:
         shapes.append((h, w, 4 if rgba else 1))
     dev = planes[0].device
     files: List[bytes] = []
-    first = 0
-    while first < len(planes):
-        last, used = first, 0
-        while last < len(planes):
-            need = _device_bytes(*shapes[last]) + shapes[last][0] * shapes[last][1] * shapes[last][2]
-            if last > first and used + need > workspace_bytes:
-                break
-            used += need
-            last += 1
+    for first, last in _c.chunks([_device_bytes(h, w, ch) + h * w * ch for h, w, ch in shapes], workspace_bytes):
         with torch.cuda.device(dev):
             ones = [alphas[k] if alphas[k] is not None else planes[k] for k in range(first, last)]   # 1 byte per pixel
             threes = [planes[k] for k in range(first, last) if alphas[k] is not None]                # 3 bytes per pixel
@@ -123,7 +110,6 @@ def encode_png_batch(planes, alphas: Optional[Sequence] = None, workspace_bytes:
                     items.append((RGBA, h, w) + rat[r] + pat[j])
                     r += 1
             files += png_encode_planes(pbuf, rbuf, items)
-        first = last
     return files
 
 

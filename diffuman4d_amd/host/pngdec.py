@@ -5,18 +5,23 @@
 ``decode_plans`` uploads the concatenated IDAT payloads and has csrc/pngdec.hip decode the batch into a caller-given device buffer at
 caller-given offsets (``dm4d_png_decode_u8``): one workgroup per image inflates the zlib stream through an LDS window into the filtered
 scanlines, a second launch undoes the row filters in a skewed wavefront.  ``decode_png_batch`` is the list-in, tensors-out form.
+What is specific to PNG is here (``probe``, ``Plan``, ``stage_chunk``, ``launch_chunk``); the chunked driver behind ``decode_plans``,
+the body of ``decode_png_batch`` and the Pillow route are host/codec.py's, shared with host/jpegdec.py.
 DESIGN.md "Device PNG decode" has the definition; tests/pngdec_model.py is the same in numpy.  There is no CPU path: a non-HIP device
 is an error.
 """
 from __future__ import annotations
 
 import struct
+import sys
 import zlib
 from dataclasses import dataclass
 from typing import List, Optional, Sequence, Tuple
 
+from . import codec as _c
 from . import lib as _l
-from .jpegdec import pillow_pixels, read_file
+
+_this = sys.modules[__name__]  # the codec of host/codec.py's bodies: its attributes are looked up when they are called
 
 DEFAULT_WORKSPACE = 1 << 30
 MAX_ROW_BYTES = 32768         # lib.PNGDEC_MAX_ROW_BYTES: a band's last row is kept in LDS
@@ -40,8 +45,19 @@ class Plan:
         """bytes of the filtered scanlines = what the zlib stream must inflate to"""
         return self.h * (1 + self.w * self.channels)
 
+    # what host/codec.py asks of a plan
     @property
-    def stream_len(self) -> int:
+    def bytes_per_pixel(self) -> int:
+        return self.channels
+
+    @property
+    def workspace_need(self) -> int:
+        """bytes of the workspace: the filtered scanlines, 16-byte aligned"""
+        return _l.align16(self.filtered_bytes)
+
+    @property
+    def payload_len(self) -> int:
+        """bytes of the file that go up: the zlib stream"""
         return sum(e - s for s, e in self.idat)
 
     def stream_bytes(self, data: bytes) -> bytes:
@@ -101,28 +117,7 @@ def decode_plans(plans: Sequence[Plan], files: Sequence[bytes], out, offsets: Se
     pixel (the file's own count).  -> the status words: nonzero (lib.PNGDEC_ST_* bits) = the decoder refused the file and its region of
     `out` holds nothing of use (the caller decodes it with Pillow).  The batch goes in chunks whose workspace of filtered scanlines
     stays below `workspace_bytes` (a chunk holds at least one file); one synchronisation, at the end."""
-    import torch
-    from .ops import _req
-    _req(out, "out", torch.uint8)
-    if not out.is_contiguous():
-        raise _l.Dm4dError("out: expected a contiguous uint8 tensor")
-    if not (len(plans) == len(files) == len(offsets) == len(channels)):
-        raise ValueError("decode_plans: plans, files, offsets and channels differ in length")
-    statuses = []
-    first = 0
-    with torch.cuda.device(out.device):
-        while first < len(plans):
-            last, used = first, 0
-            while last < len(plans) and last - first < 65535:
-                need = _l.align16(plans[last].filtered_bytes)
-                if last > first and used + need > workspace_bytes:
-                    break
-                used += need
-                last += 1
-            staged = stage_chunk(plans[first:last], files[first:last], offsets[first:last], channels[first:last], out.device)
-            statuses.append(launch_chunk(staged, out))
-            first = last
-        return torch.cat(statuses).cpu().tolist() if statuses else []
+    return _c.decode_plans(_this, plans, files, out, offsets, channels, workspace_bytes)
 
 
 def stage_chunk(plans, files, offsets, channels, dev) -> dict:
@@ -138,13 +133,13 @@ def stage_chunk(plans, files, offsets, channels, dev) -> dict:
         s = p.stream_bytes(files[k])
         desc[k] = torch.tensor([len(streams), len(s), p.h, p.w, p.channels, int(offsets[k]), int(channels[k]), ws0])
         streams += s + bytes(-len(s) % 4)
-        ws0 += _l.align16(p.filtered_bytes)
+        ws0 += p.workspace_need
     nbytes = int(lib.dm4d_png_decode_ws_bytes(ws0, n))
     if nbytes == 0 or not streams:
         raise _l.Dm4dError(f"decode_plans: {n} files with {ws0} filtered bytes are out of range for one call")
     streams_dev = torch.frombuffer(streams, dtype=torch.uint8).to(dev)
     desc_dev = desc.to(dev)
-    ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+    ws = _c.workspace(nbytes, dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
     return {"n": n, "streams": streams_dev, "desc": desc, "desc_dev": desc_dev, "ws": ws, "status": status,
             "bytes_up": len(streams) + desc.numel() * 8}
@@ -163,35 +158,4 @@ def decode_png_batch(files, device="cuda", *, workspace_bytes: int = DEFAULT_WOR
     ``np.asarray(Image.open(f))`` gives.  PNG files of the supported set are decoded on the device; a file ``probe`` refuses, or one
     the decoder reports a nonzero status for, is decoded by Pillow and uploaded (and raises what Pillow raises).
     stats: if given, receives "device" and "pillow" = how many files took each route, "bytes_uploaded"."""
-    import torch
-    dev = _l.hip_device(device, "decode_png_batch")
-    datas = [read_file(f) for f in files]
-    plans = [probe(d) for d in datas]
-    ours = [k for k, p in enumerate(plans) if p is not None]
-    offsets, total = [], 0
-    for k in ours:
-        offsets.append(total)
-        total += _l.align16(plans[k].h * plans[k].w * plans[k].channels)
-    out = [None] * len(datas)
-    uploaded = 0
-    if ours:
-        buf = torch.empty(total, dtype=torch.uint8, device=dev)
-        st = decode_plans([plans[k] for k in ours], [datas[k] for k in ours], buf, offsets, [plans[k].channels for k in ours], workspace_bytes)
-        for k, at, s in zip(ours, offsets, st):
-            p = plans[k]
-            uploaded += p.stream_len
-            if s == 0:
-                shape = (p.h, p.w) if p.channels == 1 else (p.h, p.w, p.channels)
-                out[k] = buf[at:at + p.h * p.w * p.channels].view(shape)
-    routed = 0
-    for k in range(len(datas)):
-        if out[k] is None:
-            a = pillow_pixels(datas[k])
-            out[k] = torch.from_numpy(a.copy()).to(dev)
-            uploaded += a.nbytes
-            routed += 1
-    if stats is not None:
-        stats["device"] = stats.get("device", 0) + len(datas) - routed
-        stats["pillow"] = stats.get("pillow", 0) + routed
-        stats["bytes_uploaded"] = stats.get("bytes_uploaded", 0) + uploaded
-    return out
+    return _c.decode_batch(_this, "decode_png_batch", files, device, workspace_bytes, stats)

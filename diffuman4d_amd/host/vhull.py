@@ -23,6 +23,7 @@ from PIL import Image
 
 from . import lib as _l
 from . import ops
+from .codec import decode_or_fallback, read_file
 from .staging import MAX_HOST_THREADS  # noqa: F401  (importable from here as before)
 
 PLY_HEADER = ("ply\n"
@@ -229,12 +230,9 @@ def _frame_bits(paths: Sequence[str], datas: Sequence[bytes], frm: str, dev) -> 
     with torch.cuda.device(dev):
         planes = torch.empty((len(paths), H, W), dtype=torch.uint8, device=dev)
         ours = [k for k, p in enumerate(plans) if p is not None]
-        if ours:
-            status = pngdec.decode_plans([plans[k] for k in ours], [datas[k] for k in ours], planes.view(-1), [k * H * W for k in ours],
-                                         [1] * len(ours))
-            for k, s in zip(ours, status):
-                if s:  # the decoder refused the stream: Pillow's pixels (or Pillow's exception)
-                    host[k] = load_binary_mask(paths[k])
+        if ours:  # a stream the decoder refuses: load_binary_mask's pixels (or its exception)
+            decode_or_fallback(pngdec, [(plans[k], datas[k], k * H * W, 1) for k in ours], planes.view(-1),
+                               lambda j: (load_binary_mask(paths[ours[j]]).to(torch.uint8) * 255).numpy())
         for k, m in host.items():
             planes[k].copy_(m.to(torch.uint8) * 255)
         return ops.vhull_pack_masks_u8(planes, 128), (H, W)
@@ -275,10 +273,7 @@ def carve_scene(fmasks_dir: str, cameras_path: str, out_vhull_dir: str, camera_r
     def paths(frm: str) -> List[str]:
         return [os.path.join(fmasks_dir, cam, f"{frm}.png") for cam in cam_labels]
 
-    if device_decode:
-        from .jpegdec import read_file as fetch
-    else:
-        fetch = load_binary_mask
+    fetch = read_file if device_decode else load_binary_mask
 
     def carve_bits(frm: str, datas) -> torch.Tensor:
         """carve_visual_hull from the frame's file bytes: the same checks, grid and launches, the bits made on the device"""

@@ -21,13 +21,11 @@ from __future__ import annotations
 import argparse
 import io
 import json
-import re
 import shutil
 import statistics
 import sys
 import tempfile
 import time
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import numpy as np
@@ -38,43 +36,8 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
+from bench_common import alternate, device_time, kernel_shares, pillow_decode, pillow_times  # noqa: E402
 from diffuman4d_amd.host import jpegdec, matting, metrics  # noqa: E402
-
-
-def device_time(fn, reps: int) -> float:
-    """Median over `reps` calls of the HIP-event time of one call, in seconds, after one warm-up call."""
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b) / 1e3)
-    return statistics.median(times)
-
-
-def kernel_shares(fn):
-    """{kernel name: device seconds} of one call, from torch's profiler; None where it does not see the library's kernels."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        out = {}
-        for e in prof.key_averages():
-            m = re.search(r"jpegdec_\w+_kernel", e.key)
-            if m:
-                out[m.group(0)] = out.get(m.group(0), 0.0) + getattr(e, "device_time_total", getattr(e, "cuda_time_total", 0.0)) / 1e6
-        return out or None
-    except Exception:
-        return None
-
-
-def pillow_decode(data: bytes) -> int:
-    return np.asarray(Image.open(io.BytesIO(data))).size
 
 
 def save_jpeg(a: np.ndarray, quality: int = 90) -> bytes:
@@ -111,7 +74,7 @@ def main(argv=None):
         staged = jpegdec.stage_chunk(plans, files, offsets, [3] * n, dev)
         call = lambda: jpegdec.launch_chunk(staged, out)
         t = device_time(call, args.reps)
-        shares = kernel_shares(call)
+        shares = kernel_shares(call, r"jpegdec_\w+_kernel")
         status = call().cpu().tolist()
         got = out.view(n, h, w, 3)[:4].cpu().numpy()
         equal = status == [0] * n and all(np.array_equal(got[i], np.asarray(Image.open(io.BytesIO(four[i])))) for i in range(4))
@@ -120,16 +83,8 @@ def main(argv=None):
                 "entropy_share": (shares["jpegdec_entropy_kernel"] / sum(shares.values())
                                   if shares and "jpegdec_entropy_kernel" in shares else None),
                 "timing": f"HIP events around one dm4d_jpeg_decode_u8 call for {n} files, warm, median of {args.reps}"}
-        torch.set_num_threads(1)
-        for threads in (1, 16):
-            sub = files[:max(4, n // 8)] if threads == 1 else files
-            t0 = time.perf_counter()
-            if threads == 1:
-                [pillow_decode(d) for d in sub]
-            else:
-                with ThreadPoolExecutor(max_workers=threads) as pool:
-                    list(pool.map(pillow_decode, sub))
-            line[f"pillow_seconds_per_image_{threads}_threads"] = (time.perf_counter() - t0) / len(sub)
+        for threads, (seconds, _) in pillow_times(pillow_decode, files).items():
+            line[f"pillow_seconds_per_image_{threads}_threads"] = seconds
         lines.append(line)
         lines.append({"what": "bytes", "files": label, "pcie_bytes_per_image_flag_off": h * w * 3, "pcie_bytes_per_image_flag_on": staged["bytes_up"] / n})
         lines.append({"what": "equal", "files": label, "device_equals_pillow": bool(equal)})
@@ -153,16 +108,17 @@ def main(argv=None):
                 Image.fromarray(a).save(p, **kw)
         ev = {"what": "evaluate", "pairs": args.pairs, "image": [h, w], "batch_size": 16, "decode_threads": 8,
               "timing": "wall clock of evaluate_results; the first run of each route is a warm-up", "jpeg": "predictions only (ground truths are WebP)"}
-        times, texts = {False: [], True: []}, {}
-        for r in range(args.rounds + 1):
-            for flag in (False, True):
-                t0 = time.perf_counter()
-                metrics.evaluate_results(str(tmp / "pred"), str(tmp / "gt"), str(tmp / "fmasks"), ".jpg", ".webp", ".png",
-                                         out_metrics_path=str(tmp / f"m{int(flag)}.json"), background_color="white", gpu_ids=[dev.index],
-                                         device_decode=flag)
-                if r > 0:
-                    times[flag].append(time.perf_counter() - t0)
-                texts[flag] = (tmp / f"m{int(flag)}.json").read_text()
+        texts = {}
+
+        def run_eval(flag, r):
+            t0 = time.perf_counter()
+            metrics.evaluate_results(str(tmp / "pred"), str(tmp / "gt"), str(tmp / "fmasks"), ".jpg", ".webp", ".png",
+                                     out_metrics_path=str(tmp / f"m{int(flag)}.json"), background_color="white", gpu_ids=[dev.index],
+                                     device_decode=flag)
+            dt = time.perf_counter() - t0
+            texts[flag] = (tmp / f"m{int(flag)}.json").read_text()
+            return dt
+        times = alternate(run_eval, args.rounds)
         ev["flag_off_seconds"], ev["flag_on_seconds"] = times[False], times[True]
         ev["flag_off_seconds_median"], ev["flag_on_seconds_median"] = statistics.median(times[False]), statistics.median(times[True])
         ev["same_metrics_json"] = texts[False] == texts[True]
@@ -176,19 +132,17 @@ def main(argv=None):
         stage = {"what": "stage", "images": args.stage_images, "image": [2448, 2048], "batch_size": 8, "num_workers": 16,
                  "network_stand_in": "lambda x: x[:, :1]", "device_png": True,
                  "timing": "wall clock of remove_background (decode, upload, kernels, PNG files written), per image; the first run of each route is a warm-up"}
-        times = {False: [], True: []}
-        for r in range(args.rounds + 1):
-            for flag in (False, True):
-                out = tmp / f"out_{r}_{int(flag)}"
-                t0 = time.perf_counter()
-                res = matting.remove_background(str(tmp / "images"), str(out / "fmasks"), str(out / "images_alpha"), image_ext=".jpg", batch_size=8,
-                                                num_workers=16, gpu_ids=[dev.index], matting_model=lambda x: x[:, :1], device_png=True,
-                                                device_decode=flag)
-                dt = time.perf_counter() - t0
-                assert res["written"] == args.stage_images
-                if r > 0:
-                    times[flag].append(dt / args.stage_images)
-                shutil.rmtree(out)
+        def run_stage(flag, r):
+            out = tmp / f"out_{r}_{int(flag)}"
+            t0 = time.perf_counter()
+            res = matting.remove_background(str(tmp / "images"), str(out / "fmasks"), str(out / "images_alpha"), image_ext=".jpg", batch_size=8,
+                                            num_workers=16, gpu_ids=[dev.index], matting_model=lambda x: x[:, :1], device_png=True,
+                                            device_decode=flag)
+            dt = time.perf_counter() - t0
+            assert res["written"] == args.stage_images
+            shutil.rmtree(out)
+            return dt / args.stage_images
+        times = alternate(run_stage, args.rounds)
         stage["flag_off_seconds_per_image"], stage["flag_on_seconds_per_image"] = times[False], times[True]
         stage["flag_off_seconds_per_image_median"] = statistics.median(times[False])
         stage["flag_on_seconds_per_image_median"] = statistics.median(times[True])

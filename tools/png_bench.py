@@ -24,7 +24,6 @@ import statistics
 import sys
 import tempfile
 import time
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import numpy as np
@@ -35,6 +34,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
+from bench_common import alternate, device_time, pillow_times  # noqa: E402
 from diffuman4d_amd.host import lib as L  # noqa: E402
 from diffuman4d_amd.host import matting, ops, png  # noqa: E402
 
@@ -51,21 +51,6 @@ def descriptors(items):
         desc[k, 7], desc[k, 8] = filt0, stripe0
         filt0, stripe0, bound = filt0 + h * (1 + w * ch), stripe0 + png.n_stripes(h, w, ch), bound + int(lib.dm4d_png_bound(h, w, ch))
     return desc, bound, int(lib.dm4d_png_ws_bytes(filt0, stripe0, len(items)))
-
-
-def device_time(fn, reps: int) -> float:
-    """Median over `reps` calls of the HIP-event time of one call, in seconds, after one warm-up call."""
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b) / 1e3)
-    return statistics.median(times)
 
 
 def pillow_bytes(img: Image.Image) -> int:
@@ -115,19 +100,11 @@ def main(argv=None):
     enc["device_pair_seconds_per_image"] = enc["device_mask_seconds_per_file"] + enc["device_rgba_seconds_per_file"]
 
     # Pillow through 16 threads: the same files, into memory
-    torch.set_num_threads(1)
     pil_masks = [Image.fromarray(pairs[i % 4][1]) for i in range(n)]
     pil_rgba = [Image.fromarray(np.dstack(pairs[i % 4])) for i in range(n)]
     for kind, ims in (("mask", pil_masks), ("rgba", pil_rgba)):
-        for threads in (1, 16):
-            sub = ims[:max(4, n // 8)] if threads == 1 else ims
-            t0 = time.perf_counter()
-            if threads == 1:
-                got = [pillow_bytes(im) for im in sub]
-            else:
-                with ThreadPoolExecutor(max_workers=threads) as pool:
-                    got = list(pool.map(pillow_bytes, sub))
-            enc[f"pillow_{kind}_seconds_per_file_{threads}_threads"] = (time.perf_counter() - t0) / len(sub)
+        for threads, (seconds, got) in pillow_times(pillow_bytes, ims).items():
+            enc[f"pillow_{kind}_seconds_per_file_{threads}_threads"] = seconds
         sizes[f"pillow_{kind}_file_bytes_mean"] = sum(got) / len(got)
     enc["pillow_pair_seconds_per_image_16_threads"] = enc["pillow_mask_seconds_per_file_16_threads"] + enc["pillow_rgba_seconds_per_file_16_threads"]
     sizes["device_route_bytes_down_per_image"] = sizes["device_mask_file_bytes_mean"] + sizes["device_rgba_file_bytes_mean"]
@@ -148,18 +125,16 @@ def main(argv=None):
             Image.fromarray(pairs[i % 4][0]).save(p, quality=90)
         stage = {"what": "stage", "images": args.stage_images, "batch_size": 8, "num_workers": 16, "network_stand_in": "lambda x: x[:, :1]",
                  "timing": "wall clock of remove_background (decode, upload, kernels, PNG files written), per image; the first run of each route is a warm-up"}
-        times = {False: [], True: []}
-        for r in range(args.stage_rounds + 1):
-            for device_png in (False, True):
-                out = tmp / f"out_{r}_{int(device_png)}"
-                t0 = time.perf_counter()
-                res = matting.remove_background(str(tmp / "images"), str(out / "fmasks"), str(out / "images_alpha"), image_ext=".jpg", batch_size=8,
-                                                num_workers=16, gpu_ids=[dev.index], matting_model=lambda x: x[:, :1], device_png=device_png)
-                dt = time.perf_counter() - t0
-                assert res["written"] == args.stage_images
-                if r > 0:
-                    times[device_png].append(dt / args.stage_images)
-                shutil.rmtree(out)
+        def run_stage(device_png, r):
+            out = tmp / f"out_{r}_{int(device_png)}"
+            t0 = time.perf_counter()
+            res = matting.remove_background(str(tmp / "images"), str(out / "fmasks"), str(out / "images_alpha"), image_ext=".jpg", batch_size=8,
+                                            num_workers=16, gpu_ids=[dev.index], matting_model=lambda x: x[:, :1], device_png=device_png)
+            dt = time.perf_counter() - t0
+            assert res["written"] == args.stage_images
+            shutil.rmtree(out)
+            return dt / args.stage_images
+        times = alternate(run_stage, args.stage_rounds)
         stage["pillow_route_seconds_per_image"] = times[False]
         stage["device_png_route_seconds_per_image"] = times[True]
         stage["pillow_route_seconds_per_image_median"] = statistics.median(times[False])

@@ -20,13 +20,11 @@ from __future__ import annotations
 import argparse
 import io
 import json
-import re
 import shutil
 import statistics
 import sys
 import tempfile
 import time
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import numpy as np
@@ -37,43 +35,8 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 sys.path.insert(0, str(ROOT / "tests"))
 
+from bench_common import alternate, device_time, kernel_shares, pillow_decode, pillow_times  # noqa: E402
 from diffuman4d_amd.host import metrics, pngdec, vhull  # noqa: E402
-
-
-def device_time(fn, reps: int) -> float:
-    """Median over `reps` calls of the HIP-event time of one call, in seconds, after one warm-up call."""
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        fn()
-        b.record()
-        b.synchronize()
-        times.append(a.elapsed_time(b) / 1e3)
-    return statistics.median(times)
-
-
-def kernel_shares(fn):
-    """{kernel name: device seconds} of one call, from torch's profiler; None where it does not see the library's kernels."""
-    try:
-        from torch.profiler import ProfilerActivity, profile
-        with profile(activities=[ProfilerActivity.CUDA]) as prof:
-            fn()
-            torch.cuda.synchronize()
-        out = {}
-        for e in prof.key_averages():
-            m = re.search(r"pngdec_\w+_kernel", e.key)
-            if m:
-                out[m.group(0)] = out.get(m.group(0), 0.0) + getattr(e, "device_time_total", getattr(e, "cuda_time_total", 0.0)) / 1e6
-        return out or None
-    except Exception:
-        return None
-
-
-def pillow_decode(data: bytes) -> int:
-    return np.asarray(Image.open(io.BytesIO(data))).size
 
 
 def save_png(a: np.ndarray) -> bytes:
@@ -97,17 +60,6 @@ def camera(angle: float, dist: float) -> list:
     m = np.eye(4)
     m[:3, 0], m[:3, 1], m[:3, 2], m[:3, 3] = x, np.cross(z, x), z, pos
     return m.tolist()
-
-
-def alternate(run, rounds: int) -> dict:
-    """run(flag) -> seconds, flag off and on alternately; the first run of each route is a warm-up"""
-    times = {False: [], True: []}
-    for r in range(rounds + 1):
-        for flag in (False, True):
-            dt = run(flag)
-            if r > 0:
-                times[flag].append(dt)
-    return times
 
 
 def main(argv=None):
@@ -143,7 +95,7 @@ def main(argv=None):
         staged = pngdec.stage_chunk(plans, files, offsets, [ch] * n, dev)
         call = lambda: pngdec.launch_chunk(staged, out)
         t = device_time(call, args.reps)
-        shares = kernel_shares(call)
+        shares = kernel_shares(call, r"pngdec_\w+_kernel")
         status = call().cpu().tolist()
         got = out.view((n, h, w) if ch == 1 else (n, h, w, ch))[:4].cpu().numpy()
         equal = status == [0] * n and all(np.array_equal(got[i], np.asarray(Image.open(io.BytesIO(four[i])))) for i in range(4))
@@ -152,16 +104,8 @@ def main(argv=None):
                 "inflate_share": shares["pngdec_inflate_kernel"] / sum(shares.values()) if shares and "pngdec_inflate_kernel" in shares else None,
                 "unfilter_share": shares["pngdec_unfilter_kernel"] / sum(shares.values()) if shares and "pngdec_unfilter_kernel" in shares else None,
                 "timing": f"HIP events around one dm4d_png_decode_u8 call for {n} files, warm, median of {args.reps}"}
-        torch.set_num_threads(1)
-        for threads in (1, 16):
-            sub = files[:max(4, n // 8)] if threads == 1 else files
-            t0 = time.perf_counter()
-            if threads == 1:
-                [pillow_decode(d) for d in sub]
-            else:
-                with ThreadPoolExecutor(max_workers=threads) as pool:
-                    list(pool.map(pillow_decode, sub))
-            line[f"pillow_seconds_per_image_{threads}_threads"] = (time.perf_counter() - t0) / len(sub)
+        for threads, (seconds, _) in pillow_times(pillow_decode, files).items():
+            line[f"pillow_seconds_per_image_{threads}_threads"] = seconds
         lines.append(line)
         lines.append({"what": "bytes", "files": label, "pcie_bytes_per_image_flag_off": h * w * ch, "pcie_bytes_per_image_flag_on": staged["bytes_up"] / n})
         lines.append({"what": "equal", "files": label, "device_equals_pillow": bool(equal)})
@@ -184,7 +128,7 @@ def main(argv=None):
                  "timing": "wall clock of carve_scene (files read, decoded, carved, PLY files written), per frame; the first run of each route is a warm-up"}
         trees = {}
 
-        def run_carve(flag):
+        def run_carve(flag, r):
             out = tmp / f"surfs_{int(flag)}"
             shutil.rmtree(out, ignore_errors=True)
             t0 = time.perf_counter()
@@ -216,7 +160,7 @@ def main(argv=None):
               "timing": "wall clock of evaluate_results; the first run of each route is a warm-up", "png": "predictions, ground truths and masks"}
         texts = {}
 
-        def run_eval(flag):
+        def run_eval(flag, r):
             t0 = time.perf_counter()
             metrics.evaluate_results(str(tmp / "pred"), str(tmp / "gt"), str(tmp / "fmasks"), ".png", ".png", ".png",
                                      out_metrics_path=str(tmp / f"m{int(flag)}.json"), background_color="white", gpu_ids=[dev.index],

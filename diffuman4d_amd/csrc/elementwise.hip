@@ -64,7 +64,7 @@ __device__ __forceinline__ void put_in(u16* row, int c, int cpad, float v) {  //
 }
 template <typename T, bool H16 = false>
 __global__ void pack_kernel(T* latents, const T* pv, const T* pl, const T* sk, const T* mask, const int32_t* is_cond,
-                            const int32_t* frame_idx, u16* out, int F, int HW, int cpad, int use_cfg) {
+                            const int32_t* frame_idx, u16* out, int F, int HW, int cpad, int use_cfg, const int32_t* out_row, int Fo) {
   constexpr bool SPLIT = sizeof(T) == 4 && !H16;
   constexpr int OUT = H16 ? 2 : (SPLIT ? 1 : 0);
   const int ldo = SPLIT ? 2 * cpad : cpad;
@@ -86,9 +86,18 @@ __global__ void pack_kernel(T* latents, const T* pv, const T* pl, const T* sk, c
 #pragma unroll
     for (int c = 0; c < 4; ++c) lat[c] = ldv(latents + i * 4 + c);
   }
+  // row subset (out_row != NULL): frame f goes to row out_row[f] of a compact [Fo] half, or nowhere (< 0: only the aliasing above)
+  int64_t oo = o;
+  if (out_row) {
+    const int r = out_row[f];
+    if (r < 0) return;
+    oo = (int64_t)r * HW + (o - (int64_t)f * HW);
+  } else {
+    Fo = F;
+  }
   const float m = ldv(mask + i);
   const int nsk = sk ? 4 : 0;
-  u16* pos = out + ((use_cfg ? (int64_t)F * HW : 0) + o) * ldo;
+  u16* pos = out + ((use_cfg ? (int64_t)Fo * HW : 0) + oo) * ldo;
   int c = 0;
   for (int k = 0; k < 4; ++k) put(pos, c++, lat[k]);
   for (int k = 0; k < 6; ++k) put(pos, c++, ldv(pl + i * 6 + k));
@@ -96,7 +105,7 @@ __global__ void pack_kernel(T* latents, const T* pv, const T* pl, const T* sk, c
   put(pos, c++, m);
   for (; c < cpad; ++c) put(pos, c, 0.f);
   if (use_cfg) {
-    u16* neg = out + o * ldo;
+    u16* neg = out + oo * ldo;
     c = 0;
     for (int k = 0; k < 4; ++k) put(neg, c++, cond ? 1.0f : lat[k]);
     for (int k = 0; k < 6; ++k) put(neg, c++, 0.f);
@@ -425,14 +434,23 @@ extern "C" int dm4d_silu_bf16(void* stream, const void* X, void* Y, int64_t n) {
 
 template <typename T, bool H16 = false>
 static int pack_impl(void* stream, void* latents, const void* pv_lat, const void* plucker, const void* skel, const void* mask,
-                     const int32_t* is_cond, const int32_t* frame_idx, void* out, int F, int HW, int cpad, int use_cfg) {
+                     const int32_t* is_cond, const int32_t* frame_idx, void* out, int F, int HW, int cpad, int use_cfg,
+                     const int32_t* out_row = nullptr, int Fo = 0) {
   if (!latents || !pv_lat || !plucker || !mask || !is_cond || !out || F <= 0 || HW <= 0)
     return dm4d_set_error(DM4D_ERR_ARG, "pack_model_input: null pointer or empty shape");
   if (cpad < 11 + (skel ? 4 : 0)) return dm4d_set_error(DM4D_ERR_ARG, "pack_model_input: cpad too small");
   hipLaunchKernelGGL((pack_kernel<T, H16>), grid1d((int64_t)F * HW, 256), dim3(256), 0, (hipStream_t)stream, (T*)latents,
                      (const T*)pv_lat, (const T*)plucker, (const T*)skel, (const T*)mask, is_cond, frame_idx,
-                     (u16*)out, F, HW, cpad, use_cfg);
+                     (u16*)out, F, HW, cpad, use_cfg, out_row, Fo);
   return dm4d_check_launch("pack_kernel");
+}
+// the row-subset entries: out_row int32 [F] on the device, Fo = rows of one half of the compact result
+template <typename T, bool H16 = false>
+static int pack_rows_impl(void* stream, void* latents, const void* pv_lat, const void* plucker, const void* skel, const void* mask,
+                          const int32_t* is_cond, const int32_t* frame_idx, const int32_t* out_row, void* out, int F, int Fo, int HW,
+                          int cpad, int use_cfg) {
+  if (!out_row || Fo <= 0 || Fo > F) return dm4d_set_error(DM4D_ERR_ARG, "pack_model_input_rows: no row table, or a row count outside 1..F");
+  return pack_impl<T, H16>(stream, latents, pv_lat, plucker, skel, mask, is_cond, frame_idx, out, F, HW, cpad, use_cfg, out_row, Fo);
 }
 extern "C" int dm4d_pack_model_input_bf16(void* stream, void* latents, const void* pv_lat, const void* plucker,
                                           const void* skel, const void* mask, const int32_t* is_cond,
@@ -448,6 +466,97 @@ extern "C" int dm4d_pack_model_input_f32_f16(void* stream, float* latents, const
                                              const float* skel, const float* mask, const int32_t* is_cond,
                                              const int32_t* frame_idx, void* out, int F, int HW, int cpad, int use_cfg) {
   return pack_impl<float, true>(stream, latents, pv_lat, plucker, skel, mask, is_cond, frame_idx, out, F, HW, cpad, use_cfg);
+}
+extern "C" int dm4d_pack_model_input_rows_bf16(void* stream, void* latents, const void* pv_lat, const void* plucker,
+                                               const void* skel, const void* mask, const int32_t* is_cond,
+                                               const int32_t* frame_idx, const int32_t* out_row, void* out, int F, int Fo, int HW,
+                                               int cpad, int use_cfg) {
+  return pack_rows_impl<u16>(stream, latents, pv_lat, plucker, skel, mask, is_cond, frame_idx, out_row, out, F, Fo, HW, cpad, use_cfg);
+}
+extern "C" int dm4d_pack_model_input_rows_f32_split(void* stream, float* latents, const float* pv_lat, const float* plucker,
+                                                    const float* skel, const float* mask, const int32_t* is_cond,
+                                                    const int32_t* frame_idx, const int32_t* out_row, void* out, int F, int Fo,
+                                                    int HW, int cpad, int use_cfg) {
+  return pack_rows_impl<float>(stream, latents, pv_lat, plucker, skel, mask, is_cond, frame_idx, out_row, out, F, Fo, HW, cpad, use_cfg);
+}
+extern "C" int dm4d_pack_model_input_rows_f32_f16(void* stream, float* latents, const float* pv_lat, const float* plucker,
+                                                  const float* skel, const float* mask, const int32_t* is_cond,
+                                                  const int32_t* frame_idx, const int32_t* out_row, void* out, int F, int Fo,
+                                                  int HW, int cpad, int use_cfg) {
+  return pack_rows_impl<float, true>(stream, latents, pv_lat, plucker, skel, mask, is_cond, frame_idx, out_row, out, F, Fo, HW, cpad,
+                                     use_cfg);
+}
+
+// ---- row mover: dst[dst_idx[r]] = src[src_idx[r]] for whole rows, a small table of jobs per launch (dm4d.h: dm4d_rows_move) ----
+namespace {
+
+constexpr int kMoveThreads = 256, kMoveUnroll = 4;
+constexpr int64_t kMoveSeg = (int64_t)kMoveThreads * kMoveUnroll;  // 16-byte pieces a workgroup moves per step: 16 KB of one row
+constexpr int kMoveBlocks = 4096;                                  // workgroups of a launch, dealt to the jobs by their bytes
+
+// job i owns the workgroups first_block[i] .. first_block[i + 1] - 1
+struct RowsMoveTable {
+  Dm4dRowsMoveJob job[DM4D_ROWS_MOVE_MAX_JOBS];
+  int first_block[DM4D_ROWS_MOVE_MAX_JOBS + 1];
+  int n_jobs;
+};
+
+inline int64_t move_steps(const Dm4dRowsMoveJob& j) { return (int64_t)j.n_rows * ((j.row_bytes / 16 + kMoveSeg - 1) / kMoveSeg); }
+
+// The workgroups of a job stride over its (row, 16 KB segment) pairs.  Every address is a base plus a 64-bit offset.
+__global__ void __launch_bounds__(kMoveThreads) rows_move_kernel(RowsMoveTable tab) {
+  int ji = 0;
+  while (ji + 1 < tab.n_jobs && (int)blockIdx.x >= tab.first_block[ji + 1]) ++ji;
+  const Dm4dRowsMoveJob& j = tab.job[ji];
+  const int64_t pieces = j.row_bytes / 16, segs = (pieces + kMoveSeg - 1) / kMoveSeg, total = (int64_t)j.n_rows * segs;
+  const int64_t stride = tab.first_block[ji + 1] - tab.first_block[ji];
+  const uint4* src = (const uint4*)j.src;
+  uint4* dst = (uint4*)j.dst;
+  for (int64_t t = (int)blockIdx.x - tab.first_block[ji]; t < total; t += stride) {
+    const int64_t r = t / segs, first = (t - r * segs) * kMoveSeg + threadIdx.x;
+    const uint4* s = src + (int64_t)j.src_row_idx[r] * pieces;
+    uint4* d = dst + (int64_t)j.dst_row_idx[r] * pieces;
+    uint4 v[kMoveUnroll];
+#pragma unroll
+    for (int k = 0; k < kMoveUnroll; ++k) {
+      const int64_t c = first + (int64_t)k * kMoveThreads;
+      if (c < pieces) v[k] = s[c];
+    }
+#pragma unroll
+    for (int k = 0; k < kMoveUnroll; ++k) {
+      const int64_t c = first + (int64_t)k * kMoveThreads;
+      if (c < pieces) d[c] = v[k];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" int dm4d_rows_move(void* stream, const Dm4dRowsMoveJob* jobs, int n_jobs) {
+  if (!jobs || n_jobs <= 0) return dm4d_set_error(DM4D_ERR_ARG, "rows_move: no jobs");
+  if (n_jobs > DM4D_ROWS_MOVE_MAX_JOBS) return dm4d_set_error(DM4D_ERR_ARG, "rows_move: too many jobs for one launch");
+  RowsMoveTable tab{};
+  int64_t all = 0;
+  for (int i = 0; i < n_jobs; ++i) {
+    const Dm4dRowsMoveJob& j = jobs[i];
+    if (j.n_rows < 0 || j.row_bytes <= 0) return dm4d_set_error(DM4D_ERR_ARG, "rows_move: negative row count or empty rows");
+    if (j.row_bytes % 16) return dm4d_set_error(DM4D_ERR_ARG, "rows_move: row_bytes must be a multiple of 16");
+    if (j.n_rows > 0 && (!j.src || !j.dst || !j.src_row_idx || !j.dst_row_idx)) return dm4d_set_error(DM4D_ERR_ARG, "rows_move: null pointer");
+    if (((uintptr_t)j.src | (uintptr_t)j.dst) % 16) return dm4d_set_error(DM4D_ERR_ARG, "rows_move: src and dst must be 16-byte aligned");
+    if (((uintptr_t)j.src_row_idx | (uintptr_t)j.dst_row_idx) % 4) return dm4d_set_error(DM4D_ERR_ARG, "rows_move: misaligned index table");
+    tab.job[i] = j;
+    all += move_steps(j);
+  }
+  if (all == 0) return DM4D_OK;  // nothing to move
+  tab.n_jobs = n_jobs;
+  for (int i = 0; i < n_jobs; ++i) {  // a job's share of the workgroups, at least one and at most one per step
+    const int64_t steps = move_steps(jobs[i]);
+    int64_t nb = (steps * kMoveBlocks + all - 1) / all;
+    nb = nb > steps ? steps : nb;
+    tab.first_block[i + 1] = tab.first_block[i] + (int)nb;
+  }
+  hipLaunchKernelGGL(rows_move_kernel, dim3((unsigned)tab.first_block[n_jobs]), dim3(kMoveThreads), 0, (hipStream_t)stream, tab);
+  return dm4d_check_launch("rows_move_kernel");
 }
 
 template <typename T>

@@ -783,7 +783,17 @@ __global__ __launch_bounds__(256) void softmax32_split_kernel(const float* S, in
   }
 }
 
+// dm4d_groupnorm_plan_batch: the batch this thread's GroupNorm launches plan their statistics chunks for (0 = each launch's own)
+thread_local int t_gn_plan_batch = 0;
+inline int gn_plan_nchunk(int B, int HW) { return gn_nchunk(t_gn_plan_batch > B ? t_gn_plan_batch : B, HW); }
+
 }  // namespace
+
+extern "C" int dm4d_groupnorm_plan_batch(int B) {
+  if (B < 0) return dm4d_set_error(DM4D_ERR_ARG, "groupnorm_plan_batch: negative batch");
+  t_gn_plan_batch = B;
+  return DM4D_OK;
+}
 
 extern "C" size_t dm4d_groupnorm_ws_bytes(int B, int HW, int groups) {
   return (size_t)B * gn_nchunk(B, HW) * groups * 2 * sizeof(float);
@@ -802,7 +812,7 @@ static int groupnorm_impl(void* stream, const void* X1, int C1, const void* X2, 
   const int C = C1 + C2;
   if ((C1 & 7) || (C2 & 7) || C % groups != 0 || C > GN_MAXC)
     return dm4d_set_error(DM4D_ERR_ARG, "groupnorm: channels must be multiples of 8, divisible by groups, <= 4096");
-  GNParams p{X1, X2, C1, C2, B, HW, groups, gn_nchunk(B, HW), eps, (const u16*)gamma, (const u16*)beta, (u16*)Y, apply_silu, ws, (u16*)Yraw};
+  GNParams p{X1, X2, C1, C2, B, HW, groups, gn_plan_nchunk(B, HW), eps, (const u16*)gamma, (const u16*)beta, (u16*)Y, apply_silu, ws, (u16*)Yraw};
   hipStream_t st = (hipStream_t)stream;
   {
     int gps, SV, RPB, NV;
@@ -848,7 +858,7 @@ static int groupnorm_f32_impl(void* stream, const float* X1, int C1, const float
     return dm4d_set_error(DM4D_ERR_ARG, "groupnorm_f32: bad arguments");
   const int C = C1 + C2;
   if (C % groups != 0 || C > GN_MAXC) return dm4d_set_error(DM4D_ERR_ARG, "groupnorm_f32: channels must divide into groups and be <= 4096");
-  GNParams p{X1, X2, C1, C2, B, HW, groups, gn_nchunk(B, HW), eps, (const u16*)gamma, (const u16*)beta, (u16*)Y, apply_silu, ws, nullptr};
+  GNParams p{X1, X2, C1, C2, B, HW, groups, gn_plan_nchunk(B, HW), eps, (const u16*)gamma, (const u16*)beta, (u16*)Y, apply_silu, ws, nullptr};
   const bool vec4 = C1 % 4 == 0 && C2 % 4 == 0 && ((uintptr_t)X1 & 15) == 0 && (C2 == 0 || ((uintptr_t)X2 & 15) == 0) && ((uintptr_t)Y & 7) == 0;
   return vec4 ? gn32_launch<4, Out>(p, (hipStream_t)stream) : gn32_launch<1, Out>(p, (hipStream_t)stream);
 }

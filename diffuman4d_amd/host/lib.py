@@ -96,6 +96,12 @@ SIGNATURES = {
     "dm4d_attn_out_ff_geglu_fused_f16": (_i, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i,
                                                _i]),
     "dm4d_pack_model_input_f32_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i]),
+    # the per-sweep prefix cache (host/pipeline.py): model input of a subset of a window's frames, and the row mover
+    "dm4d_pack_model_input_rows_bf16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "dm4d_pack_model_input_rows_f32_split": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "dm4d_pack_model_input_rows_f32_f16": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i]),
+    "dm4d_rows_move": (_i, [_vp, _vp, _i]),
+    "dm4d_groupnorm_plan_batch": (_i, [_i]),
     "dm4d_tune_set_gemm_config": (_i, [_i]),
     "dm4d_tune_set_groupnorm_resident": (_i, [_i]),
     "dm4d_nchw_to_nhwc_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
@@ -211,6 +217,12 @@ PNGDEC_ST_DISTANCE = 8
 PNGDEC_ST_END = 16
 PNGDEC_ST_ADLER = 32
 PNGDEC_ST_FILTER = 64
+ROWS_MOVE_MAX_JOBS = 16
+
+
+class RowsMoveJob(C.Structure):
+    """Dm4dRowsMoveJob of include/dm4d.h."""
+    _fields_ = [("src", _vp), ("dst", _vp), ("src_row_idx", _vp), ("dst_row_idx", _vp), ("n_rows", _i64), ("row_bytes", _i64)]
 
 
 class Dm4dError(RuntimeError):

@@ -23,7 +23,7 @@ import torch
 
 from . import lib as _l
 from .lib import (CAPTURE_FIELDS, EVAL_BG_SHIFT, EVAL_CROP_MASKS, EVAL_FIELDS, EVAL_IMAGE_F32, EVAL_MASK_F32, EVAL_OUT,  # noqa: F401
-                  LOG2E, LPIPS_IN_COLS, LPIPS_TAPS, SKEL_CIRCLE, SKEL_COORD_MAX, SKEL_COORD_MIN, SKEL_FIELDS, SKEL_LINE, SKEL_MAX_PRIMS,
+                  LOG2E, LPIPS_IN_COLS, LPIPS_TAPS, ROWS_MOVE_MAX_JOBS, SKEL_CIRCLE, SKEL_COORD_MAX, SKEL_COORD_MIN, SKEL_FIELDS, SKEL_LINE, SKEL_MAX_PRIMS,
                   TRIANG_MAX_VIEWS, VHULL_BLOCK, VHULL_MAX_CHUNK)
 
 BF16 = torch.bfloat16
@@ -530,6 +530,21 @@ def groupnorm(x1: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups:
     return y
 
 
+class groupnorm_as_in_batch:
+    """with groupnorm_as_in_batch(B): the GroupNorm launches of this thread on fewer than B samples chunk their statistics as a launch
+    on B samples does, so a sample gets the bits it has inside the batch of B (dm4d.h: dm4d_groupnorm_plan_batch)."""
+
+    def __init__(self, batch: int):
+        self.batch = int(batch)
+
+    def __enter__(self):
+        _l.call("dm4d_groupnorm_plan_batch", self.batch)
+
+    def __exit__(self, *exc):
+        _l.call("dm4d_groupnorm_plan_batch", 0)
+        return False
+
+
 def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float = 1e-5) -> torch.Tensor:
     """fp32 input (wide precisions): the result leaves as an operand -- parity: two-term [..., 2 C]; fp16 (fp16 gamma / beta): one fp16
     plane."""
@@ -725,10 +740,13 @@ def silu(x: torch.Tensor) -> torch.Tensor:
 
 
 def pack_model_input(latents, pv_lat, plucker, skel, mask, is_cond, cpad: int, use_cfg: bool,
-                     frame_idx: Optional[torch.Tensor] = None, h16: bool = False) -> torch.Tensor:
+                     frame_idx: Optional[torch.Tensor] = None, h16: bool = False, out_row: Optional[torch.Tensor] = None,
+                     rows: int = 0) -> torch.Tensor:
     """Inputs NHWC [N, HW, c] (task level); is_cond int32 [F]; frame_idx int32 [F] selects the window's frames
     (None: F = N, identity).  Mutates the cond rows of `latents` (reference aliasing).
-    fp32 task tensors (wide precisions): the result is conv_in's operand -- [hi | lo] bf16, or (h16) one fp16 plane."""
+    fp32 task tensors (wide precisions): the result is conv_in's operand -- [hi | lo] bf16, or (h16) one fp16 plane.
+    out_row (int32 [F], with `rows`): only the frames with out_row[f] >= 0 are written, frame f to row out_row[f] of a compact result of
+    `rows` rows per CFG half (dm4d.h: dm4d_pack_model_input_rows_bf16); the aliasing still covers every cond frame."""
     dt = F32 if latents.dtype == F32 else BF16  # fp32 task tensors = parity precision: the result is conv_in's two-term operand
     for t, n in ((latents, "latents"), (pv_lat, "pv_lat"), (plucker, "plucker"), (mask, "mask")):
         _req(t, n, dt)
@@ -743,15 +761,46 @@ def pack_model_input(latents, pv_lat, plucker, skel, mask, is_cond, cpad: int, u
     else:
         assert latents.shape[0] == F
     assert not h16 or dt == F32
-    out = torch.empty(((2 if use_cfg else 1) * F, HW, 2 * cpad if (dt == F32 and not h16) else cpad), dtype=F16 if h16 else BF16,
+    Fo = F
+    if out_row is not None:
+        _req(out_row, "out_row", torch.int32)
+        if out_row.shape[0] != F or not 1 <= rows <= F:
+            raise _l.Dm4dError("pack_model_input: out_row needs one entry per window frame and 1 <= rows <= F")
+        Fo = int(rows)
+    out = torch.empty(((2 if use_cfg else 1) * Fo, HW, 2 * cpad if (dt == F32 and not h16) else cpad), dtype=F16 if h16 else BF16,
                       device=latents.device)
-    if dt == F32:
-        name = "dm4d_pack_model_input_f32_f16" if h16 else "dm4d_pack_model_input_f32_split"
+    suffix = ("f32_f16" if h16 else "f32_split") if dt == F32 else "bf16"
+    front = (_stream(), _p(latents), _p(pv_lat), _p(plucker), _p(skel), _p(mask), _p(is_cond), _p(frame_idx))
+    if out_row is None:
+        _l.call("dm4d_pack_model_input_" + suffix, *front, _p(out), F, HW, cpad, 1 if use_cfg else 0)
     else:
-        name = "dm4d_pack_model_input_bf16"
-    _l.call(name, _stream(), _p(latents), _p(pv_lat), _p(plucker), _p(skel), _p(mask), _p(is_cond), _p(frame_idx), _p(out), F, HW, cpad,
-            1 if use_cfg else 0)
+        _l.call("dm4d_pack_model_input_rows_" + suffix, *front, _p(out_row), _p(out), F, Fo, HW, cpad, 1 if use_cfg else 0)
     return out
+
+
+def rows_move(jobs) -> None:
+    """One launch: dst[dst_idx[r]] = src[src_idx[r]] for every job (src, dst, src_idx, dst_idx) of `jobs` (dm4d.h: dm4d_rows_move; at most
+    ROWS_MOVE_MAX_JOBS).  src / dst: contiguous device tensors of one dtype whose rows (dim 0) have the same byte size, a multiple of 16;
+    src_idx / dst_idx: int32 device vectors of one length (0: the job is skipped).  The caller vouches for the indices -- they are not
+    read here (no host sync) -- and for distinct dst rows."""
+    if not jobs:
+        return
+    if len(jobs) > _l.ROWS_MOVE_MAX_JOBS:
+        raise _l.Dm4dError(f"rows_move: {len(jobs)} jobs, one launch takes {_l.ROWS_MOVE_MAX_JOBS}")
+    tab = (_l.RowsMoveJob * len(jobs))()
+    moved = 0
+    for t, (src, dst, si, di) in zip(tab, jobs):
+        _req(src, "src", src.dtype), _req(dst, "dst", src.dtype), _req(si, "src_idx", torch.int32), _req(di, "dst_idx", torch.int32)
+        if not (src.is_contiguous() and dst.is_contiguous() and si.is_contiguous() and di.is_contiguous()):
+            raise _l.Dm4dError("rows_move: tensors and index vectors must be contiguous")
+        rb = src[0].numel() * src.element_size() if src.shape[0] else 0
+        if si.ndim != 1 or si.shape != di.shape or (si.shape[0] and (rb == 0 or dst.shape[0] == 0 or dst[0].numel() * dst.element_size() != rb)):
+            raise _l.Dm4dError("rows_move: src and dst rows differ in size, or the index vectors in length")
+        t.src, t.dst, t.src_row_idx, t.dst_row_idx, t.n_rows, t.row_bytes = _p(src), _p(dst), _p(si), _p(di), si.shape[0], max(rb, 16)
+        moved += si.shape[0] * rb
+    import ctypes
+    with _Prof("rows_move", 2.0 * moved, "byte", 0):
+        _l.call("dm4d_rows_move", _stream(), ctypes.cast(tab, ctypes.c_void_p), len(jobs))
 
 
 def _cfg_step_inputs(latents, noise_pred, coef, is_cond, frame_idx):

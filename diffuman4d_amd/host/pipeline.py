@@ -15,6 +15,7 @@ Differences that do not change results:
 from __future__ import annotations
 
 import json
+import os
 from pathlib import Path
 from typing import Callable, Dict, List, NamedTuple, Optional
 
@@ -22,12 +23,16 @@ import numpy as np
 import torch
 
 from . import ops
+from .prefix_cache import PrefixBook
 from .schedule import SweepPlan, history_counts, history_flags, plan_sweep
 from .scheduler import DDIMScheduler
 from .unet import UNetMultiviewConditionModel
 
 BF16 = torch.bfloat16
 F32 = torch.float32
+
+# the per-sweep prefix cache of window_call; off = the launches of a call are what they are without it (A/B, tests)
+PREFIX_CACHE = os.environ.get("DM4D_PREFIX_CACHE", "1") != "0"
 
 
 def _identity_tqdm(it, **kw):
@@ -67,6 +72,11 @@ class Diffuman4DPipeline:
         # extension (off = compute what the reference computes): after the last 3-D attention layer run only the rows
         # whose noise prediction the DDIM step reads, i.e. drop the conditioning frames from the per-frame tail of the UNet
         self.prune_cond_rows = False
+        # the per-sweep prefix cache (window_call): what the UNet's per-frame head gives for a conditioning frame is
+        # computed once per sweep and copied into the later window calls; it changes no result.  A sweep whose cache would outgrow
+        # prefix_cache_max_bytes runs without one
+        self.prefix_cache = PREFIX_CACHE
+        self.prefix_cache_max_bytes = 12 << 30
 
     def clear_vae_cache(self):
         self._vae_cache = {"pixel": {}, "skeleton": {}}
@@ -230,8 +240,10 @@ class Diffuman4DPipeline:
         # rows of the CFG batch whose noise prediction is consumed (non-conditioning frames, both halves), per call
         F = win.shape[1]
         keep = [up(np.concatenate([np.nonzero(~c)[0] + h * F for h in range(cfg)]).astype(np.int64)) for c in cond]
+        # win_host / cond_host: what the prefix cache plans from (window_call); the cache itself lives and dies with this dict
         return dict(win=up(win), cond=up(cond.astype(np.int32)), t=up(t_in), coef=up(coef), calls=win.shape[0], cfg=cfg,
-                    win_full=up(win_full.astype(np.int64)), keep=keep, frames_per_group=group, copies=copies)
+                    win_full=up(win_full.astype(np.int64)), keep=keep, frames_per_group=group, copies=copies,
+                    win_host=win.copy(), cond_host=cond.copy(), sharded=shard is not None)
 
     def denoise_latents(self, pv_lat, pl_lat, sk_lat, cm_lat, lat, plan: SweepPlan, domain: str, guidance_scale: float,
                         tqdm: Callable = _identity_tqdm, tables=None, shard=None):
@@ -261,6 +273,49 @@ class Diffuman4DPipeline:
             self.window_call(lat3, pv3, pl3, sk3, cm3, tb, i, h, w, domains, guidance_scale, use_cfg, vpred, shard, x0_prev)
         return lat
 
+    # -- per-sweep prefix cache -------------------------------------------------------------------
+    def _prefix_cache_of(self, tb, inputs, h, w, use_cfg, shard, pose):
+        """The prefix cache of the sweep whose tables are `tb`, kept inside `tb` (one worker stream owns it, it is freed with it), or
+        None where the call takes the single path: the switch is off, a frame shard, a pose-encoder or temporal-embedding model, a UNet
+        without a 3-D down block, tables without their host copies, task tensors that are not on a HIP device (a stand-in pipeline of
+        the CPU tests), or a cache that could outgrow prefix_cache_max_bytes.  The cache is
+        valid for the task tensors it was filled from: another tensor, or an in-place write to one (its _version), drops it."""
+        unet = self.unet
+        if (not self.prefix_cache or shard is not None or pose is not None or "win_host" not in tb or tb.get("sharded") or not inputs[0].is_cuda
+                or getattr(unet, "head_steps", None) is None or unet.tpe is not None or unet.pose_encoder is not None):
+            return None
+        cache = tb.get("prefix")
+        key = (h, w, bool(use_cfg), id(unet))
+        if cache is not None and (cache["key"] != key or any(
+                a is not b or (a is not None and a._version != v) for a, b, v in zip(inputs, cache["inputs"], cache["versions"]))):
+            cache = None
+        if cache is None:
+            # off: set by the sweep's first call, once the size of a slot is known, when the whole cache would exceed the cap
+            cache = tb["prefix"] = dict(key=key, inputs=tuple(inputs), versions=tuple(None if a is None else a._version for a in inputs),
+                                        book=PrefixBook(tb["win_host"], tb["cond_host"], tb["cfg"]), chunks={}, device_tables={},
+                                        slot_bytes=None, off=False)
+        return None if cache["off"] else cache
+
+    def _prefix_chunk(self, cache, c: int, k: int, like: torch.Tensor) -> torch.Tensor:
+        """Chunk c of the cache for head tensor k (rows shaped like those of `like`), allocated on first use."""
+        ch = cache["chunks"].get((c, k))
+        if ch is None:
+            ch = cache["chunks"][(c, k)] = torch.empty((cache["book"].chunk_slots,) + tuple(like.shape[1:]), dtype=like.dtype,
+                                                       device=like.device)
+        return ch
+
+    def _prefix_device_tables(self, cache, t):
+        """The index tables of a call on the device, uploaded once per memoised CallTables (a steady-state call copies nothing)."""
+        dv = cache["device_tables"].get(id(t))
+        if dv is None:
+            def up(a):
+                return torch.from_numpy(a).to(self._device)
+            dv = dict(out_row=up(t.out_row), batch_rows=up(t.batch_rows), scatter=(up(t.scatter.src), up(t.scatter.dst)),
+                      stores=[(m.chunk, up(m.src), up(m.dst)) for m in t.stores],
+                      gathers=[(m.chunk, up(m.src), up(m.dst)) for m in t.gathers], tables=t)
+            cache["device_tables"][id(t)] = dv
+        return dv
+
     def window_call(self, lat3, pv3, pl3, sk3, cm3, tb, i, h, w, domains, guidance_scale, use_cfg, vpred, shard=None,
                     x0_prev=None):
         """One window: pack -> UNet -> CFG + scheduler step (pipeline_diffuman4d.py:369-423), all on device, no host sync.
@@ -273,13 +328,44 @@ class Diffuman4DPipeline:
             if use_cfg:
                 pose = torch.cat([sk3.neg.expand(F, -1, -1, -1), pose])
             sk3 = None
-        x = ops.pack_model_input(lat3, pv3, pl3, sk3, cm3, cond, self.unet.IN_PAD, use_cfg, frame_idx=widx, h16=self.h16)
         keep = tb["keep"][i] if self.prune_cond_rows else None
         fpg = tb.get("frames_per_group", F)  # < F when several tasks share the call (upload_plan copies)
         if len(domains) * fpg != tb["cfg"] * F:
             domains = list(domains[:1]) * (tb["cfg"] * F // fpg)
-        eps = self.unet(x.view(tb["cfg"] * F, h, w, -1), tb["t"][i], domains=domains, num_frames=fpg, shard=shard,
-                        pose_features=pose, keep_rows=keep)
+        cache = self._prefix_cache_of(tb, (pv3, pl3, sk3, cm3), h, w, use_cfg, shard, pose)
+        if cache is None:
+            x = ops.pack_model_input(lat3, pv3, pl3, sk3, cm3, cond, self.unet.IN_PAD, use_cfg, frame_idx=widx, h16=self.h16)
+            eps = self.unet(x.view(tb["cfg"] * F, h, w, -1), tb["t"][i], domains=domains, num_frames=fpg, shard=shard,
+                            pose_features=pose, keep_rows=keep)
+        else:
+            # the head on the rows that need it, one row-mover launch (computed rows into the full batch, cached rows into the full
+            # batch, new conditioning rows into the cache), then the rest of the network on the full batch
+            t = cache["book"].tables(i)
+            dv = self._prefix_device_tables(cache, t)
+            tproj = self.unet.time_proj(tb["t"][i], domains, fpg)
+            if t.whole:
+                x = ops.pack_model_input(lat3, pv3, pl3, sk3, cm3, cond, self.unet.IN_PAD, use_cfg, frame_idx=widx, h16=self.h16)
+                full = part = self.unet.run_head(x.view(tb["cfg"] * F, h, w, -1), tproj)
+            else:
+                x = ops.pack_model_input(lat3, pv3, pl3, sk3, cm3, cond, self.unet.IN_PAD, use_cfg, frame_idx=widx, h16=self.h16,
+                                         out_row=dv["out_row"], rows=len(t.frames))
+                part = self.unet.run_head(x.view(tb["cfg"] * len(t.frames), h, w, -1), tproj.index_select(0, dv["batch_rows"]),
+                                          batch=tb["cfg"] * F)
+                full = [torch.empty((tb["cfg"] * F,) + tuple(p.shape[1:]), dtype=p.dtype, device=p.device) for p in part]
+            if cache["slot_bytes"] is None:  # first call of the sweep (nothing cached yet: t.whole): now the size of a slot is known
+                cache["slot_bytes"] = sum(p[0].numel() * p.element_size() for p in part)
+                cache["off"] = cache["book"].total_slots() * cache["slot_bytes"] > self.prefix_cache_max_bytes
+            jobs = []
+            for k, (p, f) in enumerate(zip(part, full) if not cache["off"] else ()):
+                if not t.whole:
+                    jobs.append((p, f, dv["scatter"][0], dv["scatter"][1]))
+                jobs += [(p, self._prefix_chunk(cache, c, k, p), s, d) for c, s, d in dv["stores"]]
+                jobs += [(self._prefix_chunk(cache, c, k, p), f, s, d) for c, s, d in dv["gathers"]]
+            for a in range(0, len(jobs), ops.ROWS_MOVE_MAX_JOBS):
+                ops.rows_move(jobs[a:a + ops.ROWS_MOVE_MAX_JOBS])
+            if not cache["off"]:
+                cache["book"].commit(t)
+            eps = self.unet(None, tb["t"][i], domains=domains, num_frames=fpg, keep_rows=keep, head=full, tproj=tproj)
         if keep is not None:  # back to one row per CFG-batch entry; the rows left at zero are never read by the step kernel
             full = torch.zeros((tb["cfg"] * F,) + tuple(eps.shape[1:]), dtype=eps.dtype, device=eps.device)
             eps = full.index_copy_(0, keep, eps)

@@ -423,6 +423,7 @@ class UNetMultiviewConditionModel:
                 us = ops.Upsampler(W.conv3(p + "upsamplers.0.conv.weight"), W.vec(p + "upsamplers.0.conv.bias"), parity=self.parity,
                                    h16=self.h16)
             self.up.append((res, att, us))
+        self._plan_down()
         self.no_w, self.no_b = W.vec("conv_norm_out.weight"), W.vec("conv_norm_out.bias")
         self.conv_out_w, self.conv_out_b = W.conv3("conv_out.weight"), W.vec("conv_out.bias")
         # one [sum(Cout), 4*C0] weight for all time_emb_proj layers
@@ -470,10 +471,68 @@ class UNetMultiviewConditionModel:
                            residual=emb, out_f32=P)
         return ops.gemm(op(emb, silu=True), self.tproj_w, bias=self.tproj_b, out_f32=P)  # [B, sum Cout]
 
+    def _check_sample(self, sample: torch.Tensor) -> None:
+        if sample.shape[-1] != (2 * self.IN_PAD if self.parity else self.IN_PAD):
+            raise ValueError(f"sample must be NHWC with {self.IN_PAD} (padded) channels" + (" as a two-term operand [hi | lo]" if self.parity else ""))
+        if sample.dtype != (F16 if self.h16 else BF16):
+            raise ValueError(f"sample must be {'fp16' if self.h16 else 'bf16'} for precision '{self.precision}'")
+
+    def _plan_down(self) -> None:
+        """The down path as a flat list of steps in forward's order, and where its per-frame head ends: `head_steps` = index of the
+        first 3-D transformer (None: no down block is 3-D), `head_tensors` = skips stored in front of it + the running tensor."""
+        cfg, nd = self.config, len(self.down)
+        self._down_plan = []
+        for i, (res, att, ds) in enumerate(self.down):
+            is3d = att is not None and nd - i - 1 < cfg.num_3d_attn_blocks  # :560
+            for j, r in enumerate(res):
+                self._down_plan.append(("res", r, False))
+                if att is not None:
+                    self._down_plan.append(("att", att[j], is3d))
+                self._down_plan.append(("skip", None, False))
+            if ds is not None:
+                self._down_plan.append(("ds", ds, False))
+                self._down_plan.append(("skip", None, False))
+        self.head_steps = next((k for k, (kind, _, is3d) in enumerate(self._down_plan) if kind == "att" and is3d), None)
+        self.head_tensors = 0 if self.head_steps is None else 2 + sum(1 for kind, _, _ in self._down_plan[:self.head_steps] if kind == "skip")
+
+    def _down_steps(self, x, skips: List, tproj, num_frames: int, shard, first: int, last: int):
+        P = self.wide
+        for kind, layer, is3d in self._down_plan[first:last]:
+            if kind == "res":
+                x = layer(x, tproj)
+            elif kind == "att":
+                x = layer(x, num_frames if is3d else 1, shard if is3d else None)
+            elif kind == "ds":
+                x = ops.conv3x3(ops.split(x, h16=self.h16) if P else x, layer[0], bias=layer[1], stride=2, pad=1, out_f32=P)
+            else:
+                skips.append(x)
+        return x
+
+    def time_proj(self, timestep: torch.Tensor, domains: Sequence[str], num_frames: int) -> torch.Tensor:
+        """Every resnet's time-embedding projection of a call, one row per batch row (what forward computes first)."""
+        return self._temb(timestep, domains, num_frames)
+
+    @torch.no_grad()
+    def run_head(self, sample: torch.Tensor, tproj: torch.Tensor, batch: int = 0) -> List[torch.Tensor]:
+        """The layers in front of the first 3-D transformer on ANY batch of rows (they are per frame: no row's value depends on another
+        row): sample [R, h, w, IN_PAD...] as in forward, tproj [R, sum Cout] = those rows of time_proj.  Returns the skip tensors stored so
+        far and, last, the input of the first 3-D transformer: what forward(head=...) takes for the full batch.
+        batch: rows of the batch these rows belong to -- the one launch plan that follows the batch, GroupNorm's statistics chunks, is
+        made for it, so every row has the bits forward gives it inside that batch."""
+        if self.head_steps is None or self.pose_encoder is not None or self.tpe is not None:
+            raise ValueError("run_head: needs a 3-D down block, no pose encoder and no temporal embedding")
+        self._check_sample(sample)
+        with ops.groupnorm_as_in_batch(max(int(batch), sample.shape[0])):
+            x = ops.conv3x3(sample, self.conv_in_w, bias=self.conv_in_b, out_f32=self.wide)
+            skips = [x]
+            x = self._down_steps(x, skips, tproj, 1, None, 0, self.head_steps)
+        return skips + [x]
+
     @torch.no_grad()
     def forward(self, sample: torch.Tensor, timestep: torch.Tensor, skeletons=None, domains: Sequence[str] = ("spatial",),
                 num_frames: int = 1, shard=None, pose_features: Optional[torch.Tensor] = None,
-                keep_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
+                keep_rows: Optional[torch.Tensor] = None, head: Optional[Sequence[torch.Tensor]] = None,
+                tproj: Optional[torch.Tensor] = None) -> torch.Tensor:
         """sample [B, h, w, 32] NHWC bf16 (channels beyond in_channels zero); timestep [B]; -> [B, h, w, out_channels].
         precision "parity": sample is the two-term operand [B, h, w, 64] = [hi(32) | lo(32)] (ops.pack_model_input / ops.split of an
         fp32 sample), the result is fp32.  precision "fp16": sample is the fp16 operand [B, h, w, 32], the result is fp32.
@@ -482,16 +541,23 @@ class UNetMultiviewConditionModel:
         discards the noise prediction of conditioning rows, pipeline_diffuman4d.py:413-421).
         With `shard` (parallel.FrameShard) sample/timestep hold this rank's frames and num_frames is the LOCAL count.
         enable_pose_encoder checkpoints (:551-552): pass `skeletons` [B, 8h, 8w, 4] NHWC (encoded here, as the
-        reference does on every call) or `pose_features` [B, h, w, C0] computed once with ``self.pose_encoder``."""
+        reference does on every call) or `pose_features` [B, h, w, C0] computed once with ``self.pose_encoder``.
+        head (with sample=None; optional extension): the full-batch tensors ``run_head`` gives, assembled by the caller from compact
+        runs and cached rows -- the layers in front of the first 3-D transformer are then skipped.  tproj: ``time_proj`` of this
+        call, when the caller has computed it already.  Without these two the launches are what they always were."""
         cfg, P = self.config, self.wide
-        if sample.shape[-1] != (2 * self.IN_PAD if self.parity else self.IN_PAD):
-            raise ValueError(f"sample must be NHWC with {self.IN_PAD} (padded) channels" + (" as a two-term operand [hi | lo]" if self.parity else ""))
-        if sample.dtype != (F16 if self.h16 else BF16):
-            raise ValueError(f"sample must be {'fp16' if self.h16 else 'bf16'} for precision '{self.precision}'")
-        if sample.shape[0] % num_frames != 0:
-            raise ValueError("batch must be a multiple of num_frames")
-        tproj = self._temb(timestep, domains, num_frames, shard)
-        if self.pose_encoder is not None:
+        if head is not None:
+            if sample is not None or self.head_steps is None or self.pose_encoder is not None or len(head) != self.head_tensors:
+                raise ValueError("head: pass sample=None and the tensors run_head returns (a model with a 3-D down block, no pose encoder)")
+            if head[-1].shape[0] % num_frames != 0:
+                raise ValueError("batch must be a multiple of num_frames")
+        else:
+            self._check_sample(sample)
+            if sample.shape[0] % num_frames != 0:
+                raise ValueError("batch must be a multiple of num_frames")
+        if tproj is None:
+            tproj = self._temb(timestep, domains, num_frames, shard)
+        if head is None and self.pose_encoder is not None:
             if pose_features is None:
                 if skeletons is None:
                     raise ValueError("enable_pose_encoder: skeletons or pose_features are required")
@@ -501,19 +567,13 @@ class UNetMultiviewConditionModel:
             pose_features = pose_features.contiguous()
         else:
             pose_features = None
-        x = ops.conv3x3(sample, self.conv_in_w, bias=self.conv_in_b, residual=pose_features, out_f32=P)
-        skips = [x]
-        nd = len(self.down)
-        for i, (res, att, ds) in enumerate(self.down):
-            is3d = att is not None and nd - i - 1 < cfg.num_3d_attn_blocks  # :560
-            for j, r in enumerate(res):
-                x = r(x, tproj)
-                if att is not None:
-                    x = att[j](x, num_frames if is3d else 1, shard if is3d else None)
-                skips.append(x)
-            if ds is not None:
-                x = ops.conv3x3(ops.split(x, h16=self.h16) if P else x, ds[0], bias=ds[1], stride=2, pad=1, out_f32=P)
-                skips.append(x)
+        if head is None:
+            x = ops.conv3x3(sample, self.conv_in_w, bias=self.conv_in_b, residual=pose_features, out_f32=P)
+            skips = [x]
+            x = self._down_steps(x, skips, tproj, num_frames, shard, 0, len(self._down_plan))
+        else:
+            skips, x = list(head[:-1]), head[-1]
+            x = self._down_steps(x, skips, tproj, num_frames, shard, self.head_steps, len(self._down_plan))
         x = self.mid[0][0](x, tproj)
         x = self.mid[1](x, num_frames, shard)  # :570
         x = self.mid[0][1](x, tproj)

@@ -821,6 +821,45 @@ int dm4d_pack_model_input_f32_f16(void* stream, float* latents, const float* pv_
                                   const float* mask, const int32_t* is_cond, const int32_t* frame_idx, void* out, int F, int HW,
                                   int cpad, int use_cfg);
 
+/* Model-input assembly for a SUBSET of a window's frames (the per-sweep prefix cache of host/pipeline.py): as dm4d_pack_model_input_*,
+ *   but frame f is written to row out_row[f] of a compact result [cfg*Fo, HW, ...] = [negative half (Fo) | positive half (Fo)], and a
+ *   frame whose out_row is negative is not written at all.  out_row: int32 [F] on the device, its non-negative entries a permutation
+ *   of 0 .. Fo-1 (1 <= Fo <= F).  The aliasing side effect latents[cond rows] <- image latents covers EVERY conditioning frame of
+ *   the window, written or not.                                                                                                      */
+int dm4d_pack_model_input_rows_bf16(void* stream, void* latents, const void* pv_lat, const void* plucker, const void* skel,
+                                    const void* mask, const int32_t* is_cond, const int32_t* frame_idx, const int32_t* out_row,
+                                    void* out, int F, int Fo, int HW, int cpad, int use_cfg);
+int dm4d_pack_model_input_rows_f32_split(void* stream, float* latents, const float* pv_lat, const float* plucker, const float* skel,
+                                         const float* mask, const int32_t* is_cond, const int32_t* frame_idx,
+                                         const int32_t* out_row, void* out, int F, int Fo, int HW, int cpad, int use_cfg);
+int dm4d_pack_model_input_rows_f32_f16(void* stream, float* latents, const float* pv_lat, const float* plucker, const float* skel,
+                                       const float* mask, const int32_t* is_cond, const int32_t* frame_idx, const int32_t* out_row,
+                                       void* out, int F, int Fo, int HW, int cpad, int use_cfg);
+
+/* Row mover: one launch copies whole rows for a small table of jobs, dst[dst_row_idx[r]] = src[src_row_idx[r]] for r < n_rows of
+ *   every job, in 16-byte pieces with 64-bit addressing (tensors may exceed 4 GiB).  `jobs` is a HOST array of n_jobs <=
+ *   DM4D_ROWS_MOVE_MAX_JOBS entries (it travels in the kernel arguments); src, dst and the int32 index tables are device pointers, src
+ *   and dst 16-byte aligned, row_bytes a positive multiple of 16; a job with n_rows = 0 is skipped and its pointers are not looked at.
+ *   Rows are dense: row i of a tensor starts at byte i * row_bytes.  The caller vouches for the indices (they are not read on the host)
+ *   and for dst rows that are written once per launch; a src row may be read by several.                                              */
+#define DM4D_ROWS_MOVE_MAX_JOBS 16
+typedef struct {
+  const void* src;
+  void* dst;
+  const int32_t* src_row_idx;
+  const int32_t* dst_row_idx;
+  int64_t n_rows;
+  int64_t row_bytes;
+} Dm4dRowsMoveJob;
+int dm4d_rows_move(void* stream, const Dm4dRowsMoveJob* jobs, int n_jobs);
+
+/* The GroupNorm statistics of a sample are summed over chunks of its pixels, and the number of chunks follows the batch of the launch
+ *   (more samples, fewer chunks each), so a sample's fp32 sums round differently in a batch of another size.  A caller that runs SOME
+ *   rows of a batch on their own and needs the bits they have inside the whole batch (the prefix cache's compact head runs) names that
+ *   batch here: until it is reset with 0, every GroupNorm launch of THIS THREAD with fewer than B samples plans its chunks as for B.
+ *   The workspace sizes of dm4d_groupnorm_ws_bytes / _f32_ws_bytes for the launch's own batch still suffice (fewer chunks).           */
+int dm4d_groupnorm_plan_batch(int B);
+
 /* Tuning hook (not part of the operator surface): force one GEMM/conv kernel configuration id for all
  * subsequent launches of this process; 0 restores the built-in heuristic.  Used by tools/gemm_tune.py. */
 int dm4d_tune_set_gemm_config(int id);

@@ -180,3 +180,172 @@ extern "C" int dm4d_capture_crop_resize_f32(void* stream, const void* staging, i
                      (const uint8_t*)scratch, pixel_values, skeletons, H, W);
   return dm4d_check_launch("capture_vpass_kernel");
 }
+
+// Box and byte sum of decoded planes, and masks that are filled rectangles: what SpaTemDataset(device_decode=True) needs of planes that
+// were decoded on the device and never visit the host (the crop box, the empty and 2 % checks, the has_gt_target=False box mask).
+//
+//   partial  grid (blocks, planes): a block walks its share of its plane's 16-byte vectors (planes start on 16-byte addresses; the tail
+//            of up to 15 bytes goes to block 0).  An all-zero vector costs one load and one test; any other adds its bytes (four
+//            sums of absolute differences against 0) and is walked by box_scan_word.  Shuffles reduce a wave, LDS the block, and
+//            thread 0 stores {first column, first row, last column, last row, sum} in the workspace.  Planes differ in size: a
+//            plane uses the first stats_blocks(its bytes) blocks of its grid row, the others leave at once.
+//   fold     one wave per plane folds its partials (a fixed assignment to lanes, then the shuffle tree) into out[plane].
+//   fill     grid (blocks, planes): rect_fill_plane of every descriptor's rectangle.
+//
+// min, max and sums of integers: no atomics, no block waits on another, and a plane's row does not depend on the batch it is in.
+namespace {
+
+constexpr int kStatsThreads = 256;
+constexpr int kStatsMaxBlocks = 256;    // per plane
+constexpr int kStatsVecsPerThread = 8;  // 32 KiB of a plane per block before the grid stride sets in
+constexpr int kStatsMaxSide = 1 << 15;  // h * w * 3 stays below 2^32
+
+enum { S_OFF = 0, S_H, S_W, S_CH };                       // DM4D_CAPTURE_PLANE_FIELDS
+enum { R_OFF = 0, R_H, R_W, R_C0, R_R0, R_C1, R_R1 };     // DM4D_CAPTURE_RECT_FIELDS
+
+__host__ __device__ inline int stats_blocks(int64_t plane_bytes) {
+  const int64_t per_block = (int64_t)kStatsThreads * kStatsVecsPerThread * 16;
+  const int64_t n = (plane_bytes + per_block - 1) / per_block;
+  return (int)(n < 1 ? 1 : n > kStatsMaxBlocks ? kStatsMaxBlocks : n);
+}
+
+__device__ __forceinline__ uint32_t byte_sum(uint32_t word, uint32_t acc) { return __builtin_amdgcn_sad_u8(word, 0u, acc); }
+
+template <int BPP>
+__device__ __forceinline__ void stats_scan_plane(const uint8_t* __restrict__ src, int64_t total_bytes, int row_bytes, int64_t first_vec,
+                                                 int64_t vec_stride, bool do_tail, Box& b, int64_t& sum) {
+  const int64_t nvec = total_bytes / 16;
+  for (int64_t v = first_vec; v < nvec; v += vec_stride) {
+    const int64_t at = v * 16;
+    const U4 q = ldg16(src + at);
+    if ((q.x | q.y | q.z | q.w) == 0) continue;
+    sum += byte_sum(q.x, byte_sum(q.y, byte_sum(q.z, byte_sum(q.w, 0u))));
+    box_scan_word<BPP, 0xffffffffu>(b, q.x, 4, at, row_bytes);
+    box_scan_word<BPP, 0xffffffffu>(b, q.y, 4, at + 4, row_bytes);
+    box_scan_word<BPP, 0xffffffffu>(b, q.z, 4, at + 8, row_bytes);
+    box_scan_word<BPP, 0xffffffffu>(b, q.w, 4, at + 12, row_bytes);
+  }
+  if (do_tail) {
+    const int64_t t = nvec * 16 + threadIdx.x;
+    if (t < total_bytes) {
+      const uint32_t v = src[t];
+      sum += v;
+      box_scan_word<BPP, 0xffffffffu>(b, v, 1, t, row_bytes);
+    }
+  }
+}
+
+__device__ __forceinline__ int64_t sum_wave_reduce(int64_t s) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  return s;
+}
+
+__global__ void __launch_bounds__(kStatsThreads) capture_stats_partial_kernel(const uint8_t* __restrict__ blob, const int64_t* __restrict__ desc,
+                                                                              int64_t* __restrict__ partials) {
+  __shared__ int64_t s_sum[kStatsThreads / 64];
+  const int tid = threadIdx.x, p = blockIdx.y;
+  const int64_t* d = desc + (int64_t)p * DM4D_CAPTURE_PLANE_FIELDS;
+  const int h = (int)d[S_H], w = (int)d[S_W], ch = (int)d[S_CH];
+  const int64_t plane_bytes = (int64_t)h * w * ch;
+  const int nblocks = stats_blocks(plane_bytes);
+  if ((int)blockIdx.x >= nblocks) return;  // the same for every thread of the block
+  Box b{w, h, -1, -1};
+  int64_t sum = 0;
+  const uint8_t* src = blob + d[S_OFF];
+  const int64_t first = (int64_t)blockIdx.x * kStatsThreads + tid, stride = (int64_t)nblocks * kStatsThreads;
+  if (ch == 3)
+    stats_scan_plane<3>(src, plane_bytes, w * 3, first, stride, blockIdx.x == 0, b, sum);
+  else
+    stats_scan_plane<1>(src, plane_bytes, w, first, stride, blockIdx.x == 0, b, sum);
+  sum = sum_wave_reduce(sum);
+  if ((tid & 63) == 0) s_sum[tid >> 6] = sum;
+  box_block_reduce<kStatsThreads>(b);  // its barrier also publishes s_sum
+  if (tid == 0) {
+    for (int k = 1; k < kStatsThreads / 64; ++k) sum += s_sum[k];
+    int64_t* dst = partials + ((int64_t)p * gridDim.x + blockIdx.x) * 5;
+    dst[0] = b.fc, dst[1] = b.fr, dst[2] = b.lc, dst[3] = b.lr, dst[4] = sum;
+  }
+}
+
+__global__ void __launch_bounds__(64) capture_stats_fold_kernel(const int64_t* __restrict__ desc, const int64_t* __restrict__ partials,
+                                                                int row_blocks, int64_t* __restrict__ out) {
+  const int p = blockIdx.x, lane = threadIdx.x;  // one wave per plane
+  const int64_t* d = desc + (int64_t)p * DM4D_CAPTURE_PLANE_FIELDS;
+  const int h = (int)d[S_H], w = (int)d[S_W];
+  const int nblocks = stats_blocks((int64_t)h * w * d[S_CH]);
+  Box b{w, h, -1, -1};
+  int64_t sum = 0;
+  const int64_t* src = partials + (int64_t)p * row_blocks * 5;
+  for (int k = lane; k < nblocks; k += 64) {
+    box_merge(b, Box{(int)src[5 * k], (int)src[5 * k + 1], (int)src[5 * k + 2], (int)src[5 * k + 3]});
+    sum += src[5 * k + 4];
+  }
+  box_wave_reduce(b);
+  sum = sum_wave_reduce(sum);
+  if (lane == 0) {
+    int64_t* dst = out + (int64_t)p * 5;
+    dst[0] = b.fc, dst[1] = b.fr, dst[2] = b.lc, dst[3] = b.lr, dst[4] = sum;
+  }
+}
+
+__global__ void __launch_bounds__(kStatsThreads) capture_fill_rects_kernel(uint8_t* __restrict__ blob, const int64_t* __restrict__ desc) {
+  const int64_t* d = desc + (int64_t)blockIdx.y * DM4D_CAPTURE_RECT_FIELDS;
+  rect_fill_plane(blob + d[R_OFF], (int)d[R_H], (int)d[R_W], (int)d[R_C0], (int)d[R_R0], (int)d[R_C1], (int)d[R_R1],
+                  (int64_t)blockIdx.x * kStatsThreads + threadIdx.x, (int64_t)gridDim.x * kStatsThreads, blockIdx.x == 0);
+}
+
+}  // namespace
+
+extern "C" size_t dm4d_capture_plane_stats_ws_bytes(int n, int64_t max_plane_bytes) {
+  if (n <= 0 || n > 65535 || max_plane_bytes <= 0 || max_plane_bytes > (int64_t)kStatsMaxSide * kStatsMaxSide * 3) return 0;
+  return (size_t)n * stats_blocks(max_plane_bytes) * 5 * sizeof(int64_t);
+}
+
+extern "C" int dm4d_capture_plane_stats_u8(void* stream, const void* blob, int64_t blob_bytes, const int64_t* desc_host, const int64_t* desc_dev,
+                                           int n, int64_t* out, void* ws, int64_t ws_bytes) {
+  if (!blob || !desc_host || !desc_dev || !out || !ws) return dm4d_set_error(DM4D_ERR_ARG, "capture_plane_stats: null pointer");
+  if (n < 1 || n > 65535) return dm4d_set_error(DM4D_ERR_ARG, "capture_plane_stats: n outside 1..65535");
+  if (blob_bytes < 1) return dm4d_set_error(DM4D_ERR_ARG, "capture_plane_stats: empty blob");
+  if (((uintptr_t)blob & 15) || ((uintptr_t)desc_dev & 7) || ((uintptr_t)out & 7) || ((uintptr_t)ws & 7))
+    return dm4d_set_error(DM4D_ERR_ARG, "capture_plane_stats: blob (16 bytes), desc_dev, out and workspace (8 bytes) must be aligned");
+  int64_t max_bytes = 0;
+  for (int p = 0; p < n; ++p) {
+    const int64_t* d = desc_host + (int64_t)p * DM4D_CAPTURE_PLANE_FIELDS;
+    const int64_t off = d[S_OFF], h = d[S_H], w = d[S_W], ch = d[S_CH];
+    if (h < 1 || w < 1 || h > kStatsMaxSide || w > kStatsMaxSide) return dm4d_set_error(DM4D_ERR_ARG, "capture_plane_stats: a plane's size is outside 1..32768");
+    if (ch != 1 && ch != 3) return dm4d_set_error(DM4D_ERR_ARG, "capture_plane_stats: channels must be 1 or 3");
+    if (off & 15) return dm4d_set_error(DM4D_ERR_ARG, "capture_plane_stats: a plane's offset is not 16-byte aligned");
+    if (off < 0 || off > blob_bytes || h * w * ch > blob_bytes - off) return dm4d_set_error(DM4D_ERR_ARG, "capture_plane_stats: a plane lies outside the blob");
+    if (h * w * ch > max_bytes) max_bytes = h * w * ch;
+  }
+  if (ws_bytes < 0 || (size_t)ws_bytes < dm4d_capture_plane_stats_ws_bytes(n, max_bytes))
+    return dm4d_set_error(DM4D_ERR_ARG, "capture_plane_stats: the workspace is smaller than dm4d_capture_plane_stats_ws_bytes");
+  const hipStream_t s = (hipStream_t)stream;
+  const int nb = stats_blocks(max_bytes);
+  hipLaunchKernelGGL(capture_stats_partial_kernel, dim3(nb, n), dim3(kStatsThreads), 0, s, (const uint8_t*)blob, desc_dev, (int64_t*)ws);
+  const int rc = dm4d_check_launch("capture_stats_partial_kernel");
+  if (rc) return rc;
+  hipLaunchKernelGGL(capture_stats_fold_kernel, dim3(n), dim3(64), 0, s, desc_dev, (const int64_t*)ws, nb, out);
+  return dm4d_check_launch("capture_stats_fold_kernel");
+}
+
+extern "C" int dm4d_capture_fill_rects_u8(void* stream, void* blob, int64_t blob_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n) {
+  if (!blob || !desc_host || !desc_dev) return dm4d_set_error(DM4D_ERR_ARG, "capture_fill_rects: null pointer");
+  if (n < 1 || n > 65535) return dm4d_set_error(DM4D_ERR_ARG, "capture_fill_rects: n outside 1..65535");
+  if (blob_bytes < 1) return dm4d_set_error(DM4D_ERR_ARG, "capture_fill_rects: empty blob");
+  if ((uintptr_t)desc_dev & 7) return dm4d_set_error(DM4D_ERR_ARG, "capture_fill_rects: desc_dev must be 8-byte aligned");
+  int64_t max_bytes = 0;
+  for (int p = 0; p < n; ++p) {
+    const int64_t* d = desc_host + (int64_t)p * DM4D_CAPTURE_RECT_FIELDS;
+    const int64_t off = d[R_OFF], h = d[R_H], w = d[R_W];
+    if (h < 1 || w < 1 || h > kStatsMaxSide || w > kStatsMaxSide) return dm4d_set_error(DM4D_ERR_ARG, "capture_fill_rects: a plane's size is outside 1..32768");
+    if (off < 0 || off > blob_bytes || h * w > blob_bytes - off) return dm4d_set_error(DM4D_ERR_ARG, "capture_fill_rects: a plane lies outside the blob");
+    if (d[R_C0] < 0 || d[R_C0] > d[R_C1] || d[R_C1] > w || d[R_R0] < 0 || d[R_R0] > d[R_R1] || d[R_R1] > h)
+      return dm4d_set_error(DM4D_ERR_ARG, "capture_fill_rects: a rectangle lies outside its plane");
+    if (h * w > max_bytes) max_bytes = h * w;
+  }
+  hipLaunchKernelGGL(capture_fill_rects_kernel, dim3(stats_blocks(max_bytes), n), dim3(kStatsThreads), 0, (hipStream_t)stream, (uint8_t*)blob,
+                     desc_dev);
+  return dm4d_check_launch("capture_fill_rects_kernel");
+}

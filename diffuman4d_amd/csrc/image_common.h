@@ -1,6 +1,7 @@
 // The parts that the uint8 image kernels share (capture.hip, jpeg.hip, skeleton.hip, pose.hip, vhull.hip), each defined once:
 //   Pillow resample   the fixed-point rule of libImaging/Resample.c and the host-side check of a coefficient table
-//   pixel box         the bounding box of the set pixels of a uint8 plane: the walk, the wave reduction and the block fold
+//   pixel box         the bounding box of the set pixels of a uint8 plane: the walk, the wave reduction and the block fold; and the
+//                     writing of a plane that is a filled rectangle
 //   scan              the 64-lane inclusive scan and the one-block exclusive scan with a carry
 // Integer code only, so -ffp-contract=off (build.py EXTRA_FLAGS gives it to some of the including files) cannot change what this
 // header compiles to.  Everything assumes one-dimensional blocks (lane = threadIdx.x & 63).
@@ -145,6 +146,44 @@ __device__ __forceinline__ void box_block_reduce(Box& b) {
   __syncthreads();
   if (tid == 0)
     for (int k = 1; k < THREADS / 64; ++k) box_merge(b, Box{s_box[k][0], s_box[k][1], s_box[k][2], s_box[k][3]});
+}
+
+// One thread's share of writing a [h, w] plane that is 255 on rows r0 .. r1 - 1 and columns c0 .. c1 - 1 and 0 elsewhere: the 16-byte
+// vectors first_vec, first_vec + vec_stride, ... between a scalar head and tail as in box_scan_plane (a byte per thread, where
+// do_head_tail).  Every byte of the plane is written, none outside it.
+__device__ __forceinline__ void rect_fill_plane(uint8_t* __restrict__ dst, int h, int w, int c0, int r0, int c1, int r1, int64_t first_vec,
+                                                int64_t vec_stride, bool do_head_tail) {
+  const int64_t total = (int64_t)h * w;
+  int64_t head = (16 - (int64_t)((uintptr_t)dst & 15)) & 15;
+  if (head > total) head = total;
+  const int64_t nvec = (total - head) / 16;
+  const int64_t tail0 = head + nvec * 16;
+  auto value = [&](int row, int col) -> uint32_t { return (row >= r0 && row < r1 && col >= c0 && col < c1) ? 255u : 0u; };
+  for (int64_t v = first_vec; v < nvec; v += vec_stride) {
+    const int64_t at = head + v * 16;
+    int row = (int)(at / w), col = (int)(at % w);
+    uint32_t q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        word |= value(row, col) << (8 * j);
+        if (++col == w) {
+          col = 0;
+          ++row;
+        }
+      }
+      q[k] = word;
+    }
+    stg16(dst + at, U4{q[0], q[1], q[2], q[3]});
+  }
+  if (do_head_tail) {
+    const int tid = threadIdx.x;
+    if (tid < head) dst[tid] = (uint8_t)value((int)(tid / w), (int)(tid % w));
+    const int64_t t = tail0 + tid;
+    if (t < total) dst[t] = (uint8_t)value((int)(t / w), (int)(t % w));
+  }
 }
 
 // -- scan ---------------------------------------------------------------------------------------------------------------------------------

@@ -301,38 +301,8 @@ __global__ void __launch_bounds__(kBoxThreads) skeleton_box_fill_kernel(const in
     c0 = max(fc - 1 - pad_x, 0), c1 = min(lc + 1 + pad_x, w);
     r0 = max(fr - 1 - pad_top, 0), r1 = min(lr + 1 + pad_bottom, h);
   }
-  uint8_t* dst = masks + (int64_t)f * mask_stride;
-  const int64_t total = (int64_t)h * w;
-  int64_t head = (16 - (int64_t)((uintptr_t)dst & 15)) & 15;
-  if (head > total) head = total;
-  const int64_t nvec = (total - head) / 16;
-  const int64_t tail0 = head + nvec * 16;
-  auto value = [&](int row, int col) -> uint32_t { return (row >= r0 && row < r1 && col >= c0 && col < c1) ? 255u : 0u; };
-  for (int64_t v = (int64_t)blockIdx.x * kBoxThreads + threadIdx.x; v < nvec; v += (int64_t)gridDim.x * kBoxThreads) {
-    const int64_t at = head + v * 16;
-    int row = (int)(at / w), col = (int)(at % w);
-    uint32_t q[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      uint32_t word = 0;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        word |= value(row, col) << (8 * j);
-        if (++col == w) {
-          col = 0;
-          ++row;
-        }
-      }
-      q[k] = word;
-    }
-    stg16(dst + at, U4{q[0], q[1], q[2], q[3]});
-  }
-  if (blockIdx.x == 0) {
-    const int tid = threadIdx.x;
-    if (tid < head) dst[tid] = (uint8_t)value((int)(tid / w), (int)(tid % w));
-    const int64_t t = tail0 + tid;
-    if (t < total) dst[t] = (uint8_t)value((int)(t / w), (int)(t % w));
-  }
+  rect_fill_plane(masks + (int64_t)f * mask_stride, h, w, c0, r0, c1, r1, (int64_t)blockIdx.x * kBoxThreads + threadIdx.x,
+                  (int64_t)gridDim.x * kBoxThreads, blockIdx.x == 0);
 }
 
 }  // namespace

@@ -16,6 +16,13 @@ Offsets, the pinned buffer, its filling and the table / descriptor pack are host
 ``skeleton_source="kp2d"`` (opt-in) reads no skeleton image: every frame's map is drawn on the device from its ``poses_2d`` keypoint
 file (host/skeleton.py, ``dm4d_skeleton_draw_u8``) straight into the device staging buffer, and for ``has_gt_target=False`` targets
 ``dm4d_skeleton_box_mask_u8`` derives the box mask and the bounding box there as well; only the boxes (16 bytes per frame) come back.
+
+``device_decode=True`` (opt-in, either skeleton source) moves the decode of JPEG and PNG files to the device as well: the pool reads
+and probes the files (``_read``), host/jpegdec.py and host/pngdec.py decode them into the device staging buffer, and what the host
+route takes from decoded pixels -- the crop box, the empty and 2 % checks, the ``has_gt_target=False`` box mask -- comes from
+``dm4d_capture_plane_stats_u8`` (40 bytes per plane come back) and ``dm4d_capture_fill_rects_u8`` (``_settle_frames``,
+``_resize_on_device_decoded``).  Files the decoders do not take (WebP, progressive JPEG, ...) are decoded by Pillow as before, inside
+the same call.  The sample and every exception are the flag-off call's.
 """
 from __future__ import annotations
 
@@ -32,7 +39,9 @@ import numpy as np
 import torch
 from PIL import Image
 
+from . import lib as _l
 from . import ops
+from .codec import StagedFile, decode_staged, probe_file
 from .dataset import plucker_maps, relative_poses
 from .staging import Layout, fill, pack_meta, pinned, write_meta
 from .resample import PRECISION_BITS, TableSet, bicubic_table  # noqa: F401  (tests and tools import the first and the last from here)
@@ -134,11 +143,18 @@ def skeleton_mask_rect(box: Sequence[int], h: int, w: int) -> Tuple[int, int, in
     return max(fc - 1 - px, 0), max(fr - 1 - pt, 0), min(lc + 1 + px, w), min(lr + 1 + py, h)
 
 
+def _sum_mean_at_most(total: int, size: int, limit: float) -> Optional[bool]:
+    """_mask_mean_at_most from the sum of the mask's `size` bytes alone, or None where the exact mean is so close to `limit` that the
+    float32 mean decides."""
+    exact = float(total) / (255.0 * size)
+    return exact <= limit if abs(exact - limit) > 1e-4 else None
+
+
 def _mask_mean_at_most(mask: np.ndarray, limit: float) -> bool:
     """TF.to_tensor(mask).mean() <= limit, decided exactly: the float32 mean only where the exact mean is close to `limit`."""
-    exact = float(mask.sum(dtype=np.int64)) / (255.0 * mask.size)
-    if abs(exact - limit) > 1e-4:
-        return exact <= limit
+    decided = _sum_mean_at_most(int(mask.sum(dtype=np.int64)), mask.size, limit)
+    if decided is not None:
+        return decided
     return bool(torch.from_numpy(mask).to(torch.float32).div(255).mean() <= limit)
 
 
@@ -147,6 +163,62 @@ def _open(path: str, mode: str) -> np.ndarray:
         if im.mode != mode:
             raise ValueError(f"{path}: image mode {im.mode!r}, expected {mode!r} (no conversion is made: it would change values)")
         return np.asarray(im)
+
+
+# -- device_decode=True: files that may decode on the device, and the checks that then wait for their statistics ----------------------
+def _read(path: str, mode: str):
+    """_open for a frame whose files may decode on the device: a JPEG or PNG file the decoders take (host/jpegdec.py, host/pngdec.py
+    ``probe``) -> a codec.StagedFile, its mode checked on the plan with _open's error; any other file -> _open's pixels, as ever."""
+    from . import jpegdec, pngdec
+    f = probe_file(path, (jpegdec, pngdec))
+    if f is None:
+        return _open(path, mode)
+    if f.mode != mode:
+        raise ValueError(f"{path}: image mode {f.mode!r}, expected {mode!r} (no conversion is made: it would change values)")
+    return f
+
+
+def _hw(a) -> Tuple[int, int]:
+    """(h, w) of a decoded plane or of a StagedFile."""
+    return (a.h, a.w) if isinstance(a, StagedFile) else (int(a.shape[0]), int(a.shape[1]))
+
+
+def _settle_frame(fr: Dict, row: Sequence[int]) -> None:
+    """What _load_frame / _load_frame_kp2d do once a frame's pixels are known, from `row` = {first column, first row, last column, last
+    row, sum} (dm4d_capture_plane_stats_u8) of the frame's mask or, for a has_gt_target=False target, of its skeleton map -- in their
+    order and with their errors: the empty check, then fr["crop"] (and fr["rect"], the target's mask rectangle), the size assertion,
+    the 2 % assertion."""
+    fc, fr_, lc, lr, total = (int(v) for v in row)
+    if fr["mask"] is None:  # the skeleton serves as image, its box as mask
+        if lc < 0:
+            raise ValueError(f"skeleton is empty, no mask can be made from it: {fr['path']}")
+        h, w = fr["hw"]
+        c0, r0, c1, r1 = fr["rect"] = skeleton_mask_rect((fc, fr_, lc, lr), h, w)
+        fr["crop"] = _crop_from_bbox((c0 - 1, r0 - 1, c1, r1), h, w)  # mask_bbox of the rectangle
+        return
+    if lc < 0:
+        raise ValueError(f"foreground mask is empty: {fr['img_path']}")
+    h, w = _hw(fr["mask"])
+    fr["crop"] = _crop_from_bbox((fc - 1, fr_ - 1, lc + 1, lr + 1), h, w)
+    isz, msz, ssz = ((s[1], s[0]) for s in (_hw(fr["img"]), (h, w), fr["hw"]))  # PIL's (w, h)
+    if not (isz == msz == ssz):
+        raise AssertionError(f"Error: image size: {isz} != fmask size: {msz} != skeleton size: {ssz}")
+    if fr["check"]:
+        decided = _sum_mean_at_most(total, h * w, 0.02)
+        if decided is None:  # too close to the limit for the sum to say: this one mask is decoded on the host
+            mask = _open(fr["mask"].path, "L") if isinstance(fr["mask"], StagedFile) else fr["mask"]
+            decided = _mask_mean_at_most(mask, 0.02)
+        if decided:
+            raise AssertionError("Error: foreground mask < 2%. Please check the data.")
+
+
+def _settle_frames(frames: List, rows: Dict[int, Sequence[int]]) -> None:
+    """_settle_frame over a task's frames in label order, so that the error raised is the first bad frame's.  An entry of `frames`
+    that is an exception is a frame whose files could not be read: it is raised when its turn comes."""
+    for i, fr in enumerate(frames):
+        if isinstance(fr, BaseException):
+            raise fr
+        _settle_frame(fr, rows[i])
 
 
 def _intrinsic(K: torch.Tensor, crop: List[int], height: int) -> torch.Tensor:
@@ -176,7 +248,11 @@ class SpaTemDataset:
     ``palette`` (a path or a Palette, as ``skeleton.load_palette`` takes it), exactly as ``skeleton.draw_skeleton_maps([kp2d_path],
     [score_path], kp2d_canvas_shape or the camera's (height, width), (h, w), palette=palette)[0]`` with (h, w) the decoded image's size
     or, for a frame that loads none, the camera's.  No skeleton file is read and no map crosses PCIe.  The result equals the file
-    route's on skeleton files that hold those maps losslessly; it differs from it on lossy files by exactly the codec's loss."""
+    route's on skeleton files that hold those maps losslessly; it differs from it on lossy files by exactly the codec's loss.
+
+    ``device_decode``: baseline JPEG and 8-bit PNG files (images, masks, skeleton files) are decoded on the device instead of by
+    Pillow in the pool; needs a HIP device (Dm4dError otherwise).  ``get_item`` returns and raises what it does without the flag;
+    ``decode_stats`` ("device", "pillow", "bytes_uploaded", as ``codec.decode_batch`` counts them) is added to by every call."""
 
     def __init__(self, data_dir: str, camera_path_pat: str = "{data_dir}/{scene_label}/transforms.json",
                  image_path_pat: str = "{data_dir}/{scene_label}/images/{spa_label}/{tem_label}.webp",
@@ -185,9 +261,14 @@ class SpaTemDataset:
                  scene_label: Optional[str] = None, height: int = 1024, width: int = 1024, has_gt_target: bool = True,
                  plucker: str = "host", device=None, decode_threads: int = 8, skeleton_source: str = "files",
                  kp2d_path_pat: str = KP2D_PATH_PAT, kp2d_score_path_pat: Optional[str] = None,
-                 kp2d_canvas_shape: Optional[Tuple[int, int]] = None, palette=None):
+                 kp2d_canvas_shape: Optional[Tuple[int, int]] = None, palette=None, device_decode: bool = False):
         if plucker not in ("host", "cameras"):
             raise ValueError("plucker must be 'host' or 'cameras'")
+        self.device_decode = bool(device_decode)
+        if self.device_decode:  # there is no CPU path: the planes are decoded where the resize reads them
+            _l.hip_device("cuda" if device is None else device, "SpaTemDataset(device_decode=True)")
+        self.decode_stats = {"device": 0, "pillow": 0, "bytes_uploaded": 0}  # device_decode=True: added to by every get_item
+        self._stats_lock = threading.Lock()
         if skeleton_source not in SKELETON_SOURCES:
             raise ValueError(f"skeleton_source must be one of {SKELETON_SOURCES}, got {skeleton_source!r}")
         self.skeleton_source, self.kp2d_path_pat, self.kp2d_score_path_pat = skeleton_source, kp2d_path_pat, kp2d_score_path_pat
@@ -277,6 +358,41 @@ class SpaTemDataset:
                 raise AssertionError("Error: foreground mask < 2%. Please check the data.")
         return fr
 
+    # -- device_decode=True: the host half of one frame, for both skeleton sources -------------------------------------------------
+    def _load_frame_deferred(self, label, input_spa_labels):
+        """_load_frame / _load_frame_kp2d up to the pixels: the frame's files are read and probed (_read), not decoded, in the same
+        order; the crop and the checks that need pixels wait for _settle_frame.  fr["hw"]: the (h, w) of the frame's skeleton map.
+        What reading raises is returned, not raised: _settle_frames raises it when the frame's turn comes."""
+        scene_label, spa, tem = label
+        kp2d = self.skeleton_source == "kp2d"
+        target = not self.has_gt_target and spa not in input_spa_labels
+        fr = {"img": None, "mask": None, "skel": None, "plan": None, "crop": None, "check": self.has_gt_target and spa in input_spa_labels}
+        try:
+            if kp2d:
+                sk, cam = self._sk, self.cameras[scene_label][spa]
+                fr["path"] = fr["img_path"] = self.get_file_path(self.kp2d_path_pat, scene_label, spa, tem)
+                inst = sk._read_instance(fr["path"])
+                score = None if self.kp2d_score_path_pat is None else sk._read_instance(self.get_file_path(self.kp2d_score_path_pat, scene_label, spa, tem))
+                hw = (int(cam["height"]), int(cam["width"]))
+            else:
+                fr["path"] = fr["img_path"] = self.get_file_path(self.skeleton_path_pat, scene_label, spa, tem)
+                fr["skel"] = _read(fr["path"], "RGB")
+                fr["hw"] = _hw(fr["skel"])
+            if not target:
+                fr["img_path"] = self.get_file_path(self.image_path_pat, scene_label, spa, tem)
+                fr["img"] = _read(fr["img_path"], "RGB")
+                fr["mask"] = _read(self.get_file_path(self.fmask_path_pat, scene_label, spa, tem), "L")
+            if kp2d:
+                if not target:
+                    hw = _hw(fr["img"])
+                sk._check_out_shape(hw)
+                canvas = self.kp2d_canvas_shape or (int(cam["height"]), int(cam["width"]))
+                fr["plan"] = sk.plan_draw_calls(inst, score, (canvas, hw), self.palette)
+                fr["hw"] = (fr["plan"].out_size[1], fr["plan"].out_size[0])
+        except Exception as e:  # noqa: BLE001  (kept for its turn in label order)
+            return e
+        return fr
+
     # -- tables and descriptors of a task whose crops are known ----------------------------------------------------------------
     def _tables(self, frames: List[Dict]) -> Tuple[Dict[Tuple[int, int], Tuple[int, int]], np.ndarray]:
         """Pillow's coefficient tables of every distinct (crop size, output size) pair -> ({pair: (offset in int32 units, ksize)},
@@ -311,8 +427,45 @@ class SpaTemDataset:
         The first two parts exist on the device only; the third goes up from the pinned buffer in one copy, queued while the device
         draws.  Every size in it is known before the targets' crops are.  Tables and descriptors depend on those crops: they go up
         afterwards in a small buffer of their own (the library takes them by pointer, they need not lie in the staging buffer)."""
-        sk = self._sk
         H, W = self.height, self.width
+        n = len(frames)
+        cur, skel_offs, mask_offs, regions = self._kp2d_regions(frames)
+        lay = Layout(cur)
+        file_off = lay.total  # where the planes that come from files start
+        file_offs = [[None if fr[name] is None else lay.add(fr[name].size) for name in ("img", "mask")] for fr in frames]
+        total = lay.total
+
+        on_gpu = device.type == "cuda"
+        blob = pinned(total - file_off, device)
+        st = self._stream(device) if on_gpu else None
+        with (torch.cuda.device(device) if on_gpu else contextlib.nullcontext()), (torch.cuda.stream(st) if on_gpu else contextlib.nullcontext()):
+            dev_blob = torch.empty(total, dtype=torch.uint8, device=device)
+            boxes = self._kp2d_draw(frames, regions, dev_blob)
+            # the image planes go into the pinned buffer, and up, while the device draws
+            jobs = [(o - file_off, fr[name]) for fr, offs in zip(frames, file_offs) for o, name in zip(offs, ("img", "mask")) if o is not None]
+            fill(blob.numpy(), jobs, self._pool)
+            if total > file_off:
+                dev_blob[file_off:].copy_(blob, non_blocking=True)
+            for idx, h, w, b in boxes:  # 16 bytes per target; .cpu() waits for the stream
+                for i, box in zip(idx, b.cpu().tolist()):
+                    if box[2] < 0:
+                        raise ValueError(f"skeleton is empty, no mask can be made from it: {frames[i]['path']}")
+                    c0, r0, c1, r1 = skeleton_mask_rect(box, h, w)
+                    frames[i]["crop"] = _crop_from_bbox((c0 - 1, r0 - 1, c1, r1), h, w)  # mask_bbox of the rectangle
+            tables, tab = self._tables(frames)
+            shapes = [(fr["plan"].out_size[1], fr["plan"].out_size[0]) for fr in frames]
+            plane_offs = [(oi, mask_offs[i] if om is None else om, skel_offs[i]) for i, (oi, om) in enumerate(file_offs)]
+            desc = self._descriptors(frames, plane_offs, shapes, tables, tab)
+            meta_dev, meta, tab_off, tab_len, desc_off = pack_meta(tab, desc, device)
+            pix, skel = ops.capture_crop_resize(dev_blob, meta, n, desc_off, tab_off, tab_len, H, W, meta=meta_dev)
+        if on_gpu:
+            st.synchronize()  # as _resize_on_device: the tensors are complete when handed over, the pinned buffers may be released
+        return pix, skel
+
+    def _kp2d_regions(self, frames: List[Dict]):
+        """Where the drawn maps and the targets' masks of a "kp2d" task lie in the device staging buffer -> (the bytes they take, skeleton
+        offsets per frame, mask offsets per frame (None: the frame's mask comes from a file), regions = [frame indices, number of
+        targets among them, h, w, maps' offset, masks' offset or None] per group)."""
         n = len(frames)
         # groups of one canvas shape and one map size; the targets (whose maps feed dm4d_skeleton_box_mask_u8) come first in each
         groups: Dict[Tuple, List[int]] = {}
@@ -332,38 +485,91 @@ class SpaTemDataset:
                 for k, i in enumerate(idx[:n_targets]):
                     mask_offs[i] = cur + k * h * w
                 cur += n_targets * h * w
-        lay = Layout(cur)
-        file_off = lay.total  # where the planes that come from files start
-        file_offs = [[None if fr[name] is None else lay.add(fr[name].size) for name in ("img", "mask")] for fr in frames]
-        total = lay.total
+        return cur, skel_offs, mask_offs, regions
 
-        on_gpu = device.type == "cuda"
-        blob = pinned(total - file_off, device)
+    def _kp2d_draw(self, frames: List[Dict], regions, dev_blob: torch.Tensor) -> List[Tuple]:
+        """Draw every group's maps into `dev_blob` and derive the targets' boxes and box masks there, on the current stream ->
+        [(target frame indices, h, w, their device int32 [n, 4] boxes)]."""
+        boxes = []
+        for idx, nt, h, w, start, mask_start in regions:
+            maps = dev_blob[start: start + len(idx) * h * w * 3].view(len(idx), h, w, 3)
+            self._sk.draw_plans_into([frames[i]["plan"] for i in idx], maps)
+            if nt:
+                masks = dev_blob[mask_start: mask_start + nt * h * w].view(nt, h, w)
+                boxes.append((idx[:nt], h, w, ops.skeleton_box_mask(maps[:nt], skeleton_mask_pads(h, w), masks=masks)[0]))
+        return boxes
+
+    def _resize_on_device_decoded(self, frames: List, device: torch.device, stats: Dict) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The device half with device_decode=True, for both skeleton sources; fills in every frame's crop.  Staging buffer on the device:
+
+            ["kp2d": the drawn maps and the targets' masks, as in _resize_on_device_kp2d | "files": one h x w mask per target |
+             planes Pillow decoded | planes the device decodes]
+
+        Only the third part comes up from the pinned buffer, in one copy: the files the decoders did not take.  The fourth is decoded
+        from the files' bytes (codec.decode_staged; a file its decoder refuses is decoded by Pillow after all).  One
+        dm4d_capture_plane_stats_u8 launch over every mask and every skeleton map that serves as image, and its read-back of 40 bytes
+        a plane, give _settle_frames what the host route takes from pixels; the files route's target masks are then filled by one
+        dm4d_capture_fill_rects_u8 launch.  `frames` may hold exceptions (_load_frame_deferred): the frames before the first are
+        checked, then it is raised."""
+        H, W = self.height, self.width
+        kp2d = self.skeleton_source == "kp2d"
+        live = frames[: next((i for i, fr in enumerate(frames) if isinstance(fr, BaseException)), len(frames))]
+        n = len(live)
+        if n == 0:
+            _settle_frames(frames, {})
+        if kp2d:
+            cur, skel_offs, mask_offs, regions = self._kp2d_regions(live)
+            lay = Layout(cur)
+        else:
+            lay, regions = Layout(), []
+            mask_offs = [lay.add(fr["hw"][0] * fr["hw"][1]) if fr["mask"] is None else None for fr in live]
+        files = [(i, name, fr[name]) for i, fr in enumerate(live) for name in ("img", "mask", "skel") if fr[name] is not None]
+        offs, lo = {}, lay.total
+        for i, name, a in files:
+            if not isinstance(a, StagedFile):
+                offs[i, name] = lay.add(a.size)
+        hi = lay.total
+        for i, name, a in files:
+            if isinstance(a, StagedFile):
+                offs[i, name] = lay.add(a.nbytes)
+        blob = pinned(hi - lo, device)
+        on_gpu = device.type == "cuda"  # as in _resize_on_device_kp2d: without a device the ops calls decide (the tests' stand-ins)
         st = self._stream(device) if on_gpu else None
         with (torch.cuda.device(device) if on_gpu else contextlib.nullcontext()), (torch.cuda.stream(st) if on_gpu else contextlib.nullcontext()):
-            dev_blob = torch.empty(total, dtype=torch.uint8, device=device)
-            boxes = []
-            for idx, nt, h, w, start, mask_start in regions:
-                maps = dev_blob[start: start + len(idx) * h * w * 3].view(len(idx), h, w, 3)
-                sk.draw_plans_into([frames[i]["plan"] for i in idx], maps)
-                if nt:
-                    masks = dev_blob[mask_start: mask_start + nt * h * w].view(nt, h, w)
-                    boxes.append((idx[:nt], h, w, ops.skeleton_box_mask(maps[:nt], skeleton_mask_pads(h, w), masks=masks)[0]))
-            # the image planes go into the pinned buffer, and up, while the device draws
-            jobs = [(o - file_off, fr[name]) for fr, offs in zip(frames, file_offs) for o, name in zip(offs, ("img", "mask")) if o is not None]
-            fill(blob.numpy(), jobs, self._pool)
-            if total > file_off:
-                dev_blob[file_off:].copy_(blob, non_blocking=True)
-            for idx, h, w, b in boxes:  # 16 bytes per target; .cpu() waits for the stream
-                for i, box in zip(idx, b.cpu().tolist()):
-                    if box[2] < 0:
-                        raise ValueError(f"skeleton is empty, no mask can be made from it: {frames[i]['path']}")
-                    c0, r0, c1, r1 = skeleton_mask_rect(box, h, w)
-                    frames[i]["crop"] = _crop_from_bbox((c0 - 1, r0 - 1, c1, r1), h, w)  # mask_bbox of the rectangle
-            tables, tab = self._tables(frames)
-            shapes = [(fr["plan"].out_size[1], fr["plan"].out_size[0]) for fr in frames]
-            plane_offs = [(oi, mask_offs[i] if om is None else om, skel_offs[i]) for i, (oi, om) in enumerate(file_offs)]
-            desc = self._descriptors(frames, plane_offs, shapes, tables, tab)
+            dev_blob = torch.empty(max(lay.total, 16), dtype=torch.uint8, device=device)
+            boxes = self._kp2d_draw(live, regions, dev_blob)
+            hosted = [(offs[i, name] - lo, a) for i, name, a in files if not isinstance(a, StagedFile)]
+            fill(blob.numpy(), hosted, self._pool)
+            if hi > lo:
+                dev_blob[lo:hi].copy_(blob, non_blocking=True)
+            stats["pillow"] += len(hosted)
+            stats["bytes_uploaded"] += sum(a.size for _, a in hosted)
+            staged = [(offs[i, name], a, a.plan.bytes_per_pixel) for i, name, a in files if isinstance(a, StagedFile)]
+            if staged:
+                decode_staged(staged, dev_blob, lambda f: _open(f.path, f.mode), stats)
+            planes = [(i, offs[i, "mask"], *_hw(fr["mask"]), 1) for i, fr in enumerate(live) if fr["mask"] is not None]
+            if not kp2d:
+                planes += [(i, offs[i, "skel"], *fr["hw"], 3) for i, fr in enumerate(live) if fr["mask"] is None]
+            rows = {}
+            if planes:
+                desc = np.zeros((len(planes), _l.CAPTURE_PLANE_FIELDS), dtype=np.int64)
+                desc[:, :4] = [p[1:] for p in planes]
+                meta_dev, meta, _, _, desc_off = pack_meta(None, desc, device)
+                out = ops.capture_plane_stats(dev_blob, meta_dev, meta, len(planes), desc_off).cpu().tolist()  # waits for the stream
+                rows = {p[0]: r for p, r in zip(planes, out)}
+            for idx, _, _, b in boxes:  # "kp2d": 16 bytes per target
+                rows.update({i: box + [0] for i, box in zip(idx, b.cpu().tolist())})
+            _settle_frames(frames, rows)
+            rects = [(mask_offs[i], *fr["hw"], *fr["rect"]) for i, fr in enumerate(live) if fr["mask"] is None and not kp2d]
+            if rects:
+                desc = np.zeros((len(rects), _l.CAPTURE_RECT_FIELDS), dtype=np.int64)
+                desc[:, :7] = rects
+                rect_dev, rect_meta, _, _, desc_off = pack_meta(None, desc, device)
+                ops.capture_fill_rects(dev_blob, rect_dev, rect_meta, len(rects), desc_off)
+            tables, tab = self._tables(live)
+            plane_offs = [(offs.get((i, "img")), offs.get((i, "mask"), mask_offs[i]), skel_offs[i] if kp2d else offs[i, "skel"])
+                          for i in range(n)]
+            desc = self._descriptors(live, plane_offs, [fr["hw"] for fr in live], tables, tab)
             meta_dev, meta, tab_off, tab_len, desc_off = pack_meta(tab, desc, device)
             pix, skel = ops.capture_crop_resize(dev_blob, meta, n, desc_off, tab_off, tab_len, H, W, meta=meta_dev)
         if on_gpu:
@@ -422,7 +628,16 @@ class SpaTemDataset:
             cams = [self._nearest(cameras, spa_labels[0], input_spa_labels)] + list(spa_labels)
             labels = [(scene_label, s, t) for s in cams for t in tem_labels]
 
-        if self.skeleton_source == "kp2d":  # the targets' crops come from the device: the resize runs before the bookkeeping
+        if self.device_decode:  # every crop comes from the device: the resize runs before the bookkeeping
+            frames = list(self._pool.map(lambda lab: self._load_frame_deferred(lab, input_spa_labels), labels))
+            stats = {"device": 0, "pillow": 0, "bytes_uploaded": 0}
+            try:
+                pixel_values, skeletons = self._resize_on_device_decoded(frames, self._device(), stats)
+            finally:
+                with self._stats_lock:
+                    for k, v in stats.items():
+                        self.decode_stats[k] += v
+        elif self.skeleton_source == "kp2d":  # the targets' crops come from the device: the resize runs before the bookkeeping
             frames = list(self._pool.map(lambda lab: self._load_frame_kp2d(lab, input_spa_labels), labels))
             pixel_values, skeletons = self._resize_on_device_kp2d(frames, self._device())
         else:
@@ -431,7 +646,7 @@ class SpaTemDataset:
         poses = relative_poses(torch.stack([cameras[s]["pose"] for _, s, _ in labels]))
         hws = [(cameras[s]["height"], cameras[s]["width"]) for _, s, _ in labels]
         crops = [fr["crop"] for fr in frames]
-        if self.skeleton_source != "kp2d":
+        if self.skeleton_source != "kp2d" and not self.device_decode:
             pixel_values, skeletons = self._resize_on_device(frames, self._device())
         del frames
 

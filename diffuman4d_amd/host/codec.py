@@ -1,11 +1,13 @@
-"""What the image codecs (``jpeg``, ``png``, ``jpegdec``, ``pngdec``) and their consumers (``metrics``, ``matting``, ``vhull``) say
-around the library calls, written once:
+"""What the image codecs (``jpeg``, ``png``, ``jpegdec``, ``pngdec``) and their consumers (``metrics``, ``matting``, ``vhull``,
+``capture``, ``pose``) say around the library calls, written once:
 
   * ``read_file``, ``pillow_pixels``: a file's bytes, and the Pillow route of a file;
   * ``chunks``: the ranges of a batch whose device memory stays within a budget;
   * ``workspace``, ``read_back``: the workspace tensor of a call, and the files of an encoder call brought to the host;
   * ``decode_plans``, ``decode_batch``: the bodies of a decoder module's ``decode_plans`` and ``decode_*_batch``;
-  * ``decode_or_fallback``: one ``decode_plans`` call into a consumer's buffer, the refused files filled in by the consumer.
+  * ``decode_or_fallback``: one ``decode_plans`` call into a consumer's buffer, the refused files filled in by the consumer;
+  * ``StagedFile``, ``probe_file``, ``decode_staged``: a file of either decoder that stands in a consumer's staging plan where its
+    pixels would (``capture``, ``pose``), and one ``decode_or_fallback`` per codec over a mixed list of them, with ``decode_batch``'s stats.
 
 A `codec` is a decoder module (``jpegdec``, ``pngdec``): ``probe``, ``stage_chunk``, ``launch_chunk``, ``decode_plans``, and plans with
 ``h``, ``w``, ``bytes_per_pixel``, ``workspace_need`` and ``payload_len``.  Its attributes are looked up when they are called.
@@ -128,6 +130,42 @@ def decode_batch(codec, what: str, files, device, workspace_bytes: int, stats: O
         stats["pillow"] = stats.get("pillow", 0) + routed
         stats["bytes_uploaded"] = stats.get("bytes_uploaded", 0) + uploaded
     return out
+
+
+class StagedFile:
+    """A file that `codec` (``jpegdec`` or ``pngdec``) will decode into its region of a consumer's device buffer: it stands where the
+    decoded uint8 array would, with the plan's ``h``, ``w``, ``mode`` and ``nbytes``, and holds the file's bytes instead of pixels."""
+
+    def __init__(self, path, codec, plan, data: bytes):
+        self.path, self.codec, self.plan, self.data = path, codec, plan, data
+        self.h, self.w, self.mode = plan.h, plan.w, plan.mode
+        self.nbytes = plan.h * plan.w * plan.bytes_per_pixel
+
+
+def probe_file(path, codecs: Sequence) -> Optional[StagedFile]:
+    """Read the file at `path` and ask each of `codecs` in turn -> the StagedFile of the first that takes it, or None (the file keeps its
+    Pillow route).  Nothing is decoded."""
+    data = read_file(path)
+    for codec in codecs:
+        plan = codec.probe(data)
+        if plan is not None:
+            return StagedFile(path, codec, plan, data)
+    return None
+
+
+def decode_staged(entries: Sequence[Tuple[int, StagedFile, int]], buf, fallback: Callable[[StagedFile], object], stats: Optional[dict] = None) -> None:
+    """Decode `entries` = [(byte offset in `buf`, file, output channels)] into the uint8 device buffer `buf`: one ``decode_or_fallback``
+    per codec on the current stream; ``fallback(file)`` gives the pixels of a file its decoder refused.  stats: "device", "pillow" and
+    "bytes_uploaded" are added to, as ``decode_batch`` counts them."""
+    for codec in dict.fromkeys(f.codec for _, f, _ in entries):
+        part = [e for e in entries if e[1].codec is codec]
+        status = decode_or_fallback(codec, [(f.plan, f.data, off, ch) for off, f, ch in part], buf, lambda k: fallback(part[k][1]))
+        if stats is not None:
+            refused = sum(1 for s in status if s)
+            stats["device"] = stats.get("device", 0) + len(part) - refused
+            stats["pillow"] = stats.get("pillow", 0) + refused
+            stats["bytes_uploaded"] = stats.get("bytes_uploaded", 0) + sum(f.plan.payload_len for _, f, _ in part) + \
+                sum(off_f[1].h * off_f[1].w * off_f[2] for off_f, s in zip(part, status) if s)
 
 
 def decode_or_fallback(codec, entries: Sequence[Tuple], buf, fallback: Callable[[int], object]) -> List[int]:

@@ -108,6 +108,10 @@ SIGNATURES = {
     "dm4d_nhwc_to_nchw_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     # captured frames: crop + Pillow-exact bicubic resize + the dataset's fp32 epilogue (host/capture.py)
     "dm4d_capture_crop_resize_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i]),
+    # box + byte sum of planes decoded on the device, and rectangle masks (host/capture.py, device_decode=True)
+    "dm4d_capture_plane_stats_ws_bytes": (C.c_size_t, [_i, _i64]),
+    "dm4d_capture_plane_stats_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64]),
+    "dm4d_capture_fill_rects_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i]),
     # result evaluation: composite + nearest resize + mask crop + PSNR / SSIM of a batch of image pairs (host/metrics.py)
     "dm4d_eval_ws_bytes": (C.c_size_t, [_i, _i, _i]),
     "dm4d_eval_psnr_ssim_f64": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _vp, _vp, _i, _i]),
@@ -163,6 +167,8 @@ EPI_F32SIDE = 8
 EPI_SPLITOUT = 16
 LOG2E = 1.4426950408889634
 CAPTURE_FIELDS = 16
+CAPTURE_PLANE_FIELDS = 8
+CAPTURE_RECT_FIELDS = 8
 EVAL_FIELDS = 16
 EVAL_OUT = 8
 EVAL_IMAGE_F32 = 1

@@ -974,6 +974,38 @@ def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: i
     return pix, skel
 
 
+def _capture_planes(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, fields: int, n: int, desc_off: int) -> torch.Tensor:
+    """The checks that capture_plane_stats and capture_fill_rects share -> the host int64 [n, fields] view of the descriptors."""
+    _req(blob, "blob", torch.uint8), _req(meta, "meta", torch.uint8)
+    _check_meta(meta, meta_host, fields, n, desc_off)
+    if meta.device != blob.device or not blob.is_contiguous() or blob.numel() == 0:
+        raise _l.Dm4dError("blob / meta: expected contiguous non-empty tensors on one device")
+    return meta_host[desc_off: desc_off + n * fields * 8].view(torch.int64).reshape(n, fields)
+
+
+def capture_plane_stats(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int) -> torch.Tensor:
+    """{first column, first row, last column, last row, sum} of the `n` uint8 planes of `blob` that the int64 CAPTURE_PLANE_FIELDS
+    descriptors {byte offset (16-byte aligned), h, w, channels 1 or 3} at byte `desc_off` of `meta` name (host/capture.py) -> int64
+    [n, 5] on blob's device; {w, h, -1, -1} for a plane without a non-zero pixel.  `meta_host`: the host copy of `meta`, on which the
+    library checks every descriptor before it launches.  Two launches on the current stream; nothing is read back."""
+    lib = _l.load()
+    desc = _capture_planes(blob, meta, meta_host, _l.CAPTURE_PLANE_FIELDS, n, desc_off)
+    nbytes = int(lib.dm4d_capture_plane_stats_ws_bytes(n, int((desc[:, 1] * desc[:, 2] * desc[:, 3]).max())))
+    ws = torch.empty(max(nbytes, 8) // 8, dtype=torch.int64, device=blob.device)  # 0: out of range, which the call itself refuses
+    out = torch.empty((n, 5), dtype=torch.int64, device=blob.device)
+    _l.call("dm4d_capture_plane_stats_u8", _stream(), _p(blob), blob.numel(), desc.data_ptr(), meta.data_ptr() + desc_off, n, _p(out), _p(ws),
+            ws.numel() * 8)
+    return out
+
+
+def capture_fill_rects(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int) -> None:
+    """Write the `n` [h, w] uint8 mask planes of `blob` that the int64 CAPTURE_RECT_FIELDS descriptors {byte offset, h, w, c0, r0, c1,
+    r1} at byte `desc_off` of `meta` name: 255 on rows r0 .. r1 - 1 and columns c0 .. c1 - 1, 0 elsewhere.  meta / meta_host as for
+    capture_plane_stats.  One launch on the current stream."""
+    desc = _capture_planes(blob, meta, meta_host, _l.CAPTURE_RECT_FIELDS, n, desc_off)
+    _l.call("dm4d_capture_fill_rects_u8", _stream(), _p(blob), blob.numel(), desc.data_ptr(), meta.data_ptr() + desc_off, n)
+
+
 def eval_psnr_ssim(blob: torch.Tensor, desc: torch.Tensor, desc_off: Optional[int] = None, debug: bool = False):
     """PSNR / SSIM of a batch of image pairs (host/metrics.py; the reference's ImageEvaluator.__call__) -> (out [n, EVAL_OUT] fp64 =
     {psnr, ssim, pred min, pred max, gt min, gt max, squared-error sum, SSIM-map sum}, boxes [n, 4] int32 = the crops used) on blob's

@@ -8,7 +8,8 @@ any callable (``pose_model``).  Everything around it runs on the device (csrc/po
   * ``pose_inputs``: images (and foreground masks) are decoded with Pillow in a thread pool into pinned staging and uploaded once
     (host/staging.py lays the planes out, fills them and packs {tables | descriptors}; ``plane_layout`` and ``descriptors`` say where);
     one launch composites each image over black through its mask, warps every person box to the network's input and normalises it.
-    The warp is an integer rule of this package (DESIGN.md, "Keypoint prediction"), modelled on OpenCV's bilinear warpAffine;
+    The warp is an integer rule of this package ("Keypoint prediction"), modelled on OpenCV's bilinear warpAffine.  With
+    ``device_decode=True`` the JPEG / PNG files among them are decoded on the device into the same planes (``_device_files``);
   * ``decode_heatmaps``: one launch takes the heatmaps, which never visit the host, to refined keypoints (UDP / DARK decoding); the
     last two linear maps to image pixels are done on the host in fp64, as the reference's numpy does.
 
@@ -28,6 +29,7 @@ import torch
 from . import lib as _l
 from . import ops
 from . import staging as _st
+from .codec import decode_staged, probe_file
 from .staging import MAX_HOST_THREADS  # noqa: F401  (importable from here as before)
 
 MEAN = (123.5, 116.5, 103.5)   # vis_pose.py:451-452, RGB order (preprocess_pose's two BGR swaps cancel)
@@ -124,14 +126,43 @@ def descriptors(rows: Sequence[Tuple[int, int]], sizes, image_off, mask_off) -> 
     return desc
 
 
-def _stage(ims, mks, sizes, device: torch.device, pool: Optional[ThreadPoolExecutor]):
+def _device_files(ims, mks, sizes, pool: Optional[ThreadPoolExecutor]) -> dict:
+    """{("image" | "mask", index): the codec.StagedFile} of the images and masks that were opened from files csrc/jpegdec.hip or
+    csrc/pngdec.hip decodes into the plane the kernels read: an RGB image (or a grayscale JPEG, which the decoder replicates as
+    convert("RGB") does) and a mode-L mask.  Masks of mode ``1``, WebP files and whatever else the probes refuse are not in it."""
+    from . import jpegdec, pngdec
+
+    def probe(job):
+        kind, k, im = job
+        name = getattr(im, "filename", "") if im is not None else ""
+        if not name or im.format not in ("JPEG", "PNG"):
+            return None
+        f = probe_file(name, (jpegdec, pngdec))
+        if f is None or (f.h, f.w) != tuple(sizes[k]) or f.mode != im.mode:
+            return None
+        ok = f.mode == "L" if kind == "mask" else (f.mode == "RGB" or (f.mode == "L" and f.codec is jpegdec))
+        return f if ok else None
+    jobs = [("image", k, im) for k, im in enumerate(ims or [])] + [("mask", k, m) for k, m in enumerate(mks)]
+    return {job[:2]: f for job, f in zip(jobs, _st.pool_map(pool, probe, jobs)) if f is not None}
+
+
+def _stage(ims, mks, sizes, device: torch.device, pool: Optional[ThreadPoolExecutor], device_decode: bool = False):
     """Decode one batch into pinned staging and queue its upload -> (blob uint8 on the device, the pinned buffer, image offsets, mask
-    offsets).  The pinned buffer has to stay alive until the consumer has synchronised."""
+    offsets).  The pinned buffer has to stay alive until the consumer has synchronised.  device_decode: the files of ``_device_files``
+    are not decoded by Pillow: their bytes go up and the device decodes them into their planes of the blob (a file its decoder
+    refuses keeps the Pillow route)."""
     image_off, mask_off, total = plane_layout(sizes, ims is not None, [m is not None for m in mks])
-    jobs = [(o, (ims[k], "RGB")) for k, o in enumerate(image_off) if o >= 0] + [(o, (mks[k], "L")) for k, o in enumerate(mask_off) if o >= 0]
+    on_device = _device_files(ims, mks, sizes, pool) if device_decode else {}
+    jobs = [(o, (ims[k], "RGB")) for k, o in enumerate(image_off) if o >= 0 and ("image", k) not in on_device] + \
+           [(o, (mks[k], "L")) for k, o in enumerate(mask_off) if o >= 0 and ("mask", k) not in on_device]
     host = _st.pinned(total, device)
     _st.fill(host.numpy(), jobs, pool)
-    return host.to(device, non_blocking=True), host, image_off, mask_off
+    blob = host.to(device, non_blocking=True) if jobs else torch.empty(total, dtype=torch.uint8, device=device)
+    if on_device:
+        entries = [((image_off if kind == "image" else mask_off)[k], f, 3 if kind == "image" else 1) for (kind, k), f in on_device.items()]
+        mode = {id(f): "RGB" if ch == 3 else "L" for _, f, ch in entries}
+        decode_staged(entries, blob, lambda f: np.asarray(_st.open_image(f.path).convert(mode[id(f)])))
+    return blob, host, image_off, mask_off
 
 
 def _mask_boxes(blob: torch.Tensor, sizes, image_off, mask_off) -> np.ndarray:
@@ -140,13 +171,13 @@ def _mask_boxes(blob: torch.Tensor, sizes, image_off, mask_off) -> np.ndarray:
     return ops.pose_mask_box(blob, meta, meta_host, n, desc_off).cpu().numpy()  # .cpu() synchronises: meta_host may go
 
 
-def fmask_boxes(fmasks, device="cuda") -> np.ndarray:
+def fmask_boxes(fmasks, device="cuda", *, device_decode: bool = False) -> np.ndarray:
     """[n, 4] int32: per mask (path, PIL image or uint8 array; mode ``L`` or ``1``) the box [x1, y1, x2, y2] of its pixels >= 128, x2 and
-    y2 exclusive; the whole image for a mask without one.  One launch (dm4d_pose_mask_box_u8)."""
+    y2 exclusive; the whole image for a mask without one.  One launch (dm4d_pose_mask_box_u8).  device_decode: as for ``pose_inputs``."""
     _, mks, sizes = _open_all(None, list(fmasks), None)
     dev = _l.hip_device(device, "fmask_boxes")
     with torch.cuda.device(dev):
-        blob, _host, image_off, mask_off = _stage(None, mks, sizes, dev, None)
+        blob, _host, image_off, mask_off = _stage(None, mks, sizes, dev, None, device_decode)
         return _mask_boxes(blob, sizes, image_off, mask_off)
 
 
@@ -162,7 +193,7 @@ def _boxes_of(b, h: int, w: int) -> List:
 
 
 def pose_inputs(images, fmasks=None, bboxes=None, shape: Tuple[int, int] = (1024, 768), device="cuda", *, bbox_source: str = "image",
-                pool: Optional[ThreadPoolExecutor] = None) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
+                pool: Optional[ThreadPoolExecutor] = None, device_decode: bool = False) -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
     """The pose network's input for a batch of images -> (tensor fp32 [rows, 3, H, W] on `device`, centers [rows, 2], scales [rows, 2]
     float64; rows in image order, an image's boxes in their order).
 
@@ -170,7 +201,12 @@ def pose_inputs(images, fmasks=None, bboxes=None, shape: Tuple[int, int] = (1024
     otherwise), of the image's size, or None for an image without one; the image is composited over black through it, as
     ``Image.composite(image, black, fmask)``.  bboxes: per image ``[x1, y1, x2, y2]`` or several of them, float, or None for the whole
     image; bboxes=None: whole images, or, with ``bbox_source="fmask"``, the box of each mask's pixels >= 128.  shape: the network's
-    input (H, W)."""
+    input (H, W).
+
+    device_decode: images that are baseline JPEG files of the supported set (host/jpegdec.py::probe) or 8-bit RGB PNG files
+    (host/pngdec.py::probe), and mode-L masks that are such PNG (or JPEG) files, are not decoded by Pillow: their file bytes go up and the
+    device decodes them into the planes the kernels read, byte for byte Pillow's pixels, so the result is the same.  Masks of mode
+    ``1``, WebP images and every other input keep the Pillow route."""
     if bbox_source not in ("image", "fmask"):
         raise ValueError(f'bbox_source must be "image" or "fmask", got {bbox_source!r}')
     H, W = int(shape[0]), int(shape[1])
@@ -182,7 +218,7 @@ def pose_inputs(images, fmasks=None, bboxes=None, shape: Tuple[int, int] = (1024
         raise ValueError('bbox_source="fmask" needs a mask for every image')
     dev = _l.hip_device(device, "pose_inputs")
     with torch.cuda.device(dev):
-        blob, _host, image_off, mask_off = _stage(ims, mks, sizes, dev, pool)
+        blob, _host, image_off, mask_off = _stage(ims, mks, sizes, dev, pool, device_decode)
         if bboxes is None:
             boxes = _mask_boxes(blob, sizes, image_off, mask_off)[:, None, :] if bbox_source == "fmask" else [[[0, 0, w, h]] for h, w in sizes]
         else:
@@ -281,7 +317,7 @@ def write_instances(path: str, keypoints: np.ndarray, scores: np.ndarray) -> Non
 def predict_keypoints(images_dir: str, out_kp2d_dir: str, fmasks_dir: Optional[str] = None, sapiens_ckpt_path: Optional[str] = None,
                       detector_ckpt_path: Optional[str] = None, gpu_ids: Optional[Sequence[int]] = None, num_workers: int = 4, *,
                       pose_model: Optional[Callable] = None, shape: Tuple[int, int] = (1024, 768), heatmap_scale: int = 4,
-                      batch_size: int = 4, skip_exists: bool = True, bbox_source: str = "image") -> dict:
+                      batch_size: int = 4, skip_exists: bool = True, bbox_source: str = "image", device_decode: bool = False) -> dict:
     """Predict the 2-D keypoints of every image under `images_dir` and write ``out_kp2d_dir/{camera}/{frame}.json``.
 
     pose_model: any callable taking fp32 [n, 3, H, W] on the device and returning [n, K, H / heatmap_scale, W / heatmap_scale] on the
@@ -289,7 +325,8 @@ def predict_keypoints(images_dir: str, out_kp2d_dir: str, fmasks_dir: Optional[s
     caller's network: its output never visits the host.  A ``detector_ckpt_path`` is refused (the reference's RTMDet detector needs mmdet, which this package does not carry): the box
     is the whole image, or the box of the foreground mask with ``bbox_source="fmask"``.  The reference's ``flip`` is not taken (it
     averages the flipped pass without flipping it back).  One worker thread per GPU id; decoding and the
-    JSON files go through a pool of `num_workers` threads.  Returns counts."""
+    JSON files go through a pool of `num_workers` threads.  Returns counts.  device_decode: handed to ``pose_inputs`` (the same files are
+    written)."""
     if detector_ckpt_path:
         raise NotImplementedError("detector_ckpt_path: the person detector is mmdet's RTMDet, which diffuman4d_amd does not carry; "
                                   'the box is the whole image, or bbox_source="fmask"')
@@ -313,7 +350,7 @@ def predict_keypoints(images_dir: str, out_kp2d_dir: str, fmasks_dir: Optional[s
 
     def process_batch(model: Callable, batch: List[int], dev: torch.device, pool: ThreadPoolExecutor) -> List:
         x, centers, scales = pose_inputs([images[k] for k in batch], None if fmasks is None else [fmasks[k] for k in batch], None,
-                                         (H, W), dev, bbox_source=bbox_source, pool=pool)
+                                         (H, W), dev, bbox_source=bbox_source, pool=pool, **({"device_decode": True} if device_decode else {}))
         heat = model(x)
         if not isinstance(heat, torch.Tensor) or heat.device.type != "cuda" or heat.dim() != 4 or heat.shape[0] != x.shape[0]:
             raise _l.Dm4dError("pose_model: expected a [n, K, Hh, Wh] tensor on the device")

@@ -241,6 +241,27 @@ int dm4d_capture_crop_resize_f32(void* stream, const void* staging, int64_t stag
                                  const int64_t* desc_dev, int n_frames, const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len,
                                  void* scratch, int64_t scratch_bytes, float* pixel_values, float* skeletons, int H, int W);
 
+/* Box and byte sum of uint8 planes that lie in a device blob, and masks that are filled rectangles (capture.hip): what
+ *   SpaTemDataset(device_decode=True) needs of planes that were decoded on the device and never visit the host.
+ * dm4d_capture_plane_stats_u8: desc = n x DM4D_CAPTURE_PLANE_FIELDS int64 = {byte offset in blob (16-byte aligned) | h | w | channels: 1
+ *   or 3 | 0 ...}; planes are HWC with tight rows, of any sizes from 1 to 32768 a side.  out [n, 5] int64 = {first column, first row,
+ *   last column, last row, sum}: columns and rows of the pixels with at least one non-zero channel, {w, h, -1, -1} for a plane without
+ *   one (as dm4d_skeleton_box_mask_u8), and the sum of all the plane's bytes.  Two launches on `stream`: per-block partials over
+ *   16-byte loads (a scalar tail where a plane does not end on one), then one wave per plane that folds them.  Integers only, no
+ *   atomics, no block waits on another: a plane's row is the same alone or in any batch, and bitwise repeatable.
+ *   ws: dm4d_capture_plane_stats_ws_bytes(n, the largest plane's bytes) bytes (0 for arguments out of range), 8-byte aligned.
+ * dm4d_capture_fill_rects_u8: desc = n x DM4D_CAPTURE_RECT_FIELDS int64 = {mask byte offset in blob (any alignment) | h | w | c0 | r0 |
+ *   c1 | r1 | 0}; the whole [h, w] plane is written: 255 on rows r0 .. r1 - 1 and columns c0 .. c1 - 1, 0 elsewhere (c0 == c1 or
+ *   r0 == r1: all 0).  One launch.  With the rectangle of capture.py's skeleton_mask_rect the plane is skeleton_to_mask's byte for byte.
+ * desc_host is the host copy of the bytes at desc_dev: n, every size, offset and rectangle (0 <= c0 <= c1 <= w, 0 <= r0 <= r1 <= h, the
+ *   plane inside the blob) is validated on it before anything is launched.                                                        */
+#define DM4D_CAPTURE_PLANE_FIELDS 8
+#define DM4D_CAPTURE_RECT_FIELDS 8
+size_t dm4d_capture_plane_stats_ws_bytes(int n, int64_t max_plane_bytes);
+int dm4d_capture_plane_stats_u8(void* stream, const void* blob, int64_t blob_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
+                                int64_t* out, void* ws, int64_t ws_bytes);
+int dm4d_capture_fill_rects_u8(void* stream, void* blob, int64_t blob_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n);
+
 /* Result evaluation of n_pairs (predicted, ground-truth) images (diffuman4d_amd/host/metrics.py::ImageEvaluator; the reference's
  *   ImageEvaluator.__call__, data/utils/metric_utils.py:98-137, called from evaluate_results :157-182 and sampling_runner.py:64-77):
  *   apply_fmask (x * m + (1 - m) * bg, fp32, each operation rounded on its own), torchvision's nearest resize to the canvas

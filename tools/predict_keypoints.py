@@ -37,13 +37,15 @@ def main(argv=None) -> int:
     ap.add_argument("--batch_size", type=int, default=4)
     ap.add_argument("--bbox_source", choices=("image", "fmask"), default="image")
     ap.add_argument("--no_skip_exists", action="store_true", help="predict again even where a file exists and parses")
+    ap.add_argument("--device_decode", action="store_true", help="decode JPEG / PNG images and PNG masks on the GPU (the same files are written)")
     args = ap.parse_args(argv)
     if len(args.shape) != 2:
         ap.error("--shape takes height,width")
     from diffuman4d_amd.host import pose
     res = pose.predict_keypoints(args.images_dir, args.out_kp2d_dir, args.fmasks_dir, args.sapiens_ckpt_path, args.detector_ckpt_path, args.gpu_ids,
                                  args.num_workers, shape=tuple(args.shape), heatmap_scale=args.heatmap_scale, batch_size=args.batch_size,
-                                 skip_exists=not args.no_skip_exists, bbox_source=args.bbox_source)
+                                 skip_exists=not args.no_skip_exists, bbox_source=args.bbox_source,
+                                 **({"device_decode": True} if args.device_decode else {}))
     print(json.dumps(res))
     return 0
 

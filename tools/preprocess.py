@@ -82,7 +82,7 @@ def run(data_dir: str, actions, *, matting_model_dir=None, sapiens_ckpt_path=Non
             res = STAGES[act](f"{d}/fmasks", f"{d}/transforms.json", f"{d}/surfs", **({"device_decode": True} if device_decode else {}))
             shutil.copyfile(f"{d}/surfs/000000.ply", f"{d}/sparse_pcd.ply")
         elif act == "predict_keypoints":
-            res = STAGES[act](f"{d}/images", f"{d}/poses_sapiens", f"{d}/fmasks", sapiens_ckpt_path)
+            res = STAGES[act](f"{d}/images", f"{d}/poses_sapiens", f"{d}/fmasks", sapiens_ckpt_path, **({"device_decode": True} if device_decode else {}))
         elif act == "triangulate_skeleton":
             res = STAGES[act](f"{d}/transforms.json", f"{d}/poses_sapiens", f"{d}/poses_3d", out_pcd_dir=f"{d}/poses_pcd",
                               out_kp2d_proj_dir=f"{d}/poses_2d")
@@ -101,7 +101,7 @@ def main(argv=None) -> int:
     ap.add_argument("--palette", default=None, help="draw_skeleton: JSON file with keypoint_colors, links and x_link_color")
     ap.add_argument("--batch_size", type=int, default=8, help="remove_background: images per batch (decrease it if memory runs out)")
     ap.add_argument("--device_png", action="store_true", help="remove_background: encode the mask PNG files on the GPU (same pixels, other bytes)")
-    ap.add_argument("--device_decode", action="store_true", help="remove_background: decode baseline JPEG inputs on the GPU; carve_vhull: decode the PNG masks there (same files written)")
+    ap.add_argument("--device_decode", action="store_true", help="remove_background: decode baseline JPEG inputs on the GPU; carve_vhull: decode the PNG masks there; predict_keypoints: decode JPEG / PNG images and PNG masks there (same files written)")
     args = ap.parse_args(argv)
     try:
         actions = parse_actions(args.actions)

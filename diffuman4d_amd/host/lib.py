@@ -156,6 +156,8 @@ SIGNATURES = {
     # 8-bit PNG files decoded into a caller's buffer: inflate through an LDS window, then the unfilter wavefront (host/pngdec.py)
     "dm4d_png_decode_ws_bytes": (C.c_size_t, [_i64, _i]),
     "dm4d_png_decode_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp]),
+    # raw captures: colour table + undistortion + area resize + crop of a batch of images, one launch (host/rectify.py)
+    "dm4d_rectify_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i64]),
 }
 
 # The constants of include/dm4d.h that the host uses, under the header's names without the DM4D_ prefix.  This block is their ONLY
@@ -223,6 +225,9 @@ PNGDEC_ST_DISTANCE = 8
 PNGDEC_ST_END = 16
 PNGDEC_ST_ADLER = 32
 PNGDEC_ST_FILTER = 64
+RECTIFY_FIELDS = 20
+RECTIFY_MAX_SIDE = 16384
+RECTIFY_MAX_SCALE = 8
 ROWS_MOVE_MAX_JOBS = 16
 
 

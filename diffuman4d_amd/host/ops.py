@@ -1344,3 +1344,22 @@ def png_encode(planes: torch.Tensor, rgb: Optional[torch.Tensor], desc: torch.Te
     _l.call("dm4d_png_encode_u8", _stream(), _p(planes), planes.numel(), _p(rgb), 0 if rgb is None else rgb.numel(), desc.data_ptr(),
             _p(desc_dev), n, _p(ws), ws.numel() * 8, _p(blob), blob.numel(), _p(out))
     return blob, out
+
+
+def rectify(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int,
+            lut: torch.Tensor, out_bytes: int) -> torch.Tensor:
+    """Colour table + undistortion + area resize + crop of `n` staged raw captures (host/rectify.py) -> the packed uint8 RGB results,
+    `out_bytes` bytes on blob's device, one launch on the current stream.  `blob`: device uint8 holding the RGB sources; `meta`: device
+    uint8 holding the int32 / fp32 tables at byte `tab_off` and the int64 RECTIFY_FIELDS descriptors at byte `desc_off` (a descriptor
+    names its result's 16-byte aligned offset), `meta_host` its host copy, on which the library checks every size, offset, window and
+    crop before it launches.  lut: device fp32 [n, 3, 256], the colour correction of every byte of every image."""
+    _req(blob, "blob", torch.uint8), _req(meta, "meta", torch.uint8), _req(lut, "lut", F32)
+    _check_meta(meta, meta_host, _l.RECTIFY_FIELDS, n, desc_off, tab_off, tab_len)
+    if tuple(lut.shape) != (n, 3, 256) or not lut.is_contiguous() or not blob.is_contiguous() or blob.numel() == 0 or out_bytes < 1 or \
+            len({blob.device, meta.device, lut.device}) != 1:
+        raise _l.Dm4dError(f"blob / meta / lut: expected contiguous non-empty tensors on one device, lut [{n}, 3, 256]")
+    out = torch.empty(out_bytes, dtype=torch.uint8, device=blob.device)
+    host, dev = meta_host.data_ptr(), meta.data_ptr()
+    _l.call("dm4d_rectify_u8", _stream(), _p(blob), blob.numel(), host + desc_off, dev + desc_off, n, host + tab_off, dev + tab_off, tab_len,
+            _p(lut), _p(out), out_bytes)
+    return out

@@ -1,5 +1,5 @@
 """The host's way to the device, written once for every module that stages bytes for a kernel (``capture``, ``metrics``, ``pose``,
-``matting``) or drives a per-GPU stage around a caller's network (``pose.predict_keypoints``, ``matting.remove_background``):
+``matting``, ``rectify``) or drives a per-GPU stage (``pose.predict_keypoints``, ``matting.remove_background``, ``rectify.extract_images``):
 
   * ``Layout``: byte offsets of the regions of one buffer (planes, int32 tables, int64 descriptors), each 16-byte aligned;
   * ``pinned`` + ``fill``: the host buffer (page-locked when it goes to a HIP device) and its filling from arrays or from PIL images

@@ -631,6 +631,30 @@ size_t dm4d_png_decode_ws_bytes(int64_t total_filtered_bytes, int n);
 int dm4d_png_decode_u8(void* stream, const void* streams, int64_t streams_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
                        void* workspace, int64_t workspace_bytes, void* out, int64_t out_bytes, int32_t* status);
 
+/* Raw-capture rectification (rectify.hip; diffuman4d_amd/host/rectify.py::extract_images; the reference's
+ *   scripts/download/extract_dnar_images.py:89-120 calib_undist_image): colour correction, undistortion to a pinhole camera, area resize
+ *   and crop of n uint8 RGB images of different sizes, cameras and tables in ONE launch.  tests/rectify_model.py is the definition in
+ *   numpy and DESIGN.md "Raw-capture rectification" its text; the result is the model's byte for byte.  A workgroup owns a 32 x 8 tile of
+ *   an image's cropped output and keeps the patch of the undistorted image that the tile's area windows name in LDS only.  No atomics, no
+ *   workgroup waits on another; an image's result depends on its own descriptor, tables and source: independent of the batch, bitwise
+ *   repeatable.
+ * staging: uint8 RGB sources, HWC with tight rows.  desc: n x DM4D_RECTIFY_FIELDS int64 = {byte offset of the source in staging (16-byte
+ *   aligned) | h, w of the source | uh, uw of the undistorted image | rh, rw of the resized image (all 1..DM4D_RECTIFY_MAX_SIDE, each
+ *   axis' scale uw / rw, uh / rh in 1..DM4D_RECTIFY_MAX_SCALE) | top, left, height, width of the crop of the resized image | offset of
+ *   the horizontal table in tab (int32 elements), its taps per window (ksize) | the same for the vertical table | offset of the camera
+ *   constants in tab | byte offset of the result in out (16-byte aligned; height x width x 3 bytes, rows tight) | 0 ...}.
+ * tab: int32 / fp32 words.  A table of an axis n_in -> n_out: n_out windows {first source cell, taps (1..ksize)}, starts and ends
+ *   ascending, inside 0..n_in; then n_out x ksize fp32 weights.  Camera constants: 16 fp32 = {fx, fy, cx, cy of the distorted camera |
+ *   k1, k2, p1, p2, k3 | cx, cy of the undistorted camera | fp32(1 / fx), fp32(1 / fy) of it, divided in fp64 | 0, 0, 0}.
+ * lut_dev: n x 3 x 256 fp32 on the device: what the colour correction makes of every byte of every channel of image k.
+ * desc_host / tab_host are the host copies of desc_dev / tab_dev: every size, offset, window and crop is validated on them before
+ *   anything is launched (DM4D_ERR_ARG).                                                                                              */
+#define DM4D_RECTIFY_FIELDS 20
+#define DM4D_RECTIFY_MAX_SIDE 16384
+#define DM4D_RECTIFY_MAX_SCALE 8
+int dm4d_rectify_u8(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
+                    const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len, const void* lut_dev, void* out, int64_t out_bytes);
+
 /* VaeImageProcessor.postprocess(do_denormalize): (x/2 + 0.5).clamp(0,1), NHWC(ldx) -> NCHW (:282-284)  */
 int dm4d_postprocess_images_bf16(void* stream, const void* X, void* Y, int B, int C, int HW, int ldx);
 

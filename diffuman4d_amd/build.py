@@ -11,7 +11,7 @@ ROOT = Path(__file__).resolve().parent
 CSRC = ROOT / "csrc"
 INCLUDE = ROOT.parent / "include"
 LIB = ROOT / "libdm4d.so"
-SOURCES = ["api.hip", "gemm.hip", "gemm_h16.hip", "ff_fused.hip", "conv_direct.hip", "attention.hip", "attention_hd.hip", "norm.hip", "elementwise.hip", "parity.hip", "capture.hip", "metrics.hip", "lpips.hip", "vhull.hip", "triang.hip", "skeleton.hip", "jpeg.hip", "pose.hip", "matting.hip", "png.hip", "jpegdec.hip", "pngdec.hip", "rectify.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_h16.hip", "ff_fused.hip", "conv_direct.hip", "attention.hip", "attention_hd.hip", "norm.hip", "elementwise.hip", "parity.hip", "capture.hip", "metrics.hip", "lpips.hip", "vhull.hip", "triang.hip", "skeleton.hip", "jpeg.hip", "pose.hip", "matting.hip", "png.hip", "jpegdec.hip", "pngdec.hip", "rectify.hip", "detect.hip"]
 # attention.hip: the 4-wave x 64-row kernel form needs more than 256 registers per lane; without this flag hipcc puts every MFMA
 # result of such a kernel into AGPRs and copies the score accumulators to VGPRs and back on every step (0.67x, measured);
 # kernels that fit in 256 registers are unaffected
@@ -23,9 +23,12 @@ SOURCES = ["api.hip", "gemm.hip", "gemm_h16.hip", "ff_fused.hip", "conv_direct.h
 # pose.hip: the network input's (v - mean) / std is bit-equal to torch CPU, and the decode's fp32 differences and fp64 2 x 2 solve are the
 # reference's operations one by one (the blur's multiply-adds are written as fmaf())
 # rectify.hip: the undistortion, the bilinear taps and the area sums are the fp32 operations of tests/rectify_model.py one by one
+# detect.hip: the detector input's (v - mean) / std and the NMS's areas and overlaps are the fp32 operations of tests/detect_model.py
+# one by one
 EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "capture.hip": ["-ffp-contract=off"],
                "metrics.hip": ["-ffp-contract=off"], "lpips.hip": ["-ffp-contract=off"], "vhull.hip": ["-ffp-contract=off"],
-               "triang.hip": ["-ffp-contract=off"], "pose.hip": ["-ffp-contract=off"], "rectify.hip": ["-ffp-contract=off"]}
+               "triang.hip": ["-ffp-contract=off"], "pose.hip": ["-ffp-contract=off"], "rectify.hip": ["-ffp-contract=off"],
+               "detect.hip": ["-ffp-contract=off"]}
 # sources that #include another .hip source (gemm_h16.hip = the PAR = 2 instantiations of gemm.hip's kernels)
 EXTRA_DEPS = {"gemm_h16.hip": ["gemm.hip"]}
 

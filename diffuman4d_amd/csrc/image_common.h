@@ -1,14 +1,22 @@
-// The parts that the uint8 image kernels share (capture.hip, jpeg.hip, skeleton.hip, pose.hip, vhull.hip), each defined once:
+// The parts that the uint8 image kernels share (capture.hip, jpeg.hip, skeleton.hip, pose.hip, detect.hip, vhull.hip), each defined once:
 //   Pillow resample   the fixed-point rule of libImaging/Resample.c and the host-side check of a coefficient table
 //   pixel box         the bounding box of the set pixels of a uint8 plane: the walk, the wave reduction and the block fold; and the
 //                     writing of a plane that is a filled rectangle
 //   scan              the 64-lane inclusive scan and the one-block exclusive scan with a carry
+//   composite         Pillow's MULDIV255, the per-byte rule of Image.composite over black (pose.hip, detect.hip)
 // Integer code only, so -ffp-contract=off (build.py EXTRA_FLAGS gives it to some of the including files) cannot change what this
 // header compiles to.  Everything assumes one-dimensional blocks (lane = threadIdx.x & 63).
 #pragma once
 #include <stdint.h>
 
 #include "common.h"
+
+// -- composite ------------------------------------------------------------------------------------------------------------------------------
+// Image.composite(image, black, mask) for an L mask: Pillow's MULDIV255
+__device__ __forceinline__ uint32_t muldiv255(uint32_t p, uint32_t m) {
+  const uint32_t t = p * m + 128u;
+  return ((t >> 8) + t) >> 8;
+}
 
 // -- Pillow resample --------------------------------------------------------------------------------------------------------------------
 // int32 coefficients with 22 fractional bits; every output value is clip8((2^21 + sum u * k) >> 22)

@@ -19,6 +19,7 @@
 #include "dm4d.h"
 #include "errors.h"
 #include "image_common.h"
+#include "pose_rows.h"
 
 namespace {
 
@@ -28,12 +29,6 @@ constexpr int kInThreads = 256;
 struct PoseNorm {
   float mean[3], stdv[3];
 };
-
-// Image.composite(image, black, mask) for an L mask: Pillow's MULDIV255
-__device__ __forceinline__ uint32_t muldiv255(uint32_t p, uint32_t m) {
-  const uint32_t t = p * m + 128u;
-  return ((t >> 8) + t) >> 8;
-}
 
 // grid (ceil(H W / kInThreads), rows): one output pixel per thread, its three channels
 __global__ void __launch_bounds__(kInThreads) pose_input_kernel(const uint8_t* __restrict__ staging, const int64_t* __restrict__ desc,
@@ -236,30 +231,6 @@ __global__ void __launch_bounds__(kDecThreads) pose_udp_decode_kernel(const floa
   locs[2 * (int64_t)map + 1] = (float)((double)ay - oy);
 }
 
-int check_rows(const char* what, int64_t staging_bytes, const int64_t* desc_host, int rows, bool need_image, bool need_mask) {
-  static thread_local char msg[160];
-  for (int r = 0; r < rows; ++r) {
-    const int64_t* d = desc_host + (int64_t)r * DM4D_POSE_FIELDS;
-    const int64_t h = d[2], w = d[3];
-    const char* bad = nullptr;
-    if (h < 1 || h > DM4D_POSE_MAX_SIDE || w < 1 || w > DM4D_POSE_MAX_SIDE)
-      bad = "image size outside 1..16384";
-    else if (need_image && (d[0] < 0 || d[0] > staging_bytes || h * w * 3 > staging_bytes - d[0]))
-      bad = "image outside the staging buffer";
-    else if (d[1] < (need_mask ? 0 : -1))
-      bad = "mask offset is negative";
-    else if (d[1] >= 0 && (d[1] > staging_bytes || h * w > staging_bytes - d[1]))
-      bad = "mask outside the staging buffer";
-    else if (d[5] || d[6] || d[7])
-      bad = "spare fields must be 0";
-    if (bad) {
-      snprintf(msg, sizeof msg, "%s: row %d: %s", what, r, bad);
-      return dm4d_set_error(DM4D_ERR_ARG, msg);
-    }
-  }
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int dm4d_pose_input_u8_f32(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host,
@@ -278,7 +249,7 @@ extern "C" int dm4d_pose_input_u8_f32(void* stream, const void* staging, int64_t
     if (!isfinite(norm.mean[c]) || !isfinite(norm.stdv[c]) || norm.stdv[c] == 0.f)
       return dm4d_set_error(DM4D_ERR_ARG, "pose_input: mean must be finite and std finite and non-zero");
   }
-  int rc = check_rows("pose_input", staging_bytes, desc_host, rows, true, false);
+  int rc = pose_check_rows("pose_input", staging_bytes, desc_host, rows, true, false, false);
   if (rc) return rc;
   const int64_t per_row = 2 * ((int64_t)W + H);
   for (int r = 0; r < rows; ++r) {
@@ -301,7 +272,7 @@ extern "C" int dm4d_pose_mask_box_u8(void* stream, const void* staging, int64_t 
   if (staging_bytes < 1) return dm4d_set_error(DM4D_ERR_ARG, "pose_mask_box: empty staging buffer");
   if (((uintptr_t)boxes & 3) || ((uintptr_t)desc_dev & 7))
     return dm4d_set_error(DM4D_ERR_ARG, "pose_mask_box: boxes (4 bytes) and desc_dev (8 bytes) must be aligned");
-  const int rc = check_rows("pose_mask_box", staging_bytes, desc_host, n, false, true);
+  const int rc = pose_check_rows("pose_mask_box", staging_bytes, desc_host, n, false, true, false);
   if (rc) return rc;
   hipLaunchKernelGGL(pose_mask_box_kernel, dim3(n), dim3(kBoxThreads), 0, (hipStream_t)stream, (const uint8_t*)staging, desc_dev, boxes);
   return dm4d_check_launch("pose_mask_box_kernel");

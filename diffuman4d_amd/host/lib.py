@@ -142,6 +142,10 @@ SIGNATURES = {
     "dm4d_pose_input_u8_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i, _i]),
     "dm4d_pose_mask_box_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp]),
     "dm4d_pose_udp_decode_f32": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    # person boxes around a caller-named detector: composite + keep-ratio resize + pad + normalise, and threshold + top-k + NMS
+    # (host/detect.py)
+    "dm4d_detect_input_u8_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i]),
+    "dm4d_detect_select_f32": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _i, _vp, _vp, _vp]),
     # foreground masks around a caller-named matting network: rotate + bilinear resize + normalise, and logits -> bytes + bicubic
     # resize + rotate back (host/matting.py)
     "dm4d_matting_input_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i]),
@@ -198,6 +202,11 @@ POSE_MAX_SIDE = 16384
 POSE_MAX_HEATMAP_H = 4096
 POSE_MAX_HEATMAP_W = 1024
 POSE_TAB_LIMIT = 1 << 29
+DETECT_MAX_ANCHORS = 1 << 20
+DETECT_MAX_CLASSES = 4096
+DETECT_MAX_KEEP = 256
+DETECT_MAX_CANVAS = 4096
+DETECT_COEF_ONE = 2048
 MATTING_FIELDS = 8
 MATTING_MAX_SIDE = 16384
 PNG_FIELDS = 16

@@ -51,7 +51,7 @@ def _req(t: torch.Tensor, name: str, dtype=BF16):
         raise _l.Dm4dError(f"{name}: expected a tensor on a HIP device (no CPU fallback in diffuman4d_amd)")
     if t.dtype != dtype:
         raise _l.Dm4dError(f"{name}: expected dtype {dtype}, got {t.dtype}")
-    if t.stride(-1) != 1:
+    if t.stride(-1) != 1 and t.shape[-1] != 1:  # the stride of a dimension of size 1 says nothing
         raise _l.Dm4dError(f"{name}: last dim must be contiguous")
     return t
 
@@ -1280,6 +1280,44 @@ def pose_udp_decode(heatmaps: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]
     scores = torch.empty((n, K), dtype=F32, device=heatmaps.device)
     _l.call("dm4d_pose_udp_decode_f32", _stream(), _p(heatmaps), n, K, Hh, Wh, _p(scores), _p(locs))
     return locs, scores
+
+
+def detect_input(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int,
+                 H: int, W: int, norm: torch.Tensor, pad_value: int, bgr: bool) -> torch.Tensor:
+    """The detector's input for `n` staged images (host/detect.py) -> fp32 [n, 3, H, W] on blob's device, one launch on the current
+    stream.  blob / meta / meta_host as for pose_input, the tables being the resize tables of include/dm4d.h (dm4d_detect_input_u8_f32).
+    norm: host fp32 [6] = mean | std per output plane; bgr: plane c is the staged channel 2 - c."""
+    _pose_blob(blob, meta)
+    _check_meta(meta, meta_host, _l.POSE_FIELDS, n, desc_off, tab_off, tab_len)
+    if norm.device.type != "cpu" or norm.dtype != F32 or norm.numel() != 6 or not norm.is_contiguous():
+        raise _l.Dm4dError("norm: expected a contiguous host fp32 tensor of 6 values")
+    out = torch.empty((n, 3, H, W), dtype=F32, device=blob.device)
+    host, dev = meta_host.data_ptr(), meta.data_ptr()
+    _l.call("dm4d_detect_input_u8_f32", _stream(), _p(blob), blob.numel(), host + desc_off, dev + desc_off, n, host + tab_off, dev + tab_off,
+            tab_len, norm.data_ptr(), _p(out), H, W, int(pad_value), int(bool(bgr)))
+    return out
+
+
+def detect_select(boxes: torch.Tensor, scores: torch.Tensor, inv_scale: torch.Tensor, cat: int, score_thr: float, nms_thr: float,
+                  max_per_img: int) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Dense detector output -> kept boxes (include/dm4d.h, dm4d_detect_select_f32): boxes fp32 [n, A, 4], scores fp32 [n, A, C],
+    inv_scale fp32 [n, 2], contiguous on one device -> (counts int32 [n, 3] = kept | dropped | above the threshold, fp32
+    [n, max_per_img, 5] = x1, y1, x2, y2, score in kept order, int32 [n, max_per_img] anchor indices).  One launch on the current stream."""
+    _req(boxes, "boxes", F32), _req(scores, "scores", F32), _req(inv_scale, "inv_scale", F32)
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or scores.dim() != 3 or scores.shape[:2] != boxes.shape[:2] or boxes.numel() == 0 or \
+            scores.numel() == 0 or tuple(inv_scale.shape) != (boxes.shape[0], 2):
+        raise _l.Dm4dError(f"boxes / scores / inv_scale: expected [n, A, 4], [n, A, C] and [n, 2], got {tuple(boxes.shape)}, "
+                           f"{tuple(scores.shape)} and {tuple(inv_scale.shape)}")
+    if not (boxes.is_contiguous() and scores.is_contiguous() and inv_scale.is_contiguous()) or len({boxes.device, scores.device, inv_scale.device}) != 1:
+        raise _l.Dm4dError("boxes / scores / inv_scale: expected contiguous tensors on one device")
+    n, A, C = scores.shape
+    keep = min(max(int(max_per_img), 1), _l.DETECT_MAX_KEEP)  # the library refuses what is out of range; the results are sized for what it accepts
+    counts = torch.empty((n, 3), dtype=torch.int32, device=boxes.device)
+    out = torch.empty((n, keep, 5), dtype=F32, device=boxes.device)
+    idx = torch.empty((n, keep), dtype=torch.int32, device=boxes.device)
+    _l.call("dm4d_detect_select_f32", _stream(), _p(boxes), _p(scores), _p(inv_scale), n, A, C, int(cat), float(score_thr), float(nms_thr),
+            int(max_per_img), _p(counts), _p(out), _p(idx))
+    return counts, out, idx
 
 
 def matting_input(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int,

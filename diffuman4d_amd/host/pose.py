@@ -13,6 +13,9 @@ any callable (``pose_model``).  Everything around it runs on the device (csrc/po
   * ``decode_heatmaps``: one launch takes the heatmaps, which never visit the host, to refined keypoints (UDP / DARK decoding); the
     last two linear maps to image pixels are done on the host in fp64, as the reference's numpy does.
 
+A batch is staged once (``stage_batch``) for every reader of its planes: ``pose_inputs_staged`` here and, on the detector route of
+``predict_keypoints``, ``detect.detector_inputs_staged`` (host/detect.py: the person boxes of a detector the caller names).
+
 There is no CPU path: a ``device`` that is not a HIP device is an error.
 """
 from __future__ import annotations
@@ -21,7 +24,7 @@ import json
 import os
 from concurrent.futures import ThreadPoolExecutor
 from glob import glob
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -165,6 +168,29 @@ def _stage(ims, mks, sizes, device: torch.device, pool: Optional[ThreadPoolExecu
     return blob, host, image_off, mask_off
 
 
+class Staged(NamedTuple):
+    """One batch on the device: what ``pose_inputs`` and ``detect.detector_inputs`` both read.  `host`, the pinned source of the upload,
+    has to stay alive until a consumer has synchronised."""
+    blob: torch.Tensor
+    host: torch.Tensor
+    image_off: List[int]
+    mask_off: List[int]
+    sizes: List[Tuple[int, int]]
+    device: torch.device
+
+
+def stage_batch(images, fmasks, device, pool: Optional[ThreadPoolExecutor] = None, device_decode: bool = False, what: str = "stage_batch",
+                check: Optional[Callable] = None) -> Staged:
+    """Open, decode and upload a batch once (``_open_all`` + ``_stage``) for every consumer of its planes.  check(sizes): a consumer's
+    refusal of the sizes [(h, w)], called once the files are open and before the device is touched."""
+    ims, mks, sizes = _open_all(list(images), None if fmasks is None else list(fmasks), pool)
+    if check is not None:
+        check(sizes)
+    dev = _l.hip_device(device, what)
+    with torch.cuda.device(dev):
+        return Staged(*_stage(ims, mks, sizes, dev, pool, device_decode), sizes, dev)
+
+
 def _mask_boxes(blob: torch.Tensor, sizes, image_off, mask_off) -> np.ndarray:
     n = len(sizes)
     meta, meta_host, _, _, desc_off = _st.pack_meta(None, descriptors([(k, 0) for k in range(n)], sizes, image_off, mask_off), blob.device)
@@ -218,7 +244,16 @@ def pose_inputs(images, fmasks=None, bboxes=None, shape: Tuple[int, int] = (1024
         raise ValueError('bbox_source="fmask" needs a mask for every image')
     dev = _l.hip_device(device, "pose_inputs")
     with torch.cuda.device(dev):
-        blob, _host, image_off, mask_off = _stage(ims, mks, sizes, dev, pool, device_decode)
+        return pose_inputs_staged(Staged(*_stage(ims, mks, sizes, dev, pool, device_decode), sizes, dev), bboxes, (H, W), bbox_source)
+
+
+def pose_inputs_staged(staged: Staged, bboxes, shape: Tuple[int, int], bbox_source: str = "image") -> Tuple[torch.Tensor, np.ndarray, np.ndarray]:
+    """``pose_inputs`` for a batch that is already on the device (``stage_batch``): the same result, nothing decoded or uploaded again.
+    `bboxes` has been checked against the batch by the caller."""
+    H, W = int(shape[0]), int(shape[1])
+    blob, _host, image_off, mask_off, sizes, dev = staged
+    n = len(sizes)
+    with torch.cuda.device(dev):
         if bboxes is None:
             boxes = _mask_boxes(blob, sizes, image_off, mask_off)[:, None, :] if bbox_source == "fmask" else [[[0, 0, w, h]] for h, w in sizes]
         else:
@@ -317,21 +352,31 @@ def write_instances(path: str, keypoints: np.ndarray, scores: np.ndarray) -> Non
 def predict_keypoints(images_dir: str, out_kp2d_dir: str, fmasks_dir: Optional[str] = None, sapiens_ckpt_path: Optional[str] = None,
                       detector_ckpt_path: Optional[str] = None, gpu_ids: Optional[Sequence[int]] = None, num_workers: int = 4, *,
                       pose_model: Optional[Callable] = None, shape: Tuple[int, int] = (1024, 768), heatmap_scale: int = 4,
-                      batch_size: int = 4, skip_exists: bool = True, bbox_source: str = "image", device_decode: bool = False) -> dict:
+                      batch_size: int = 4, skip_exists: bool = True, bbox_source: str = "image", device_decode: bool = False,
+                      person_detector=None, det_shape: Tuple[int, int] = (640, 640), det_cat_id: int = 0, bbox_thr: float = 0.3,
+                      nms_thr: float = 0.3) -> dict:
     """Predict the 2-D keypoints of every image under `images_dir` and write ``out_kp2d_dir/{camera}/{frame}.json``.
 
     pose_model: any callable taking fp32 [n, 3, H, W] on the device and returning [n, K, H / heatmap_scale, W / heatmap_scale] on the
     device; by default ``load_pose_model(sapiens_ckpt_path)``, once per GPU (which must then accept fp32 input; see there).  It is the
-    caller's network: its output never visits the host.  A ``detector_ckpt_path`` is refused (the reference's RTMDet detector needs mmdet, which this package does not carry): the box
-    is the whole image, or the box of the foreground mask with ``bbox_source="fmask"``.  The reference's ``flip`` is not taken (it
-    averages the flipped pass without flipping it back).  One worker thread per GPU id; decoding and the
+    caller's network: its output never visits the host.
+
+    The person boxes (bbox_source): "image", the whole image; "fmask", the box of the foreground mask; "detector", the reference's
+    route: `person_detector` -- a callable (``detect.load_person_detector`` says what it takes and returns) or the path of a local
+    TorchScript file, loaded once per GPU -- runs on every image, and every kept box (``detect.select_boxes`` with `det_cat_id`,
+    `bbox_thr`, `nms_thr`; `det_shape` is the detector's input) becomes a row of the pose network and an entry of the image's
+    ``instance_info``, best first; an image without a kept box gets the whole image (vis_pose.py:438-440).  A batch is staged once: the
+    detector's input and the pose network's are two readers of the same planes.  "detector" without `person_detector` is refused, and
+    so is a ``detector_ckpt_path``: the reference's own detector checkpoint needs mmdet, which this package does not carry.  The
+    reference's ``flip`` is not taken (it averages the flipped pass without flipping it back).  One worker thread per GPU id; decoding and the
     JSON files go through a pool of `num_workers` threads.  Returns counts.  device_decode: handed to ``pose_inputs`` (the same files are
     written)."""
     if detector_ckpt_path:
         raise NotImplementedError("detector_ckpt_path: the person detector is mmdet's RTMDet, which diffuman4d_amd does not carry; "
-                                  'the box is the whole image, or bbox_source="fmask"')
-    if bbox_source not in ("image", "fmask"):
-        raise ValueError(f'bbox_source must be "image" or "fmask", got {bbox_source!r}')
+                                  'the box is the whole image, or bbox_source="fmask", or hand over a network of your own: '
+                                  'person_detector with bbox_source="detector"')
+    if bbox_source not in ("image", "fmask") and not (bbox_source == "detector" and person_detector is not None):
+        raise ValueError(f'bbox_source must be "image" or "fmask", or "detector" together with person_detector, got {bbox_source!r}')
     if bbox_source == "fmask" and (fmasks_dir is None or fmasks_dir == "None"):
         raise ValueError('bbox_source="fmask" needs fmasks_dir')
     if pose_model is None and not sapiens_ckpt_path:
@@ -348,18 +393,45 @@ def predict_keypoints(images_dir: str, out_kp2d_dir: str, fmasks_dir: Optional[s
     batches = [todo[i: i + batch_size] for i in range(0, len(todo), batch_size)]
     hm_size = (int(W / heatmap_scale), int(H / heatmap_scale))
 
-    def process_batch(model: Callable, batch: List[int], dev: torch.device, pool: ThreadPoolExecutor) -> List:
-        x, centers, scales = pose_inputs([images[k] for k in batch], None if fmasks is None else [fmasks[k] for k in batch], None,
-                                         (H, W), dev, bbox_source=bbox_source, pool=pool, **({"device_decode": True} if device_decode else {}))
-        heat = model(x)
-        if not isinstance(heat, torch.Tensor) or heat.device.type != "cuda" or heat.dim() != 4 or heat.shape[0] != x.shape[0]:
+    def check_heat(heat, rows: int) -> None:
+        if not isinstance(heat, torch.Tensor) or heat.device.type != "cuda" or heat.dim() != 4 or heat.shape[0] != rows:
             raise _l.Dm4dError("pose_model: expected a [n, K, Hh, Wh] tensor on the device")
         if (heat.shape[3], heat.shape[2]) != hm_size:
             raise _l.Dm4dError(f"pose_model: heatmaps of {heat.shape[3]} x {heat.shape[2]}, expected {hm_size[0]} x {hm_size[1]} "
                                f"(input {W} x {H}, heatmap_scale {heatmap_scale})")
+
+    def process_batch(model: Callable, batch: List[int], dev: torch.device, pool: ThreadPoolExecutor) -> List:
+        x, centers, scales = pose_inputs([images[k] for k in batch], None if fmasks is None else [fmasks[k] for k in batch], None,
+                                         (H, W), dev, bbox_source=bbox_source, pool=pool, **({"device_decode": True} if device_decode else {}))
+        heat = model(x)
+        check_heat(heat, x.shape[0])
         kp, sc = decode_heatmaps(heat, (W, H), centers, scales)
         return [pool.submit(write_instances, outs[k], kp[r: r + 1], sc[r: r + 1]) for r, k in enumerate(batch)]  # one box per image here
 
+    def process_batch_detector(models, batch: List[int], dev: torch.device, pool: ThreadPoolExecutor) -> List:
+        from . import detect  # here, not at the top: detect imports this module
+        model, detector = models
+        staged = stage_batch([images[k] for k in batch], None if fmasks is None else [fmasks[k] for k in batch], dev, pool, device_decode,
+                             "predict_keypoints", lambda sizes: detect.detector_tables(sizes, det_shape))
+        xd, meta = detect.detector_inputs_staged(staged, det_shape)
+        found = detector(xd)
+        if not isinstance(found, (tuple, list)) or len(found) != 2:
+            raise _l.Dm4dError("person_detector: expected (boxes [n, A, 4], scores [n, A, C]) on the device")
+        kept, _ = detect.select_boxes(found[0], found[1], meta, det_cat_id=det_cat_id, bbox_thr=bbox_thr, nms_thr=nms_thr)
+        boxes = [list(b) if len(b) else None for b in kept]  # None: the whole image
+        x, centers, scales = pose_inputs_staged(staged, boxes, (H, W))
+        heats = []
+        for r in range(0, x.shape[0], batch_size):
+            heats.append(model(x[r: r + batch_size]))
+            check_heat(heats[-1], min(batch_size, x.shape[0] - r))
+        kp, sc = decode_heatmaps(torch.cat(heats), (W, H), centers, scales)
+        first = np.concatenate([[0], np.cumsum([max(len(b), 1) for b in kept])])
+        return [pool.submit(write_instances, outs[k], kp[first[i]: first[i + 1]], sc[first[i]: first[i + 1]]) for i, k in enumerate(batch)]
+
     load_model = lambda dev: pose_model if pose_model is not None else load_pose_model(sapiens_ckpt_path, dev)
+    if bbox_source == "detector":
+        from . import detect
+        load_detector = lambda dev: detect.load_person_detector(person_detector, dev) if isinstance(person_detector, (str, os.PathLike)) else person_detector
+        load_model, process_batch = (lambda dev, pose_net=load_model: (pose_net(dev), load_detector(dev))), process_batch_detector
     result["written"] = _st.run_stage("predict_keypoints", gpu_ids, num_workers, "dm4d-pose", batches, load_model, process_batch)
     return result

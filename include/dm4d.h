@@ -502,6 +502,45 @@ int dm4d_pose_mask_box_u8(void* stream, const void* staging, int64_t staging_byt
                           int32_t* boxes);
 int dm4d_pose_udp_decode_f32(void* stream, const float* heatmaps, int n, int K, int Hh, int Wh, float* scores, float* locs);
 
+/* Person boxes around a caller-named detector (detect.hip, diffuman4d_amd/host/detect.py; the reference's detector step of
+ *   predict_keypoints: scripts/preprocess/sapiens/lite/demo/vis_pose.py:425-440, detector_utils.py process_one_image_bbox, pose_utils.py
+ *   nms).  The network itself is the caller's; these are the steps on either side of it.  tests/detect_model.py is the definition in
+ *   numpy and DESIGN.md "Person boxes" its text.  No global atomics, no float atomics, no workgroup waits on another; an image's result
+ *   is a function of its own descriptor, table, planes and rows: independent of the batch, bitwise repeatable.
+ *
+ * dm4d_detect_input_u8_f32: the detector's input for n staged images of different sizes in one launch -> out [n, 3, H, W] fp32.
+ *   staging / desc (n x DM4D_POSE_FIELDS) / desc_host / tab_host as for dm4d_pose_input_u8_f32, with every plane offset 16-byte aligned
+ *   and field 4 the offset of the image's resize table in tab, in int32 elements.  The table = {nw, nh | xofs[nw] | yofs[nh] | alpha[nw]
+ *   | beta[nh]}: the size nw x nh (1..W x 1..H) of the keep-ratio resized image in the canvas' top-left corner; the first source column /
+ *   row of every output column / row (0..w - 1, 0..h - 1); and per column / row the two int16 weights c0 | c1 << 16 (each 0..2048) of the
+ *   taps s and min(s + 1, last).  A tap is the composited pixel MULDIV255(p, m) (p itself without a mask).  Horizontal pass in int32:
+ *   S = t[s] c0 + t[s + 1] c1 per row; vertical: v = (((b0 (S0 >> 4)) >> 16) + ((b1 (S1 >> 4)) >> 16) + 2) >> 2.  Integers only up to
+ *   here: a rule modelled on OpenCV's 8-bit INTER_LINEAR resize, not a copy of its code paths.  Outside nw x nh, v = pad_value (0..255).
+ *   out plane c = (float(v of channel c, or of channel 2 - c with bgr != 0) - mean[c]) / std[c], each operation rounded to fp32 on its
+ *   own; norm_host = {mean[3] | std[3]} fp32 on the host.  A workgroup owns a 64 x 4 tile of the canvas.
+ * dm4d_detect_select_f32: dense detector output -> kept boxes, one workgroup per image.  boxes [n, A, 4] fp32 (x1, y1, x2, y2 in
+ *   network-input pixels), scores [n, A, C] fp32, inv_scale [n, 2] fp32 = {inv_w, inv_h}, all on the device, contiguous; 1 <= A <=
+ *   DM4D_DETECT_MAX_ANCHORS, 1 <= C <= DM4D_DETECT_MAX_CLASSES, 0 <= cat < C, 1 <= max_per_img <= DM4D_DETECT_MAX_KEEP, thresholds finite.
+ *   (1) candidates: scores[a, cat] > score_thr (NaN never passes); (2) image box = (x1 inv_w, y1 inv_h, x2 inv_w, y2 inv_h), one fp32
+ *   multiply each; a candidate whose image box is not finite or has x2 <= x1 or y2 <= y1 is dropped; (3) the rest ordered by score
+ *   descending (-0 counts as +0), then anchor index ascending; the first max_per_img stay; (4) greedy NMS in that order in fp32, every
+ *   operation rounded on its own: area = (x2 - x1 + 1)(y2 - y1 + 1), w = max(0, min(x2) - max(x1) + 1), h likewise, ovr = w h / (area_i
+ *   + area_j - w h) by IEEE division; a later box survives iff ovr <= nms_thr (a NaN ovr does not).  Out: counts [n, 3] int32 = {kept,
+ *   dropped in (2), candidates of (1)}; out_boxes [n, max_per_img, 5] fp32 = x1, y1, x2, y2, score in kept order, zeros behind `kept`;
+ *   out_idx [n, max_per_img] int32 anchor indices, -1 behind `kept`.  The selection is exact whatever the number of candidates: a radix
+ *   select (8 bits a pass, LDS histograms with integer LDS atomics) over the unique 64-bit keys {ordered score bits << 32 | ~index}, run
+ *   only when more than max_per_img candidates remain, then a bitonic sort of at most DM4D_DETECT_MAX_KEEP keys.                     */
+#define DM4D_DETECT_MAX_ANCHORS (1 << 20)
+#define DM4D_DETECT_MAX_CLASSES 4096
+#define DM4D_DETECT_MAX_KEEP 256
+#define DM4D_DETECT_MAX_CANVAS 4096
+#define DM4D_DETECT_COEF_ONE 2048 /* the sum of a tap pair's weights */
+int dm4d_detect_input_u8_f32(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host, const int64_t* desc_dev,
+                             int n, const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len, const float* norm_host, float* out,
+                             int H, int W, int pad_value, int bgr);
+int dm4d_detect_select_f32(void* stream, const float* boxes, const float* scores, const float* inv_scale, int n, int A, int C, int cat,
+                           float score_thr, float nms_thr, int max_per_img, int32_t* counts, float* out_boxes, int32_t* out_idx);
+
 /* Foreground-mask prediction around a caller-named matting network (matting.hip, diffuman4d_amd/host/matting.py::remove_background; the
  *   reference's remove_background stage, scripts/preprocess/remove_background.py:15-22 and :36-93).  The network itself is the caller's;
  *   these are the steps on either side of it.  Integer arithmetic apart from the table lookups; no atomics, no workgroup waits on

@@ -3,7 +3,8 @@
 package's native stage, with the reference's action names, default order and default sub-directories of ``--data_dir``.
 
   python tools/preprocess.py --data_dir DATA/SCENE [--actions remove_background,carve_vhull,...] \\
-      --matting_model_dir CKPT/BiRefNet --sapiens_ckpt_path CKPT/sapiens_..._torchscript.pt2 --palette palette.json
+      --matting_model_dir CKPT/BiRefNet --sapiens_ckpt_path CKPT/sapiens_..._torchscript.pt2 --palette palette.json \\
+      [--person_detector CKPT/rtmdet_dense.pt --bbox_source detector [--bbox_thr 0.3 --nms_thr 0.3 --det_shape 640,640]]
 
   remove_background      images/ -> fmasks/                                   (tools/remove_background.py; needs --matting_model_dir)
   carve_vhull            fmasks/ + transforms.json -> surfs/, and surfs/000000.ply is copied to sparse_pcd.ply (tools/carve_visual_hull.py)
@@ -68,8 +69,10 @@ def parse_actions(text) -> list:
 
 
 def run(data_dir: str, actions, *, matting_model_dir=None, sapiens_ckpt_path=None, palette=None, batch_size: int = 8,
-        device_png: bool = False, device_decode: bool = False) -> list:
-    """Run `actions` on the scene under `data_dir` (preprocess.sh:31-77) -> [(action, what its stage returned)]."""
+        device_png: bool = False, device_decode: bool = False, person_detector=None, bbox_source=None, bbox_thr=None, nms_thr=None,
+        det_shape=None) -> list:
+    """Run `actions` on the scene under `data_dir` (preprocess.sh:31-77) -> [(action, what its stage returned)].  person_detector,
+    bbox_source, bbox_thr, nms_thr, det_shape: handed to predict_keypoints when given."""
     d = str(data_dir)
     out = []
     for act in actions:
@@ -82,7 +85,10 @@ def run(data_dir: str, actions, *, matting_model_dir=None, sapiens_ckpt_path=Non
             res = STAGES[act](f"{d}/fmasks", f"{d}/transforms.json", f"{d}/surfs", **({"device_decode": True} if device_decode else {}))
             shutil.copyfile(f"{d}/surfs/000000.ply", f"{d}/sparse_pcd.ply")
         elif act == "predict_keypoints":
-            res = STAGES[act](f"{d}/images", f"{d}/poses_sapiens", f"{d}/fmasks", sapiens_ckpt_path, **({"device_decode": True} if device_decode else {}))
+            extra = {"device_decode": True} if device_decode else {}
+            extra.update({k: v for k, v in (("person_detector", person_detector), ("bbox_source", bbox_source), ("bbox_thr", bbox_thr),
+                                            ("nms_thr", nms_thr), ("det_shape", det_shape)) if v is not None})
+            res = STAGES[act](f"{d}/images", f"{d}/poses_sapiens", f"{d}/fmasks", sapiens_ckpt_path, **extra)
         elif act == "triangulate_skeleton":
             res = STAGES[act](f"{d}/transforms.json", f"{d}/poses_sapiens", f"{d}/poses_3d", out_pcd_dir=f"{d}/poses_pcd",
                               out_kp2d_proj_dir=f"{d}/poses_2d")
@@ -98,6 +104,12 @@ def main(argv=None) -> int:
     ap.add_argument("--actions", default=None, help=f"comma-separated, run in the given order (default: {','.join(ALL_ACTIONS)})")
     ap.add_argument("--matting_model_dir", default=None, help="remove_background: the matting network, a local directory")
     ap.add_argument("--sapiens_ckpt_path", default=None, help="predict_keypoints: the pose checkpoint, a local file")
+    ap.add_argument("--person_detector", default=None, help="predict_keypoints: a person detector, a local TorchScript file; with --bbox_source detector")
+    ap.add_argument("--bbox_source", choices=("image", "fmask", "detector"), default=None, help="predict_keypoints: where the person boxes come from (default: the whole image)")
+    ap.add_argument("--bbox_thr", type=float, default=None, help="predict_keypoints with a detector: score threshold (default 0.3)")
+    ap.add_argument("--nms_thr", type=float, default=None, help="predict_keypoints with a detector: NMS overlap threshold (default 0.3)")
+    ap.add_argument("--det_shape", type=lambda t: tuple(int(p) for p in t.strip("()[] ").split(",")), default=None,
+                    help="predict_keypoints with a detector: its input height,width (default 640,640)")
     ap.add_argument("--palette", default=None, help="draw_skeleton: JSON file with keypoint_colors, links and x_link_color")
     ap.add_argument("--batch_size", type=int, default=8, help="remove_background: images per batch (decrease it if memory runs out)")
     ap.add_argument("--device_png", action="store_true", help="remove_background: encode the mask PNG files on the GPU (same pixels, other bytes)")
@@ -110,10 +122,14 @@ def main(argv=None) -> int:
     for act, flag in (("remove_background", "matting_model_dir"), ("predict_keypoints", "sapiens_ckpt_path"), ("draw_skeleton", "palette")):
         if act in actions and not getattr(args, flag):
             ap.error(f"{act} needs --{flag}")
+    if "predict_keypoints" in actions and (args.bbox_source == "detector") != bool(args.person_detector):
+        ap.error("--bbox_source detector and --person_detector go together")
     if not os.path.isdir(args.data_dir):
         ap.error(f"--data_dir {args.data_dir!r} is not a directory")
     for act, res in run(args.data_dir, actions, matting_model_dir=args.matting_model_dir, sapiens_ckpt_path=args.sapiens_ckpt_path,
-                        palette=args.palette, batch_size=args.batch_size, device_png=args.device_png, device_decode=args.device_decode):
+                        palette=args.palette, batch_size=args.batch_size, device_png=args.device_png, device_decode=args.device_decode,
+                        person_detector=args.person_detector, bbox_source=args.bbox_source, bbox_thr=args.bbox_thr, nms_thr=args.nms_thr,
+                        det_shape=args.det_shape):
         print(json.dumps({"action": act, "result": res}, default=str))
     return 0
 

@@ -25,10 +25,12 @@ SOURCES = ["api.hip", "gemm.hip", "gemm_h16.hip", "ff_fused.hip", "conv_direct.h
 # rectify.hip: the undistortion, the bilinear taps and the area sums are the fp32 operations of tests/rectify_model.py one by one
 # detect.hip: the detector input's (v - mean) / std and the NMS's areas and overlaps are the fp32 operations of tests/detect_model.py
 # one by one
+# skeleton.hip: the plan kernel's fp64 scaling (u * ratio, then + offset) and fp32 colour dimming are NumPy's operations one by one, and
+# it shares triang.hip's projection (project_common.h); the rasteriser is integer arithmetic and is not affected
 EXTRA_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "capture.hip": ["-ffp-contract=off"],
                "metrics.hip": ["-ffp-contract=off"], "lpips.hip": ["-ffp-contract=off"], "vhull.hip": ["-ffp-contract=off"],
                "triang.hip": ["-ffp-contract=off"], "pose.hip": ["-ffp-contract=off"], "rectify.hip": ["-ffp-contract=off"],
-               "detect.hip": ["-ffp-contract=off"]}
+               "detect.hip": ["-ffp-contract=off"], "skeleton.hip": ["-ffp-contract=off"]}
 # sources that #include another .hip source (gemm_h16.hip = the PAR = 2 instantiations of gemm.hip's kernels)
 EXTRA_DEPS = {"gemm_h16.hip": ["gemm.hip"]}
 

@@ -14,12 +14,19 @@
 //
 // A tile with an empty list stores zeros and skips the passes (most of a map is black).  The result is a function of the frame's own
 // list only: no atomics, nothing depends on the order of blocks, on the batch or on the tile size.  Integer arithmetic throughout.
+//
+// The list comes either from the host (dm4d_skeleton_draw_u8: records and offsets validated there) or from a plan made on the device
+// (dm4d_skeleton_draw_planned_u8: a fixed stride per frame, the count clamped in the kernel); the plan kernel, which projects a scene's
+// 3-D keypoints and does host/skeleton.py plan_draw_calls' arithmetic in fp64 / fp32, is at the end of this file.
+#include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "common.h"
 #include "dm4d.h"
 #include "errors.h"
 #include "image_common.h"
+#include "project_common.h"
 
 namespace {
 
@@ -66,7 +73,7 @@ __host__ __device__ inline size_t lds_bytes(int T, int cap, int fh, int fw) {
 template <int T>
 __global__ void __launch_bounds__(kThreads) skeleton_draw_kernel(const int32_t* __restrict__ prims, const int32_t* __restrict__ offsets,
                                                                  const int32_t* __restrict__ htab, int hk, const int32_t* __restrict__ vtab,
-                                                                 int vk, int h, int w, int cap, int fh_max, int fw_max,
+                                                                 int vk, int h, int w, int cap, int fh_max, int fw_max, int stride,
                                                                  uint8_t* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   int32_t* s_list = reinterpret_cast<int32_t*>(smem);                      // [cap][DM4D_SKEL_FIELDS]
@@ -86,8 +93,10 @@ __global__ void __launch_bounds__(kThreads) skeleton_draw_kernel(const int32_t* 
   const int fy0 = vtab[2 * oy0], fy1 = vtab[2 * (oy0 + nrows - 1)] + vtab[2 * (oy0 + nrows - 1) + 1];
   const int fw = fx1 - fx0, fh = fy1 - fy0;
 
-  // cull, keeping the order
-  const int p0 = offsets[f], np = offsets[f + 1] - p0;
+  // cull, keeping the order.  The two front ends differ here only: stride == 0: frame f owns records offsets[f] .. offsets[f + 1] - 1
+  // (validated on the host); stride > 0 (a device plan): records f * stride .. + offsets[f] - 1, the count clamped to the stride
+  const int p0 = stride ? f * stride : offsets[f];
+  const int np = stride ? min(max(offsets[f], 0), stride) : offsets[f + 1] - p0;
   int n = 0;
   for (int base = 0; base < np; base += kThreads) {
     const int i = base + tid;
@@ -190,11 +199,50 @@ int max_extent(const int32_t* tab, int n, int T) {
 
 template <int T>
 int launch(hipStream_t stream, const int32_t* prims, const int32_t* offsets, int n_frames, const int32_t* htab, int hk, const int32_t* vtab,
-           int vk, int h, int w, int cap, int fh, int fw, uint8_t* out) {
+           int vk, int h, int w, int cap, int fh, int fw, int stride, uint8_t* out) {
   const dim3 grid((unsigned)((w + T - 1) / T), (unsigned)((h + T - 1) / T), (unsigned)n_frames);
   hipLaunchKernelGGL(skeleton_draw_kernel<T>, grid, dim3(kThreads), lds_bytes(T, cap, fh, fw), stream, prims, offsets, htab, hk, vtab, vk, h,
-                     w, cap, fh, fw, out);
+                     w, cap, fh, fw, stride, out);
   return dm4d_check_launch("skeleton_draw_kernel");
+}
+
+// what both draw entries know on the host: shapes and alignment, then (after an entry's own checks) tables and windows
+int draw_error(const char* who, const char* what) {
+  static thread_local char msg[256];
+  snprintf(msg, sizeof(msg), "%s: %s", who, what);
+  return dm4d_set_error(DM4D_ERR_ARG, msg);
+}
+
+int check_draw_shapes(const char* who, const void* prims_dev, const void* counts_dev, int n_frames, const void* htab_dev, int hk,
+                      const void* vtab_dev, int vk, int H, int W, int h, int w) {
+  if (n_frames <= 0 || n_frames > 65535 || H <= 0 || W <= 0 || H > kMaxCanvas || W > kMaxCanvas || h <= 0 || w <= 0 || h > (1 << 15) ||
+      w > (1 << 15) || hk < 1 || vk < 1 || hk > kMaxTaps || vk > kMaxTaps)
+    return draw_error(who, "empty or oversized shape");
+  if (((uintptr_t)prims_dev & 15) || ((uintptr_t)counts_dev & 3) || ((uintptr_t)htab_dev & 3) || ((uintptr_t)vtab_dev & 3))
+    return draw_error(who, "the records must be 16-byte aligned, offsets and tables 4-byte aligned");
+  return 0;
+}
+
+int check_draw_tables(const char* who, const int32_t* htab_host, int hk, const int32_t* vtab_host, int vk, int H, int W, int h, int w) {
+  if (!pillow_table_ok(htab_host, (int64_t)w * (2 + hk), 0, hk, kMaxTaps, w, W, true) ||
+      !pillow_table_ok(vtab_host, (int64_t)h * (2 + vk), 0, vk, kMaxTaps, h, H, true))
+    return draw_error(who, "a coefficient table's windows leave the canvas, exceed ksize or are not ordered");
+  return 0;
+}
+
+// the largest tile whose footprint fits in LDS beside a list of `cap` records; stride as skeleton_draw_kernel takes it
+int launch_draw(const char* who, void* stream, const int32_t* prims_dev, const int32_t* counts_dev, int n_frames, int cap, int stride,
+                const int32_t* htab_host, const int32_t* htab_dev, int hk, const int32_t* vtab_host, const int32_t* vtab_dev, int vk, int h,
+                int w, uint8_t* out) {
+  const hipStream_t s = (hipStream_t)stream;
+  for (int T : {32, 16, 8}) {
+    const int fw = max_extent(htab_host, w, T), fh = max_extent(vtab_host, h, T);
+    if (lds_bytes(T, cap, fh, fw) > (size_t)kLdsLimit || (w + T - 1) / T > 65535 || (h + T - 1) / T > 65535) continue;
+    if (T == 32) return launch<32>(s, prims_dev, counts_dev, n_frames, htab_dev, hk, vtab_dev, vk, h, w, cap, fh, fw, stride, out);
+    if (T == 16) return launch<16>(s, prims_dev, counts_dev, n_frames, htab_dev, hk, vtab_dev, vk, h, w, cap, fh, fw, stride, out);
+    return launch<8>(s, prims_dev, counts_dev, n_frames, htab_dev, hk, vtab_dev, vk, h, w, cap, fh, fw, stride, out);
+  }
+  return draw_error(who, "the canvas is too large for the output: an 8 x 8 tile's footprint does not fit in LDS");
 }
 
 }  // namespace
@@ -204,11 +252,7 @@ extern "C" int dm4d_skeleton_draw_u8(void* stream, const int32_t* prims_host, co
                                      const int32_t* vtab_host, const int32_t* vtab_dev, int vk, int H, int W, int h, int w, uint8_t* out) {
   if (!prims_host || !prims_dev || !offsets_host || !offsets_dev || !htab_host || !htab_dev || !vtab_host || !vtab_dev || !out)
     return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: null pointer");
-  if (n_frames <= 0 || n_frames > 65535 || H <= 0 || W <= 0 || H > kMaxCanvas || W > kMaxCanvas || h <= 0 || w <= 0 || h > (1 << 15) ||
-      w > (1 << 15) || hk < 1 || vk < 1 || hk > kMaxTaps || vk > kMaxTaps)
-    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: empty or oversized shape");
-  if (((uintptr_t)prims_dev & 15) || ((uintptr_t)offsets_dev & 3) || ((uintptr_t)htab_dev & 3) || ((uintptr_t)vtab_dev & 3))
-    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: the records must be 16-byte aligned, offsets and tables 4-byte aligned");
+  if (const int rc = check_draw_shapes("skeleton_draw", prims_dev, offsets_dev, n_frames, htab_dev, hk, vtab_dev, vk, H, W, h, w)) return rc;
   if (offsets_host[0] != 0) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: offsets[0] must be 0");
   int cap = 1;
   for (int f = 0; f < n_frames; ++f) {
@@ -227,18 +271,22 @@ extern "C" int dm4d_skeleton_draw_u8(void* stream, const int32_t* prims_host, co
       return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a thickness below 1, a negative radius, or a size above DM4D_SKEL_MAX_SIZE");
     if ((uint32_t)p[P_COLOR] >> 24) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a colour has bits above r | g << 8 | b << 16");
   }
-  if (!pillow_table_ok(htab_host, (int64_t)w * (2 + hk), 0, hk, kMaxTaps, w, W, true) ||
-      !pillow_table_ok(vtab_host, (int64_t)h * (2 + vk), 0, vk, kMaxTaps, h, H, true))
-    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: a coefficient table's windows leave the canvas, exceed ksize or are not ordered");
-  const hipStream_t s = (hipStream_t)stream;
-  for (int T : {32, 16, 8}) {
-    const int fw = max_extent(htab_host, w, T), fh = max_extent(vtab_host, h, T);
-    if (lds_bytes(T, cap, fh, fw) > (size_t)kLdsLimit || (w + T - 1) / T > 65535 || (h + T - 1) / T > 65535) continue;
-    if (T == 32) return launch<32>(s, prims_dev, offsets_dev, n_frames, htab_dev, hk, vtab_dev, vk, h, w, cap, fh, fw, out);
-    if (T == 16) return launch<16>(s, prims_dev, offsets_dev, n_frames, htab_dev, hk, vtab_dev, vk, h, w, cap, fh, fw, out);
-    return launch<8>(s, prims_dev, offsets_dev, n_frames, htab_dev, hk, vtab_dev, vk, h, w, cap, fh, fw, out);
-  }
-  return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw: the canvas is too large for the output: an 8 x 8 tile's footprint does not fit in LDS");
+  if (const int rc = check_draw_tables("skeleton_draw", htab_host, hk, vtab_host, vk, H, W, h, w)) return rc;
+  return launch_draw("skeleton_draw", stream, prims_dev, offsets_dev, n_frames, cap, 0, htab_host, htab_dev, hk, vtab_host, vtab_dev, vk, h, w, out);
+}
+
+// the same rasteriser and reduction on a plan that dm4d_skeleton_plan_kp3d left on the device
+extern "C" int dm4d_skeleton_draw_planned_u8(void* stream, const int32_t* records, const int32_t* counts, int n_frames, int stride,
+                                             const int32_t* htab_host, const int32_t* htab_dev, int hk, const int32_t* vtab_host,
+                                             const int32_t* vtab_dev, int vk, int H, int W, int h, int w, uint8_t* out) {
+  if (!records || !counts || !htab_host || !htab_dev || !vtab_host || !vtab_dev || !out)
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw_planned: null pointer");
+  if (stride < 3 || stride > DM4D_SKEL_MAX_PRIMS || stride % 3)
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_draw_planned: stride must be 3 L, a multiple of 3 in 3 .. DM4D_SKEL_MAX_PRIMS");
+  if (const int rc = check_draw_shapes("skeleton_draw_planned", records, counts, n_frames, htab_dev, hk, vtab_dev, vk, H, W, h, w)) return rc;
+  if (const int rc = check_draw_tables("skeleton_draw_planned", htab_host, hk, vtab_host, vk, H, W, h, w)) return rc;
+  return launch_draw("skeleton_draw_planned", stream, records, counts, n_frames, stride, stride, htab_host, htab_dev, hk, vtab_host, vtab_dev, vk,
+                     h, w, out);
 }
 
 // Bounding box and box mask of drawn maps (crop_utils.py skeleton_to_mask on the maps above, for SpaTemDataset's has_gt_target=False
@@ -335,4 +383,200 @@ extern "C" int dm4d_skeleton_box_mask_u8(void* stream, const uint8_t* maps, int 
   hipLaunchKernelGGL(skeleton_box_fill_kernel, dim3(box_blocks((int64_t)h * w), n_frames), dim3(kBoxThreads), 0, s, (const int32_t*)boxes, h, w,
                      pad_top, pad_bottom, pad_x, masks, mask_stride);
   return dm4d_check_launch("skeleton_box_fill_kernel");
+}
+
+// A map's draw plan straight from poses_3d (host/skeleton.py plan_draw_calls on the poses_2d file that triangulate_skeleton would have
+// written for the map's frame and camera; DESIGN.md "Skeleton maps from poses_3d").  One wave = one workgroup = one map.
+//
+//   keypoints  lanes over the k keypoints: project_point (project_common.h, the function dm4d_project_points_f64 evaluates), u, v and
+//              depth rounded to fp32 (what reading the file into a float32 array does), score 0 where min(u, v) < 0, the scaling and
+//              centring in fp64 on the widened fp32 values, rint, the [COORD_MIN, COORD_MAX] test -> LDS.  Ballots tell whether any
+//              depth is non-zero and whether any score differs from 1 (over all keypoints, linked or not: the sort branch).
+//   links      lanes over the L links: line score, the keep / non-finite / dropped / no-colour decisions and the sort key -> LDS
+//   rank       a kept link's place is the number of kept links with a smaller key plus the number with an equal key earlier in the list
+//              (descending depth: the key is the negated mean depth): Python's stable sorted() without a sort; every lane counts over all
+//              L keys in LDS, so the result does not depend on any schedule.  The link writes its three records at 3 x rank.
+//
+// The slots past the map's count are zeroed: the whole output is a function of the map's own inputs.  Every loop runs to k or L.
+namespace {
+
+constexpr int kPlanThreads = 64;
+
+__host__ __device__ inline size_t plan_lds_bytes(int k, int L) { return (size_t)L * 12 + (size_t)k * 20; }
+
+// np.round(rgb * norm).astype(np.uint8) of one channel (norm lies in [0, 1] up to rounding; a NaN gives 0)
+__device__ __forceinline__ uint32_t dim_channel(float c, float norm) {
+  const float v = rintf(c * norm);
+  return v >= 255.0f ? 255u : v > 0.0f ? (uint32_t)v : 0u;
+}
+
+// dimmed() of host/skeleton.py: (clip(score, low, high) - low) / span in fp32, span = fp32(high - low) formed in fp64 on the host
+__device__ __forceinline__ uint32_t dimmed(const float* __restrict__ rgb, float score, float low, float high, float span) {
+  const float clipped = score != score ? score : fminf(fmaxf(score, low), high);
+  const float norm = (clipped - low) / span;
+  return dim_channel(rgb[0], norm) | (dim_channel(rgb[1], norm) << 8) | (dim_channel(rgb[2], norm) << 16);
+}
+
+// np.minimum: a NaN wins
+__device__ __forceinline__ float min_nan(float a, float b) { return a != a ? a : b != b ? b : fminf(a, b); }
+
+__device__ __forceinline__ void store_record(int32_t* dst, int kind, int x1, int y1, int x2, int y2, int size, uint32_t color) {
+  *reinterpret_cast<U4*>(dst) = U4{(uint32_t)kind, (uint32_t)x1, (uint32_t)y1, (uint32_t)x2};
+  *reinterpret_cast<U4*>(dst + 4) = U4{(uint32_t)y2, (uint32_t)size, color, 0u};
+}
+
+__global__ void __launch_bounds__(kPlanThreads) skeleton_plan_kp3d_kernel(
+    const double* __restrict__ kp3d, const double* __restrict__ K, const double* __restrict__ T, const int32_t* __restrict__ jobs,
+    const float* __restrict__ scores, const double* __restrict__ scale, const int32_t* __restrict__ sizes, const int32_t* __restrict__ links,
+    const float* __restrict__ colors, int k, int L, float low, float high, float span, int32_t* __restrict__ records,
+    int32_t* __restrict__ counts, int32_t* __restrict__ status) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  double* s_key = reinterpret_cast<double*>(smem);         // [L]
+  int32_t* s_keep = reinterpret_cast<int32_t*>(s_key + L); // [L]
+  int32_t* s_x = s_keep + L;                               // [k] rounded, 0 when out of range
+  int32_t* s_y = s_x + k;
+  float* s_score = reinterpret_cast<float*>(s_y + k);
+  float* s_depth = s_score + k;
+  int32_t* s_flag = reinterpret_cast<int32_t*>(s_depth + k);  // 1: finite on the canvas, 2: inside [COORD_MIN, COORD_MAX]
+
+  const int lane = threadIdx.x, map = blockIdx.x;
+  const int f = jobs[2 * map], cam = jobs[2 * map + 1];
+  const double ratio = scale[2 * map], offset = scale[2 * map + 1];
+  const int radius = sizes[2 * map], thickness = sizes[2 * map + 1];
+  const double* Kc = K + (int64_t)cam * 9;
+  const double* Tc = T + (int64_t)cam * 16;
+
+  bool any_depth = false, any_score = false;
+  for (int base = 0; base < k; base += kPlanThreads) {
+    const int i = base + lane;
+    if (i < k) {
+      const double* Xp = kp3d + ((int64_t)f * k + i) * 3;
+      const double X[3] = {Xp[0], Xp[1], Xp[2]};
+      double u, v, z;
+      project_point(Kc, Tc, X, u, v, z);
+      const float uf = (float)u, vf = (float)v, df = (float)z;
+      float s = scores ? scores[(int64_t)map * k + i] : 1.0f;
+      if (uf == uf && vf == vf && (uf < 0.0f || vf < 0.0f)) s = 0.0f;  // kpts.min(axis=1) < 0: a NaN makes the minimum NaN
+      const double xs = (double)uf * ratio + offset, ys = (double)vf * ratio + offset;
+      const double rx = rint(xs), ry = rint(ys);
+      int flag = 0;
+      if (isfinite(xs) && isfinite(ys)) flag |= 1;
+      if (rx >= DM4D_SKEL_COORD_MIN && rx <= DM4D_SKEL_COORD_MAX && ry >= DM4D_SKEL_COORD_MIN && ry <= DM4D_SKEL_COORD_MAX) flag |= 2;
+      s_x[i] = (flag & 2) ? (int)rx : 0;
+      s_y[i] = (flag & 2) ? (int)ry : 0;
+      s_score[i] = s;
+      s_depth[i] = df;
+      s_flag[i] = flag;
+      any_depth |= df != 0.0f;
+      any_score |= s != 1.0f;
+    }
+  }
+  const bool by_depth = __ballot(any_depth) != 0;
+  const bool by_score = !by_depth && __ballot(any_score) != 0;
+  __syncthreads();
+
+  int n_keep = 0, dropped = 0, first_nocolor = L;
+  bool nonfinite = false;
+  for (int base = 0; base < L; base += kPlanThreads) {
+    const int l = base + lane;
+    bool keep = false;
+    if (l < L) {
+      const int i1 = links[l * DM4D_SKEL_LINK_FIELDS], i2 = links[l * DM4D_SKEL_LINK_FIELDS + 1];
+      const float line_score = min_nan(s_score[i1], s_score[i2]);
+      keep = !(line_score < low);
+      if (keep && !((s_flag[i1] & s_flag[i2]) & 1)) nonfinite = true;
+      const bool inside = ((s_flag[i1] & s_flag[i2]) & 2) != 0;
+      if (keep && !inside) ++dropped;
+      keep = keep && inside;
+      if (keep && (colors[i1 * 4 + 3] == 0.0f || colors[i2 * 4 + 3] == 0.0f) && l < first_nocolor) first_nocolor = l;
+      s_key[l] = by_depth ? -(((double)s_depth[i1] + (double)s_depth[i2]) / 2) : by_score ? (double)line_score : 0.0;
+      s_keep[l] = keep;
+    }
+    n_keep += __popcll(__ballot(keep));
+  }
+  __syncthreads();
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    dropped += __shfl_xor(dropped, off);
+    first_nocolor = min(first_nocolor, __shfl_xor(first_nocolor, off));
+  }
+  const bool any_nonfinite = __ballot(nonfinite) != 0;
+
+  int32_t* rec = records + (int64_t)map * 3 * L * DM4D_SKEL_FIELDS;
+  for (int base = 0; base < L; base += kPlanThreads) {
+    const int l = base + lane;
+    if (l < L && s_keep[l]) {
+      const double key = s_key[l];
+      int rank = 0;
+      for (int j = 0; j < L; ++j) {
+        const double kj = s_key[j];
+        if (s_keep[j] && (kj < key || (kj == key && j < l))) ++rank;
+      }
+      const int32_t* link = links + l * DM4D_SKEL_LINK_FIELDS;
+      const int i1 = link[0], i2 = link[1];
+      const float s1 = s_score[i1], s2 = s_score[i2];
+      int32_t* dst = rec + (int64_t)rank * 3 * DM4D_SKEL_FIELDS;
+      store_record(dst, DM4D_SKEL_LINE, s_x[i1], s_y[i1], s_x[i2], s_y[i2], thickness * link[4],
+                   dimmed(colors + (int64_t)(k + l) * 4, min_nan(s1, s2), low, high, span));
+      store_record(dst + DM4D_SKEL_FIELDS, DM4D_SKEL_CIRCLE, s_x[i1], s_y[i1], s_x[i1], s_y[i1], radius * link[3],
+                   dimmed(colors + i1 * 4, s1, low, high, span));
+      store_record(dst + 2 * DM4D_SKEL_FIELDS, DM4D_SKEL_CIRCLE, s_x[i2], s_y[i2], s_x[i2], s_y[i2], radius * link[3],
+                   dimmed(colors + i2 * 4, s2, low, high, span));
+    }
+  }
+  for (int slot = 3 * n_keep + lane; slot < 3 * L; slot += kPlanThreads) store_record(rec + (int64_t)slot * DM4D_SKEL_FIELDS, 0, 0, 0, 0, 0, 0, 0u);
+  if (lane == 0) {
+    counts[map] = 3 * n_keep;
+    const int nocolor = first_nocolor < L;
+    status[2 * map] = (any_nonfinite ? DM4D_SKEL_ST_NONFINITE : 0) | (nocolor ? DM4D_SKEL_ST_NOCOLOR | (first_nocolor << DM4D_SKEL_ST_LINK_SHIFT) : 0);
+    status[2 * map + 1] = dropped;
+  }
+}
+
+}  // namespace
+
+extern "C" int dm4d_skeleton_plan_kp3d(void* stream, const double* kp3d, const double* K, const double* T, int F, int m, int k,
+                                       const int32_t* jobs_host, const int32_t* jobs_dev, int n_maps, const float* scores,
+                                       const double* scale_host, const double* scale_dev, const int32_t* sizes_host, const int32_t* sizes_dev,
+                                       const int32_t* links_host, const int32_t* links_dev, int L, const float* colors_host,
+                                       const float* colors_dev, float low_thr, float high_thr, float thr_span, int32_t* records,
+                                       int32_t* counts, int32_t* status) {
+  if (!kp3d || !K || !T || !jobs_host || !jobs_dev || !scale_host || !scale_dev || !sizes_host || !sizes_dev || !links_host || !links_dev ||
+      !colors_host || !colors_dev || !records || !counts || !status)
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: null pointer");
+  if (F <= 0 || m <= 0 || k <= 0 || L <= 0 || n_maps <= 0 || n_maps > 65535 || k > DM4D_SKEL_MAX_KPTS)
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: empty shape, more than 65535 maps or more than DM4D_SKEL_MAX_KPTS keypoints");
+  if (3 * (int64_t)L > DM4D_SKEL_MAX_PRIMS)
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: 3 L records a map exceed DM4D_SKEL_MAX_PRIMS");
+  if ((((uintptr_t)kp3d | (uintptr_t)K | (uintptr_t)T | (uintptr_t)scale_dev) & 7) || ((uintptr_t)records & 15) ||
+      (((uintptr_t)jobs_dev | (uintptr_t)scores | (uintptr_t)sizes_dev | (uintptr_t)links_dev | (uintptr_t)colors_dev | (uintptr_t)counts |
+        (uintptr_t)status) & 3))
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: misaligned pointer (fp64 tensors 8 bytes, records 16, the others 4)");
+  if (!isfinite(low_thr) || !isfinite(high_thr) || !isfinite(thr_span) || !(thr_span > 0.0f))
+    return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: the thresholds must be finite with high_thr above low_thr");
+  for (int i = 0; i < n_maps; ++i) {
+    if (jobs_host[2 * i] < 0 || jobs_host[2 * i] >= F || jobs_host[2 * i + 1] < 0 || jobs_host[2 * i + 1] >= m)
+      return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: a job names a frame outside [0, F) or a camera outside [0, m)");
+    if (!isfinite(scale_host[2 * i]) || !isfinite(scale_host[2 * i + 1]))
+      return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: a map's scale ratio or offset is not finite");
+    if (sizes_host[2 * i] < 0 || sizes_host[2 * i] > DM4D_SKEL_MAX_SIZE / 2 || sizes_host[2 * i + 1] < 1 || sizes_host[2 * i + 1] > DM4D_SKEL_MAX_SIZE / 2)
+      return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: a thickness below 1, a negative radius, or a size above DM4D_SKEL_MAX_SIZE / 2");
+  }
+  for (int l = 0; l < L; ++l) {
+    const int32_t* q = links_host + (int64_t)l * DM4D_SKEL_LINK_FIELDS;
+    if (q[0] < 0 || q[0] >= k || q[1] < 0 || q[1] >= k) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: a link joins a keypoint outside [0, k)");
+    if (q[2] < 0 || q[2] >= L) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: a link id lies outside [0, L)");
+    if ((q[3] != 1 && q[3] != 2) || (q[4] != 1 && q[4] != 2))
+      return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: a link's radius or thickness multiplier is neither 1 nor 2");
+  }
+  for (int64_t i = 0; i < (int64_t)k + L; ++i) {
+    const float* c = colors_host + i * 4;
+    for (int j = 0; j < 3; ++j)
+      if (!(c[j] >= 0.0f && c[j] <= 255.0f)) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: a colour channel lies outside [0, 255]");
+    if (c[3] != 0.0f && c[3] != 1.0f) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: a has-colour flag is neither 0 nor 1");
+    if (i >= k && c[3] != 1.0f) return dm4d_set_error(DM4D_ERR_ARG, "skeleton_plan_kp3d: a link has no colour");
+  }
+  hipLaunchKernelGGL(skeleton_plan_kp3d_kernel, dim3((unsigned)n_maps), dim3(kPlanThreads), plan_lds_bytes(k, L), (hipStream_t)stream, kp3d, K, T,
+                     jobs_dev, scores, scale_dev, sizes_dev, links_dev, colors_dev, k, L, low_thr, high_thr, thr_span, records, counts, status);
+  return dm4d_check_launch("skeleton_plan_kp3d_kernel");
 }

@@ -30,6 +30,7 @@
 #include "common.h"
 #include "dm4d.h"
 #include "errors.h"
+#include "project_common.h"
 
 namespace {
 
@@ -64,17 +65,7 @@ struct View {
   double u, v, s;
 };
 
-__device__ __forceinline__ void projection(const double* __restrict__ K, const double* __restrict__ T, double* P) {
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) P[r * 4 + c] = fma(K[r * 3 + 2], T[8 + c], fma(K[r * 3 + 1], T[4 + c], K[r * 3] * T[c]));
-}
-
-// h_r = P[r] . (X, 1), accumulated in index order
-__device__ __forceinline__ double project_row(const double* p, const double* X) {
-  return fma(p[2], X[2], fma(p[1], X[1], p[0] * X[0])) + p[3];
-}
+// projection(), project_row() and project_point(): project_common.h, shared with the skeleton plan kernel
 
 // pr . (X, 1) - obs (p2 . (X, 1) + 1e-9) in double-double, rounded once at the end
 __device__ __forceinline__ double residual_numerator(const double* pr, const double* p2, double obs, const double* X) {
@@ -354,14 +345,8 @@ __global__ void __launch_bounds__(kThreads) project_kernel(const double* __restr
   const int64_t f = fm / m, cam = fm - f * m;
   const double* Xp = kp3d + (f * k + i) * 3;
   const double X[3] = {Xp[0], Xp[1], Xp[2]};
-  double u = kInvalid, v = kInvalid, z = kInvalid;
-  if (X[0] != kInvalid && X[1] != kInvalid && X[2] != kInvalid) {
-    double P[12];
-    projection(K + cam * 9, T + cam * 16, P);
-    z = project_row(P + 8, X);
-    u = project_row(P, X) / (z + 1e-9);
-    v = project_row(P + 4, X) / (z + 1e-9);
-  }
+  double u, v, z;
+  project_point(K + cam * 9, T + cam * 16, X, u, v, z);
   kp2d[idx * 2] = u, kp2d[idx * 2 + 1] = v;
   depth[idx] = z;
 }

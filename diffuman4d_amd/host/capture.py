@@ -16,6 +16,8 @@ Offsets, the pinned buffer, its filling and the table / descriptor pack are host
 ``skeleton_source="kp2d"`` (opt-in) reads no skeleton image: every frame's map is drawn on the device from its ``poses_2d`` keypoint
 file (host/skeleton.py, ``dm4d_skeleton_draw_u8``) straight into the device staging buffer, and for ``has_gt_target=False`` targets
 ``dm4d_skeleton_box_mask_u8`` derives the box mask and the bounding box there as well; only the boxes (16 bytes per frame) come back.
+``skeleton_source="kp3d"`` (opt-in) needs no ``poses_2d`` files either: the maps are projected from ``poses_3d`` into the scene's cameras,
+planned and drawn on the device (``dm4d_skeleton_plan_kp3d``, ``dm4d_skeleton_draw_planned_u8``); the rest is the "kp2d" route's code.
 
 ``device_decode=True`` (opt-in, either skeleton source) moves the decode of JPEG and PNG files to the device as well: the pool reads
 and probes the files (``_read``), host/jpegdec.py and host/pngdec.py decode them into the device staging buffer, and what the host
@@ -232,8 +234,9 @@ def _intrinsic(K: torch.Tensor, crop: List[int], height: int) -> torch.Tensor:
     return K
 
 
-SKELETON_SOURCES = ("files", "kp2d")
+SKELETON_SOURCES = ("files", "kp2d", "kp3d")
 KP2D_PATH_PAT = "{data_dir}/{scene_label}/poses_2d/{spa_label}/{tem_label}.json"
+KP3D_PATH_PAT = "{data_dir}/{scene_label}/poses_3d/{tem_label}.json"
 
 
 class SpaTemDataset:
@@ -249,6 +252,10 @@ class SpaTemDataset:
     [score_path], kp2d_canvas_shape or the camera's (height, width), (h, w), palette=palette)[0]`` with (h, w) the decoded image's size
     or, for a frame that loads none, the camera's.  No skeleton file is read and no map crosses PCIe.  The result equals the file
     route's on skeleton files that hold those maps losslessly; it differs from it on lossy files by exactly the codec's loss.
+    "kp3d" needs no ``poses_2d`` directory either: a task reads each distinct frame's ``kp3d_path_pat`` file (``poses_3d``) once, and
+    the maps are projected into the scene's cameras (``triang.scene_cameras``, uploaded once per scene), planned and drawn on the device
+    (``skeleton.plan_and_draw``); ``kp2d_score_path_pat``, ``kp2d_canvas_shape`` and ``palette`` as for "kp2d".  Sample and exceptions are
+    those of "kp2d" on the ``poses_2d`` files ``triang.triangulate_skeleton`` writes from the same poses and cameras.
 
     ``device_decode``: baseline JPEG and 8-bit PNG files (images, masks, skeleton files) are decoded on the device instead of by
     Pillow in the pool; needs a HIP device (Dm4dError otherwise).  ``get_item`` returns and raises what it does without the flag;
@@ -261,7 +268,8 @@ class SpaTemDataset:
                  scene_label: Optional[str] = None, height: int = 1024, width: int = 1024, has_gt_target: bool = True,
                  plucker: str = "host", device=None, decode_threads: int = 8, skeleton_source: str = "files",
                  kp2d_path_pat: str = KP2D_PATH_PAT, kp2d_score_path_pat: Optional[str] = None,
-                 kp2d_canvas_shape: Optional[Tuple[int, int]] = None, palette=None, device_decode: bool = False):
+                 kp2d_canvas_shape: Optional[Tuple[int, int]] = None, kp3d_path_pat: str = KP3D_PATH_PAT, palette=None,
+                 device_decode: bool = False):
         if plucker not in ("host", "cameras"):
             raise ValueError("plucker must be 'host' or 'cameras'")
         self.device_decode = bool(device_decode)
@@ -273,15 +281,20 @@ class SpaTemDataset:
             raise ValueError(f"skeleton_source must be one of {SKELETON_SOURCES}, got {skeleton_source!r}")
         self.skeleton_source, self.kp2d_path_pat, self.kp2d_score_path_pat = skeleton_source, kp2d_path_pat, kp2d_score_path_pat
         self.kp2d_canvas_shape = None if kp2d_canvas_shape is None else tuple(int(v) for v in kp2d_canvas_shape)
-        self.palette = None
-        if skeleton_source == "kp2d":
+        self.kp3d_path_pat = kp3d_path_pat
+        self.palette = self._plan_tables = None
+        self._drawn = skeleton_source in ("kp2d", "kp3d")  # the maps are drawn on the device; "kp3d": planned there as well
+        self._scene_cams: Dict = {}                         # "kp3d": (scene_label, device) -> (camera labels, K and T on the device)
+        if self._drawn:
             from . import skeleton as _sk  # here, not at the top: host/skeleton.py imports host/triang.py, which imports this module
             if palette is None:
-                raise ValueError("skeleton_source='kp2d' needs palette=: a path or a Palette, as skeleton.load_palette takes it (no colour "
+                raise ValueError(f"skeleton_source={skeleton_source!r} needs palette=: a path or a Palette, as skeleton.load_palette takes it (no colour "
                                  f"or link table is part of this package); {_sk.PALETTE_HELP}")
             if self.kp2d_canvas_shape is not None and (len(self.kp2d_canvas_shape) != 2 or min(self.kp2d_canvas_shape) < 1):
                 raise ValueError(f"kp2d_canvas_shape must be (height, width), got {kp2d_canvas_shape!r}")
             self._sk, self.palette = _sk, _sk.load_palette(palette)
+            if skeleton_source == "kp3d":
+                self._plan_tables = _sk.plan_tables(self.palette)
         if width % 4 != 0:
             raise ValueError(f"width must be a multiple of 4 (dm4d_capture_crop_resize_f32), got {width}")
         self.data_dir = os.path.expandvars(data_dir) if "$" in data_dir else data_dir
@@ -358,17 +371,111 @@ class SpaTemDataset:
                 raise AssertionError("Error: foreground mask < 2%. Please check the data.")
         return fr
 
+    # -- skeleton_source="kp3d": the scene's cameras, a task's poses, the host half of one frame ---------------------------------------
+    def _cameras_on_device(self, scene_label: str, device: torch.device):
+        """(camera labels, K fp64 [m, 3, 3], T fp64 [m, 4, 4] on `device`) of the scene as triangulate_skeleton builds them
+        (triang.scene_cameras: not normalised, float32 inverse), uploaded once per scene and device."""
+        key = (scene_label, str(device))
+        with self._stats_lock:
+            if key not in self._scene_cams:
+                from . import triang
+                labels = sorted(self.cameras[scene_label])
+                Ks, Ts = triang.scene_cameras(self.camera_path_pat.format(data_dir=self.data_dir, scene_label=scene_label), labels)
+                self._scene_cams[key] = (labels, torch.from_numpy(Ks).to(device), torch.from_numpy(Ts).to(device))
+            return self._scene_cams[key]
+
+    def _read_poses(self, labels) -> Dict:
+        """{(scene_label, tem_label): fp64 [k, 3] | the exception reading raised} for the distinct frames of a task: one read each."""
+        keys = list(dict.fromkeys((scene_label, tem) for scene_label, _, tem in labels))
+
+        def read(key):
+            try:
+                return self._sk.read_kp3d(self.get_file_path(self.kp3d_path_pat, key[0], "", key[1]))
+            except Exception as e:  # noqa: BLE001  (raised when the first frame that needs the file has its turn)
+                return e
+        return dict(zip(keys, self._pool.map(read, keys)))
+
+    def _kp3d_pose_and_score(self, label, poses: Dict):
+        """The frame's pose (what reading it raised is raised here, at the frame's turn) and its score override, read as "kp2d" reads
+        its two keypoint files: before the images."""
+        scene_label, spa, tem = label
+        if isinstance(poses[scene_label, tem], BaseException):
+            raise poses[scene_label, tem]
+        score = None
+        if self.kp2d_score_path_pat is not None:
+            score = self._sk._read_scores(self.get_file_path(self.kp2d_score_path_pat, scene_label, spa, tem))
+        return poses[scene_label, tem], score
+
+    def _kp3d_job(self, kp3d: np.ndarray, score, canvas, hw):
+        """What plan_draw_calls checks before it looks at a keypoint, with its errors, -> the frame's skeleton.Kp3dJob (frame and camera
+        are indices that _kp3d_draw fills in)."""
+        if len(self.palette.keypoint_colors) != len(kp3d):
+            raise ValueError(f"the length of kpt_color ({len(self.palette.keypoint_colors)}) does not matches that of keypoints ({len(kp3d)})")
+        return self._sk.Kp3dJob(-1, -1, self._sk.map_params((canvas, hw)), score)
+
+    def _load_frame_kp3d(self, label, input_spa_labels, poses: Dict):
+        """_load_frame_kp2d with the plan left to the device, in its order: what it raises before plan_draw_calls looks at a keypoint
+        is returned (not raised); what it raises afterwards -- the crop, the size and the 2 % checks -- is kept in fr["late"].  The
+        errors in between are the device's (skeleton.plan_error); _resize_on_device_kp2d raises the three in the order of "kp2d"."""
+        scene_label, spa, tem = label
+        sk, cam = self._sk, self.cameras[scene_label][spa]
+        try:
+            kp3d, score = self._kp3d_pose_and_score(label, poses)
+            kp_path = self.get_file_path(self.kp3d_path_pat, scene_label, spa, tem)
+            if not self.has_gt_target and spa not in input_spa_labels:
+                img, mask, img_path, hw = None, None, kp_path, (int(cam["height"]), int(cam["width"]))
+            else:
+                img_path = self.get_file_path(self.image_path_pat, scene_label, spa, tem)
+                fmask_path = self.get_file_path(self.fmask_path_pat, scene_label, spa, tem)
+                img, mask = _open(img_path, "RGB"), _open(fmask_path, "L")
+                hw = img.shape[:2]
+            sk._check_out_shape(hw)
+            canvas = self.kp2d_canvas_shape or (int(cam["height"]), int(cam["width"]))
+            plan = self._kp3d_job(kp3d, score, canvas, hw)
+        except Exception as e:  # noqa: BLE001  (kept for its turn in label order)
+            return e
+        fr = {"img": img, "mask": mask, "plan": plan, "crop": None, "path": kp_path, "label": label, "late": None, "kp3d": kp3d}
+        try:
+            if mask is not None:
+                fr["crop"] = crop_box(mask, img_path)
+                size = lambda a: (a.shape[1], a.shape[0])  # PIL's (w, h)
+                if not (size(img) == size(mask) == plan.out_size):
+                    raise AssertionError(f"Error: image size: {size(img)} != fmask size: {size(mask)} != skeleton size: {plan.out_size}")
+                if self.has_gt_target and spa in input_spa_labels and _mask_mean_at_most(mask, 0.02):
+                    raise AssertionError("Error: foreground mask < 2%. Please check the data.")
+        except Exception as e:  # noqa: BLE001
+            fr["late"] = e
+        return fr
+
+    def _plan_errors(self, frames: List[Dict], status) -> List:
+        """`status` of _kp2d_draw read back (the one read-back of a task's plans; waits for the stream) -> per frame the ValueError
+        plan_draw_calls raises for it, or None."""
+        if status is None:
+            return [None] * len(frames)
+        order, st = status
+        flags = st[:, 0].cpu().tolist()
+        errs: List = [None] * len(frames)
+        for i, f in zip(order, flags):
+            errs[i] = self._sk.plan_error(f, self._plan_tables)
+        return errs
+
     # -- device_decode=True: the host half of one frame, for both skeleton sources -------------------------------------------------
-    def _load_frame_deferred(self, label, input_spa_labels):
+    def _load_frame_deferred(self, label, input_spa_labels, poses: Optional[Dict] = None):
         """_load_frame / _load_frame_kp2d up to the pixels: the frame's files are read and probed (_read), not decoded, in the same
         order; the crop and the checks that need pixels wait for _settle_frame.  fr["hw"]: the (h, w) of the frame's skeleton map.
         What reading raises is returned, not raised: _settle_frames raises it when the frame's turn comes."""
         scene_label, spa, tem = label
-        kp2d = self.skeleton_source == "kp2d"
+        kp2d, kp3d = self._drawn, self.skeleton_source == "kp3d"
         target = not self.has_gt_target and spa not in input_spa_labels
-        fr = {"img": None, "mask": None, "skel": None, "plan": None, "crop": None, "check": self.has_gt_target and spa in input_spa_labels}
+        fr = {"img": None, "mask": None, "skel": None, "plan": None, "crop": None, "check": self.has_gt_target and spa in input_spa_labels,
+              "label": label}
         try:
-            if kp2d:
+            if kp3d:
+                sk, cam = self._sk, self.cameras[scene_label][spa]
+                fr["kp3d"], score = self._kp3d_pose_and_score(label, poses)
+                fr["path"] = fr["img_path"] = self.get_file_path(self.kp3d_path_pat, scene_label, spa, tem)
+                hw = (int(cam["height"]), int(cam["width"]))
+            elif kp2d:
                 sk, cam = self._sk, self.cameras[scene_label][spa]
                 fr["path"] = fr["img_path"] = self.get_file_path(self.kp2d_path_pat, scene_label, spa, tem)
                 inst = sk._read_instance(fr["path"])
@@ -387,7 +494,7 @@ class SpaTemDataset:
                     hw = _hw(fr["img"])
                 sk._check_out_shape(hw)
                 canvas = self.kp2d_canvas_shape or (int(cam["height"]), int(cam["width"]))
-                fr["plan"] = sk.plan_draw_calls(inst, score, (canvas, hw), self.palette)
+                fr["plan"] = self._kp3d_job(fr["kp3d"], score, canvas, hw) if kp3d else sk.plan_draw_calls(inst, score, (canvas, hw), self.palette)
                 fr["hw"] = (fr["plan"].out_size[1], fr["plan"].out_size[0])
         except Exception as e:  # noqa: BLE001  (kept for its turn in label order)
             return e
@@ -419,14 +526,19 @@ class SpaTemDataset:
                        scratch.add((y_last - y_first) * W * 8), y_first, y_last - y_first]
         return desc
 
-    def _resize_on_device_kp2d(self, frames: List[Dict], device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    def _resize_on_device_kp2d(self, frames: List[Dict], device: torch.device, pending: Optional[BaseException] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The device half in "kp2d" mode; fills in the crop of every has_gt_target=False target.  Staging buffer on the device:
 
             [per group: n x h x w x 3 skeleton planes, tight | per group: one h x w mask per target | image planes and decoded masks]
 
         The first two parts exist on the device only; the third goes up from the pinned buffer in one copy, queued while the device
         draws.  Every size in it is known before the targets' crops are.  Tables and descriptors depend on those crops: they go up
-        afterwards in a small buffer of their own (the library takes them by pointer, they need not lie in the staging buffer)."""
+        afterwards in a small buffer of their own (the library takes them by pointer, they need not lie in the staging buffer).
+
+        "kp3d": `frames` are the frames before the first one that _load_frame_kp3d returned an exception for, `pending` is that
+        exception.  The errors come in the order of "kp2d", whose loader raises at the first bad frame: per frame the plan's error
+        (read back from the device after the draw was queued), then what the loader kept in fr["late"]; then `pending`; and only then
+        the targets' empty maps."""
         H, W = self.height, self.width
         n = len(frames)
         cur, skel_offs, mask_offs, regions = self._kp2d_regions(frames)
@@ -440,12 +552,17 @@ class SpaTemDataset:
         st = self._stream(device) if on_gpu else None
         with (torch.cuda.device(device) if on_gpu else contextlib.nullcontext()), (torch.cuda.stream(st) if on_gpu else contextlib.nullcontext()):
             dev_blob = torch.empty(total, dtype=torch.uint8, device=device)
-            boxes = self._kp2d_draw(frames, regions, dev_blob)
+            boxes, status = self._kp2d_draw(frames, regions, dev_blob)
             # the image planes go into the pinned buffer, and up, while the device draws
             jobs = [(o - file_off, fr[name]) for fr, offs in zip(frames, file_offs) for o, name in zip(offs, ("img", "mask")) if o is not None]
             fill(blob.numpy(), jobs, self._pool)
             if total > file_off:
                 dev_blob[file_off:].copy_(blob, non_blocking=True)
+            for fr, err in zip(frames, self._plan_errors(frames, status)):
+                if err is not None or fr.get("late") is not None:
+                    raise err if err is not None else fr["late"]
+            if pending is not None:
+                raise pending
             for idx, h, w, b in boxes:  # 16 bytes per target; .cpu() waits for the stream
                 for i, box in zip(idx, b.cpu().tolist()):
                     if box[2] < 0:
@@ -487,17 +604,40 @@ class SpaTemDataset:
                 cur += n_targets * h * w
         return cur, skel_offs, mask_offs, regions
 
-    def _kp2d_draw(self, frames: List[Dict], regions, dev_blob: torch.Tensor) -> List[Tuple]:
+    def _kp2d_draw(self, frames: List[Dict], regions, dev_blob: torch.Tensor):
         """Draw every group's maps into `dev_blob` and derive the targets' boxes and box masks there, on the current stream ->
-        [(target frame indices, h, w, their device int32 [n, 4] boxes)]."""
-        boxes = []
+        ([(target frame indices, h, w, their device int32 [n, 4] boxes)], "kp3d": (the frame index of every planned job, the plans'
+        device int32 [n, 2] status) | None)."""
+        boxes, status = [], None
+        if self.skeleton_source == "kp3d" and regions:
+            status = self._kp3d_draw(frames, regions, dev_blob)
         for idx, nt, h, w, start, mask_start in regions:
             maps = dev_blob[start: start + len(idx) * h * w * 3].view(len(idx), h, w, 3)
-            self._sk.draw_plans_into([frames[i]["plan"] for i in idx], maps)
+            if status is None:
+                self._sk.draw_plans_into([frames[i]["plan"] for i in idx], maps)
             if nt:
                 masks = dev_blob[mask_start: mask_start + nt * h * w].view(nt, h, w)
                 boxes.append((idx[:nt], h, w, ops.skeleton_box_mask(maps[:nt], skeleton_mask_pads(h, w), masks=masks)[0]))
-        return boxes
+        return boxes, status
+
+    def _kp3d_draw(self, frames: List[Dict], regions, dev_blob: torch.Tensor):
+        """One plan launch for the task's frames (its distinct poses go up here, the jobs with them; the cameras are on the device
+        already) and one draw launch per region, into the regions' maps -> (the frame index of every job, the status on the device)."""
+        sk, dev = self._sk, dev_blob.device
+        order = [i for reg in regions for i in reg[0]]
+        scene_label = frames[order[0]]["label"][0]
+        cam_labels, K_d, T_d = self._cameras_on_device(scene_label, dev)
+        pose_of = {}  # a task's distinct frames: one pose each
+        for i in order:
+            pose_of.setdefault(frames[i]["label"][2], frames[i]["kp3d"])
+        tems = list(pose_of)
+        scene = sk.DeviceScene(torch.from_numpy(np.stack(list(pose_of.values()))).to(dev), K_d, T_d)
+        jobs = [frames[i]["plan"]._replace(frame=tems.index(frames[i]["label"][2]), camera=cam_labels.index(frames[i]["label"][1])) for i in order]
+        groups, first = [], 0
+        for idx, _, h, w, start, _ in regions:
+            groups.append((first, len(idx), dev_blob[start: start + len(idx) * h * w * 3].view(len(idx), h, w, 3)))
+            first += len(idx)
+        return order, sk.plan_and_draw(scene, jobs, groups, self._plan_tables)[1]
 
     def _resize_on_device_decoded(self, frames: List, device: torch.device, stats: Dict) -> Tuple[torch.Tensor, torch.Tensor]:
         """The device half with device_decode=True, for both skeleton sources; fills in every frame's crop.  Staging buffer on the device:
@@ -512,7 +652,7 @@ class SpaTemDataset:
         dm4d_capture_fill_rects_u8 launch.  `frames` may hold exceptions (_load_frame_deferred): the frames before the first are
         checked, then it is raised."""
         H, W = self.height, self.width
-        kp2d = self.skeleton_source == "kp2d"
+        kp2d = self._drawn
         live = frames[: next((i for i, fr in enumerate(frames) if isinstance(fr, BaseException)), len(frames))]
         n = len(live)
         if n == 0:
@@ -537,7 +677,7 @@ class SpaTemDataset:
         st = self._stream(device) if on_gpu else None
         with (torch.cuda.device(device) if on_gpu else contextlib.nullcontext()), (torch.cuda.stream(st) if on_gpu else contextlib.nullcontext()):
             dev_blob = torch.empty(max(lay.total, 16), dtype=torch.uint8, device=device)
-            boxes = self._kp2d_draw(live, regions, dev_blob)
+            boxes, status = self._kp2d_draw(live, regions, dev_blob)
             hosted = [(offs[i, name] - lo, a) for i, name, a in files if not isinstance(a, StagedFile)]
             fill(blob.numpy(), hosted, self._pool)
             if hi > lo:
@@ -559,6 +699,9 @@ class SpaTemDataset:
                 rows = {p[0]: r for p, r in zip(planes, out)}
             for idx, _, _, b in boxes:  # "kp2d": 16 bytes per target
                 rows.update({i: box + [0] for i, box in zip(idx, b.cpu().tolist())})
+            bad = next(((i, e) for i, e in enumerate(self._plan_errors(live, status)) if e is not None), None)
+            if bad is not None:  # "kp3d": the plan's error takes the frame's turn, as the loader's does for "kp2d"
+                frames = frames[:bad[0]] + [bad[1]]
             _settle_frames(frames, rows)
             rects = [(mask_offs[i], *fr["hw"], *fr["rect"]) for i, fr in enumerate(live) if fr["mask"] is None and not kp2d]
             if rects:
@@ -628,8 +771,9 @@ class SpaTemDataset:
             cams = [self._nearest(cameras, spa_labels[0], input_spa_labels)] + list(spa_labels)
             labels = [(scene_label, s, t) for s in cams for t in tem_labels]
 
+        kp3d_files = self._read_poses(labels) if self.skeleton_source == "kp3d" else None
         if self.device_decode:  # every crop comes from the device: the resize runs before the bookkeeping
-            frames = list(self._pool.map(lambda lab: self._load_frame_deferred(lab, input_spa_labels), labels))
+            frames = list(self._pool.map(lambda lab: self._load_frame_deferred(lab, input_spa_labels, kp3d_files), labels))
             stats = {"device": 0, "pillow": 0, "bytes_uploaded": 0}
             try:
                 pixel_values, skeletons = self._resize_on_device_decoded(frames, self._device(), stats)
@@ -637,6 +781,12 @@ class SpaTemDataset:
                 with self._stats_lock:
                     for k, v in stats.items():
                         self.decode_stats[k] += v
+        elif self.skeleton_source == "kp3d":  # as "kp2d"; the plans' errors come back from the device with the targets' boxes
+            frames = list(self._pool.map(lambda lab: self._load_frame_kp3d(lab, input_spa_labels, kp3d_files), labels))
+            bad = next((i for i, fr in enumerate(frames) if isinstance(fr, BaseException)), len(frames))
+            if bad == 0:
+                raise frames[0]
+            pixel_values, skeletons = self._resize_on_device_kp2d(frames[:bad], self._device(), frames[bad] if bad < len(frames) else None)
         elif self.skeleton_source == "kp2d":  # the targets' crops come from the device: the resize runs before the bookkeeping
             frames = list(self._pool.map(lambda lab: self._load_frame_kp2d(lab, input_spa_labels), labels))
             pixel_values, skeletons = self._resize_on_device_kp2d(frames, self._device())
@@ -646,7 +796,7 @@ class SpaTemDataset:
         poses = relative_poses(torch.stack([cameras[s]["pose"] for _, s, _ in labels]))
         hws = [(cameras[s]["height"], cameras[s]["width"]) for _, s, _ in labels]
         crops = [fr["crop"] for fr in frames]
-        if self.skeleton_source != "kp2d" and not self.device_decode:
+        if not self._drawn and not self.device_decode:
             pixel_values, skeletons = self._resize_on_device(frames, self._device())
         del frames
 

@@ -278,7 +278,8 @@ NATIVE_FALLBACKS = {"src.data.spatem_dataset.SpaTemDataset": "diffuman4d_amd.hos
 
 # keywords of the native dataset beyond the reference's, with their defaults (host/capture.py)
 NATIVE_DATASET_KEYS = {"skeleton_source": "files", "palette": None, "kp2d_score_path_pat": None, "kp2d_canvas_shape": None,
-                       "kp2d_path_pat": "{data_dir}/{scene_label}/poses_2d/{spa_label}/{tem_label}.json", "device_decode": False}
+                       "kp2d_path_pat": "{data_dir}/{scene_label}/poses_2d/{spa_label}/{tem_label}.json", "device_decode": False,
+                       "kp3d_path_pat": "{data_dir}/{scene_label}/poses_3d/{tem_label}.json"}
 
 
 def _import_attr(path: str):
@@ -309,7 +310,7 @@ def instantiate(node: Dict[str, Any], **kwargs):
     """hydra.utils.instantiate for flat ``_target_`` nodes."""
     node = dict(node)
     path = node.pop("_target_")
-    # data.skeleton_source / palette / kp2d_* / device_decode are keywords of the native SpaTemDataset only: one that is set selects the native class even
+    # data.skeleton_source / palette / kp2d_* / kp3d_path_pat / device_decode are keywords of the native SpaTemDataset only: one that is set selects the native class even
     # where the reference's imports; given at their defaults they ask for nothing new and are not handed to the reference's class
     given = [k for k in NATIVE_DATASET_KEYS if k in node] if TARGET_ALIASES.get(path, path) in NATIVE_FALLBACKS else []
     target = locate(path, native=any(node[k] != NATIVE_DATASET_KEYS[k] for k in given))

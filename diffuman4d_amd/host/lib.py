@@ -130,6 +130,10 @@ SIGNATURES = {
     "dm4d_project_points_f64": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     # skeleton maps: a batch of frames' draw calls rasterised per output tile in LDS + Pillow's bicubic resize (host/skeleton.py)
     "dm4d_skeleton_draw_u8": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    # skeleton maps from poses_3d: project + plan on the device, and the draw of a device plan (host/skeleton.py draw_skeleton_maps_kp3d)
+    "dm4d_skeleton_plan_kp3d": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _f, _f, _f,
+                                     _vp, _vp, _vp]),
+    "dm4d_skeleton_draw_planned_u8": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _i, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     # bounding box + box mask of drawn maps, for the dataset's skeleton-only targets (host/capture.py, skeleton_source="kp2d")
     "dm4d_skeleton_box_mask_ws_bytes": (C.c_size_t, [_i, _i, _i]),
     "dm4d_skeleton_box_mask_u8": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _i64, _vp, _i64]),
@@ -192,6 +196,12 @@ SKEL_CIRCLE = 1
 SKEL_MAX_PRIMS = 512
 SKEL_COORD_MIN = -8192
 SKEL_COORD_MAX = 8191
+SKEL_MAX_SIZE = 16384
+SKEL_MAX_KPTS = 2048
+SKEL_LINK_FIELDS = 8
+SKEL_ST_NONFINITE = 1
+SKEL_ST_NOCOLOR = 2
+SKEL_ST_LINK_SHIFT = 8
 RESTORE_FIELDS = 16
 JPEG_FIELDS = 8
 JPEG_MCU_UNSTUFFED = 1248  # workspace bytes of unstuffed scan per 16 x 16 MCU

@@ -23,7 +23,8 @@ import torch
 
 from . import lib as _l
 from .lib import (CAPTURE_FIELDS, EVAL_BG_SHIFT, EVAL_CROP_MASKS, EVAL_FIELDS, EVAL_IMAGE_F32, EVAL_MASK_F32, EVAL_OUT,  # noqa: F401
-                  LOG2E, LPIPS_IN_COLS, LPIPS_TAPS, ROWS_MOVE_MAX_JOBS, SKEL_CIRCLE, SKEL_COORD_MAX, SKEL_COORD_MIN, SKEL_FIELDS, SKEL_LINE, SKEL_MAX_PRIMS,
+                  LOG2E, LPIPS_IN_COLS, LPIPS_TAPS, ROWS_MOVE_MAX_JOBS, SKEL_CIRCLE, SKEL_COORD_MAX, SKEL_COORD_MIN, SKEL_FIELDS, SKEL_LINE, SKEL_LINK_FIELDS,
+                  SKEL_MAX_KPTS, SKEL_MAX_PRIMS, SKEL_MAX_SIZE, SKEL_ST_LINK_SHIFT, SKEL_ST_NOCOLOR, SKEL_ST_NONFINITE,
                   TRIANG_MAX_VIEWS, VHULL_BLOCK, VHULL_MAX_CHUNK)
 
 BF16 = torch.bfloat16
@@ -1206,6 +1207,81 @@ def skeleton_draw(prims_host: torch.Tensor, prims: torch.Tensor, offsets_host: t
             raise _l.Dm4dError(f"out: expected a contiguous [{B}, {h}, {w}, 3] tensor on {prims.device}, got {tuple(out.shape)} on {out.device}")
     _l.call("dm4d_skeleton_draw_u8", _stream(), prims_host.data_ptr(), _p(prims), offsets_host.data_ptr(), _p(offsets), B, htab_host.data_ptr(),
             _p(htab), int(hk), vtab_host.data_ptr(), _p(vtab), int(vk), int(H), int(W), int(h), int(w), _p(out))
+    return out
+
+
+def _host_twin(dev: torch.Tensor, host, name: str, dtype, shape) -> None:
+    """`dev` is a contiguous `dtype` tensor of `shape` on a HIP device and `host` the host copy of it."""
+    _req(dev, name, dtype)
+    if tuple(dev.shape) != tuple(shape) or not dev.is_contiguous():
+        raise _l.Dm4dError(f"{name}: expected a contiguous {list(shape)} tensor, got {tuple(dev.shape)}")
+    if not isinstance(host, torch.Tensor) or host.device.type != "cpu" or host.dtype != dtype or host.shape != dev.shape or not host.is_contiguous():
+        raise _l.Dm4dError(f"{name}_host: expected the host copy of {name}")
+
+
+def skeleton_plan_kp3d(kp3d: torch.Tensor, K: torch.Tensor, T: torch.Tensor, jobs_host: torch.Tensor, jobs: torch.Tensor,
+                       scores: Optional[torch.Tensor], scale_host: torch.Tensor, scale: torch.Tensor, sizes_host: torch.Tensor,
+                       sizes: torch.Tensor, links_host: torch.Tensor, links: torch.Tensor, colors_host: torch.Tensor, colors: torch.Tensor,
+                       low_thr: float, high_thr: float, thr_span: float) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Draw plans of n maps straight from 3-D keypoints, one launch on the current stream (dm4d_skeleton_plan_kp3d, include/dm4d.h) ->
+    (records int32 [n, 3 L, SKEL_FIELDS], counts int32 [n], status int32 [n, 2] = {flag bits, dropped links}) on kp3d's device.
+    kp3d fp64 [F, k, 3], K fp64 [m, 3, 3], T fp64 [m, 4, 4]; jobs int32 [n, 2] = {frame, camera}; scores fp32 [n, k] or None; scale
+    fp64 [n, 2] = {scale_ratio, offset}; sizes int32 [n, 2] = {radius, thickness}; links int32 [L, SKEL_LINK_FIELDS]; colors fp32
+    [k + L, 4]; every *_host tensor is the host copy of its device twin, which the library validates before it launches."""
+    _req(kp3d, "kp3d", torch.float64)
+    m = _cameras(K, T)
+    if kp3d.dim() != 3 or kp3d.shape[2] != 3 or not kp3d.is_contiguous():
+        raise _l.Dm4dError(f"kp3d: expected a contiguous [F, k, 3] tensor, got {tuple(kp3d.shape)}")
+    F, k, _ = kp3d.shape
+    n = jobs.shape[0] if isinstance(jobs, torch.Tensor) and jobs.dim() == 2 else 0
+    L = links.shape[0] if isinstance(links, torch.Tensor) and links.dim() == 2 else 0
+    if n < 1 or L < 1:
+        raise _l.Dm4dError("jobs / links: expected [n >= 1, 2] and [L >= 1, SKEL_LINK_FIELDS]")
+    _host_twin(jobs, jobs_host, "jobs", torch.int32, (n, 2))
+    _host_twin(scale, scale_host, "scale", torch.float64, (n, 2))
+    _host_twin(sizes, sizes_host, "sizes", torch.int32, (n, 2))
+    _host_twin(links, links_host, "links", torch.int32, (L, SKEL_LINK_FIELDS))
+    _host_twin(colors, colors_host, "colors", F32, (k + L, 4))
+    if scores is not None:
+        _req(scores, "scores", F32)
+        if tuple(scores.shape) != (n, k) or not scores.is_contiguous():
+            raise _l.Dm4dError(f"scores: expected a contiguous [{n}, {k}] tensor, got {tuple(scores.shape)}")
+    if 3 * L > SKEL_MAX_PRIMS:
+        raise _l.Dm4dError(f"links: 3 x {L} records a map exceed SKEL_MAX_PRIMS = {SKEL_MAX_PRIMS}")
+    records = torch.empty((n, 3 * L, SKEL_FIELDS), dtype=torch.int32, device=kp3d.device)
+    counts = torch.empty((n,), dtype=torch.int32, device=kp3d.device)
+    status = torch.empty((n, 2), dtype=torch.int32, device=kp3d.device)
+    _l.call("dm4d_skeleton_plan_kp3d", _stream(), _p(kp3d), _p(K), _p(T), F, m, k, jobs_host.data_ptr(), _p(jobs), n, _p(scores),
+            scale_host.data_ptr(), _p(scale), sizes_host.data_ptr(), _p(sizes), links_host.data_ptr(), _p(links), L, colors_host.data_ptr(),
+            _p(colors), float(low_thr), float(high_thr), float(thr_span), _p(records), _p(counts), _p(status))
+    return records, counts, status
+
+
+def skeleton_draw_planned(records: torch.Tensor, counts: torch.Tensor, htab_host: torch.Tensor, htab: torch.Tensor, hk: int,
+                          vtab_host: torch.Tensor, vtab: torch.Tensor, vk: int, H: int, W: int, h: int, w: int,
+                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """skeleton_draw on plans that skeleton_plan_kp3d left on the device: records int32 [B, 3 L, SKEL_FIELDS] and counts int32 [B]
+    (contiguous; a slice along B of the plan's tensors is fine) -> uint8 [B, h, w, 3], one launch on the current stream.  Tables and
+    `out` as skeleton_draw takes them."""
+    _req(records, "records", torch.int32), _req(counts, "counts", torch.int32)
+    if records.dim() != 3 or records.shape[2] != SKEL_FIELDS or records.shape[0] < 1 or not records.is_contiguous():
+        raise _l.Dm4dError(f"records: expected a contiguous [B >= 1, 3 L, {SKEL_FIELDS}] tensor, got {tuple(records.shape)}")
+    B, stride, _ = records.shape
+    if tuple(counts.shape) != (B,) or not counts.is_contiguous() or counts.device != records.device:
+        raise _l.Dm4dError(f"counts: expected a contiguous [{B}] tensor on {records.device}, got {tuple(counts.shape)}")
+    for name, dev, host in (("htab", htab, htab_host), ("vtab", vtab, vtab_host)):
+        _req(dev, name, torch.int32)
+        _host_twin(dev, host, name, torch.int32, dev.shape)
+    if htab.numel() != w * (2 + hk) or vtab.numel() != h * (2 + vk):
+        raise _l.Dm4dError(f"htab / vtab: expected {w} x (2 + {hk}) and {h} x (2 + {vk}) entries, got {htab.numel()} and {vtab.numel()}")
+    if out is None:
+        out = torch.empty((B, h, w, 3), dtype=torch.uint8, device=records.device)
+    else:
+        _req(out, "out", torch.uint8)
+        if tuple(out.shape) != (B, h, w, 3) or not out.is_contiguous() or out.device != records.device:
+            raise _l.Dm4dError(f"out: expected a contiguous [{B}, {h}, {w}, 3] tensor on {records.device}, got {tuple(out.shape)} on {out.device}")
+    _l.call("dm4d_skeleton_draw_planned_u8", _stream(), _p(records), _p(counts), B, int(stride), htab_host.data_ptr(), _p(htab), int(hk),
+            vtab_host.data_ptr(), _p(vtab), int(vk), int(H), int(W), int(h), int(w), _p(out))
     return out
 
 

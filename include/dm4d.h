@@ -398,6 +398,49 @@ int dm4d_skeleton_draw_u8(void* stream, const int32_t* prims_host, const int32_t
                           const int32_t* offsets_dev, int n_frames, const int32_t* htab_host, const int32_t* htab_dev, int hk,
                           const int32_t* vtab_host, const int32_t* vtab_dev, int vk, int H, int W, int h, int w, uint8_t* out);
 
+/* Skeleton maps straight from poses_3d (diffuman4d_amd/host/skeleton.py::draw_skeleton_maps_kp3d; DESIGN.md "Skeleton maps from
+ *   poses_3d"): the plan that host/skeleton.py::plan_draw_calls makes of the poses_2d file which triangulate_skeleton would have written
+ *   for a map's frame and camera, made on the device, and the draw of such a plan.
+ *
+ * dm4d_skeleton_plan_kp3d: n_maps maps (at most 65535) in one launch, one wave per map.  kp3d [F, k, 3], K [m, 3, 3], T [m, 4, 4] fp64 as
+ *   dm4d_project_points_f64 takes them (k <= DM4D_SKEL_MAX_KPTS); jobs [n_maps, 2] int32 = {frame, camera}; scores [n_maps, k] fp32 or
+ *   null (all ones): the score override.  Per map, computed on the host as plan_draw_calls does: scale [n_maps, 2] fp64 = {scale_ratio,
+ *   centring offset}, sizes [n_maps, 2] int32 = {radius, thickness} after int(round(.)) (thickness >= 1, both <= DM4D_SKEL_MAX_SIZE / 2).
+ *   Per palette: links [L, DM4D_SKEL_LINK_FIELDS] int32 = {keypoint 1, keypoint 2, id, radius multiplier, thickness multiplier (1 or 2:
+ *   the MAJOR_LINKS rule), 0, 0, 0} in plan_draw_calls' order, X links appended; colors [k + L, 4] fp32 = {r, g, b, has-colour flag} of the
+ *   keypoints, then of the links; low_thr, high_thr and thr_span = (float)(high_thr - low_thr) with the difference formed in fp64.
+ *   A keypoint: project (the device function of dm4d_project_points_f64), u, v, depth rounded to fp32, score 0 where min(u, v) < 0 in
+ *   fp32, x = (double)u * scale_ratio + offset (two fp64 roundings, likewise y), rint (half to even), inside iff both lie in
+ *   [DM4D_SKEL_COORD_MIN, DM4D_SKEL_COORD_MAX].  A link: line_score = min of its endpoints' scores (fp32, a NaN wins); kept unless
+ *   line_score < low_thr; a kept link with an endpoint that is not finite on the canvas sets DM4D_SKEL_ST_NONFINITE; a kept link with
+ *   an endpoint not inside is dropped with its circles and counted; a link still kept that joins a keypoint without a colour sets
+ *   DM4D_SKEL_ST_NOCOLOR, and the first such link's list index is stored above DM4D_SKEL_ST_LINK_SHIFT.  Colours: c * ((clip(score,
+ *   low_thr, high_thr) - low_thr) / thr_span) in fp32, rint, uint8.  Paint order = Python's stable sorted(): descending on the fp64 mean of the
+ *   two fp32 depths when any keypoint's depth is non-zero; else ascending on line_score when any keypoint's score differs from 1; else
+ *   list order -- as a rank counted over all kept links (keys smaller, plus equal keys earlier in the list), no sort.
+ *   -> records [n_maps, 3 L, DM4D_SKEL_FIELDS] int32 (16-byte aligned; a kept link gives {line, circle at keypoint 1, circle at
+ *   keypoint 2}; the slots past a map's count are zero), counts [n_maps] int32, status [n_maps, 2] int32 = {flag bits, dropped links}.
+ *   3 L <= DM4D_SKEL_MAX_PRIMS.  *_host are host copies of the bytes at *_dev, validated before the launch (jobs inside F and m, sizes,
+ *   link indices inside k, ids inside L, multipliers, colours inside [0, 255], every link coloured).  No atomics, no workgroup waits on
+ *   another; a map's output is a function of its own inputs: bitwise repeatable and independent of the batch.
+ * dm4d_skeleton_draw_planned_u8: dm4d_skeleton_draw_u8 (one kernel body) on such a plan: map f owns records f * stride .. f * stride +
+ *   counts[f] - 1 with stride = 3 L; the kernel clamps the count it reads to [0, stride].  Shapes, alignment, stride and the tables'
+ *   windows are validated on the host; the records are in range by construction.  Same output layout.                                  */
+#define DM4D_SKEL_MAX_KPTS 2048
+#define DM4D_SKEL_LINK_FIELDS 8
+#define DM4D_SKEL_ST_NONFINITE 1
+#define DM4D_SKEL_ST_NOCOLOR 2
+#define DM4D_SKEL_ST_LINK_SHIFT 8
+int dm4d_skeleton_plan_kp3d(void* stream, const double* kp3d, const double* K, const double* T, int F, int m, int k,
+                            const int32_t* jobs_host, const int32_t* jobs_dev, int n_maps, const float* scores,
+                            const double* scale_host, const double* scale_dev, const int32_t* sizes_host, const int32_t* sizes_dev,
+                            const int32_t* links_host, const int32_t* links_dev, int L, const float* colors_host,
+                            const float* colors_dev, float low_thr, float high_thr, float thr_span, int32_t* records,
+                            int32_t* counts, int32_t* status);
+int dm4d_skeleton_draw_planned_u8(void* stream, const int32_t* records, const int32_t* counts, int n_frames, int stride,
+                                  const int32_t* htab_host, const int32_t* htab_dev, int hk, const int32_t* vtab_host,
+                                  const int32_t* vtab_dev, int vk, int H, int W, int h, int w, uint8_t* out);
+
 /* Bounding box and box mask of drawn skeleton maps (diffuman4d_amd/host/capture.py::SpaTemDataset, skeleton_source="kp2d"; the reference's
  *   src/data/utils/crop_utils.py skeleton_to_mask, called from spatem_dataset.py:124-127 for has_gt_target=False targets).
  *   maps [n_frames, h, w, 3] uint8, tight (what dm4d_skeleton_draw_u8 writes).  A pixel counts when any of its channels is non-zero.

@@ -11,6 +11,7 @@ package's native stage, with the reference's action names, default order and def
   predict_keypoints      images/ + fmasks/ -> poses_sapiens/                  (tools/predict_keypoints.py; needs --sapiens_ckpt_path)
   triangulate_skeleton   transforms.json + poses_sapiens/ -> poses_3d/, poses_pcd/, poses_2d/      (tools/triangulate_skeleton.py)
   draw_skeleton          poses_2d/ -> skeletons/                              (tools/draw_skeleton.py; needs --palette)
+                         with --skeleton_from kp3d: poses_3d/ + transforms.json -> skeletons/, and no poses_2d/ is written
 
 The two networks and the palette are the caller's files; nothing is downloaded.  An unknown action is an error before anything runs.
 Prints one JSON line per action with the stage's counts.
@@ -70,9 +71,12 @@ def parse_actions(text) -> list:
 
 def run(data_dir: str, actions, *, matting_model_dir=None, sapiens_ckpt_path=None, palette=None, batch_size: int = 8,
         device_png: bool = False, device_decode: bool = False, person_detector=None, bbox_source=None, bbox_thr=None, nms_thr=None,
-        det_shape=None) -> list:
+        det_shape=None, skeleton_from: str = "kp2d") -> list:
     """Run `actions` on the scene under `data_dir` (preprocess.sh:31-77) -> [(action, what its stage returned)].  person_detector,
-    bbox_source, bbox_thr, nms_thr, det_shape: handed to predict_keypoints when given."""
+    bbox_source, bbox_thr, nms_thr, det_shape: handed to predict_keypoints when given.  skeleton_from="kp3d": triangulate_skeleton
+    writes no poses_2d directory and draw_skeleton projects poses_3d into the cameras of transforms.json on the device (the same maps)."""
+    if skeleton_from not in ("kp2d", "kp3d"):
+        raise ValueError(f"skeleton_from must be 'kp2d' or 'kp3d', got {skeleton_from!r}")
     d = str(data_dir)
     out = []
     for act in actions:
@@ -90,8 +94,10 @@ def run(data_dir: str, actions, *, matting_model_dir=None, sapiens_ckpt_path=Non
                                             ("nms_thr", nms_thr), ("det_shape", det_shape)) if v is not None})
             res = STAGES[act](f"{d}/images", f"{d}/poses_sapiens", f"{d}/fmasks", sapiens_ckpt_path, **extra)
         elif act == "triangulate_skeleton":
-            res = STAGES[act](f"{d}/transforms.json", f"{d}/poses_sapiens", f"{d}/poses_3d", out_pcd_dir=f"{d}/poses_pcd",
-                              out_kp2d_proj_dir=f"{d}/poses_2d")
+            extra = {"out_kp2d_proj_dir": f"{d}/poses_2d"} if skeleton_from == "kp2d" else {}
+            res = STAGES[act](f"{d}/transforms.json", f"{d}/poses_sapiens", f"{d}/poses_3d", out_pcd_dir=f"{d}/poses_pcd", **extra)
+        elif skeleton_from == "kp3d":
+            res = STAGES[act](None, f"{d}/skeletons", palette=palette, kp3d_dir=f"{d}/poses_3d", camera_path=f"{d}/transforms.json")
         else:
             res = STAGES[act](f"{d}/poses_2d", f"{d}/skeletons", palette=palette)
         out.append((act, res))
@@ -114,6 +120,8 @@ def main(argv=None) -> int:
     ap.add_argument("--batch_size", type=int, default=8, help="remove_background: images per batch (decrease it if memory runs out)")
     ap.add_argument("--device_png", action="store_true", help="remove_background: encode the mask PNG files on the GPU (same pixels, other bytes)")
     ap.add_argument("--device_decode", action="store_true", help="remove_background: decode baseline JPEG inputs on the GPU; carve_vhull: decode the PNG masks there; predict_keypoints: decode JPEG / PNG images and PNG masks there (same files written)")
+    ap.add_argument("--skeleton_from", choices=("kp2d", "kp3d"), default="kp2d",
+                    help="kp3d: triangulate_skeleton writes no poses_2d/ and draw_skeleton draws from poses_3d/ and transforms.json (the same maps)")
     args = ap.parse_args(argv)
     try:
         actions = parse_actions(args.actions)
@@ -129,7 +137,7 @@ def main(argv=None) -> int:
     for act, res in run(args.data_dir, actions, matting_model_dir=args.matting_model_dir, sapiens_ckpt_path=args.sapiens_ckpt_path,
                         palette=args.palette, batch_size=args.batch_size, device_png=args.device_png, device_decode=args.device_decode,
                         person_detector=args.person_detector, bbox_source=args.bbox_source, bbox_thr=args.bbox_thr, nms_thr=args.nms_thr,
-                        det_shape=args.det_shape):
+                        det_shape=args.det_shape, skeleton_from=args.skeleton_from):
         print(json.dumps({"action": act, "result": res}, default=str))
     return 0
 

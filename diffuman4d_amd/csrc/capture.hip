@@ -9,9 +9,17 @@
 // (diffuman4d_amd/host/resample.py) in float64 exactly as Pillow computes them; this file only applies them, with clip8 and the
 // constants of image_common.h (the 7-channel, 4-columns-per-lane register layout of its two loops is its own).
 //
+// The device cell cache (host/capture_cache.py) splits the same arithmetic at the epilogue: dm4d_capture_crop_resize_packed_u8 is the two
+// passes with the vertical one storing its clip8 values as 8-byte pixels into caller-named cells, dm4d_capture_unpack_cells_f32 applies
+// the epilogue to cells.  The epilogue is one function, capture_epilogue, for both.
+//
 // This translation unit is compiled with -ffp-contract=off (build.py EXTRA_FLAGS): the epilogue rounds every fp32 operation on its
 // own, as PyTorch's CPU kernels do, and a contracted multiply-add would change the last bit.
 #include <stdint.h>
+
+#include <algorithm>
+#include <utility>
+#include <vector>
 
 #include "common.h"
 #include "dm4d.h"
@@ -79,11 +87,53 @@ __global__ void __launch_bounds__(kThreads) capture_hpass_kernel(const uint8_t* 
 // TF.to_tensor(u8) * 2 - 1: a true division, then two separately rounded operations
 __device__ __forceinline__ float unit(uint32_t u) { return __fdiv_rn((float)u, 255.0f) * 2.0f - 1.0f; }
 
-// Vertical pass + epilogue: one lane = 4 consecutive output columns of one output row; reads 32 bytes of each scratch row of its
-// window, writes 16 bytes to each of the 3 pixel_values and 3 skeleton planes.
+// The dataset's fp32 epilogue of one resized pixel {i0 i1 i2 m s0 s1 s2}: the one copy, for the fused vertical pass and for the cells.
+// apply_fmask(image, fmask, "white", vae_normalized=True): both operands * 0.5 + 0.5, image * m + (1 - m) * 1, then * 2 - 1
+__device__ __forceinline__ void capture_epilogue(uint32_t i0, uint32_t i1, uint32_t i2, uint32_t mask, uint32_t s0, uint32_t s1, uint32_t s2,
+                                                 float (&pv)[3], float (&sk)[3]) {
+  const float m = unit(mask) * 0.5f + 0.5f;
+  const float bg = 1.0f - m;
+  const uint32_t img[3] = {i0, i1, i2}, skl[3] = {s0, s1, s2};
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float i = unit(img[c]) * 0.5f + 0.5f;
+    pv[c] = (i * m + bg) * 2.0f - 1.0f;
+    sk[c] = unit(skl[c]);
+  }
+}
+
+// 4 columns of one row of 3 + 3 fp32 planes: px[j] = the 7 bytes of column x0 + j; o = the offset of (row, x0) in plane 0
+__device__ __forceinline__ void capture_store_planes(const uint32_t (&px)[4][7], float* __restrict__ pix, float* __restrict__ skel, int64_t o,
+                                                     int64_t plane) {
+  float pv[3][4], sk[3][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float p[3], s[3];
+    capture_epilogue(px[j][0], px[j][1], px[j][2], px[j][3], px[j][4], px[j][5], px[j][6], p, s);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pv[c][j] = p[c], sk[c][j] = s[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    *reinterpret_cast<f32x4_t*>(pix + o + c * plane) = f32x4_t{pv[c][0], pv[c][1], pv[c][2], pv[c][3]};
+    *reinterpret_cast<f32x4_t*>(skel + o + c * plane) = f32x4_t{sk[c][0], sk[c][1], sk[c][2], sk[c][3]};
+  }
+}
+
+// cell descriptor fields (int64 each, DM4D_CAPTURE_CELL_FIELDS per row), see dm4d.h
+enum { C_SLAB = 0, C_BYTES, C_OFF, C_ROW };
+
+__device__ __forceinline__ uint8_t* cell_base(const int64_t* __restrict__ c) {
+  return reinterpret_cast<uint8_t*>((uintptr_t)c[C_SLAB]) + c[C_OFF];
+}
+
+// Vertical pass: one lane = 4 consecutive output columns of one output row; reads 32 bytes of each scratch row of its window.
+// kPacked = false: + epilogue, 16 bytes to each of the 3 pixel_values and 3 skeleton planes of frame f.
+// kPacked = true:  the clip8 values themselves, 32 bytes {i0 i1 i2 m s0 s1 s2 0} x 4 into cell f (the scratch row format).
+template <bool kPacked>
 __global__ void __launch_bounds__(kThreads) capture_vpass_kernel(const int64_t* __restrict__ desc, const int32_t* __restrict__ tab,
                                                                  const uint8_t* __restrict__ scratch, float* __restrict__ pix,
-                                                                 float* __restrict__ skel, int H, int W) {
+                                                                 float* __restrict__ skel, const int64_t* __restrict__ cells, int H, int W) {
   const int f = blockIdx.z;
   const int64_t* d = desc + (int64_t)f * DM4D_CAPTURE_FIELDS;
   const int oy = blockIdx.y;
@@ -109,41 +159,59 @@ __global__ void __launch_bounds__(kThreads) capture_vpass_kernel(const int64_t* 
 #pragma unroll
       for (int c = 0; c < 7; ++c) acc[j][c] += (int32_t)((v[2 * j + (c >> 2)] >> (8 * (c & 3))) & 0xffu) * w;
   }
-  float pv[3][4], sk[3][4];
+  uint32_t px[4][7];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    // apply_fmask(image, fmask, "white", vae_normalized=True): both operands * 0.5 + 0.5, image * m + (1 - m) * 1, then * 2 - 1
-    const float m = unit(clip8(acc[j][3])) * 0.5f + 0.5f;
-    const float bg = 1.0f - m;
+  for (int j = 0; j < 4; ++j)
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float i = unit(clip8(acc[j][c])) * 0.5f + 0.5f;
-      pv[c][j] = (i * m + bg) * 2.0f - 1.0f;
-      sk[c][j] = unit(clip8(acc[j][4 + c]));
+    for (int c = 0; c < 7; ++c) px[j][c] = clip8(acc[j][c]);
+  if constexpr (kPacked) {
+    uint32_t out[8];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      out[2 * j] = px[j][0] | (px[j][1] << 8) | (px[j][2] << 16) | (px[j][3] << 24);
+      out[2 * j + 1] = px[j][4] | (px[j][5] << 8) | (px[j][6] << 16);
     }
-  }
-  const int64_t plane = (int64_t)H * W;
-  const int64_t o = (int64_t)f * 3 * plane + (int64_t)oy * W + x0;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    *reinterpret_cast<f32x4_t*>(pix + o + c * plane) = f32x4_t{pv[c][0], pv[c][1], pv[c][2], pv[c][3]};
-    *reinterpret_cast<f32x4_t*>(skel + o + c * plane) = f32x4_t{sk[c][0], sk[c][1], sk[c][2], sk[c][3]};
+    U4* dst = reinterpret_cast<U4*>(cell_base(cells + (int64_t)f * DM4D_CAPTURE_CELL_FIELDS) + ((int64_t)oy * W + x0) * 8);
+    dst[0] = U4{out[0], out[1], out[2], out[3]};
+    dst[1] = U4{out[4], out[5], out[6], out[7]};
+  } else {
+    const int64_t plane = (int64_t)H * W;
+    capture_store_planes(px, pix, skel, (int64_t)f * 3 * plane + (int64_t)oy * W + x0, plane);
   }
 }
 
-}  // namespace
+// Cells -> samples: one lane = 4 consecutive columns of one row of one cell; one 32-byte load, the epilogue, six 16-byte stores into
+// row cells[r][C_ROW] of pixel_values / skeletons.  Rows no descriptor names are not touched.
+__global__ void __launch_bounds__(kThreads) capture_unpack_kernel(const int64_t* __restrict__ cells, float* __restrict__ pix,
+                                                                  float* __restrict__ skel, int H, int W) {
+  const int64_t* c = cells + (int64_t)blockIdx.z * DM4D_CAPTURE_CELL_FIELDS;
+  const int oy = blockIdx.y;
+  const int x0 = (blockIdx.x * kThreads + threadIdx.x) * 4;
+  if (x0 >= W) return;
+  const U4* src = reinterpret_cast<const U4*>(cell_base(c) + ((int64_t)oy * W + x0) * 8);
+  const U4 a = src[0], b = src[1];
+  const uint32_t v[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  uint32_t px[4][7];
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int ch = 0; ch < 7; ++ch) px[j][ch] = (v[2 * j + (ch >> 2)] >> (8 * (ch & 3))) & 0xffu;
+  const int64_t plane = (int64_t)H * W;
+  capture_store_planes(px, pix, skel, c[C_ROW] * 3 * plane + (int64_t)oy * W + x0, plane);
+}
 
-extern "C" int dm4d_capture_crop_resize_f32(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host,
-                                            const int64_t* desc_dev, int n_frames, const int32_t* tab_host, const int32_t* tab_dev,
-                                            int64_t tab_len, void* scratch, int64_t scratch_bytes, float* pixel_values, float* skeletons,
-                                            int H, int W) {
-  if (!staging || !desc_host || !desc_dev || !tab_host || !tab_dev || !scratch || !pixel_values || !skeletons)
+// What dm4d_capture_crop_resize_f32 and dm4d_capture_crop_resize_packed_u8 check alike, in the order the first always had: `other_null`
+// and `other_bits` stand for the pointers that are the entry's own (any of them null; the OR of those that must be 16-byte aligned).
+int capture_check_resize(const void* staging, int64_t staging_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n_frames,
+                         const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len, const void* scratch, int64_t scratch_bytes,
+                         bool other_null, uintptr_t other_bits, int H, int W, int* max_rows_out) {
+  if (!staging || !desc_host || !desc_dev || !tab_host || !tab_dev || !scratch || other_null)
     return dm4d_set_error(DM4D_ERR_ARG, "capture_crop_resize: null pointer");
   if (n_frames <= 0 || n_frames > 65535 || H <= 0 || W <= 0 || H > 65535 || W > (1 << 20) || staging_bytes <= 0 || tab_len <= 0 ||
       scratch_bytes <= 0)
     return dm4d_set_error(DM4D_ERR_ARG, "capture_crop_resize: empty or oversized shape");
   if (W % 4 != 0) return dm4d_set_error(DM4D_ERR_ARG, "capture_crop_resize: W must be a multiple of 4");
-  if (((uintptr_t)scratch | (uintptr_t)pixel_values | (uintptr_t)skeletons) & 15)
+  if (((uintptr_t)scratch | other_bits) & 15)
     return dm4d_set_error(DM4D_ERR_ARG, "capture_crop_resize: scratch and outputs must be 16-byte aligned");
   int max_rows = 0;
   for (int f = 0; f < n_frames; ++f) {
@@ -170,15 +238,94 @@ extern "C" int dm4d_capture_crop_resize_f32(void* stream, const void* staging, i
       return dm4d_set_error(DM4D_ERR_ARG, "capture_crop_resize: scratch region out of range or not 16-byte aligned");
     if (n_rows > max_rows) max_rows = (int)n_rows;
   }
-  const dim3 block(kThreads);
+  *max_rows_out = max_rows;
+  return 0;
+}
+
+// Every cell of `n` descriptors a whole H x W x 8-byte region of its slab, on a 16-byte address
+int capture_check_cells(const int64_t* cell_host, int n, int H, int W) {
+  const int64_t cell_bytes = (int64_t)H * W * 8;
+  for (int r = 0; r < n; ++r) {
+    const int64_t* c = cell_host + (int64_t)r * DM4D_CAPTURE_CELL_FIELDS;
+    if (c[C_SLAB] == 0 || (c[C_SLAB] & 15)) return dm4d_set_error(DM4D_ERR_ARG, "capture_cells: a slab address is zero or not 16-byte aligned");
+    if (c[C_OFF] < 0 || (c[C_OFF] & 15) || c[C_BYTES] < cell_bytes || c[C_OFF] > c[C_BYTES] - cell_bytes)
+      return dm4d_set_error(DM4D_ERR_ARG, "capture_cells: a cell's offset is negative, not 16-byte aligned or the cell leaves its slab");
+  }
+  return 0;
+}
+
+void capture_launch_hpass(hipStream_t stream, const void* staging, const int64_t* desc_dev, const int32_t* tab_dev, void* scratch,
+                          int max_rows, int n_frames, int W) {
   const unsigned gx = (unsigned)((W / 4 + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(capture_hpass_kernel, dim3(gx, max_rows, n_frames), block, 0, (hipStream_t)stream, (const uint8_t*)staging,
-                     desc_dev, tab_dev, (uint8_t*)scratch, W);
-  int rc = dm4d_check_launch("capture_hpass_kernel");
+  hipLaunchKernelGGL(capture_hpass_kernel, dim3(gx, max_rows, n_frames), dim3(kThreads), 0, stream, (const uint8_t*)staging, desc_dev,
+                     tab_dev, (uint8_t*)scratch, W);
+}
+
+}  // namespace
+
+extern "C" int dm4d_capture_crop_resize_f32(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host,
+                                            const int64_t* desc_dev, int n_frames, const int32_t* tab_host, const int32_t* tab_dev,
+                                            int64_t tab_len, void* scratch, int64_t scratch_bytes, float* pixel_values, float* skeletons,
+                                            int H, int W) {
+  int max_rows = 0;
+  int rc = capture_check_resize(staging, staging_bytes, desc_host, desc_dev, n_frames, tab_host, tab_dev, tab_len, scratch, scratch_bytes,
+                                !pixel_values || !skeletons, (uintptr_t)pixel_values | (uintptr_t)skeletons, H, W, &max_rows);
   if (rc) return rc;
-  hipLaunchKernelGGL(capture_vpass_kernel, dim3(gx, H, n_frames), block, 0, (hipStream_t)stream, desc_dev, tab_dev,
-                     (const uint8_t*)scratch, pixel_values, skeletons, H, W);
+  capture_launch_hpass((hipStream_t)stream, staging, desc_dev, tab_dev, scratch, max_rows, n_frames, W);
+  rc = dm4d_check_launch("capture_hpass_kernel");
+  if (rc) return rc;
+  const unsigned gx = (unsigned)((W / 4 + kThreads - 1) / kThreads);
+  hipLaunchKernelGGL(capture_vpass_kernel<false>, dim3(gx, H, n_frames), dim3(kThreads), 0, (hipStream_t)stream, desc_dev, tab_dev,
+                     (const uint8_t*)scratch, pixel_values, skeletons, (const int64_t*)nullptr, H, W);
   return dm4d_check_launch("capture_vpass_kernel");
+}
+
+extern "C" int dm4d_capture_crop_resize_packed_u8(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host,
+                                                  const int64_t* desc_dev, int n_frames, const int32_t* tab_host, const int32_t* tab_dev,
+                                                  int64_t tab_len, void* scratch, int64_t scratch_bytes, const int64_t* cell_host,
+                                                  const int64_t* cell_dev, int H, int W) {
+  int max_rows = 0;
+  int rc = capture_check_resize(staging, staging_bytes, desc_host, desc_dev, n_frames, tab_host, tab_dev, tab_len, scratch, scratch_bytes,
+                                !cell_host || !cell_dev, 0, H, W, &max_rows);
+  if (rc) return rc;
+  if ((uintptr_t)cell_dev & 7) return dm4d_set_error(DM4D_ERR_ARG, "capture_crop_resize_packed: cell_dev must be 8-byte aligned");
+  rc = capture_check_cells(cell_host, n_frames, H, W);
+  if (rc) return rc;
+  std::vector<std::pair<int64_t, int64_t>> at(n_frames);  // (slab, offset) of every frame: no two alike
+  for (int f = 0; f < n_frames; ++f) at[f] = {cell_host[(int64_t)f * DM4D_CAPTURE_CELL_FIELDS + C_SLAB], cell_host[(int64_t)f * DM4D_CAPTURE_CELL_FIELDS + C_OFF]};
+  std::sort(at.begin(), at.end());
+  if (std::adjacent_find(at.begin(), at.end()) != at.end())
+    return dm4d_set_error(DM4D_ERR_ARG, "capture_crop_resize_packed: two frames name the same cell");
+  capture_launch_hpass((hipStream_t)stream, staging, desc_dev, tab_dev, scratch, max_rows, n_frames, W);
+  rc = dm4d_check_launch("capture_hpass_kernel");
+  if (rc) return rc;
+  const unsigned gx = (unsigned)((W / 4 + kThreads - 1) / kThreads);
+  hipLaunchKernelGGL(capture_vpass_kernel<true>, dim3(gx, H, n_frames), dim3(kThreads), 0, (hipStream_t)stream, desc_dev, tab_dev,
+                     (const uint8_t*)scratch, (float*)nullptr, (float*)nullptr, cell_dev, H, W);
+  return dm4d_check_launch("capture_vpass_kernel<packed>");
+}
+
+extern "C" int dm4d_capture_unpack_cells_f32(void* stream, const int64_t* cell_host, const int64_t* cell_dev, int n_rows, float* pixel_values,
+                                             float* skeletons, int n_out_rows, int H, int W) {
+  if (!cell_host || !cell_dev || !pixel_values || !skeletons) return dm4d_set_error(DM4D_ERR_ARG, "capture_unpack_cells: null pointer");
+  if (n_rows <= 0 || n_rows > 65535 || n_out_rows <= 0 || n_out_rows > 65535 || H <= 0 || W <= 0 || H > 65535 || W > (1 << 20))
+    return dm4d_set_error(DM4D_ERR_ARG, "capture_unpack_cells: empty or oversized shape");
+  if (W % 4 != 0) return dm4d_set_error(DM4D_ERR_ARG, "capture_unpack_cells: W must be a multiple of 4");
+  if ((((uintptr_t)pixel_values | (uintptr_t)skeletons) & 15) || ((uintptr_t)cell_dev & 7))
+    return dm4d_set_error(DM4D_ERR_ARG, "capture_unpack_cells: outputs (16 bytes) and cell_dev (8 bytes) must be aligned");
+  int rc = capture_check_cells(cell_host, n_rows, H, W);
+  if (rc) return rc;
+  std::vector<char> named(n_out_rows, 0);
+  for (int r = 0; r < n_rows; ++r) {
+    const int64_t row = cell_host[(int64_t)r * DM4D_CAPTURE_CELL_FIELDS + C_ROW];
+    if (row < 0 || row >= n_out_rows) return dm4d_set_error(DM4D_ERR_ARG, "capture_unpack_cells: an output row is outside [0, n_out_rows)");
+    if (named[row]) return dm4d_set_error(DM4D_ERR_ARG, "capture_unpack_cells: two rows name the same output row");
+    named[row] = 1;
+  }
+  const unsigned gx = (unsigned)((W / 4 + kThreads - 1) / kThreads);
+  hipLaunchKernelGGL(capture_unpack_kernel, dim3(gx, H, n_rows), dim3(kThreads), 0, (hipStream_t)stream, cell_dev, pixel_values, skeletons, H,
+                     W);
+  return dm4d_check_launch("capture_unpack_kernel");
 }
 
 // Box and byte sum of decoded planes, and masks that are filled rectangles: what SpaTemDataset(device_decode=True) needs of planes that

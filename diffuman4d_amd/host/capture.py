@@ -25,6 +25,11 @@ route takes from decoded pixels -- the crop box, the empty and 2 % checks, the `
 ``dm4d_capture_plane_stats_u8`` (40 bytes per plane come back) and ``dm4d_capture_fill_rects_u8`` (``_settle_frames``,
 ``_resize_on_device_decoded``).  Files the decoders do not take (WebP, progressive JPEG, ...) are decoded by Pillow as before, inside
 the same call.  The sample and every exception are the flag-off call's.
+
+``device_cache=True`` (opt-in, any route) keeps every resized frame on the device as a *cell* of 8 bytes per pixel
+(host/capture_cache.py, ``dm4d_capture_crop_resize_packed_u8``): a job visits each grid cell several times, and ``get_item`` then runs
+the route above on the frames it has not seen only (``_load``; its ``ops.capture_crop_resize`` call is the one hook, ``_crop_resize``)
+and builds all rows of the sample from cells with one ``dm4d_capture_unpack_cells_f32`` launch (``_load_cached``).
 """
 from __future__ import annotations
 
@@ -43,6 +48,7 @@ from PIL import Image
 
 from . import lib as _l
 from . import ops
+from .capture_cache import CellCache
 from .codec import StagedFile, decode_staged, probe_file
 from .dataset import plucker_maps, relative_poses
 from .staging import Layout, fill, pack_meta, pinned, write_meta
@@ -234,6 +240,15 @@ def _intrinsic(K: torch.Tensor, crop: List[int], height: int) -> torch.Tensor:
     return K
 
 
+def _cell_rows(rows: List[List[int]], device: torch.device) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Cell descriptors (include/dm4d.h) -> (their int64 [n, CAPTURE_CELL_FIELDS] host copy in a pinned buffer, the copy on `device`,
+    queued on the current stream by staging.pack_meta: nothing waits for it).  The caller keeps both until it has synchronised."""
+    desc = np.asarray(rows, dtype=np.int64).reshape(-1, _l.CAPTURE_CELL_FIELDS)
+    dev, host, _, _, off = pack_meta(None, desc, device)
+    view = lambda t: t[off: off + desc.nbytes].view(torch.int64).reshape(desc.shape)  # noqa: E731
+    return view(host), view(dev)
+
+
 SKELETON_SOURCES = ("files", "kp2d", "kp3d")
 KP2D_PATH_PAT = "{data_dir}/{scene_label}/poses_2d/{spa_label}/{tem_label}.json"
 KP3D_PATH_PAT = "{data_dir}/{scene_label}/poses_3d/{tem_label}.json"
@@ -259,7 +274,14 @@ class SpaTemDataset:
 
     ``device_decode``: baseline JPEG and 8-bit PNG files (images, masks, skeleton files) are decoded on the device instead of by
     Pillow in the pool; needs a HIP device (Dm4dError otherwise).  ``get_item`` returns and raises what it does without the flag;
-    ``decode_stats`` ("device", "pillow", "bytes_uploaded", as ``codec.decode_batch`` counts them) is added to by every call."""
+    ``decode_stats`` ("device", "pillow", "bytes_uploaded", as ``codec.decode_batch`` counts them) is added to by every call.
+
+    ``device_cache``: every frame ``get_item`` resizes stays on its device as a cell of ``height * width * 8`` bytes, up to
+    ``device_cache_bytes`` per device (no eviction: cells beyond the budget are loaded again each time), keyed by (device index,
+    scene_label, spa_label, tem_label, the camera is an input camera).  A later call that needs the frame opens none of its files;
+    ``decode_stats`` counts the files actually decoded.  ``get_item`` returns and raises what it does without the flag.  Files that
+    change on disk during a job are NOT noticed: call ``clear_device_cache()`` (between calls, not during one) to forget every cell.
+    ``cache_stats``: "hits", "misses", "unretained" (cells the budget did not cover), "cells" and "bytes" held, over all devices."""
 
     def __init__(self, data_dir: str, camera_path_pat: str = "{data_dir}/{scene_label}/transforms.json",
                  image_path_pat: str = "{data_dir}/{scene_label}/images/{spa_label}/{tem_label}.webp",
@@ -268,10 +290,14 @@ class SpaTemDataset:
                  scene_label: Optional[str] = None, height: int = 1024, width: int = 1024, has_gt_target: bool = True,
                  plucker: str = "host", device=None, decode_threads: int = 8, skeleton_source: str = "files",
                  kp2d_path_pat: str = KP2D_PATH_PAT, kp2d_score_path_pat: Optional[str] = None,
-                 kp2d_canvas_shape: Optional[Tuple[int, int]] = None, kp3d_path_pat: str = KP3D_PATH_PAT, palette=None,
-                 device_decode: bool = False):
+                 kp2d_canvas_shape: Optional[Tuple[int, int]] = None, kp3d_path_pat: str = KP3D_PATH_PAT, *, device_cache: bool = False,
+                 device_cache_bytes: int = 16 << 30, palette=None, device_decode: bool = False):
         if plucker not in ("host", "cameras"):
             raise ValueError("plucker must be 'host' or 'cameras'")
+        self.device_cache, self.device_cache_bytes = bool(device_cache), int(device_cache_bytes)
+        if self.device_cache_bytes < 0:
+            raise ValueError(f"device_cache_bytes must not be negative, got {device_cache_bytes}")
+        self._caches: Dict[torch.device, CellCache] = {}  # device_cache=True: one per device, created when first asked for
         self.device_decode = bool(device_decode)
         if self.device_decode:  # there is no CPU path: the planes are decoded where the resize reads them
             _l.hip_device("cuda" if device is None else device, "SpaTemDataset(device_decode=True)")
@@ -574,7 +600,7 @@ class SpaTemDataset:
             plane_offs = [(oi, mask_offs[i] if om is None else om, skel_offs[i]) for i, (oi, om) in enumerate(file_offs)]
             desc = self._descriptors(frames, plane_offs, shapes, tables, tab)
             meta_dev, meta, tab_off, tab_len, desc_off = pack_meta(tab, desc, device)
-            pix, skel = ops.capture_crop_resize(dev_blob, meta, n, desc_off, tab_off, tab_len, H, W, meta=meta_dev)
+            pix, skel = self._crop_resize(dev_blob, meta, n, desc_off, tab_off, tab_len, meta=meta_dev)
         if on_gpu:
             st.synchronize()  # as _resize_on_device: the tensors are complete when handed over, the pinned buffers may be released
         return pix, skel
@@ -714,7 +740,7 @@ class SpaTemDataset:
                           for i in range(n)]
             desc = self._descriptors(live, plane_offs, [fr["hw"] for fr in live], tables, tab)
             meta_dev, meta, tab_off, tab_len, desc_off = pack_meta(tab, desc, device)
-            pix, skel = ops.capture_crop_resize(dev_blob, meta, n, desc_off, tab_off, tab_len, H, W, meta=meta_dev)
+            pix, skel = self._crop_resize(dev_blob, meta, n, desc_off, tab_off, tab_len, meta=meta_dev)
         if on_gpu:
             st.synchronize()  # as _resize_on_device: the tensors are complete when handed over, the pinned buffers may be released
         return pix, skel
@@ -746,31 +772,20 @@ class SpaTemDataset:
         fill(blob.numpy(), jobs, self._pool)
         write_meta(blob.numpy(), tab, tab_off, desc, desc_off)
         if device.type != "cuda":  # no device: the ops call decides (it refuses host tensors -- there is no CPU fallback)
-            return ops.capture_crop_resize(blob, blob, len(frames), desc_off, tab_off, tab.size, H, W)
+            return self._crop_resize(blob, blob, len(frames), desc_off, tab_off, tab.size)
         st = self._stream(device)
         with torch.cuda.device(device), torch.cuda.stream(st):
             dev_blob = blob.to(device, non_blocking=True)
-            pix, skel = ops.capture_crop_resize(dev_blob, blob, len(frames), desc_off, tab_off, tab.size, H, W)
+            pix, skel = self._crop_resize(dev_blob, blob, len(frames), desc_off, tab_off, tab.size)
         # get_item may run on a loader thread whose consumer is another stream (runner.run_round_pipelined): the tensors are
         # complete when they are handed over, and the pinned buffer may be released.  This stalls the loader thread only.
         st.synchronize()
         return pix, skel
 
-    # -- the get_item contract (spatem_dataset.py:77-229) -------------------------------------------------------------------------
-    def get_item(self, scene_label: str, spa_labels: List[str], tem_labels: List[str], input_spa_labels: List[str]) -> Dict:
-        if len(spa_labels) > 1 and len(tem_labels) == 1:
-            domain = "spatial"
-        elif len(spa_labels) == 1 and len(tem_labels) > 1:
-            domain = "temporal"
-        else:
-            raise ValueError(f"Error: invalid spa_labels and tem_labels: {spa_labels} and {tem_labels}")
-        cameras = self.cameras[scene_label]
-        if domain == "spatial":
-            labels = [(scene_label, s, tem_labels[0]) for s in spa_labels]
-        else:  # the nearest input camera's frames first, then the target's
-            cams = [self._nearest(cameras, spa_labels[0], input_spa_labels)] + list(spa_labels)
-            labels = [(scene_label, s, t) for s in cams for t in tem_labels]
-
+    # -- the route of a list of frames: load, crop, resize ---------------------------------------------------------------------------
+    def _load(self, labels: List[Tuple[str, str, str]], input_spa_labels: List[str]):
+        """Load and resize the frames `labels` name, by the route the constructor chose -> (crops, pixel_values, skeletons).  It raises
+        what the first bad frame in label order raises."""
         kp3d_files = self._read_poses(labels) if self.skeleton_source == "kp3d" else None
         if self.device_decode:  # every crop comes from the device: the resize runs before the bookkeeping
             frames = list(self._pool.map(lambda lab: self._load_frame_deferred(lab, input_spa_labels, kp3d_files), labels))
@@ -792,13 +807,134 @@ class SpaTemDataset:
             pixel_values, skeletons = self._resize_on_device_kp2d(frames, self._device())
         else:
             frames = list(self._pool.map(lambda lab: self._load_frame(lab, input_spa_labels), labels))
-        Ks = torch.stack([_intrinsic(cameras[s]["K"], fr["crop"], self.height) for (_, s, _), fr in zip(labels, frames)])
+            pixel_values, skeletons = self._resize_on_device(frames, self._device())
+        return [fr["crop"] for fr in frames], pixel_values, skeletons
+
+    def _crop_resize(self, blob: torch.Tensor, blob_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int,
+                     meta: Optional[torch.Tensor] = None):
+        """Where every route hands its staging buffer to the device: ops.capture_crop_resize -> (pixel_values, skeletons); under
+        _load_cached the packed form instead, into the cells that call named for these `n` frames -> (None, None)."""
+        sink = getattr(self._tls, "sink", None)
+        extra = {} if meta is None else {"meta": meta}  # the "files" route has no meta, and says nothing of it
+        if sink is None:
+            return ops.capture_crop_resize(blob, blob_host, n, desc_off, tab_off, tab_len, self.height, self.width, **extra)
+        if n != len(sink["cells"]):
+            raise RuntimeError(f"SpaTemDataset: {n} frames reached the resize, {len(sink['cells'])} cells were named for them")
+        rows, rows_dev = sink["rows"] = _cell_rows([[slab.data_ptr(), slab.numel(), off, 0] for slab, off in sink["cells"]], blob.device)
+        ops.capture_crop_resize_packed(blob, blob_host, n, desc_off, tab_off, tab_len, self.height, self.width, rows, rows_dev, **extra)
+        if blob.is_cuda:
+            sink["event"] = torch.cuda.Event()
+            sink["event"].record()
+        sink["packed"] = True
+        return None, None
+
+    # -- device_cache=True ------------------------------------------------------------------------------------------------------------
+    def _cache(self, device: torch.device) -> CellCache:
+        with self._stats_lock:
+            if device not in self._caches:
+                self._caches[device] = CellCache(device, self.height * self.width * 8, self.device_cache_bytes)
+            return self._caches[device]
+
+    @property
+    def cache_stats(self) -> Dict[str, int]:
+        with self._stats_lock:
+            caches = list(self._caches.values())
+        total = {"hits": 0, "misses": 0, "unretained": 0, "cells": 0, "bytes": 0}
+        for c in caches:
+            for k, v in c.stats.items():
+                total[k] += v
+        return total
+
+    def clear_device_cache(self) -> None:
+        """Forget every cell and give the slabs back (CellCache.clear: the device is synchronised first).  Between get_item calls."""
+        with self._stats_lock:
+            caches = list(self._caches.values())
+        for c in caches:
+            c.clear()
+
+    def _load_owned(self, cache: CellCache, owned: List, label_of: Dict, input_spa_labels: List[str], got: Dict) -> None:
+        """_load on the frames of the keys this call owns, packed into cells of the cache -- or of a slab of this call's own for the
+        cells the budget does not cover -- then published, or abandoned if anything was raised.  got[key] = (slab, offset, crop, None)."""
+        sink = None
+        try:
+            cells = cache.reserve(owned)
+            spare = sum(c is None for c in cells)
+            if spare:
+                own = torch.empty(spare * cache.cell_bytes, dtype=torch.uint8, device=cache.device)
+                at = iter(range(0, own.numel(), cache.cell_bytes))
+                cells = [(own, next(at)) if c is None else c for c in cells]
+                retained = [c[0] is not own for c in cells]
+            else:
+                retained = [True] * len(cells)
+            sink = self._tls.sink = {"cells": cells, "event": None, "packed": False}
+            try:
+                crops, _, _ = self._load([label_of[k] for k in owned], input_spa_labels)
+            finally:
+                self._tls.sink = None
+            if not sink["packed"]:
+                raise RuntimeError("SpaTemDataset: the route returned without reaching the resize")
+        except BaseException:
+            if sink is not None and sink["event"] is not None:
+                sink["event"].synchronize()  # the pack was queued before the route raised: its cells are free only once it has run
+            cache.abandon(owned)
+            raise
+        for k, (slab, off), crop, keep in zip(owned, cells, crops, retained):
+            got[k] = (slab, off, crop, None)
+            if keep:
+                cache.publish(k, list(crop), sink["event"])
+            else:
+                cache.abandon([k])
+
+    def _load_cached(self, labels: List[Tuple[str, str, str]], input_spa_labels: List[str]):
+        """_load through the cell cache: the route runs on the frames no earlier call left a cell of (in label order, so that the
+        first bad frame among them is the first bad frame: hits never raised), and one unpack launch writes all rows, hits and fresh
+        cells alike.  The claim protocol is capture_cache.py's: what this call owns is published or abandoned before it waits.
+        Which exception is raised: the flag-off call's whenever this call owns all its misses (every serial use).  When another thread
+        holds some of this call's keys pending, the frames this call owns are loaded first and the others' only if their owner
+        abandoned them: of two bad frames the one raised may then be the later one in label order."""
+        device = self._device()
+        cache = self._cache(device)
+        keys = [(device.index, scene_label, spa, tem, spa in input_spa_labels) for scene_label, spa, tem in labels]
+        label_of = dict(zip(keys, labels))
+        got: Dict = {}  # key -> (slab, offset, crop, the event to wait for | None)
+        on_gpu = device.type == "cuda"
+        st = self._stream(device) if on_gpu else None
+        with (torch.cuda.device(device) if on_gpu else contextlib.nullcontext()), (torch.cuda.stream(st) if on_gpu else contextlib.nullcontext()):
+            todo = list(label_of)
+            while todo:
+                hits, owned, todo = cache.claim(todo)
+                got.update({c.key: (c.slab, c.offset, c.meta, c.event) for c in hits})
+                if owned:
+                    self._load_owned(cache, owned, label_of, input_spa_labels, got)
+                if todo:
+                    cache.wait(todo)
+            for ev in {id(e): e for _, _, _, e in got.values() if e is not None}.values():
+                st.wait_event(ev)
+            rows, rows_dev = _cell_rows([[got[k][0].data_ptr(), got[k][0].numel(), got[k][1], r] for r, k in enumerate(keys)], device)
+            pixel_values, skeletons = ops.capture_unpack_cells(rows, rows_dev, len(keys), self.height, self.width)
+        if on_gpu:
+            st.synchronize()  # as _resize_on_device: the tensors are complete when handed over; a slab of this call's own may go
+        return [list(got[k][2]) for k in keys], pixel_values, skeletons
+
+    # -- the get_item contract (spatem_dataset.py:77-229) -------------------------------------------------------------------------
+    def get_item(self, scene_label: str, spa_labels: List[str], tem_labels: List[str], input_spa_labels: List[str]) -> Dict:
+        if len(spa_labels) > 1 and len(tem_labels) == 1:
+            domain = "spatial"
+        elif len(spa_labels) == 1 and len(tem_labels) > 1:
+            domain = "temporal"
+        else:
+            raise ValueError(f"Error: invalid spa_labels and tem_labels: {spa_labels} and {tem_labels}")
+        cameras = self.cameras[scene_label]
+        if domain == "spatial":
+            labels = [(scene_label, s, tem_labels[0]) for s in spa_labels]
+        else:  # the nearest input camera's frames first, then the target's
+            cams = [self._nearest(cameras, spa_labels[0], input_spa_labels)] + list(spa_labels)
+            labels = [(scene_label, s, t) for s in cams for t in tem_labels]
+
+        crops, pixel_values, skeletons = (self._load_cached if self.device_cache else self._load)(labels, input_spa_labels)
+        Ks = torch.stack([_intrinsic(cameras[s]["K"], crop, self.height) for (_, s, _), crop in zip(labels, crops)])
         poses = relative_poses(torch.stack([cameras[s]["pose"] for _, s, _ in labels]))
         hws = [(cameras[s]["height"], cameras[s]["width"]) for _, s, _ in labels]
-        crops = [fr["crop"] for fr in frames]
-        if not self._drawn and not self.device_decode:
-            pixel_values, skeletons = self._resize_on_device(frames, self._device())
-        del frames
 
         n = len(labels)
         pl = plucker_maps(self.height, self.width, Ks, poses) if self.plucker == "host" else None

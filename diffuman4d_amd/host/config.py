@@ -279,7 +279,7 @@ NATIVE_FALLBACKS = {"src.data.spatem_dataset.SpaTemDataset": "diffuman4d_amd.hos
 # keywords of the native dataset beyond the reference's, with their defaults (host/capture.py)
 NATIVE_DATASET_KEYS = {"skeleton_source": "files", "palette": None, "kp2d_score_path_pat": None, "kp2d_canvas_shape": None,
                        "kp2d_path_pat": "{data_dir}/{scene_label}/poses_2d/{spa_label}/{tem_label}.json", "device_decode": False,
-                       "kp3d_path_pat": "{data_dir}/{scene_label}/poses_3d/{tem_label}.json"}
+                       "kp3d_path_pat": "{data_dir}/{scene_label}/poses_3d/{tem_label}.json", "device_cache": False, "device_cache_gb": 16}
 
 
 def _import_attr(path: str):
@@ -310,12 +310,14 @@ def instantiate(node: Dict[str, Any], **kwargs):
     """hydra.utils.instantiate for flat ``_target_`` nodes."""
     node = dict(node)
     path = node.pop("_target_")
-    # data.skeleton_source / palette / kp2d_* / kp3d_path_pat / device_decode are keywords of the native SpaTemDataset only: one that is set selects the native class even
+    # data.skeleton_source / palette / kp2d_* / kp3d_path_pat / device_decode / device_cache / device_cache_gb are keywords of the native SpaTemDataset only: one that is set selects the native class even
     # where the reference's imports; given at their defaults they ask for nothing new and are not handed to the reference's class
     given = [k for k in NATIVE_DATASET_KEYS if k in node] if TARGET_ALIASES.get(path, path) in NATIVE_FALLBACKS else []
     target = locate(path, native=any(node[k] != NATIVE_DATASET_KEYS[k] for k in given))
     if given and target is not _import_attr(NATIVE_FALLBACKS[TARGET_ALIASES.get(path, path)]):
         for k in given:
             del node[k]
+    elif "device_cache_gb" in node:  # the configuration speaks of GB, the native dataset's keyword of bytes
+        node["device_cache_bytes"] = int(float(node.pop("device_cache_gb")) * (1 << 30))
     node.update(kwargs)
     return target(**node)

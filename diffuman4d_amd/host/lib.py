@@ -108,6 +108,9 @@ SIGNATURES = {
     "dm4d_nhwc_to_nchw_bf16": (_i, [_vp, _vp, _vp, _i, _i, _i, _i]),
     # captured frames: crop + Pillow-exact bicubic resize + the dataset's fp32 epilogue (host/capture.py)
     "dm4d_capture_crop_resize_f32": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i]),
+    # the same resize into uint8 cells kept on the device, and cells -> samples (host/capture_cache.py, device_cache=True)
+    "dm4d_capture_crop_resize_packed_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _i]),
+    "dm4d_capture_unpack_cells_f32": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _i, _i]),
     # box + byte sum of planes decoded on the device, and rectangle masks (host/capture.py, device_decode=True)
     "dm4d_capture_plane_stats_ws_bytes": (C.c_size_t, [_i, _i64]),
     "dm4d_capture_plane_stats_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _i64]),
@@ -177,6 +180,7 @@ EPI_F32SIDE = 8
 EPI_SPLITOUT = 16
 LOG2E = 1.4426950408889634
 CAPTURE_FIELDS = 16
+CAPTURE_CELL_FIELDS = 4
 CAPTURE_PLANE_FIELDS = 8
 CAPTURE_RECT_FIELDS = 8
 EVAL_FIELDS = 16

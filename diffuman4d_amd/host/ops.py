@@ -22,7 +22,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import lib as _l
-from .lib import (CAPTURE_FIELDS, EVAL_BG_SHIFT, EVAL_CROP_MASKS, EVAL_FIELDS, EVAL_IMAGE_F32, EVAL_MASK_F32, EVAL_OUT,  # noqa: F401
+from .lib import (CAPTURE_CELL_FIELDS, CAPTURE_FIELDS, EVAL_BG_SHIFT, EVAL_CROP_MASKS, EVAL_FIELDS, EVAL_IMAGE_F32, EVAL_MASK_F32, EVAL_OUT,  # noqa: F401
                   LOG2E, LPIPS_IN_COLS, LPIPS_TAPS, ROWS_MOVE_MAX_JOBS, SKEL_CIRCLE, SKEL_COORD_MAX, SKEL_COORD_MIN, SKEL_FIELDS, SKEL_LINE, SKEL_LINK_FIELDS,
                   SKEL_MAX_KPTS, SKEL_MAX_PRIMS, SKEL_MAX_SIZE, SKEL_ST_LINK_SHIFT, SKEL_ST_NOCOLOR, SKEL_ST_NONFINITE,
                   TRIANG_MAX_VIEWS, VHULL_BLOCK, VHULL_MAX_CHUNK)
@@ -950,14 +950,10 @@ def postprocess_images(x: torch.Tensor, channels: int = 3) -> torch.Tensor:
     return y
 
 
-def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: int, desc_off: int, tab_off: int, tab_len: int,
-                        H: int, W: int, meta: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
-    """Crop + Pillow-exact bicubic resize + the dataset's fp32 epilogue of `n_frames` captured frames (host/capture.py) ->
-    (pixel_values, skeletons), fp32 [n_frames, 3, H, W] on blob's device.  `blob`: the device copy of the staging buffer
-    `blob_host` (uint8: frame planes | int32 tables at byte `tab_off` | int64 descriptors at byte `desc_off`); the library checks
-    every descriptor and table on the host copy before it launches.  With `meta` (uint8, on blob's device) the tables and the
-    descriptors are read from it instead, at the same two offsets, `blob_host` is the host copy of `meta`, and `blob` holds
-    planes only, some of which may never have been on the host."""
+def _capture_resize_args(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: int, desc_off: int, tab_off: int, tab_len: int, W: int,
+                         meta: Optional[torch.Tensor]):
+    """The checks of capture_crop_resize / capture_crop_resize_packed and the arguments their entries share, up to scratch_bytes ->
+    (the arguments, the tensors that must outlive the call's launches)."""
     _req(blob, "blob", torch.uint8)
     where = blob if meta is None else _req(meta, "meta", torch.uint8)
     _check_meta(where, blob_host, CAPTURE_FIELDS, n_frames, desc_off, tab_off, tab_len, what="blob" if meta is None else "meta")
@@ -967,11 +963,64 @@ def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: i
     tab = blob_host[tab_off: tab_off + tab_len * 4].view(torch.int32)
     scratch_bytes = int((desc[:, 13] + desc[:, 15] * W * 8).max())
     scratch = torch.empty(max(scratch_bytes, 16), dtype=torch.uint8, device=blob.device)
+    base = where.data_ptr()
+    return (_stream(), blob.data_ptr(), blob.numel(), desc.data_ptr(), base + desc_off, n_frames, tab.data_ptr(), base + tab_off, tab_len,
+            _p(scratch), scratch.numel()), (scratch, desc, tab)
+
+
+def capture_crop_resize(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: int, desc_off: int, tab_off: int, tab_len: int,
+                        H: int, W: int, meta: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Crop + Pillow-exact bicubic resize + the dataset's fp32 epilogue of `n_frames` captured frames (host/capture.py) ->
+    (pixel_values, skeletons), fp32 [n_frames, 3, H, W] on blob's device.  `blob`: the device copy of the staging buffer
+    `blob_host` (uint8: frame planes | int32 tables at byte `tab_off` | int64 descriptors at byte `desc_off`); the library checks
+    every descriptor and table on the host copy before it launches.  With `meta` (uint8, on blob's device) the tables and the
+    descriptors are read from it instead, at the same two offsets, `blob_host` is the host copy of `meta`, and `blob` holds
+    planes only, some of which may never have been on the host."""
+    args, _keep = _capture_resize_args(blob, blob_host, n_frames, desc_off, tab_off, tab_len, W, meta)
     pix = torch.empty((n_frames, 3, H, W), dtype=F32, device=blob.device)
     skel = torch.empty((n_frames, 3, H, W), dtype=F32, device=blob.device)
-    base = where.data_ptr()
-    _l.call("dm4d_capture_crop_resize_f32", _stream(), blob.data_ptr(), blob.numel(), desc.data_ptr(), base + desc_off, n_frames, tab.data_ptr(),
-            base + tab_off, tab_len, _p(scratch), scratch.numel(), _p(pix), _p(skel), H, W)
+    _l.call("dm4d_capture_crop_resize_f32", *args, _p(pix), _p(skel), H, W)
+    return pix, skel
+
+
+def _capture_cells(cells_host: torch.Tensor, cells: torch.Tensor, n: int) -> None:
+    """`cells_host` is the host int64 [n, CAPTURE_CELL_FIELDS] copy of the device tensor `cells`."""
+    _req(cells, "cells", torch.int64)
+    if not isinstance(cells_host, torch.Tensor) or cells_host.device.type != "cpu" or cells_host.dtype != torch.int64 or \
+            tuple(cells_host.shape) != (n, CAPTURE_CELL_FIELDS) or tuple(cells.shape) != (n, CAPTURE_CELL_FIELDS) or \
+            not cells_host.is_contiguous() or not cells.is_contiguous():
+        raise _l.Dm4dError(f"cells: expected contiguous int64 [{n}, {CAPTURE_CELL_FIELDS}] descriptors on the device and their host copy")
+
+
+def capture_crop_resize_packed(blob: torch.Tensor, blob_host: torch.Tensor, n_frames: int, desc_off: int, tab_off: int, tab_len: int,
+                               H: int, W: int, cells_host: torch.Tensor, cells: torch.Tensor, meta: Optional[torch.Tensor] = None) -> None:
+    """capture_crop_resize up to the epilogue: frame f's resized uint8 pixels {i0 i1 i2 m s0 s1 s2 0} go into the cell that row f of
+    the int64 [n_frames, CAPTURE_CELL_FIELDS] descriptors `cells` = {slab address, slab bytes, byte offset of the cell, (unused)}
+    names (include/dm4d.h; host/capture_cache.py).  `cells_host`: their host copy, checked by the library before it launches.  The
+    slabs are device memory of blob's device that the caller keeps alive.  blob / blob_host / meta as for capture_crop_resize."""
+    args, _keep = _capture_resize_args(blob, blob_host, n_frames, desc_off, tab_off, tab_len, W, meta)
+    _capture_cells(cells_host, cells, n_frames)
+    if cells.device != blob.device:
+        raise _l.Dm4dError("cells: expected a tensor on blob's device")
+    _l.call("dm4d_capture_crop_resize_packed_u8", *args, cells_host.data_ptr(), _p(cells), H, W)
+
+
+def capture_unpack_cells(cells_host: torch.Tensor, cells: torch.Tensor, n_out_rows: int, H: int, W: int,
+                         out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The dataset's fp32 epilogue of cells that capture_crop_resize_packed wrote -> (pixel_values, skeletons), fp32 [n_out_rows, 3, H, W]
+    on cells' device: row `cells[r, 3]` of both is cell r's sample, bit for bit what capture_crop_resize gives for the frame.  One
+    launch on the current stream.  `out`: the two tensors to write into; rows that no descriptor names keep what they hold (without
+    `out` they are uninitialised)."""
+    n = int(cells_host.shape[0]) if isinstance(cells_host, torch.Tensor) and cells_host.ndim == 2 else 0
+    _capture_cells(cells_host, cells, n)
+    if out is None:
+        out = tuple(torch.empty((n_out_rows, 3, H, W), dtype=F32, device=cells.device) for _ in range(2))
+    pix, skel = out
+    for t, name in ((pix, "pixel_values"), (skel, "skeletons")):
+        _req(t, name, F32)
+        if tuple(t.shape) != (n_out_rows, 3, H, W) or not t.is_contiguous() or t.device != cells.device:
+            raise _l.Dm4dError(f"{name}: expected a contiguous [{n_out_rows}, 3, {H}, {W}] tensor on cells' device")
+    _l.call("dm4d_capture_unpack_cells_f32", _stream(), cells_host.data_ptr(), _p(cells), n, _p(pix), _p(skel), n_out_rows, H, W)
     return pix, skel
 
 

@@ -241,6 +241,30 @@ int dm4d_capture_crop_resize_f32(void* stream, const void* staging, int64_t stag
                                  const int64_t* desc_dev, int n_frames, const int32_t* tab_host, const int32_t* tab_dev, int64_t tab_len,
                                  void* scratch, int64_t scratch_bytes, float* pixel_values, float* skeletons, int H, int W);
 
+/* The same resize with the result kept as uint8 "cells" on the device, and cells turned into samples (capture.hip; the device cell cache
+ *   of SpaTemDataset(device_cache=True), diffuman4d_amd/host/capture_cache.py).
+ * A cell is one resized frame: H * W packed pixels, row-major, 8 bytes each = {i0 i1 i2 m s0 s1 s2 0} (image RGB, mask, skeleton RGB,
+ *   a zero pad): the bytes of one scratch row of the horizontal pass, and the clip8 values the vertical pass holds before its epilogue.
+ *   H * W * 8 bytes on a 16-byte address.  cell: n x DM4D_CAPTURE_CELL_FIELDS int64 = {slab address (a device allocation, 16-byte
+ *   aligned) | slab bytes | byte offset of the cell in the slab (16-byte aligned) | output row}; cells of one call may lie in any
+ *   number of slabs.  cell_host is the host copy of the bytes at cell_dev and is validated before anything is launched: a slab
+ *   address that is zero or unaligned, an offset that is negative or unaligned, a cell that leaves its slab.
+ * dm4d_capture_crop_resize_packed_u8: the arguments, checks and horizontal pass of dm4d_capture_crop_resize_f32; the vertical pass
+ *   stores frame f's packed pixels into cell f (32 bytes per lane for 4 columns) instead of the fp32 planes.  The output row field is
+ *   ignored; two frames that name the same (slab, offset) are refused.  Two launches.
+ * dm4d_capture_unpack_cells_f32: one launch; a lane loads 32 bytes (4 columns of one row of one cell), applies the epilogue of
+ *   dm4d_capture_crop_resize_f32 (the same device function) and stores 6 x 16 bytes into row `output row` of pixel_values / skeletons
+ *   [n_out_rows, 3, H, W] fp32.  Output rows outside [0, n_out_rows) and two rows with one output row are refused; rows of the outputs
+ *   that no descriptor names are not touched.  unpack(packed(x)) is dm4d_capture_crop_resize_f32(x) bit for bit.
+ * No atomics, no block waits on another; a cell's bytes and a row's floats do not depend on what else is in the call.  W % 4 == 0. */
+#define DM4D_CAPTURE_CELL_FIELDS 4
+int dm4d_capture_crop_resize_packed_u8(void* stream, const void* staging, int64_t staging_bytes, const int64_t* desc_host,
+                                       const int64_t* desc_dev, int n_frames, const int32_t* tab_host, const int32_t* tab_dev,
+                                       int64_t tab_len, void* scratch, int64_t scratch_bytes, const int64_t* cell_host,
+                                       const int64_t* cell_dev, int H, int W);
+int dm4d_capture_unpack_cells_f32(void* stream, const int64_t* cell_host, const int64_t* cell_dev, int n_rows, float* pixel_values,
+                                  float* skeletons, int n_out_rows, int H, int W);
+
 /* Box and byte sum of uint8 planes that lie in a device blob, and masks that are filled rectangles (capture.hip): what
  *   SpaTemDataset(device_decode=True) needs of planes that were decoded on the device and never visit the host.
  * dm4d_capture_plane_stats_u8: desc = n x DM4D_CAPTURE_PLANE_FIELDS int64 = {byte offset in blob (16-byte aligned) | h | w | channels: 1

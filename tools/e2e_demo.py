@@ -51,6 +51,11 @@ def main():
                          "finished file bytes over PCIe")
     ap.add_argument("--writer-processes", type=int, default=0, help="runner.writer_processes: encode the packages in N processes")
     ap.add_argument("--host-threads", type=int, default=0, help="torch.set_num_threads for the host stages (0 = torch's default)")
+    ap.add_argument("--device-cache", action="store_true",
+                    help="data.device_cache=true: resized frames stay on the GPU as cells, every grid cell is decoded once a job.  A keyword of "
+                         "the captured-scene dataset: give one in the overrides (data=dna_rendering data.data_dir=... data.scene_label=...); "
+                         "the synthetic dataset of the default run reads no files and has no such flag")
+    ap.add_argument("--device-cache-gb", type=float, default=None, help="data.device_cache_gb: the cache's budget per device (default 16)")
     ap.add_argument("--timeline", default=None, help="write per-task stage intervals (load / denoise / save: start, end, thread) as JSON")
     ap.add_argument("--unet-layout", choices=("sd21", "sd1x"), default="sd21",
                     help="attention layout of the synthetic checkpoint: sd21 = attention_head_dim (5, 10, 20, 20), head dimension 64; "
@@ -69,7 +74,13 @@ def main():
                          + (["sampler.vae_cache=true", "sampler.decode_policy=denoised"] if a.fast_vae else [])
                          + (["sampler.prune_cond_rows=true"] if a.prune else [])
                          + (["sampler.device_results=true"] if a.device_results else [])
-                         + (["sampler.device_jpeg=true"] if a.device_jpeg else []) + a.overrides)
+                         + (["sampler.device_jpeg=true"] if a.device_jpeg else []) + a.overrides
+                         + (["data.device_cache=true"] if a.device_cache else [])
+                         + ([f"data.device_cache_gb={a.device_cache_gb}"] if a.device_cache and a.device_cache_gb is not None else []))
+    captured = any(o.startswith("data=") and o != "data=synthetic" for o in a.overrides)
+    if (a.device_cache or a.device_cache_gb is not None) and not captured:
+        ap.error("--device-cache / --device-cache-gb are keywords of the captured-scene dataset: add data=dna_rendering (or fdvai) data.data_dir=DIR "
+                 "data.scene_label=SCENE to the overrides")
     if a.host_threads > 0:
         torch.set_num_threads(a.host_threads)
     t0 = time.perf_counter()

@@ -161,6 +161,10 @@ SIGNATURES = {
     "dm4d_png_bound": (C.c_size_t, [_i, _i, _i]),
     "dm4d_png_ws_bytes": (C.c_size_t, [_i64, _i64, _i]),
     "dm4d_png_encode_u8": (_i, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp]),
+    # complete lossless WebP files of a batch of RGB images (host/webp.py)
+    "dm4d_webp_bound": (C.c_size_t, [_i, _i]),
+    "dm4d_webp_ws_bytes": (C.c_size_t, [_i64, _i64, _i]),
+    "dm4d_webp_encode_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _i64, _vp, _i64, _vp]),
     # baseline JPEG files decoded into a caller's buffer: speculative Huffman decoding, IDCT, up-sampling, colour (host/jpegdec.py)
     "dm4d_jpeg_decode_ws_bytes": (C.c_size_t, [_i64, _i]),
     "dm4d_jpeg_decode_u8": (_i, [_vp, _vp, _i64, _vp, _vp, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
@@ -228,6 +232,11 @@ PNG_L = 0
 PNG_RGBA = 1
 PNG_STRIPE_BYTES = 32768
 PNG_STRIPE_REC = 1712
+WEBP_FIELDS = 8
+WEBP_MAX_SIDE = 16383
+WEBP_STRIPE_PIXELS = 8192
+WEBP_STRIPE_REC = 3200
+WEBP_IMAGE_REC = 4096
 JPEGDEC_FIELDS = 16
 JPEGDEC_TABLE_BYTES = 1104
 JPEGDEC_SUB_BITS = 1024

@@ -1509,6 +1509,26 @@ def png_encode(planes: torch.Tensor, rgb: Optional[torch.Tensor], desc: torch.Te
     return blob, out
 
 
+def webp_encode(rgb: torch.Tensor, desc: torch.Tensor, blob_bytes: int, ws_bytes: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Complete lossless WebP files of the packed RGB images that `desc` (host int64 [n, WEBP_FIELDS], include/dm4d.h) names in the device
+    uint8 buffer `rgb` -> (blob of `blob_bytes` on the device, device int64 [2 n]: the files' offsets in it, then their lengths).  Five
+    launches on the current stream; nothing is synchronised.  The library checks every descriptor against the buffer before it launches."""
+    _req(rgb, "rgb", torch.uint8)
+    if desc.device.type != "cpu" or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != _l.WEBP_FIELDS or not desc.is_contiguous() \
+            or desc.shape[0] < 1:
+        raise _l.Dm4dError(f"desc: expected a contiguous host int64 [n, {_l.WEBP_FIELDS}] tensor")
+    if not rgb.is_contiguous() or rgb.numel() == 0:
+        raise _l.Dm4dError("rgb: expected a contiguous non-empty tensor")
+    n, dev = int(desc.shape[0]), rgb.device
+    ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+    blob = torch.empty(blob_bytes, dtype=torch.uint8, device=dev)
+    out = torch.empty(2 * n, dtype=torch.int64, device=dev)
+    desc_dev = desc.to(dev)
+    _l.call("dm4d_webp_encode_u8", _stream(), _p(rgb), rgb.numel(), desc.data_ptr(), _p(desc_dev), n, _p(ws), ws.numel() * 8, _p(blob),
+            blob.numel(), _p(out))
+    return blob, out
+
+
 def rectify(blob: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tensor, n: int, desc_off: int, tab_off: int, tab_len: int,
             lut: torch.Tensor, out_bytes: int) -> torch.Tensor:
     """Colour table + undistortion + area resize + crop of `n` staged raw captures (host/rectify.py) -> the packed uint8 RGB results,

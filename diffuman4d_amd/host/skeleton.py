@@ -286,9 +286,10 @@ def _read_instance(path) -> Optional[Dict]:
 def draw_skeleton_maps(kp2d_paths: Sequence[str], kp2d_score_paths: Optional[Sequence[Optional[str]]] = None,
                        kp2d_canvas_shape=(1024, 1024), out_kpmap_shape=(1024, 1024), low_thr=0.5, high_thr=0.9, radius=2, thickness=2,
                        draw_face_keypoints: bool = False, palette=None, num_workers: int = 16, device="cuda", stats: Optional[Dict] = None,
-                       pool: Optional[ThreadPoolExecutor] = None) -> np.ndarray:
+                       pool: Optional[ThreadPoolExecutor] = None, out: Optional[torch.Tensor] = None):
     """The maps of many keypoint files -> uint8 [B, h, w, 3] (RGB), drawn in one launch; the files are read in a pool of `num_workers`
-    threads (at most 16).  `stats`, when given, receives dropped_links and the seconds spent reading, planning and on the device."""
+    threads (at most 16).  `stats`, when given, receives dropped_links and the seconds spent reading, planning and on the device.
+    With `out` (uint8 [B, h, w, 3] on the device) the maps are drawn into it (draw_plans_into) and it is returned: nothing is read back."""
     palette = load_palette(palette)
     _check_out_shape(out_kpmap_shape)
     if kp2d_score_paths is None:
@@ -307,7 +308,7 @@ def draw_skeleton_maps(kp2d_paths: Sequence[str], kp2d_score_paths: Optional[Seq
     plans = [plan_draw_calls(inst, sc, (kp2d_canvas_shape, out_kpmap_shape), palette, low_thr, high_thr, radius, thickness, draw_face_keypoints)
              for inst, sc in zip(instances, score_instances)]
     t2 = time.perf_counter()
-    maps = draw_plans(plans, device=device)
+    maps = draw_plans(plans, device=device) if out is None else draw_plans_into(plans, out)
     t3 = time.perf_counter()
     if stats is not None:
         stats["dropped_links"] = stats.get("dropped_links", 0) + sum(p.dropped_links for p in plans)
@@ -579,10 +580,16 @@ def _save(path: str, arr: np.ndarray, quality: int) -> None:
     Image.fromarray(arr).save(path, quality=quality)
 
 
+def _write(path: str, data: bytes) -> None:
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    with open(path, "wb") as f:
+        f.write(data)
+
+
 def draw_skeleton(kp2d_dir: Optional[str], out_kpmap_dir: str, kp2d_score_dir: Optional[str] = None, kp2d_canvas_shape=(1024, 1024),
                   out_kpmap_shape=(1024, 1024), spa_labels=None, tem_labels=None, image_ext: str = ".webp", image_quality: int = 85,
                   num_workers: int = 16, skip_exists: bool = False, palette=None, device="cuda", kp3d_dir: Optional[str] = None,
-                  camera_path: Optional[str] = None, intri_scale: Optional[float] = None) -> Dict:
+                  camera_path: Optional[str] = None, intri_scale: Optional[float] = None, *, device_webp: bool = False) -> Dict:
     """Draw every selected frame of a scene (draw_skeleton.py:182-226): reads ``kp2d_dir/{spa:02d}/{tem:06d}.json`` (and the scores of
     the same path under `kp2d_score_dir`) and writes ``out_kpmap_dir/{spa:02d}/{tem:06d}{image_ext}``.  Labels are lists of integers or
     default to the sorted listings of `kp2d_dir` and of its first camera, and the output path is the input path with `kp2d_dir`
@@ -599,7 +606,14 @@ def draw_skeleton(kp2d_dir: Optional[str], out_kpmap_dir: str, kp2d_score_dir: O
     cameras `spa_labels` of `camera_path` -- triang.scene_cameras(camera_path, labels, intri_scale): un-normalised, float32 inverse,
     as triangulate_skeleton builds them -- through draw_skeleton_maps_kp3d: `kp2d_dir` is not read and need not exist, and the files
     written are byte for byte those drawn from the poses_2d directory triangulate_skeleton(out_kp2d_proj_dir=...) writes.  Labels
-    default to the sorted cameras of `camera_path` and the sorted listing of `kp3d_dir`.  The poses go up once; there is no plan phase."""
+    default to the sorted cameras of `camera_path` and the sorted listing of `kp3d_dir`.  The poses go up once; there is no plan phase.
+
+    With `device_webp` a batch's maps stay on the device where they are drawn (both routes) and are encoded there as lossless WebP
+    (host/webp.py; DESIGN.md "Device WebP (lossless)"): only the files' bytes cross PCIe, they are written verbatim, and they decode to
+    exactly the maps draw_skeleton_maps returns.  `image_ext` must be ".webp"; `image_quality` is ignored (nothing is lost); seconds
+    gains "encode" (the device encoder and the copy of its files), and "write" is the time waited for the file writes."""
+    if device_webp and image_ext != ".webp":
+        raise ValueError(f"draw_skeleton(device_webp=True) writes WebP files: image_ext must be '.webp', got {image_ext!r}")
     palette = load_palette(palette)
     _check_out_shape(out_kpmap_shape)
     dev = _l.hip_device(device, "draw_skeleton")
@@ -651,23 +665,32 @@ def draw_skeleton(kp2d_dir: Optional[str], out_kpmap_dir: str, kp2d_score_dir: O
             stats["read"] = time.perf_counter() - t0
         for b0 in range(0, len(todo), step):
             idx = todo[b0:b0 + step]
+            on_dev = torch.empty((len(idx), h, w, 3), dtype=torch.uint8, device=dev) if device_webp else None
             if from_kp3d:
                 t0 = time.perf_counter()
                 scores = None if kp2d_score_dir is None else np.stack(list(readers.map(_read_scores, [score_paths[i] for i in idx])))
                 t1 = time.perf_counter()
                 maps, dropped = draw_skeleton_maps_kp3d(scene, None, None, [(slot[labels[i][1]], labels[i][0]) for i in idx],
-                                                        (kp2d_canvas_shape, out_kpmap_shape), tables, scores=scores, device=dev)
+                                                        (kp2d_canvas_shape, out_kpmap_shape), tables, scores=scores, out=on_dev, device=dev)
                 stats["read"] += t1 - t0
                 stats["launch"] = stats.get("launch", 0.0) + time.perf_counter() - t1
                 stats["dropped_links"] = stats.get("dropped_links", 0) + int(dropped.sum())
             else:
                 maps = draw_skeleton_maps([kp2d_paths[i] for i in idx], [score_paths[i] for i in idx], kp2d_canvas_shape, out_kpmap_shape,
-                                          palette=palette, device=dev, stats=stats, pool=readers)
+                                          palette=palette, device=dev, stats=stats, pool=readers, out=on_dev)
+            if device_webp:
+                from . import webp
+                t0 = time.perf_counter()
+                files = webp.encode_webp_batch(list(maps))  # synchronises
+                stats["encode"] = stats.get("encode", 0.0) + time.perf_counter() - t0
             t0 = time.perf_counter()
             for f in pending:  # the previous batch's files; at most two batches of maps are alive
                 f.result()
             stats["write"] = stats.get("write", 0.0) + time.perf_counter() - t0
-            pending = [writers.submit(_save, out_paths[i], maps[k], image_quality) for k, i in enumerate(idx)]
+            if device_webp:
+                pending = [writers.submit(_write, out_paths[i], files[k]) for k, i in enumerate(idx)]
+            else:
+                pending = [writers.submit(_save, out_paths[i], maps[k], image_quality) for k, i in enumerate(idx)]
             counts["files"] += len(idx)
         t0 = time.perf_counter()
         for f in pending:

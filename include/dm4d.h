@@ -667,6 +667,33 @@ int dm4d_png_encode_u8(void* stream, const void* planes, int64_t planes_bytes, c
                        const int64_t* desc_dev, int n, void* workspace, int64_t workspace_bytes, void* blob, int64_t blob_bytes,
                        int64_t* out);
 
+/* Lossless WebP files on the device (webp.hip; diffuman4d_amd/host/webp.py, the `device_webp` route of host/skeleton.py::draw_skeleton):
+ *   n packed 8-bit RGB images of different sizes -> n complete files (RIFF framing + one VP8L chunk) back to back in blob.
+ *   tests/webp_model.py is the definition in numpy and DESIGN.md "Device WebP (lossless)" its text: no transform, no colour cache, one
+ *   group of five prefix codes per image; the pixels p = y w + x in stripes of DM4D_WEBP_STRIPE_PIXELS; a pixel's kind is U (equals
+ *   pixel p - w), else L (equals pixel p - 1), else literal; within a stripe a maximal run of one kind is cut into backward references
+ *   of at most 4096 pixels with distance plane code 1 (U) or 2 (L); canonical codes (lengths at most 15, and 7 for the code-length
+ *   code) from the image's histograms, sent as simple codes where at most two symbols below 256 are used.  Stripes are not byte
+ *   aligned: a stripe stores the bytes it fills alone and records its first and last partial bytes, which one lane per shared byte
+ *   ORs together in the last launch.  Integer only; five launches whatever n is; no workgroup waits on another; LDS integer atomics
+ *   only; a file depends on its image alone and is the same in every call.
+ * desc: n x DM4D_WEBP_FIELDS int64 = {h, w in 1..DM4D_WEBP_MAX_SIDE | byte offset of the image in `rgb` | its row stride in bytes
+ *   (>= 3 w) | index of its first pixel = the sum of h * w before it | index of its first stripe = the stripes before it | 0, 0}.
+ *   desc_host is the host copy of desc_dev, validated before anything is launched.
+ * dm4d_webp_bound(h, w) = 800 + 6 h w (0 out of range): a pixel costs at most 45 bits, the header and code tables less than 780 bytes.
+ *   blob_bytes >= the sum of the images' bounds, or the call is an error.
+ * out: device int64 [2 n] = n byte offsets into blob, then n lengths; the host copies blob[: offset[n - 1] + length[n - 1]].
+ * workspace: dm4d_webp_ws_bytes(sum of h * w, total stripes, n) bytes, 16-byte aligned (0 for counts out of range).                  */
+#define DM4D_WEBP_FIELDS 8
+#define DM4D_WEBP_MAX_SIDE 16383
+#define DM4D_WEBP_STRIPE_PIXELS 8192
+#define DM4D_WEBP_STRIPE_REC 3200
+#define DM4D_WEBP_IMAGE_REC 4096
+size_t dm4d_webp_bound(int h, int w);
+size_t dm4d_webp_ws_bytes(int64_t pixels, int64_t stripes, int n);
+int dm4d_webp_encode_u8(void* stream, const void* rgb, int64_t rgb_bytes, const int64_t* desc_host, const int64_t* desc_dev, int n,
+                        void* workspace, int64_t workspace_bytes, void* blob, int64_t blob_bytes, int64_t* out);
+
 /* Baseline JPEG files decoded on the device (jpegdec.hip; diffuman4d_amd/host/jpegdec.py): n files of the supported set (SOF0, 8 bits,
  *   one interleaved Huffman scan without restart markers, grayscale or YCbCr at 4:4:4 / 4:2:2 / 4:2:0 -- host/jpegdec.py::probe) ->
  *   their pixels, byte for byte libjpeg's default decompression (Huffman decoding, jidctint "islow", "fancy" up-sampling, the 16-bit

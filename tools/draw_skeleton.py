@@ -7,7 +7,8 @@ scripts/preprocess/draw_skeleton.py (the ``draw_skeleton`` action of preprocess.
 reads DATA/SCENE/poses_2d/{camera}/{frame}.json, writes DATA/SCENE/skeletons/{camera}/{frame}.webp and prints one JSON line with
 counts.  With ``--kp3d_dir DATA/SCENE/poses_3d --camera_path DATA/SCENE/transforms.json`` the maps come straight from the 3-D
 keypoints, projected into the cameras on the device: no poses_2d directory is read (``--kp2d_dir`` is then not needed), and the files
-are those drawn from the poses_2d that triangulate_skeleton writes.  The palette (keypoint colours, links, the colour of the two "x" links) is not part of this package: see
+are those drawn from the poses_2d that triangulate_skeleton writes.  With ``--device_webp`` the maps are encoded on the device as
+lossless WebP and only the files' bytes come down.  The palette (keypoint colours, links, the colour of the two "x" links) is not part of this package: see
 diffuman4d_amd.host.skeleton.load_palette for the file's layout.
 """
 from __future__ import annotations
@@ -47,6 +48,8 @@ def main(argv=None) -> int:
     ap.add_argument("--skip_exists", action="store_true", help="leave files that exist and that Pillow verifies")
     ap.add_argument("--palette", required=True, help="JSON file with keypoint_colors, links and x_link_color")
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--device_webp", action="store_true",
+                    help="encode the maps on the GPU as lossless WebP: the files decode to exactly the maps; --image_ext must be .webp, --image_quality is ignored")
     args = ap.parse_args(argv)
     if (args.kp3d_dir is None) != (args.camera_path is None):
         ap.error("--kp3d_dir and --camera_path go together")
@@ -58,7 +61,7 @@ def main(argv=None) -> int:
                                  spa_labels=args.spa_labels, tem_labels=args.tem_labels, image_ext=args.image_ext,
                                  image_quality=args.image_quality, num_workers=args.num_workers, skip_exists=args.skip_exists,
                                  palette=args.palette, device=args.device, kp3d_dir=args.kp3d_dir, camera_path=args.camera_path,
-                                 intri_scale=args.intri_scale)
+                                 intri_scale=args.intri_scale, device_webp=args.device_webp)
     print(json.dumps(res))
     return 0
 

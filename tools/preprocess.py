@@ -71,10 +71,11 @@ def parse_actions(text) -> list:
 
 def run(data_dir: str, actions, *, matting_model_dir=None, sapiens_ckpt_path=None, palette=None, batch_size: int = 8,
         device_png: bool = False, device_decode: bool = False, person_detector=None, bbox_source=None, bbox_thr=None, nms_thr=None,
-        det_shape=None, skeleton_from: str = "kp2d") -> list:
+        det_shape=None, skeleton_from: str = "kp2d", device_webp: bool = False) -> list:
     """Run `actions` on the scene under `data_dir` (preprocess.sh:31-77) -> [(action, what its stage returned)].  person_detector,
     bbox_source, bbox_thr, nms_thr, det_shape: handed to predict_keypoints when given.  skeleton_from="kp3d": triangulate_skeleton
-    writes no poses_2d directory and draw_skeleton projects poses_3d into the cameras of transforms.json on the device (the same maps)."""
+    writes no poses_2d directory and draw_skeleton projects poses_3d into the cameras of transforms.json on the device (the same maps).
+    device_webp: draw_skeleton encodes its maps on the device as lossless WebP (the files decode to exactly the maps)."""
     if skeleton_from not in ("kp2d", "kp3d"):
         raise ValueError(f"skeleton_from must be 'kp2d' or 'kp3d', got {skeleton_from!r}")
     d = str(data_dir)
@@ -97,9 +98,10 @@ def run(data_dir: str, actions, *, matting_model_dir=None, sapiens_ckpt_path=Non
             extra = {"out_kp2d_proj_dir": f"{d}/poses_2d"} if skeleton_from == "kp2d" else {}
             res = STAGES[act](f"{d}/transforms.json", f"{d}/poses_sapiens", f"{d}/poses_3d", out_pcd_dir=f"{d}/poses_pcd", **extra)
         elif skeleton_from == "kp3d":
-            res = STAGES[act](None, f"{d}/skeletons", palette=palette, kp3d_dir=f"{d}/poses_3d", camera_path=f"{d}/transforms.json")
+            res = STAGES[act](None, f"{d}/skeletons", palette=palette, kp3d_dir=f"{d}/poses_3d", camera_path=f"{d}/transforms.json",
+                              **({"device_webp": True} if device_webp else {}))
         else:
-            res = STAGES[act](f"{d}/poses_2d", f"{d}/skeletons", palette=palette)
+            res = STAGES[act](f"{d}/poses_2d", f"{d}/skeletons", palette=palette, **({"device_webp": True} if device_webp else {}))
         out.append((act, res))
     return out
 
@@ -122,6 +124,7 @@ def main(argv=None) -> int:
     ap.add_argument("--device_decode", action="store_true", help="remove_background: decode baseline JPEG inputs on the GPU; carve_vhull: decode the PNG masks there; predict_keypoints: decode JPEG / PNG images and PNG masks there (same files written)")
     ap.add_argument("--skeleton_from", choices=("kp2d", "kp3d"), default="kp2d",
                     help="kp3d: triangulate_skeleton writes no poses_2d/ and draw_skeleton draws from poses_3d/ and transforms.json (the same maps)")
+    ap.add_argument("--device_webp", action="store_true", help="draw_skeleton: encode the maps on the GPU as lossless WebP (the files decode to exactly the maps)")
     args = ap.parse_args(argv)
     try:
         actions = parse_actions(args.actions)
@@ -137,7 +140,7 @@ def main(argv=None) -> int:
     for act, res in run(args.data_dir, actions, matting_model_dir=args.matting_model_dir, sapiens_ckpt_path=args.sapiens_ckpt_path,
                         palette=args.palette, batch_size=args.batch_size, device_png=args.device_png, device_decode=args.device_decode,
                         person_detector=args.person_detector, bbox_source=args.bbox_source, bbox_thr=args.bbox_thr, nms_thr=args.nms_thr,
-                        det_shape=args.det_shape, skeleton_from=args.skeleton_from):
+                        det_shape=args.det_shape, skeleton_from=args.skeleton_from, device_webp=args.device_webp):
         print(json.dumps({"action": act, "result": res}, default=str))
     return 0
 

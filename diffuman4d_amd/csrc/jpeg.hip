@@ -27,6 +27,7 @@
 #include "dm4d.h"
 #include "errors.h"
 #include "image_common.h"
+#include "stripe_emit.h"
 
 namespace {
 
@@ -388,9 +389,7 @@ __global__ void __launch_bounds__(kScanThreads) jpeg_scan_ff_kernel(const int64_
 
 // ONE block: offs[i] = sum of lens[0 .. i)
 __global__ void __launch_bounds__(kScanThreads) jpeg_offsets_kernel(const int64_t* __restrict__ lens, int64_t* __restrict__ offs, int n) {
-  for (int i = threadIdx.x; i < n; i += kScanThreads) offs[i] = lens[i];
-  __syncthreads();
-  block_excl_scan_inplace<int64_t, kScanThreads>(offs, n);
+  offsets_block<kScanThreads>(lens, offs, n);
 }
 
 __global__ void __launch_bounds__(kStuffThreads) jpeg_stuff_kernel(const int64_t* __restrict__ desc, const uint8_t* __restrict__ raw,
@@ -460,7 +459,6 @@ __global__ void __launch_bounds__(kWave) restore_vpass_kernel(const int64_t* __r
 bool size_ok(int64_t v) { return v >= 1 && v <= 65535; }
 int64_t mcus_of(int64_t h, int64_t w) { return ((h + 15) / 16) * ((w + 15) / 16); }
 int64_t chunks_of(int64_t mcus) { return (mcus * DM4D_JPEG_MCU_UNSTUFFED + DM4D_JPEG_CHUNK - 1) / DM4D_JPEG_CHUNK; }
-int64_t pad16(int64_t v) { return (v + 15) / 16 * 16; }
 constexpr int64_t kMaxMcus = (1ll << 32) / kMcuBits;  // an image's bit positions are 32-bit
 constexpr int64_t kMaxTotalMcus = 1ll << 28;
 

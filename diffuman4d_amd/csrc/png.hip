@@ -4,7 +4,9 @@
 // bytes become a literal plus distance-1 matches; one dynamic-Huffman block per stripe whose canonical code is built here from the
 // stripe's histogram; an empty stored block after it, so that every stripe is whole bytes and is its own IDAT chunk.
 //
-// Five launches on one stream for the whole batch; launch boundaries are the only ordering between workgroups:
+// Five launches on one stream for the whole batch; launch boundaries are the only ordering between workgroups.  The run finder of
+// `stripe`, the bit window of `emit` and the body of `offsets` are stripe_emit.h's, shared with webp.hip; the code lengths are
+// prefix_code.h's:
 //   filter   one lane per pixel: the filtered scanlines to the workspace (an RGBA pixel is read from the packed RGB image and the alpha
 //            plane; no RGBA buffer exists)
 //   stripe   one workgroup per stripe: run boundaries per lane segment, the token of every byte position to the workspace (uint16:
@@ -22,6 +24,7 @@
 #include "errors.h"
 #include "image_common.h"
 #include "prefix_code.h"
+#include "stripe_emit.h"
 
 namespace {
 
@@ -30,7 +33,6 @@ constexpr int kScanThreads = 1024;
 constexpr int kSyms = 286;                 // literal / length symbols
 constexpr int kSeq = 288;                  // + the two distance codes
 constexpr int kPer = 16;                   // byte positions per lane and round of the emitter
-constexpr int kRound = kThreads * kPer;
 constexpr int kWinWords = 2704;            // 7 + 4096 x 21 bits and slack
 constexpr int kHdrWords = 136;             // 17 + 57 + 288 x 14 bits at most
 constexpr int kRecWords = DM4D_PNG_STRIPE_REC / 4;
@@ -138,38 +140,13 @@ __global__ void __launch_bounds__(kThreads) png_stripe_kernel(const int64_t* __r
   for (int i = tid; i < kHdrWords; i += kThreads) hdr[i] = 0;
   if (tid < 20) clfreq[tid] = 0;
   if (tid == 0) xbits = 0, a1 = 0, a2 = 0;
-  // pass 1 over this lane's segment [a, b): the first and the last run start in it, and the Adler sums
-  const int L = (S + kThreads - 1) / kThreads;
-  const int a = min(tid * L, S), b = min(a + L, S);
-  int first = S, last = -1;
-  {
-    uint64_t s1 = 0, s2 = 0;
-    int prev = a > 0 ? f[a - 1] : -1;
-    for (int i = a; i < b; ++i) {
-      const int v = f[i];
-      if (v != prev) {
-        if (first == S) first = i;
-        last = i;
-      }
-      prev = v;
-      s1 += (uint32_t)v, s2 += (uint64_t)(uint32_t)(S - i) * (uint32_t)v;
-    }
-    sh_first[tid] = first, sh_last[tid] = last;
-    __syncthreads();
-    if (a < b) atomicAdd(&a1, (uint32_t)(s1 % kAdler)), atomicAdd(&a2, (uint32_t)(s2 % kAdler));
-  }
-  // the run that reaches into the segment started at s_in; the one that leaves it ends at e_out
-  int s_in = 0, e_out = S;
-  for (int u = tid - 1; u >= 0; --u)
-    if (sh_last[u] >= 0) {
-      s_in = sh_last[u];
-      break;
-    }
-  for (int u = tid + 1; u < kThreads; ++u)
-    if (sh_first[u] < S) {
-      e_out = sh_first[u];
-      break;
-    }
+  // pass 1: the runs that reach over this lane's segment [a, b) (stripe_emit.h), and the Adler sums
+  uint64_t s1 = 0, s2 = 0;
+  const LaneRuns lr = lane_runs<kThreads>(
+      S, sh_first, sh_last, [&](int i) { return (int)f[i]; }, [](int prev, int v) { return v != prev; },
+      [&](int i, int v) { s1 += (uint32_t)v, s2 += (uint64_t)(uint32_t)(S - i) * (uint32_t)v; });
+  const int a = lr.a, b = lr.b, s_in = lr.s_in, e_out = lr.e_out;
+  if (a < b) atomicAdd(&a1, (uint32_t)(s1 % kAdler)), atomicAdd(&a2, (uint32_t)(s2 % kAdler));
   // pass 2: run by run; every position gets its token
   for (int i = a; i < b;) {
     const int v = f[i];
@@ -279,9 +256,7 @@ __global__ void __launch_bounds__(kScanThreads) png_scan_kernel(const int64_t* _
 
 // ONE block: offs[i] = sum of lens[0 .. i)
 __global__ void __launch_bounds__(kScanThreads) png_offsets_kernel(const int64_t* __restrict__ lens, int64_t* __restrict__ offs, int n) {
-  for (int i = threadIdx.x; i < n; i += kScanThreads) offs[i] = lens[i];
-  __syncthreads();
-  block_excl_scan_inplace<int64_t, kScanThreads>(offs, n);
+  offsets_block<kScanThreads>(lens, offs, n);
 }
 
 // -- emit ----------------------------------------------------------------------------------------------------------------------------------
@@ -315,7 +290,7 @@ __global__ void __launch_bounds__(kThreads) png_emit_kernel(const int64_t* __res
   const Image im = image_of(desc, blockIdx.y);
   const int s = blockIdx.x;
   if (s >= im.stripes) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const bool first_stripe = s == 0, last_stripe = s == im.stripes - 1;
   const int row0 = s * im.rows, nrows = min(im.rows, im.h - row0);
   const int S = (int)(nrows * im.R);
@@ -331,61 +306,30 @@ __global__ void __launch_bounds__(kThreads) png_emit_kernel(const int64_t* __res
   for (int i = tid; i < kSeq; i += kThreads) tab[i] = rec[i];
   const uint32_t hdr_bits = rec[kRecMeta];
   const uint8_t* hdr = reinterpret_cast<const uint8_t*>(rec + kRecHdr);
-  uint32_t done = hdr_bits >> 3;
+  uint64_t done = hdr_bits >> 3;
   int carry_bits = (int)(hdr_bits & 7u);
   for (uint32_t i = tid; i < done; i += kThreads)
     if (i < cap) d[i] = hdr[i];
   for (int i = tid; i < kWinWords; i += kThreads) win[i] = (i == 0 && carry_bits) ? hdr[done] : 0u;
   __syncthreads();
-  for (int base = 0; base < S; base += kRound) {
-    uint32_t v[kPer];
-    int nb[kPer];
-    int tot = 0;
-    const int p0 = base + tid * kPer;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const int p = p0 + k;
-      const uint32_t t = p < S ? tk[p] : kNone;
-      v[k] = 0, nb[k] = 0;
-      if (t < 256u) {
-        const uint32_t e = tab[t];
-        v[k] = e & 0xffffu, nb[k] = (int)(e >> 16);
-      } else if (t != kNone) {
-        const int len = (int)t - 256, li = kLen.idx[len];
-        const uint32_t e = tab[257 + li];
-        const int l = (int)(e >> 16);
-        v[k] = (e & 0xffffu) | ((uint32_t)(len - kLen.base[li]) << l);
-        nb[k] = l + kLen.extra[li] + 1;  // the distance code (0, one bit) is the top bit
-      }
-      tot += nb[k];
-    }
-    const int incl = wave_incl_scan(tot);
-    if (lane == 63) wave_tot[wave] = (uint32_t)incl;
-    __syncthreads();
-    int pos = carry_bits + incl - tot, T = carry_bits;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-      if (w < wave) pos += (int)wave_tot[w];
-      T += (int)wave_tot[w];
-    }
-#pragma unroll
-    for (int k = 0; k < kPer; ++k)
-      if (nb[k]) {
-        const int i = pos >> 5, sh = pos & 31;
-        atomicOr(&win[i], v[k] << sh);
-        if (sh + nb[k] > 32) atomicOr(&win[i + 1], v[k] >> (32 - sh));
-        pos += nb[k];
-      }
-    __syncthreads();
-    const uint32_t nbytes = (uint32_t)T >> 3;
-    for (uint32_t i = tid; i < nbytes; i += kThreads)
-      if (done + i < cap) d[done + i] = (uint8_t)(win[i >> 2] >> (8 * (i & 3)));
-    const uint32_t carry = (T & 7) ? (win[nbytes >> 2] >> (8 * (nbytes & 3))) & 0xffu : 0u;
-    __syncthreads();
-    for (int i = tid; i < kWinWords; i += kThreads) win[i] = i == 0 ? carry : 0u;
-    __syncthreads();
-    done += nbytes, carry_bits = T & 7;
-  }
+  emit_window<kThreads, kPer, kWinWords, uint32_t>(
+      S, win, wave_tot, carry_bits, done,
+      [&](int p, uint32_t& v, int& nb) {
+        const uint32_t t = p < S ? tk[p] : kNone;
+        if (t < 256u) {
+          const uint32_t e = tab[t];
+          v = e & 0xffffu, nb = (int)(e >> 16);
+        } else if (t != kNone) {
+          const int len = (int)t - 256, li = kLen.idx[len];
+          const uint32_t e = tab[257 + li];
+          const int l = (int)(e >> 16);
+          v = (e & 0xffffu) | ((uint32_t)(len - kLen.base[li]) << l);
+          nb = l + kLen.extra[li] + 1;  // the distance code (0, one bit) is the top bit
+        }
+      },
+      [&](uint64_t i, uint32_t byte) {
+        if (i < cap) d[i] = (uint8_t)byte;
+      });
   if (tid == 0) {
     // end of block, then the empty stored block that brings the stripe to a byte boundary
     uint64_t acc = win[0];
@@ -398,7 +342,7 @@ __global__ void __launch_bounds__(kThreads) png_emit_kernel(const int64_t* __res
     const uint8_t stored[4] = {0, 0, 0xff, 0xff};
     for (int i = 0; i < 4; ++i, ++done)
       if (done < cap) d[done] = stored[i];
-    uint32_t datalen = done + (first_stripe ? 2u : 0u);
+    uint32_t datalen = (uint32_t)done + (first_stripe ? 2u : 0u);
     if (last_stripe) put_be32(d + done, adler[blockIdx.y]), datalen += 4;
     put_be32(ck, datalen);
     ck[4] = 'I', ck[5] = 'D', ck[6] = 'A', ck[7] = 'T';
@@ -445,7 +389,6 @@ __global__ void __launch_bounds__(kThreads) png_emit_kernel(const int64_t* __res
 
 // -- host ----------------------------------------------------------------------------------------------------------------------------------
 bool side_ok(int64_t v) { return v >= 1 && v <= DM4D_MATTING_MAX_SIDE; }
-int64_t pad16(int64_t v) { return (v + 15) / 16 * 16; }
 int64_t stripes_of(int64_t h, int64_t R) {
   const int64_t rows = rows_of(R);
   return (h + rows - 1) / rows;
@@ -470,11 +413,6 @@ Layout layout_of(int64_t filtered, int64_t stripes, int64_t n) {
   l.adler = l.clen + pad16((stripes + 1) * 4);
   l.total = l.adler + pad16(n * 4);
   return l;
-}
-
-// the h rows of `row` bytes, `stride` apart, that start at `off` lie inside a buffer of `bytes`
-bool plane_ok(int64_t off, int64_t stride, int64_t h, int64_t row, int64_t bytes) {
-  return off >= 0 && stride >= row && stride <= (1ll << 32) && off <= bytes && (h - 1) * stride + row <= bytes - off;
 }
 
 }  // namespace

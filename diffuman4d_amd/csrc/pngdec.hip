@@ -25,6 +25,7 @@
 #include "common.h"
 #include "dm4d.h"
 #include "errors.h"
+#include "stripe_emit.h"
 
 namespace {
 
@@ -565,13 +566,11 @@ __global__ void __launch_bounds__(64) pngdec_unfilter_kernel(const int64_t* __re
   if (__ballot(bad) != 0ull && threadIdx.x == 0) status[blockIdx.x] = DM4D_PNGDEC_ST_FILTER;
 }
 
-int64_t align16(int64_t v) { return (v + 15) / 16 * 16; }
-
 }  // namespace
 
 extern "C" size_t dm4d_png_decode_ws_bytes(int64_t total_filtered_bytes, int n) {
   if (total_filtered_bytes <= 0 || total_filtered_bytes > kMaxWorkspace || n <= 0 || n > 65535) return 0;
-  return (size_t)align16(total_filtered_bytes);
+  return (size_t)pad16(total_filtered_bytes);
 }
 
 extern "C" int dm4d_png_decode_u8(void* stream, const void* streams, int64_t streams_bytes, const int64_t* desc_host, const int64_t* desc_dev,
@@ -594,7 +593,7 @@ extern "C" int dm4d_png_decode_u8(void* stream, const void* streams, int64_t str
     if (d[D_OUT] < 0 || d[D_OUT] > out_bytes || h * w * ch > out_bytes - d[D_OUT])
       return dm4d_set_error(DM4D_ERR_ARG, "png_decode: an image lies outside the output buffer");
     if (d[D_WS] != ws0) return dm4d_set_error(DM4D_ERR_ARG, "png_decode: a descriptor's workspace offset is not the running sum");
-    ws0 += align16(h * (1 + w * ch));
+    ws0 += pad16(h * (1 + w * ch));
     if (ws0 > kMaxWorkspace) return dm4d_set_error(DM4D_ERR_ARG, "png_decode: too many bytes in one batch");
   }
   if (workspace_bytes < ws0) return dm4d_set_error(DM4D_ERR_ARG, "png_decode: workspace too small (dm4d_png_decode_ws_bytes)");

@@ -1,6 +1,7 @@
 // Length-limited canonical prefix codes built by one workgroup, and a one-lane bit writer: what the device encoders of deflate (png.hip)
-// and of VP8L (webp.hip) share.  The rule is tests/png_model.py's code_lengths / canonical.  Integer arithmetic; the one atomic is an
-// LDS-local integer add whose result does not depend on its order.
+// and of VP8L (webp.hip) share in building their codes.  The rule is tests/png_model.py's code_lengths / canonical.  Their run finder
+// and the emitter that puts the codes into the stream are in stripe_emit.h.  Integer arithmetic; the one atomic is an LDS-local integer
+// add whose result does not depend on its order.
 #pragma once
 #include <stdint.h>
 

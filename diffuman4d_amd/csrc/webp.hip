@@ -4,7 +4,9 @@
 // function of the pixels alone; within a stripe of DM4D_WEBP_STRIPE_PIXELS pixels a maximal run of one kind is cut into backward
 // references of at most 4096 pixels (distance plane code 1 or 2).
 //
-// Five launches on one stream for the whole batch; launch boundaries are the only ordering between workgroups:
+// Five launches on one stream for the whole batch; launch boundaries are the only ordering between workgroups.  The run finder of
+// `tokens`, the bit window of `emit` and the body of `offsets` are stripe_emit.h's, shared with png.hip; the code lengths are
+// prefix_code.h's:
 //   tokens   one workgroup per stripe: kinds to LDS, run boundaries per lane segment, the token of every pixel to the workspace (uint16:
 //            literal, kind + length of a reference, or none), the stripe's histograms (integer LDS atomics) and extra-bit count
 //   image    one workgroup per image: the histograms summed, the five codes (prefix_code.h), the header and code tables, every stripe's
@@ -22,6 +24,7 @@
 #include "errors.h"
 #include "image_common.h"
 #include "prefix_code.h"
+#include "stripe_emit.h"
 
 namespace {
 
@@ -38,7 +41,6 @@ constexpr int kIrecWords = DM4D_WEBP_IMAGE_REC / 4;
 constexpr int kHdrAt = 800, kHdrWords = 192;         // 43 + 2023 + 2 x 1855 + 11 + 12 bits at most
 constexpr int kMetaAt = kHdrAt + kHdrWords;          // header bits | payload bits lo, hi | 0
 constexpr int kPer = 8;                              // pixels per lane and round of the emitter
-constexpr int kRound = kThreads * kPer;
 constexpr int kWinWords = 2884;                      // 7 + 2048 x 45 bits and slack
 constexpr int kFraming = 20;                         // RIFF, size, WEBP, VP8L, size
 constexpr uint16_t kNone = 0xffffu, kLiteral = 0x8000u, kLeft = 0x4000u;
@@ -106,31 +108,10 @@ __global__ void __launch_bounds__(kThreads) webp_tokens_kernel(const int64_t* __
     kind[i] = (uint8_t)k;
   }
   __syncthreads();
-  // pass 1 over this lane's segment [a, b): the first and the last run start in it (a literal is a run of its own)
-  const int L = (P + kThreads - 1) / kThreads;
-  const int a = min(tid * L, P), b = min(a + L, P);
-  int first = P, last = -1;
-  for (int i = a; i < b; ++i) {
-    const int k = kind[i];
-    if (i == 0 || k == 0 || k != kind[i - 1]) {
-      if (first == P) first = i;
-      last = i;
-    }
-  }
-  sh_first[tid] = first, sh_last[tid] = last;
-  __syncthreads();
-  // the run that reaches into the segment started at s_in; the one that leaves it ends at e_out
-  int s_in = 0, e_out = P;
-  for (int u = tid - 1; u >= 0; --u)
-    if (sh_last[u] >= 0) {
-      s_in = sh_last[u];
-      break;
-    }
-  for (int u = tid + 1; u < kThreads; ++u)
-    if (sh_first[u] < P) {
-      e_out = sh_first[u];
-      break;
-    }
+  // pass 1: the runs that reach over this lane's segment [a, b) (stripe_emit.h; a literal is a run of its own)
+  const LaneRuns lr = lane_runs<kThreads>(
+      P, sh_first, sh_last, [&](int i) { return (int)kind[i]; }, [](int prev, int k) { return k == 0 || k != prev; }, [](int, int) {});
+  const int a = lr.a, b = lr.b, s_in = lr.s_in, e_out = lr.e_out;
   // pass 2: run by run; every position gets its token
   for (int i = a; i < b;) {
     const int k = kind[i];
@@ -271,9 +252,7 @@ __global__ void __launch_bounds__(kThreads) webp_image_kernel(const int64_t* __r
 
 // ONE block: offs[i] = sum of lens[0 .. i)
 __global__ void __launch_bounds__(kScanThreads) webp_offsets_kernel(const int64_t* __restrict__ lens, int64_t* __restrict__ offs, int n) {
-  for (int i = threadIdx.x; i < n; i += kScanThreads) offs[i] = lens[i];
-  __syncthreads();
-  block_excl_scan_inplace<int64_t, kScanThreads>(offs, n);
+  offsets_block<kScanThreads>(lens, offs, n);
 }
 
 // -- emit ----------------------------------------------------------------------------------------------------------------------------------
@@ -289,7 +268,7 @@ __global__ void __launch_bounds__(kThreads) webp_emit_kernel(const int64_t* __re
   const Image im = image_of(desc, blockIdx.y);
   const int s = blockIdx.x;
   if (s >= im.stripes) return;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int p0 = s * kStripe, P = min(kStripe, im.N - p0);
   const uint16_t* tk = tok + im.pix0 + p0;
   const uint32_t* irec = irecs + (int64_t)blockIdx.y * kIrecWords;
@@ -320,66 +299,32 @@ __global__ void __launch_bounds__(kThreads) webp_emit_kernel(const int64_t* __re
   uint64_t done = 0;
   int carry_bits = (int)(begin & 7);
   uint32_t head = 0;
-  for (int base = 0; base < P; base += kRound) {
-    uint64_t v[kPer];
-    int nb[kPer];
-    int tot = 0;
-    const int q0 = base + tid * kPer;
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const int q = q0 + k;
-      const uint32_t t = q < P ? tk[q] : kNone;
-      v[k] = 0, nb[k] = 0;
-      if (t == kLiteral) {
-        const uint8_t* c = pixel_at(rgb, im, p0 + q);
-        const uint32_t eg = tab[kG + c[1]], er = tab[kR + c[0]], eb = tab[kB + c[2]];
-        const int lg = (int)(eg >> 16), lr = (int)(er >> 16), lb = (int)(eb >> 16);
-        v[k] = (uint64_t)(eg & 0xffffu) | ((uint64_t)(er & 0xffffu) << lg) | ((uint64_t)(eb & 0xffffu) << (lg + lr));
-        nb[k] = lg + lr + lb;
-      } else if (t != kNone) {
-        int sym, extra;
-        uint32_t ev;
-        length_prefix((int)(t & 0xfffu) + 1, sym, extra, ev);
-        const uint32_t e = tab[kG + 256 + sym], d = tab[kD + ((t & kLeft) ? 1 : 0)];
-        const int l = (int)(e >> 16);
-        v[k] = (uint64_t)(e & 0xffffu) | ((uint64_t)ev << l) | ((uint64_t)(d & 0xffffu) << (l + extra));
-        nb[k] = l + extra + (int)(d >> 16);
-      }
-      tot += nb[k];
-    }
-    const int incl = wave_incl_scan(tot);
-    if (lane == 63) wave_tot[wave] = (uint32_t)incl;
-    __syncthreads();
-    int pos = carry_bits + incl - tot, T = carry_bits;
-#pragma unroll
-    for (int w = 0; w < kThreads / 64; ++w) {
-      if (w < wave) pos += (int)wave_tot[w];
-      T += (int)wave_tot[w];
-    }
-#pragma unroll
-    for (int k = 0; k < kPer; ++k)
-      if (nb[k]) {
-        const int i = pos >> 5, sh = pos & 31;
-        atomicOr(&win[i], (uint32_t)(v[k] << sh));
-        if (sh + nb[k] > 32) atomicOr(&win[i + 1], (uint32_t)(v[k] >> (32 - sh)));
-        if (sh + nb[k] > 64) atomicOr(&win[i + 2], (uint32_t)(v[k] >> (64 - sh)));
-        pos += nb[k];
-      }
-    __syncthreads();
-    const uint32_t nbytes = (uint32_t)T >> 3;
-    for (uint32_t i = tid; i < nbytes; i += kThreads) {
-      const uint32_t byte = (win[i >> 2] >> (8 * (i & 3))) & 0xffu;
-      if (done + i == 0 && head_partial)
-        head = byte;  // lane 0: the stripe's first byte holds bits of the piece before it
-      else if (done + i < room)
-        out[done + i] = (uint8_t)byte;
-    }
-    const uint32_t carry = (T & 7) ? (win[nbytes >> 2] >> (8 * (nbytes & 3))) & 0xffu : 0u;
-    __syncthreads();
-    for (int i = tid; i < kWinWords; i += kThreads) win[i] = i == 0 ? carry : 0u;
-    __syncthreads();
-    done += nbytes, carry_bits = T & 7;
-  }
+  emit_window<kThreads, kPer, kWinWords, uint64_t>(
+      P, win, wave_tot, carry_bits, done,
+      [&](int q, uint64_t& v, int& nb) {
+        const uint32_t t = q < P ? tk[q] : kNone;
+        if (t == kLiteral) {
+          const uint8_t* c = pixel_at(rgb, im, p0 + q);
+          const uint32_t eg = tab[kG + c[1]], er = tab[kR + c[0]], eb = tab[kB + c[2]];
+          const int lg = (int)(eg >> 16), lr = (int)(er >> 16), lb = (int)(eb >> 16);
+          v = (uint64_t)(eg & 0xffffu) | ((uint64_t)(er & 0xffffu) << lg) | ((uint64_t)(eb & 0xffffu) << (lg + lr));
+          nb = lg + lr + lb;
+        } else if (t != kNone) {
+          int sym, extra;
+          uint32_t ev;
+          length_prefix((int)(t & 0xfffu) + 1, sym, extra, ev);
+          const uint32_t e = tab[kG + 256 + sym], d = tab[kD + ((t & kLeft) ? 1 : 0)];
+          const int l = (int)(e >> 16);
+          v = (uint64_t)(e & 0xffffu) | ((uint64_t)ev << l) | ((uint64_t)(d & 0xffffu) << (l + extra));
+          nb = l + extra + (int)(d >> 16);
+        }
+      },
+      [&](uint64_t i, uint32_t byte) {
+        if (i == 0 && head_partial)
+          head = byte;  // lane 0: the stripe's first byte holds bits of the piece before it
+        else if (i < room)
+          out[i] = (uint8_t)byte;
+      });
   if (tid == 0) {
     // the last, partial byte: the stripe's tail -- or its head, where the whole stripe lies inside the byte it starts in
     uint32_t tail = 0;
@@ -420,7 +365,6 @@ __global__ void __launch_bounds__(kThreads) webp_seam_kernel(const int64_t* __re
 
 // -- host ----------------------------------------------------------------------------------------------------------------------------------
 bool side_ok(int64_t v) { return v >= 1 && v <= DM4D_WEBP_MAX_SIDE; }
-int64_t pad16(int64_t v) { return (v + 15) / 16 * 16; }
 int64_t stripes_of(int64_t h, int64_t w) { return (h * w + kStripe - 1) / kStripe; }
 int64_t bound_of(int64_t h, int64_t w) { return 800 + 6 * h * w; }
 constexpr int64_t kMaxPixels = 1ll << 38;
@@ -465,7 +409,7 @@ extern "C" int dm4d_webp_encode_u8(void* stream, const void* rgb, int64_t rgb_by
     const int64_t h = d[W_H], w = d[W_W], off = d[W_PIX], stride = d[W_STRIDE];
     if (!side_ok(h) || !side_ok(w)) return dm4d_set_error(DM4D_ERR_ARG, "webp_encode: a dimension outside 1..DM4D_WEBP_MAX_SIDE in a descriptor");
     if (stride < 3 * w || stride > (1ll << 32)) return dm4d_set_error(DM4D_ERR_ARG, "webp_encode: a row stride below 3 w (or above 2^32) in a descriptor");
-    if (off < 0 || off > rgb_bytes || (h - 1) * stride + 3 * w > rgb_bytes - off)
+    if (!plane_ok(off, stride, h, 3 * w, rgb_bytes))
       return dm4d_set_error(DM4D_ERR_ARG, "webp_encode: an image lies outside its buffer");
     if (d[W_PIX0] != pix0 || d[W_STRIPE0] != stripe0) return dm4d_set_error(DM4D_ERR_ARG, "webp_encode: a descriptor's first pixel or first stripe is not the running sum");
     for (int k = W_STRIPE0 + 1; k < DM4D_WEBP_FIELDS; ++k)

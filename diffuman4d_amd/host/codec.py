@@ -1,8 +1,9 @@
-"""What the image codecs (``jpeg``, ``png``, ``jpegdec``, ``pngdec``) and their consumers (``metrics``, ``matting``, ``vhull``,
+"""What the image codecs (``jpeg``, ``png``, ``webp``, ``jpegdec``, ``pngdec``) and their consumers (``metrics``, ``matting``, ``vhull``,
 ``capture``, ``pose``) say around the library calls, written once:
 
   * ``read_file``, ``pillow_pixels``: a file's bytes, and the Pillow route of a file;
   * ``chunks``: the ranges of a batch whose device memory stays within a budget;
+  * ``require_device_u8``, ``gather``: an encoder's check of an input tensor, and its inputs as places in one device buffer;
   * ``workspace``, ``read_back``: the workspace tensor of a call, and the files of an encoder call brought to the host;
   * ``decode_plans``, ``decode_batch``: the bodies of a decoder module's ``decode_plans`` and ``decode_*_batch``;
   * ``decode_or_fallback``: one ``decode_plans`` call into a consumer's buffer, the refused files filled in by the consumer;
@@ -60,6 +61,35 @@ def workspace(nbytes: int, dev):
     """An uninitialised device workspace of at least `nbytes`, in 16-byte units (an int64 tensor: ``numel() * 8`` bytes)."""
     import torch
     return torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+
+
+def require_device_u8(t, name: str):
+    """`t` is a uint8 tensor on a HIP device, or a Dm4dError that names it `name`."""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
+        raise _l.Dm4dError(f"{name}: expected a tensor on a HIP device (no CPU fallback in diffuman4d_amd)")
+    if t.dtype != torch.uint8:
+        raise _l.Dm4dError(f"{name}: expected uint8, got {t.dtype}")
+    return t
+
+
+def gather(tensors, bpp: int):
+    """Tensors [h, w] (`bpp` 1) or [h, w, bpp] of one byte a channel -> (one uint8 buffer, [(byte offset, row stride)]): the tensors'
+    common storage where they share one and their pixels are contiguous within a row, else a copy of them back to back.  The stride
+    of a dimension of size 1 says nothing: a one-row view's row stride is at least its row."""
+    import torch
+    base = tensors[0].untyped_storage().data_ptr()
+    rows_ok = all(t.stride(1) == bpp and (bpp == 1 or t.stride(2) == 1) and (t.shape[0] == 1 or t.stride(0) >= t.shape[1] * bpp)
+                  for t in tensors)
+    if rows_ok and all(t.untyped_storage().data_ptr() == base for t in tensors):
+        buf = torch.empty(0, dtype=torch.uint8, device=tensors[0].device).set_(tensors[0].untyped_storage())
+        return buf, [(t.data_ptr() - base, max(int(t.stride(0)), int(t.shape[1]) * bpp)) for t in tensors]
+    buf = torch.cat([t.reshape(-1) for t in tensors])
+    at, off = [], 0
+    for t in tensors:
+        at.append((off, int(t.shape[1]) * bpp))
+        off += t.numel()
+    return buf, at
 
 
 def read_back(blob, out) -> List[bytes]:

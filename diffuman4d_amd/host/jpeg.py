@@ -140,15 +140,8 @@ def jpeg_encode_chunk(images, crops, sizes, qtab) -> list:
         if img.device != dev or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
             raise _l.Dm4dError(f"images[{k}]: expected a contiguous uint8 [H, W, 3] tensor on {dev}, got {tuple(img.shape)} on {img.device}")
     with torch.cuda.device(dev):
-        base = images[0].untyped_storage().data_ptr()
-        if all(img.untyped_storage().data_ptr() == base for img in images):
-            pixels = torch.empty(0, dtype=torch.uint8, device=dev).set_(images[0].untyped_storage())
-            at = [img.data_ptr() - base for img in images]
-        else:
-            pixels = torch.cat([img.reshape(-1) for img in images])
-            at = [0]
-            for img in images[:-1]:
-                at.append(at[-1] + img.numel())
+        pixels, at = _c.gather(images, 3)
+        at = [off for off, _ in at]  # the images are contiguous: a row stride is the row
         n = len(images)
         cropped = [k for k in range(n) if crops[k] is not None]
         canvases, places = None, {}
@@ -192,9 +185,8 @@ def encode_jpeg_batch(images, quality: int = 90, crops: Optional[Sequence] = Non
         raise ValueError(f"crops: {len(crops)} entries for {len(images)} images")
     sizes = []
     for k, (img, crop) in enumerate(zip(images, crops)):
-        if not isinstance(img, torch.Tensor) or img.device.type != "cuda":
-            raise _l.Dm4dError(f"images[{k}]: expected a tensor on a HIP device (no CPU fallback in diffuman4d_amd)")
-        if img.dtype != torch.uint8 or img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
+        _c.require_device_u8(img, f"images[{k}]")
+        if img.dim() != 3 or img.shape[2] != 3 or not img.is_contiguous():
             raise _l.Dm4dError(f"images[{k}]: expected a contiguous uint8 [H, W, 3] tensor, got {img.dtype} {tuple(img.shape)}")
         if crop is not None and (len(crop) not in (4, 6) or crop[2] < 1 or crop[3] < 1):
             raise ValueError(f"Invalid crop_param: {crop}")

@@ -22,6 +22,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import lib as _l
+from .codec import workspace as _workspace
 from .lib import (CAPTURE_CELL_FIELDS, CAPTURE_FIELDS, EVAL_BG_SHIFT, EVAL_CROP_MASKS, EVAL_FIELDS, EVAL_IMAGE_F32, EVAL_MASK_F32, EVAL_OUT,  # noqa: F401
                   LOG2E, LPIPS_IN_COLS, LPIPS_TAPS, ROWS_MOVE_MAX_JOBS, SKEL_CIRCLE, SKEL_COORD_MAX, SKEL_COORD_MIN, SKEL_FIELDS, SKEL_LINE, SKEL_LINK_FIELDS,
                   SKEL_MAX_KPTS, SKEL_MAX_PRIMS, SKEL_MAX_SIZE, SKEL_ST_LINK_SHIFT, SKEL_ST_NOCOLOR, SKEL_ST_NONFINITE,
@@ -1486,6 +1487,17 @@ def matting_mask(logits: torch.Tensor, meta: torch.Tensor, meta_host: torch.Tens
     return blob
 
 
+def _encoder_buffers(desc: torch.Tensor, fields: int, dev, blob_bytes: int, ws_bytes: int):
+    """What png_encode and webp_encode do around their library call: `desc` is a host int64 [n, fields] tensor -> (n, its device
+    copy, the workspace, the blob, the int64 [2 n] result) on `dev`."""
+    if desc.device.type != "cpu" or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != fields or not desc.is_contiguous() \
+            or desc.shape[0] < 1:
+        raise _l.Dm4dError(f"desc: expected a contiguous host int64 [n, {fields}] tensor")
+    n = int(desc.shape[0])
+    return n, desc.to(dev), _workspace(ws_bytes, dev), torch.empty(blob_bytes, dtype=torch.uint8, device=dev), \
+        torch.empty(2 * n, dtype=torch.int64, device=dev)
+
+
 def png_encode(planes: torch.Tensor, rgb: Optional[torch.Tensor], desc: torch.Tensor, blob_bytes: int, ws_bytes: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Complete PNG files of the images that `desc` (host int64 [n, PNG_FIELDS], include/dm4d.h) names in the device uint8 buffers
     `planes` (L planes and alpha planes) and `rgb` (packed RGB images; None when there is no RGBA image) -> (blob of `blob_bytes` on the
@@ -1494,16 +1506,9 @@ def png_encode(planes: torch.Tensor, rgb: Optional[torch.Tensor], desc: torch.Te
     _req(planes, "planes", torch.uint8)
     if rgb is not None:
         _req(rgb, "rgb", torch.uint8)
-    if desc.device.type != "cpu" or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != _l.PNG_FIELDS or not desc.is_contiguous() \
-            or desc.shape[0] < 1:
-        raise _l.Dm4dError(f"desc: expected a contiguous host int64 [n, {_l.PNG_FIELDS}] tensor")
     if not planes.is_contiguous() or planes.numel() == 0 or (rgb is not None and (not rgb.is_contiguous() or rgb.device != planes.device)):
         raise _l.Dm4dError("planes / rgb: expected contiguous non-empty tensors on one device")
-    n, dev = int(desc.shape[0]), planes.device
-    ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
-    blob = torch.empty(blob_bytes, dtype=torch.uint8, device=dev)
-    out = torch.empty(2 * n, dtype=torch.int64, device=dev)
-    desc_dev = desc.to(dev)
+    n, desc_dev, ws, blob, out = _encoder_buffers(desc, _l.PNG_FIELDS, planes.device, blob_bytes, ws_bytes)
     _l.call("dm4d_png_encode_u8", _stream(), _p(planes), planes.numel(), _p(rgb), 0 if rgb is None else rgb.numel(), desc.data_ptr(),
             _p(desc_dev), n, _p(ws), ws.numel() * 8, _p(blob), blob.numel(), _p(out))
     return blob, out
@@ -1514,16 +1519,9 @@ def webp_encode(rgb: torch.Tensor, desc: torch.Tensor, blob_bytes: int, ws_bytes
     uint8 buffer `rgb` -> (blob of `blob_bytes` on the device, device int64 [2 n]: the files' offsets in it, then their lengths).  Five
     launches on the current stream; nothing is synchronised.  The library checks every descriptor against the buffer before it launches."""
     _req(rgb, "rgb", torch.uint8)
-    if desc.device.type != "cpu" or desc.dtype != torch.int64 or desc.dim() != 2 or desc.shape[1] != _l.WEBP_FIELDS or not desc.is_contiguous() \
-            or desc.shape[0] < 1:
-        raise _l.Dm4dError(f"desc: expected a contiguous host int64 [n, {_l.WEBP_FIELDS}] tensor")
     if not rgb.is_contiguous() or rgb.numel() == 0:
         raise _l.Dm4dError("rgb: expected a contiguous non-empty tensor")
-    n, dev = int(desc.shape[0]), rgb.device
-    ws = torch.empty((ws_bytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
-    blob = torch.empty(blob_bytes, dtype=torch.uint8, device=dev)
-    out = torch.empty(2 * n, dtype=torch.int64, device=dev)
-    desc_dev = desc.to(dev)
+    n, desc_dev, ws, blob, out = _encoder_buffers(desc, _l.WEBP_FIELDS, rgb.device, blob_bytes, ws_bytes)
     _l.call("dm4d_webp_encode_u8", _stream(), _p(rgb), rgb.numel(), desc.data_ptr(), _p(desc_dev), n, _p(ws), ws.numel() * 8, _p(blob),
             blob.numel(), _p(out))
     return blob, out

@@ -82,10 +82,8 @@ def encode_png_batch(planes, alphas: Optional[Sequence] = None, workspace_bytes:
     shapes = []
     for k, (p, a) in enumerate(zip(planes, alphas)):
         for name, t in ((f"planes[{k}]", p), (f"alphas[{k}]", a)):
-            if t is not None and (not isinstance(t, torch.Tensor) or t.device.type != "cuda"):
-                raise _l.Dm4dError(f"{name}: expected a tensor on a HIP device (no CPU fallback in diffuman4d_amd)")
-            if t is not None and t.dtype != torch.uint8:
-                raise _l.Dm4dError(f"{name}: expected uint8, got {t.dtype}")
+            if t is not None:
+                _c.require_device_u8(t, name)
         rgba = a is not None
         if p.dim() != (3 if rgba else 2) or (rgba and (p.shape[2] != 3 or tuple(a.shape) != tuple(p.shape[:2]))):
             raise _l.Dm4dError(f"planes[{k}]: expected [h, w], or [h, w, 3] with an [h, w] alpha plane, got {tuple(p.shape)}")
@@ -99,8 +97,8 @@ def encode_png_batch(planes, alphas: Optional[Sequence] = None, workspace_bytes:
         with torch.cuda.device(dev):
             ones = [alphas[k] if alphas[k] is not None else planes[k] for k in range(first, last)]   # 1 byte per pixel
             threes = [planes[k] for k in range(first, last) if alphas[k] is not None]                # 3 bytes per pixel
-            pbuf, pat = _gather(ones, 1)
-            rbuf, rat = _gather(threes, 3) if threes else (None, [])
+            pbuf, pat = _c.gather(ones, 1)
+            rbuf, rat = _c.gather(threes, 3) if threes else (None, [])
             items, r = [], 0
             for j, k in enumerate(range(first, last)):
                 h, w, ch = shapes[k]
@@ -111,19 +109,3 @@ def encode_png_batch(planes, alphas: Optional[Sequence] = None, workspace_bytes:
                     r += 1
             files += png_encode_planes(pbuf, rbuf, items)
     return files
-
-
-def _gather(tensors, bpp: int):
-    """Tensors [h, w(, 3)] of `bpp` bytes a pixel -> (one uint8 buffer, [(byte offset, row stride)]): the tensors' common storage where
-    they share one and their pixels are contiguous within a row, else a copy of them back to back."""
-    base = tensors[0].untyped_storage().data_ptr()
-    rows_ok = all(t.stride(1) == bpp and (bpp == 1 or t.stride(2) == 1) and t.stride(0) >= t.shape[1] * bpp for t in tensors)
-    if rows_ok and all(t.untyped_storage().data_ptr() == base for t in tensors):
-        buf = torch.empty(0, dtype=torch.uint8, device=tensors[0].device).set_(tensors[0].untyped_storage())
-        return buf, [(t.data_ptr() - base, int(t.stride(0))) for t in tensors]
-    buf = torch.cat([t.reshape(-1) for t in tensors])
-    at, off = [], 0
-    for t in tensors:
-        at.append((off, int(t.shape[1]) * bpp))
-        off += t.numel()
-    return buf, at

@@ -69,10 +69,7 @@ def encode_webp_batch(images, workspace_bytes: int = DEFAULT_WORKSPACE) -> List[
         return []
     shapes = []
     for k, t in enumerate(images):
-        if not isinstance(t, torch.Tensor) or t.device.type != "cuda":
-            raise _l.Dm4dError(f"images[{k}]: expected a tensor on a HIP device (no CPU fallback in diffuman4d_amd)")
-        if t.dtype != torch.uint8:
-            raise _l.Dm4dError(f"images[{k}]: expected uint8, got {t.dtype}")
+        _c.require_device_u8(t, f"images[{k}]")
         if t.dim() != 3 or t.shape[2] != 3:
             raise _l.Dm4dError(f"images[{k}]: expected [h, w, 3], got {tuple(t.shape)}")
         h, w = int(t.shape[0]), int(t.shape[1])
@@ -82,22 +79,6 @@ def encode_webp_batch(images, workspace_bytes: int = DEFAULT_WORKSPACE) -> List[
     files: List[bytes] = []
     for first, last in _c.chunks([_device_bytes(h, w) + 3 * h * w for h, w in shapes], workspace_bytes, _c.MAX_DECODE_CHUNK):
         with torch.cuda.device(images[first].device):
-            buf, at = _gather(images[first:last])
+            buf, at = _c.gather(images[first:last], 3)
             files += webp_encode_planes(buf, [shapes[first + j] + at[j] for j in range(last - first)])
     return files
-
-
-def _gather(tensors):
-    """Tensors [h, w, 3] -> (one uint8 buffer, [(byte offset, row stride)]): the tensors' common storage where they share one and their
-    pixels are contiguous within a row, else a copy of them back to back."""
-    base = tensors[0].untyped_storage().data_ptr()
-    rows_ok = all(t.stride(2) == 1 and t.stride(1) == 3 and (t.shape[0] == 1 or t.stride(0) >= t.shape[1] * 3) for t in tensors)
-    if rows_ok and all(t.untyped_storage().data_ptr() == base for t in tensors):
-        buf = torch.empty(0, dtype=torch.uint8, device=tensors[0].device).set_(tensors[0].untyped_storage())
-        return buf, [(t.data_ptr() - base, max(int(t.stride(0)), int(t.shape[1]) * 3)) for t in tensors]
-    buf = torch.cat([t.reshape(-1) for t in tensors])
-    at, off = [], 0
-    for t in tensors:
-        at.append((off, int(t.shape[1]) * 3))
-        off += t.numel()
-    return buf, at

@@ -129,3 +129,75 @@ def test_read_file_takes_paths_and_bytes(tmp_path):
     assert codec.read_file(tmp_path / "f.bin") == codec.read_file(str(tmp_path / "f.bin")) == b"\x00\x01\x02"
     for data in (b"ab", bytearray(b"ab"), memoryview(b"ab")):
         assert codec.read_file(data) == b"ab" and type(codec.read_file(data)) is bytes
+
+
+# -- the encoders' inputs --------------------------------------------------------------------------------------------------------------
+def _rows(buf, off, stride, h, row):
+    """The h rows of `row` bytes, `stride` apart, from byte `off` of a uint8 buffer."""
+    return np.stack([buf.numpy()[off + y * stride: off + y * stride + row] for y in range(h)])
+
+
+@pytest.mark.parametrize("bpp", [1, 3])
+def test_gather_reads_views_of_one_storage_in_place(bpp):
+    from diffuman4d_amd.host.codec import gather
+    shape = (12, 20) if bpp == 1 else (12, 20, 3)
+    wide = torch.from_numpy(np.random.default_rng(4).integers(0, 256, shape, dtype=np.uint8))
+    views = [wide[2:9, 3:14], wide[0:12, 19:20], wide[5:6, 0:20], wide[11:12, 7:8], wide]
+    buf, at = gather(views, bpp)
+    assert buf.dtype == torch.uint8 and buf.dim() == 1 and buf.data_ptr() == wide.data_ptr() and buf.numel() == wide.numel()  # no copy
+    for v, (off, stride) in zip(views, at):
+        h, w = v.shape[:2]
+        assert off == v.storage_offset() and stride >= w * bpp and (h == 1 or stride == 20 * bpp)
+        assert off + (h - 1) * stride + w * bpp <= buf.numel()
+        assert np.array_equal(_rows(buf, off, stride, h, w * bpp), v.numpy().reshape(h, w * bpp))
+
+
+@pytest.mark.parametrize("bpp", [1, 3])
+def test_gather_takes_the_stride_of_a_one_row_view_for_nothing(bpp):
+    """The stride of a dimension of size 1 is arbitrary: a [1, w] view that reports a stride below its row is still read in place."""
+    from diffuman4d_amd.host.codec import gather
+    shape = (6, 10) if bpp == 1 else (6, 10, 3)
+    wide = torch.arange(6 * 10 * bpp, dtype=torch.uint8).reshape(shape)
+    row = wide[4:5, 2:9]
+    odd = row.as_strided(row.shape, (1,) + tuple(row.stride()[1:]), row.storage_offset())  # the same bytes, row stride 1
+    assert odd.stride(0) == 1 and torch.equal(odd, row)
+    buf, at = gather([odd, wide[1:3, 0:4]], bpp)
+    assert buf.data_ptr() == wide.data_ptr()
+    assert at == [(row.storage_offset(), 7 * bpp), (10 * bpp, 10 * bpp)]
+    assert np.array_equal(_rows(buf, *at[0], 1, 7 * bpp), row.numpy().reshape(1, 7 * bpp))
+
+
+@pytest.mark.parametrize("bpp", [1, 3])
+def test_gather_copies_what_is_not_rows_of_one_storage(bpp):
+    from diffuman4d_amd.host.codec import gather
+    shape = (12, 20) if bpp == 1 else (12, 20, 3)
+    wide = torch.from_numpy(np.random.default_rng(5).integers(0, 256, shape, dtype=np.uint8))
+    views = [wide[2:9, 3:14], wide[5:6, 0:20], wide[0:12, 19:20]]
+    for tensors in ([v.clone() for v in views],            # different storages
+                    [views[0], wide[:, ::2], views[2]]):   # one storage, but pixels that are not contiguous within a row
+        buf, at = gather(tensors, bpp)
+        assert buf.dtype == torch.uint8 and buf.numel() == sum(t.numel() for t in tensors) and buf.data_ptr() != wide.data_ptr()
+        off = 0
+        for t, place in zip(tensors, at):
+            h, w = t.shape[:2]
+            assert place == (off, w * bpp)  # back to back
+            assert np.array_equal(_rows(buf, off, w * bpp, h, w * bpp), t.numpy().reshape(h, w * bpp))
+            off += t.numel()
+
+
+def test_require_device_u8_names_the_tensor_and_what_is_wrong():
+    from diffuman4d_amd.host import codec
+    from diffuman4d_amd.host import lib as L
+    with pytest.raises(L.Dm4dError, match=r"^images\[3\]: expected a tensor on a HIP device"):
+        codec.require_device_u8(torch.zeros(2, 2, dtype=torch.uint8), "images[3]")
+    with pytest.raises(L.Dm4dError, match=r"^mask: expected a tensor on a HIP device"):
+        codec.require_device_u8(np.zeros((2, 2), np.uint8), "mask")
+
+    from unittest import mock
+    t = mock.Mock(spec=torch.Tensor, device=SimpleNamespace(type="cuda"), dtype=torch.float32)  # what the second check sees
+    with pytest.raises(L.Dm4dError, match=r"^planes\[0\]: expected uint8, got torch.float32$"):
+        codec.require_device_u8(t, "planes[0]")
+    with pytest.raises(L.Dm4dError, match="HIP device"):  # the device is asked about first
+        codec.require_device_u8(torch.zeros(2, 2), "planes[0]")
+    t.dtype = torch.uint8
+    assert codec.require_device_u8(t, "planes[0]") is t

@@ -115,6 +115,30 @@ def test_premises_of_the_cases():
     assert sk.shape == (64, 48, 3) and (sk.reshape(-1, 3).max(axis=1) == 0).mean() > 0.5 and len(np.unique(sk.reshape(-1, 3), axis=0)) > 50
 
 
+def test_deep_literals_keep_reaching_the_third_window_word():
+    """A condition on the input, not on the device: the emitter ORs a token of nb bits into its window of 32-bit words at bit `pos`,
+    counted from the byte in which its round starts (a round is 2048 pixels within a stripe), and a token with (pos & 31) + nb > 64
+    spills into a third word.  "deep_literals" is the case that has such tokens: 10 of them, by the model's own code lengths and
+    token order, and tokens of 45 bits, the format's maximum."""
+    img = all_cases()["deep_literals"]
+    pos, kind, length = M.tokens(img)
+    assert img.shape == (4, 2583, 3) and M.n_stripes(4, 2583) == 2 and int((kind == M.LITERAL).sum()) == 10329
+    tables = [M.code_table(h) for h in M.histograms(img, pos, kind, length)]
+    lens = [np.array(t[2], dtype=np.int64) for t in tables]
+    px = img.reshape(-1, 3).astype(np.int64)[pos]
+    lit = lens[0][px[:, 1]] + lens[1][px[:, 0]] + lens[2][px[:, 2]] + lens[3][255]
+    pre = np.array([M.prefix(int(v)) for v in length], dtype=np.int64)
+    ref = lens[0][256 + pre[:, 0]] + pre[:, 1] + lens[4][np.where(kind == M.UP, 0, 1)]
+    nb = np.where(kind == M.LITERAL, lit, ref)
+    start = 43 + sum(sum(t[1]) for t in tables) + np.cumsum(nb) - nb  # the first bit of every token in the payload
+    rnd = pos // M.STRIPE_PIXELS * M.STRIPE_PIXELS + pos % M.STRIPE_PIXELS // 2048 * 2048
+    first = np.flatnonzero(np.append(True, rnd[1:] != rnd[:-1]))  # a round's first token
+    origin = (start[first] // 8 * 8)[np.cumsum(np.append(True, rnd[1:] != rnd[:-1])) - 1]
+    sh = (start - origin) % 32
+    assert int(nb.max()) == 45
+    assert int((sh + nb > 64).sum()) >= 5
+
+
 def test_prefix_of_lengths_and_plane_codes():
     assert [M.prefix(v) for v in (1, 2, 3, 4)] == [(0, 0, 0), (1, 0, 0), (2, 0, 0), (3, 0, 0)]
     assert M.prefix(5) == (4, 1, 0) and M.prefix(6) == (4, 1, 1) and M.prefix(7) == (5, 1, 0) and M.prefix(9) == (6, 2, 0)

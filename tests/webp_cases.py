@@ -21,6 +21,19 @@ def fibonacci_image() -> np.ndarray:
     return img
 
 
+def deep_literals_image() -> np.ndarray:
+    """Literals of the most bits: 16 colours whose counts are FIB[:16] in every row, each colour (11 + 3 s, 10 + 3 s, 12 + 3 s), so the
+    red, green and blue codes are all chains of depth 15 and the rarest colours cost 45 bits, the format's maximum for a token.  The
+    colours sorted by count, most frequent first, fill the even places of a row and then the odd ones, so no two neighbours are equal;
+    row r is that sequence rolled by r, so no pixel equals the one above it.  2583 pixels a row, two stripes."""
+    order = np.concatenate([np.full(c, s) for s, c in sorted(enumerate(FIB[:16]), key=lambda sc: -sc[1])])
+    seq = np.empty(order.size, dtype=np.int64)
+    seq[np.concatenate([np.arange(0, order.size, 2), np.arange(1, order.size, 2)])] = order
+    assert not (seq[1:] == seq[:-1]).any()
+    row = np.stack([11 + 3 * seq, 10 + 3 * seq, 12 + 3 * seq], axis=1).astype(np.uint8)
+    return np.stack([np.roll(row, r, axis=0) for r in range(4)])
+
+
 def long_run_image() -> np.ndarray:
     """100 pixels a row: rows 75 .. 139 are one colour, a run of kind U of 6400 pixels from pixel 7600 that crosses the stripe boundary at
     8192; noise elsewhere."""
@@ -63,6 +76,7 @@ def cases() -> dict:
     # 2 x 8192 + 1 pixels of one colour: the last stripe is one reference of length 1, a few bits that share a byte with the stripe before
     out["one_pixel_stripe"] = np.full((5, 3277, 3), (0, 0, 0), dtype=np.uint8)
     out["fibonacci"] = fibonacci_image()
+    out["deep_literals"] = deep_literals_image()
     widest = np.repeat((np.arange(M.MAX_SIDE) // 97).astype(np.uint8)[None, :, None], 3, axis=2)
     widest[0, 5000:7000] = rng.integers(0, 256, (2000, 3), dtype=np.uint8)
     out["widest"] = widest
